@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- reflections/sec per ELBO step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One "step" = one full-batch ELBO step (forward + backward + gradient norm + Adam) over all observations of the
 workload -- what the reference runs per iteration of `train_model` (careless/models/merging/variational.py:255-256).
 Workload at every N: BASELINE.json configs[2] (10 M observations, Student-T likelihood, positional-encoding metadata,
 5x64 scaler, mc-samples 8), observations sharded over the ranks (strong scaling), one all-reduce of the flat gradient.
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline figure does not need: the
+CPU baseline (one GPU, mono workloads) and the configuration BASELINE.json quotes at 4 (8) GPUs.  `--dump-outputs DIR` writes what
+the last timed step computed -- the trainable parameters after its update, its gradient and its loss terms -- as .npy files; the
+inputs and the in-kernel noise are seeded, so two builds run with the same arguments can be compared array for array.
 
 Ranks: one process per GPU.  Under `python -m torch.distributed.run ... bench.py --gpus N` the ranks exist already
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment).  A bare `python bench.py --gpus N` starts them itself: the parent
@@ -36,7 +41,11 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=HEADLINE)
     ap.add_argument("--nobs", type=int, default=None, help="override the number of observations (debugging)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU baseline and "
+                                                       "the extra configuration of --extra auto")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the last step's parameters, "
+                                                                         "gradient and loss terms to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the gradient all-reduce even with one rank")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the multi-rank "
                                                       "control flow on a single-GPU box)")
@@ -46,7 +55,7 @@ def parse(argv=None):
     ap.add_argument("--cpu-full", action="store_true", help="(the default since round 4) CPU baseline at the workload's full size, 5 timed "
                                                             "steps, as SURVEY 8d prescribes: ~2 minutes and ~50 GB of host memory for the "
                                                             "headline workload; cut to what MemAvailable holds, and said so, on a smaller host")
-    ap.add_argument("--extra", default="auto", help="'auto': with 4 (8) ranks also time the Laue (double-Wilson) configuration "
+    ap.add_argument("--extra", default="auto", help="'auto': with --full and 4 (8) ranks also time the Laue (double-Wilson) configuration "
                                                     "BASELINE.json quotes on 4 (8) GPUs and report it under 'extra_configs'; 'none'; or a workload name")
     ap.add_argument("--extra-nobs", type=int, default=None, help="observations of the extra configuration (rehearsals on a small box)")
     ap.add_argument("--launch-timeout", type=float, default=3600.0, help="seconds after which the launcher (bare `bench.py --gpus N`) "
@@ -256,7 +265,43 @@ def traffic_bytes(workload: str, world: int):
 # ----------------------------------------------------------------------------------------------------------------------------
 # one timed workload on the ranks that are up
 # ----------------------------------------------------------------------------------------------------------------------------
-def run_workload(args, name, nobs, steps, warmup, rank, world, use_dist):
+DUMP_BYTES = 64 << 20             # --dump-outputs: at most this much in all; larger outputs are written as a fixed, seeded sample
+
+
+def dump_outputs(eng, steps_total: int, out_dir: str) -> None:
+    """What the last timed step computed, as a caller of `train_step` receives it: the trainable parameters after its Adam update
+    (float32, one array per group of the flat layout), its gradient (`grad_*`, float32, after the all-reduce) and its loss terms
+    (`loss_terms`, float64: loss, F KLDiv, NLL, gradient norm).  Rank 0's copy: under the reflection-owner split the q entries
+    of the other ranks' reflections are not rank 0's to update."""
+    from careless_amd import _lib
+    lay = eng.layout          # (the engine launches on torch's current stream: the copies below wait for the last step)
+    groups = [("q_loc_raw", lay.R), ("q_scale_raw", lay.R), ("scaler_mlp", lay.P), ("image_scales", lay.n_img),
+              ("image_layers", lay.n_imgl), ("ev11", lay.n_ev11), ("dw_r_raw", lay.n_dwr)]
+    params, grads = eng.params.detach().cpu().numpy(), eng.grads.detach().cpu().numpy()
+    arrays, off = {}, 0
+    for g, n in groups:
+        if n > 0:
+            arrays[g] = params[off:off + n]
+            arrays["grad_" + g] = grads[off:off + n]
+        off += n
+    assert off == lay.n
+    rec = eng.history_buf.view(-1, _lib.CL_HIST_STRIDE)[steps_total - 1].cpu().numpy()
+    arrays["loss_terms"] = rec[:4].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:           # keep the small arrays whole; sample the large ones at the same seeded positions every run
+        small = sum(a.nbytes for a in arrays.values() if a.size <= (1 << 18))
+        big = [k for k, a in arrays.items() if a.size > (1 << 18)]
+        keep = (DUMP_BYTES - small) // (4 * len(big))
+        for k in big:
+            if arrays[k].size > keep:
+                idx = np.sort(np.random.default_rng(20240).choice(arrays[k].size, keep, replace=False))
+                arrays[k] = arrays[k][idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
+def run_workload(args, name, nobs, steps, warmup, rank, world, use_dist, dump_dir=None):
     import torch
     import torch.distributed as dist
     from careless_amd.workloads import bytes_per_obs, flops_per_obs, make_workload
@@ -405,6 +450,8 @@ def run_workload(args, name, nobs, steps, warmup, rank, world, use_dist):
     finite = bool(np.all(np.isfinite(hist["loss"]))) and len(hist["loss"]) == steps_total
     if rank != 0:
         return None
+    if dump_dir:
+        dump_outputs(eng, steps_total, dump_dir)
     N = spec["N"]
     ms = 1e3 * elapsed / steps
     F = flops_per_obs(spec["d"], spec["w"], spec["L"], spec.get("image_layers", 0))
@@ -465,8 +512,9 @@ def worker(args) -> int:
             dist.init_process_group(args.backend, rank=rank, world_size=world)
     ranks_seen = dist.get_world_size() if use_dist else 1
 
-    res = run_workload(args, args.workload, args.nobs, args.steps, args.warmup, rank, world, use_dist)
-    extra_name = EXTRA_AT.get(world) if args.extra == "auto" else (None if args.extra == "none" else args.extra)
+    res = run_workload(args, args.workload, args.nobs, args.steps, args.warmup, rank, world, use_dist, dump_dir=args.dump_outputs)
+    # the extra configuration of this GPU count is measured by a --full run only; one named with --extra always is
+    extra_name = (EXTRA_AT.get(world) if args.full else None) if args.extra == "auto" else (None if args.extra == "none" else args.extra)
     if args.workload != HEADLINE or args.nobs is not None or args.sim_world > 1:
         extra_name = extra_name if args.extra not in ("auto", "none") else None
     extras, extra_failed = {}, None
@@ -522,7 +570,7 @@ def worker(args) -> int:
         if args.sim_world > 1:
             out["diagnostic"] = f"rank 0 shard of a simulated {args.sim_world}-rank job: value is NOT a throughput of this workload"
             out["value"] = None
-        if not args.no_cpu_baseline and world == 1 and spec.get("kind", "mono") == "mono" and not spec.get("image_layers"):
+        if args.full and not args.no_cpu_baseline and world == 1 and spec.get("kind", "mono") == "mono" and not spec.get("image_layers"):
             # full size (configs[2] for >= 5 steps) unless a bounded sample was asked for; cpu_baseline() cuts the size to
             # the host's free memory and says so in `sample`
             full = args.cpu_sample is None

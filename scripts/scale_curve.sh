@@ -12,7 +12,7 @@ ngpu=$(python -c 'import torch; print(torch.cuda.device_count())')
 rc_all=0
 for n in ${GPUS:-1 2 4 8}; do
   if [ "$n" -gt "$ngpu" ]; then echo "SCALE n_gpus=$n skipped: $ngpu GPU(s) visible" | tee -a "$out/summary.txt"; continue; fi
-  python bench.py --gpus "$n" --steps "${STEPS:-20}" --warmup "${WARMUP:-3}" $([ "$n" -gt 1 ] && echo --no-cpu-baseline) > "$out/bench_n$n.json" 2> "$out/bench_n$n.err"
+  python bench.py --full --gpus "$n" --steps "${STEPS:-20}" --warmup "${WARMUP:-3}" $([ "$n" -gt 1 ] && echo --no-cpu-baseline) > "$out/bench_n$n.json" 2> "$out/bench_n$n.err"
   rc=$?; [ $rc -ne 0 ] && rc_all=$rc
   python - "$out/bench_n$n.json" "$n" "$rc" <<'PY' | tee -a "$out/summary.txt"
 import json, sys

@@ -7,6 +7,8 @@ import subprocess
 import sys
 import textwrap
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,3 +106,74 @@ def test_scale_curve_script_parses():
     assert subprocess.run(["bash", "-n", os.path.join(ROOT, "scripts", "scale_curve.sh")]).returncode == 0
     for s in ("profiles_all.sh", "pmc_passes_step.sh", "store_profiles.sh"):
         assert subprocess.run(["bash", "-n", os.path.join(ROOT, "scripts", s)]).returncode == 0, s
+
+
+def test_a_plain_run_leaves_the_extras_to_full():
+    """`bench.py --gpus 1 --steps N --warmup W` times the headline and nothing else: the CPU baseline and the configuration BASELINE.json
+    quotes at 4 (8) GPUs need `--full`; `--dump-outputs` is off unless a directory is given."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def _fake_engine(R, P, n_img, steps):
+    import torch
+    from careless_amd import _lib
+    from careless_amd.engine import FlatLayout
+
+    class Eng:
+        pass
+    e = Eng()
+    e.layout = FlatLayout(R=R, P=P, n_img=n_img, seg_off=[], seg_owner=[])
+    e.params = torch.arange(e.layout.n, dtype=torch.float32)
+    e.grads = -e.params
+    e.history_buf = torch.arange(steps * _lib.CL_HIST_STRIDE, dtype=torch.float64)
+    return e
+
+
+def test_dump_outputs_writes_the_last_step_and_samples_within_the_cap(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: one float32 array per parameter group and its gradient, the last step's loss terms in float64; past the size
+    cap the large arrays are a sample taken at the same seeded positions in every run."""
+    import numpy as np
+    from careless_amd import _lib
+    eng = _fake_engine(R=1000, P=300, n_img=9, steps=4)
+    bench.dump_outputs(eng, 4, str(tmp_path / "a"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == sorted(["q_loc_raw", "q_scale_raw", "scaler_mlp", "image_scales", "loss_terms"] +
+                                 ["grad_" + k for k in ("q_loc_raw", "q_scale_raw", "scaler_mlp", "image_scales")])
+    assert got["q_scale_raw"].dtype == np.float32 and np.array_equal(got["q_scale_raw"], np.arange(1000, 2000, dtype=np.float32))
+    assert np.array_equal(got["grad_image_scales"], -np.arange(2300, 2309, dtype=np.float32))
+    assert got["loss_terms"].dtype == np.float64 and np.array_equal(got["loss_terms"], 3 * _lib.CL_HIST_STRIDE + np.arange(4.0))
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 << 20)
+    eng = _fake_engine(R=1 << 20, P=300, n_img=9, steps=2)
+    for d in ("b", "c"):
+        bench.dump_outputs(eng, 2, str(tmp_path / d))
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert sum(a.nbytes for a in b.values()) <= 8 << 20
+    assert b["scaler_mlp.npy"].size == 300 and b["q_loc_raw.npy"].size < 1 << 20
+    assert np.all(np.diff(b["q_loc_raw.npy"]) > 0) and np.array_equal(b["q_loc_raw.npy"], -b["grad_q_loc_raw.npy"])
+    for k, a in b.items():
+        assert np.array_equal(a, np.load(tmp_path / "c" / k)), k
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat_with_the_same_arguments(tmp_path):
+    """Two plain runs with the same arguments time exactly `--steps` steps, report `ms_per_step` and leave the same outputs of their
+    last step (same seeded inputs and noise; the kernels' atomic sums may differ in the last bits)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    runs = []
+    for d in ("one", "two"):
+        argv = ["--nobs", "300000", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 4 and out["ms_per_step"] > 0 and len(out["loss_history"]) == 6 and "cpu_baseline" not in out
+        runs.append({p.name: np.load(p) for p in (tmp_path / d).iterdir()})
+        assert np.isclose(runs[-1]["loss_terms.npy"][0], out["loss_history"][-1], rtol=1e-12)
+    assert sorted(runs[0]) == sorted(runs[1]) and "grad_q_loc_raw.npy" in runs[0]
+    for k, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)), k
+        assert np.allclose(a, runs[1][k], rtol=1e-4, atol=1e-6 * np.max(np.abs(a))), k
