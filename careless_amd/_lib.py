@@ -20,6 +20,9 @@ CL_BIJ_EXP, CL_BIJ_SOFTPLUS = 0, 1
 CL_PRIOR_WILSON, CL_PRIOR_DOUBLE_WILSON = 0, 1
 CL_LAUE_LIK_MAX_BLOCKS = 2048
 CL_EV11_WAVES = 8               # wave slots per workgroup in ev11_part (include/careless_hip.h)
+# cl_mlp_route: the launcher a scaler launch goes to (include/careless_hip.h, enum cl_route)
+(CL_ROUTE_NONE, CL_ROUTE_LANE, CL_ROUTE_LANE_IMGL, CL_ROUTE_LANE_BLOCK, CL_ROUTE_NARROW, CL_ROUTE_MLP, CL_ROUTE_MLP_PACKED, CL_ROUTE_MLP_IMGL,
+ CL_ROUTE_MLP_CHAIN, CL_ROUTE_MLP_DET, CL_ROUTE_MLP_PACKED_DET, CL_ROUTE_MLP_CHAIN_DET) = range(12)
 
 _vp = C.c_void_p
 
@@ -149,13 +152,13 @@ EXPORTS = {
     "cl_mlp_param_count": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "cl_mlp_meta_rows": (C.c_int, [C.c_int]),
     "cl_mlp_max_layers": (C.c_int, [C.c_int]),
-    "cl_mlp_max_layers_imgl": (C.c_int, [C.c_int]),
     "cl_tn_forward": (C.c_int, [C.POINTER(TnArgs), _vp]),
     "cl_tn_backward": (C.c_int, [C.POINTER(TnArgs), _vp]),
     "cl_dw_prior_forward": (C.c_int, [C.POINTER(TnArgs), _vp]),
     "cl_elbo_mono_fwd_bwd": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
     "cl_mlp_forward": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
     "cl_mlp_backward_ext": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
+    "cl_mlp_route": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
     "cl_mlp_kernel_name": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_char_p, C.c_size_t]),
     "cl_wide_ld": (C.c_int, [C.c_int]),
     "cl_wide_dense_forward": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_int, _vp, C.c_int, _vp, _vp]),
@@ -271,6 +274,12 @@ def check(code: int, what: str) -> None:
     if code < 0:
         raise ValueError(f"{what}: invalid argument (code {code})")
     raise CarelessHipError(f"{what}: HIP error {code}")
+
+
+def mlp_route(lib, mode: int, **fields) -> int:
+    """`cl_mlp_route` of a launch with these `cl_mlp_args` fields (pointer fields: non-zero = a buffer is given); no device needed."""
+    a = MlpArgs(**fields)
+    return int(lib.cl_mlp_route(C.byref(a), mode))
 
 
 def ptr(t) -> Optional[int]:

@@ -42,11 +42,6 @@ int cl_mlp_max_layers(int w) {
     return w <= 16 ? CL_MLP_LMAX_W16 : (w <= 32 ? CL_MLP_LMAX_W32 : CL_MLP_LMAX_W64);      // (width 16: the 16-wide instance with explicit biases, round 5)
 }
 
-int cl_mlp_max_layers_imgl(int w) {
-    if (w < 1 || w > 64) return 0;
-    return w <= 15 ? CL_MLP_LMAX_W16_IMGL : (w <= 32 ? CL_MLP_LMAX_W32 : CL_MLP_LMAX_W64);
-}
-
 int cl_mlp_meta_rows(int d) { return d < 1 ? 0 : ((d + 3) & ~3); }
 
 size_t cl_mlp_param_count(int d, int w, int L) {
@@ -80,6 +75,11 @@ int cl_mlp_backward_ext(const cl_mlp_args* a, int grid, void* stream) {
     if (int e = check_mlp(a)) return e;
     if ((a->dO_ext == nullptr && a->dH_ext == nullptr) || a->partials == nullptr) return -1;
     return cl_launch_mlp(*a, 2, grid, (hipStream_t)stream);
+}
+
+int cl_mlp_route(const cl_mlp_args* a, int mode) {
+    if (a == nullptr || mode < 0 || mode > 2) return -1;
+    return (int)mlp_route(*a, mode);
 }
 
 int cl_mlp_kernel_name(const cl_mlp_args* a, int mode, char* out, size_t n) {

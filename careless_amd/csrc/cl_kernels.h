@@ -13,12 +13,17 @@ int cl_launch_mlp_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);
 int cl_launch_mlp_packed_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // ... with -DCL_IMGL=2 -DCL_DET=1 (single-pass Laue, no atomics)
 int cl_launch_mlp_chain_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // ... with -DCL_CHAIN=1 -DCL_DET=1 (a chain's last block, no atomics)
 int cl_launch_det_reduce(const cl_det_args& a, hipStream_t st);                     // elbo_elem.hip: fixed-order sums of the deterministic mode
+cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // elbo_mlp.hip: the launcher cl_launch_mlp hands a launch to
+int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // ... and the name of the instance it runs
+// The *_supports functions describe the shapes a kernel family holds; the A/B switches that keep shapes off a family are read by mlp_route only.
 int cl_narrow_supports(const cl_mlp_args& a);                                       // elbo_narrow.hip: width <= 15, metadata <= 15, plain layout
 int cl_launch_narrow(const cl_mlp_args& a, int grid, hipStream_t st);               // ... the full ELBO step on that kernel
 int cl_lane_supports(const cl_mlp_args& a);                                         // elbo_lane.hip: lane = observation; 20 layers, width <= 10, metadata <= 31 columns
+#ifndef CL_LANE_WMAX
+#define CL_LANE_WMAX 10                                                             // ... widest instance of every form (11, 12: twelve-wide register instances)
+#endif
 int cl_lane_kernel_name(const cl_mlp_args& a, char* out, size_t n);
 int cl_narrow_kernel_name(const cl_mlp_args& a, char* out, size_t n);
-int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // elbo_mlp.hip: the routing of cl_launch_mlp, as a name
 int cl_lane_imgl_supports(const cl_mlp_args& a);                                    // ... with one or two per-image layers on top (round 5)
 int cl_launch_lane_imgl(const cl_mlp_args& a, int grid, hipStream_t st);
 int cl_lane_imgl_kernel_name(const cl_mlp_args& a, char* out, size_t n);

@@ -1165,9 +1165,6 @@ static int launch_lane_one(const cl_mlp_args& a, int grid, hipStream_t st) {
     }
 }
 
-#ifndef CL_LANE_WMAX
-#define CL_LANE_WMAX 10
-#endif
 #define CL_LANE_IMGL_MAX 2          /* per-image layers of the lane instances with all three forms (production, full, dZ_0 out) ... */
 #define CL_LANE_IMGL_MAX_NL 3       /* ... a third one: production and full form; at the default depth in a unit of its own (CL_LANE_PART = 5) */
 #define CL_LANE_IMGL3_DEPTH_MAX 18  /* ... the third one on 2 .. 18 and on 20 Dense layers (19: see CL_LANE_PART 9) */
@@ -1236,17 +1233,13 @@ static size_t lane_rows_lds(int w, int d) {
 // are rows of an LDS buffer (LX); any number of MC samples (batches of SPRE).  4 M observations, 20 x 10, Student-T, ms per step
 // here / on elbo_narrow.hip (scripts/narrow_samples.py): S = 1 0.96 / 1.11, 2: 1.01 / 1.12, 4: 1.07 / 1.19, 8: 1.16 / 1.34.
 int cl_lane_supports(const cl_mlp_args& a) {
-    // (CARELESS_HIP_LANE_W12=0: A/B runs of widths 11 and 12 against the narrow kernel they ran on until round 6)
-    static const bool w12_on = [] { const char* e = getenv("CARELESS_HIP_LANE_W12"); return !(e != nullptr && e[0] == '0'); }();
-    const int wtop = (w12_on && a.d <= DMAX_ALL) ? CL_LANE_W12 : CL_LANE_WMAX;
+    const int wtop = a.d <= DMAX_ALL ? CL_LANE_W12 : CL_LANE_WMAX;
     if (!(a.w >= 1 && a.w <= wtop && a.S >= 1 && a.d >= 1 && a.d <= DMAX_LX && (a.L == NL || lane_has_depth(a.L)) && a.n_imgl == 0 && a.act_out == nullptr &&
           a.dH_ext == nullptr && a.dX_out == nullptr && (a.row_map != nullptr || a.gmeta == nullptr)))
         return 0;
     // the other depths (round 6): instances at widths 8 and 10 (a narrower scaler pays the padded steps: from width CL_LANE_DEPTH_WMIN on it still
     // beats elbo_narrow.hip), metadata in registers (more columns: behind the engine's peeled first layer, dZ_0 out in the plain layout)
-    // (CARELESS_HIP_LANE_DEPTHS=0: A/B runs against the narrow kernel these shapes ran on until round 5)
-    static const bool depths_on = [] { const char* e = getenv("CARELESS_HIP_LANE_DEPTHS"); return !(e != nullptr && e[0] == '0'); }();
-    if (a.L != NL) return depths_on && a.w >= CL_LANE_DEPTH_WMIN && a.d <= DMAX_ALL && (a.dZ0_out == nullptr || a.row_map == nullptr);
+    if (a.L != NL) return a.w >= CL_LANE_DEPTH_WMIN && a.d <= DMAX_ALL && (a.dZ0_out == nullptr || a.row_map == nullptr);
     // widths 11, 12 at the default depth: 22 .. 72 spilled registers -- ahead of the narrow kernel on <= 8 columns (1.05 against 1.11 ms at
     // 4 M observations), behind it on 9 .. 15 (1.17 against 1.12)
     if (a.w > CL_LANE_WMAX) return a.d <= 8;
@@ -1259,8 +1252,7 @@ int cl_lane_supports(const cl_mlp_args& a) {
 // layers stays on the IMGL instances of elbo_mlp.hip.
 // Round 6: the same at 2 .. 19 Dense layers (`--mlp-layers D --image-layers 1|2`: the instances of the per-depth units, width >= CL_LANE_DEPTH_WMIN).
 int cl_lane_imgl_supports(const cl_mlp_args& a) {
-    static const bool depths_on = [] { const char* e = getenv("CARELESS_HIP_LANE_DEPTHS"); return !(e != nullptr && e[0] == '0'); }();
-    const bool depth_ok = a.L == NL || (depths_on && lane_has_depth(a.L) && a.w >= CL_LANE_DEPTH_WMIN);
+    const bool depth_ok = a.L == NL || (lane_has_depth(a.L) && a.w >= CL_LANE_DEPTH_WMIN);
     return a.n_imgl >= 1 && a.n_imgl <= ((a.L == NL || a.L <= CL_LANE_IMGL3_DEPTH_MAX) ? CL_LANE_IMGL_MAX_NL : CL_LANE_IMGL_MAX) && a.w >= 1 && a.w <= CL_LANE_WMAX && a.S >= 1 && a.d >= 1 && a.d <= DMAX_ALL && depth_ok &&
            a.act_out == nullptr && a.dH_ext == nullptr && a.dX_out == nullptr && a.row_map != nullptr &&
            (a.gmeta == nullptr || a.tile_gmax != nullptr) && !a.use_img && a.imgl != nullptr && a.d_imgl != nullptr && a.tile_img != nullptr && a.n_images >= 1;
@@ -1269,8 +1261,7 @@ int cl_lane_imgl_supports(const cl_mlp_args& a) {
 // 1 = this launch of a head-less layer block (mode 1: forward with act_out; mode 2: backward from dH_ext) runs on the lane kernel (round 6):
 // 2 .. 20 Dense layers of width 5 .. 10 on <= 15 input columns in the plain layout, the FIRST block of a chain (no dX_out)
 int cl_lane_block_supports(const cl_mlp_args& a, int mode) {
-    static const bool on = [] { const char* e = getenv("CARELESS_HIP_LANE_BLOCKS"); return !(e != nullptr && e[0] == '0'); }();
-    if (!on || !(mode == 1 || mode == 2)) return 0;
+    if (!(mode == 1 || mode == 2)) return 0;
     if (!(a.w >= CL_LANE_DEPTH_WMIN && a.w <= (a.L == NL ? CL_LANE_WMAX : CL_LANE_W12) && a.d >= 1 && a.d <= DMAX_ALL && (a.L == NL || lane_has_depth(a.L)) && a.n_imgl == 0 &&
           a.row_map == nullptr && a.gmeta == nullptr && a.dX_out == nullptr && a.dO_ext == nullptr && a.dZ0_out == nullptr))
         return 0;

@@ -1317,10 +1317,35 @@ static int launch_one(const cl_mlp_args& a, int grid, hipStream_t st) {
 
 // Instantiated geometries: the padded width WP fixes how many layers of activations + weight-gradient blocks fit in the
 // 256-register budget of a wave: w <= 15 -> up to 20 layers (the CLI default scaler is 20 x 10), w <= 32 -> 10, w <= 64 -> 5.
+// Per-image layers on more than 32 metadata columns at hidden width <= 15: the 16-wide instance <16, 64, 24, IMGL> (864 - 880 bytes of
+// scratch per lane, the largest of the library) ends in a GPU memory fault when a workgroup walks more than one tile and crosses an
+// image border (found by a random draw late in round 6: scripts/probe/imgl_abort_probe.py, NOTEBOOK R6.4; the forward-only launch
+// is not affected).  Those shapes take the 32-wide instance, which holds up to CL_MLP_LMAX_W32 layers (deeper: the caller's
+// layer-by-layer path, as for any scaler deeper than one launch).
+// One helper for launch_mode and cl_mlp_kernel_name_of; `imgl_unit`: the per-image-layer compilation (CL_IMGL == 1).  WP = 0: no instance holds the shape.
+struct MlpGeom { int WP, DP, LMAX, KS; };
+static inline MlpGeom mlp_geom(const cl_mlp_args& a, int mode, bool imgl_unit) {
+    if (a.L < 1 || a.w < 1 || a.d < 1 || a.w > 64 || a.d > 64) return {0, 0, 0, 0};
+    const int imgl = imgl_unit ? a.n_imgl : 0;
+    const bool imgl_d64 = imgl_unit && mode != 1 && a.n_imgl > 0 && a.d > 32;
+    MlpGeom g{0, a.d <= 8 ? 8 : (a.d <= 32 ? 32 : 64), 0, 4};
+    if (a.w <= 15 && !imgl_d64) {
+        // the narrow instance comes in three step counts (hidden width <= 8, <= 12, <= 15); the forward-only launch keeps all four
+        g.WP = 16, g.LMAX = imgl_unit ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16;
+        if (mode != 1) g.KS = a.w <= 8 ? 2 : (a.w <= 12 ? 3 : 4);
+    } else if (a.w == 16 && !imgl_unit) {
+        g.WP = 16, g.LMAX = CL_MLP_LMAX_W16, g.KS = 5;         // (per-image layers keep the 32-wide instance)
+    } else if (a.w <= 32) {
+        g.WP = 32, g.LMAX = a.L + imgl <= 5 ? 5 : CL_MLP_LMAX_W32;
+    } else {
+        g.WP = 64, g.LMAX = CL_MLP_LMAX_W64;
+    }
+    if (a.L + imgl > g.LMAX) g.WP = 0;
+    return g;
+}
+
 template <int WP, int LMAX, int MODE, int KS = 4>
-static int launch_dp(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (a.L + (CL_IMGL == 1 ? a.n_imgl : 0) > LMAX) return -2;
-    const int dp = (a.d <= 8) ? 8 : (a.d <= 32 ? 32 : 64);
+static int launch_dp(const cl_mlp_args& a, int dp, int grid, hipStream_t st) {
     if (dp == 8) return launch_one<WP, 8, LMAX, MODE, KS>(a, grid, st);
     if (dp == 32) return launch_one<WP, 32, LMAX, MODE, KS>(a, grid, st);
     return launch_one<WP, 64, LMAX, MODE, KS>(a, grid, st);
@@ -1328,36 +1353,77 @@ static int launch_dp(const cl_mlp_args& a, int grid, hipStream_t st) {
 
 template <int MODE>
 static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (a.L < 1 || a.w < 1 || a.d < 1) return -2;
-    if (a.w > 64 || a.d > 64) return -2;
-    // Per-image layers on more than 32 metadata columns at hidden width <= 15: the 16-wide instance <16, 64, 24, IMGL> (864 - 880 bytes of
-    // scratch per lane, the largest of the library) ends in a GPU memory fault when a workgroup walks more than one tile and crosses an
-    // image border (found by a random draw late in round 6: scripts/probe/imgl_abort_probe.py, NOTEBOOK R6.4; the forward-only launch
-    // is not affected).  Those shapes take the 32-wide instance, which holds up to CL_MLP_LMAX_W32 layers (deeper: the caller's
-    // layer-by-layer path, as for any scaler deeper than one launch).
-    const bool imgl_d64 = (CL_IMGL == 1) && MODE != 1 && a.n_imgl > 0 && a.d > 32;
-    if (a.w <= 15 && !imgl_d64) {
-        // the narrow instance comes in three step counts (hidden width <= 8, <= 12, <= 15); the forward-only launch keeps all four
-        constexpr int L16 = (CL_IMGL == 1 ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16);
-        if (MODE != 1 && a.w <= 8) return launch_dp<16, L16, MODE, 2>(a, grid, st);
-        if (MODE != 1 && a.w <= 12) return launch_dp<16, L16, MODE, 3>(a, grid, st);
-        return launch_dp<16, L16, MODE, 4>(a, grid, st);
-    }
+    const MlpGeom g = mlp_geom(a, MODE, CL_IMGL == 1);
+    constexpr int L16 = (CL_IMGL == 1 ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16);
+    if (g.WP == 0) return -2;
+    if (g.WP == 16) {
+        if (g.KS == 2) return launch_dp<16, L16, MODE, 2>(a, g.DP, grid, st);
+        if (g.KS == 3) return launch_dp<16, L16, MODE, 3>(a, g.DP, grid, st);
 #if CL_IMGL != 1
-    if (a.w == 16) return launch_dp<16, CL_MLP_LMAX_W16, MODE, 5>(a, grid, st);       // (per-image layers keep the 32-wide instance: cl_mlp_max_layers_imgl)
+        if (g.KS == 5) return launch_dp<16, CL_MLP_LMAX_W16, MODE, 5>(a, g.DP, grid, st);
 #endif
-    if (a.w <= 32) return (a.L + (CL_IMGL == 1 ? a.n_imgl : 0) <= 5) ? launch_dp<32, 5, MODE>(a, grid, st) : launch_dp<32, CL_MLP_LMAX_W32, MODE>(a, grid, st);
-    return launch_dp<64, CL_MLP_LMAX_W64, MODE>(a, grid, st);
+        return launch_dp<16, L16, MODE, 4>(a, g.DP, grid, st);
+    }
+    if (g.WP == 32) return g.LMAX == 5 ? launch_dp<32, 5, MODE>(a, g.DP, grid, st) : launch_dp<32, CL_MLP_LMAX_W32, MODE>(a, g.DP, grid, st);
+    return launch_dp<64, CL_MLP_LMAX_W64, MODE>(a, g.DP, grid, st);
 }
 
 #if !CL_IMGL && !CL_CHAIN && !CL_DET
-static bool lane_enabled() {            // CARELESS_HIP_LANE=0 keeps narrow scalers off the lane-per-observation kernel (A/B runs)
-    static const bool on = [] { const char* e = getenv("CARELESS_HIP_LANE"); return !(e != nullptr && e[0] == '0'); }();
-    return on;
+// The A/B switches (bisection and measurement runs; unset or anything but "0" = on), read here and nowhere else.  Each keeps shapes off
+// a kernel family, which then go to the next kernel down mlp_route's order:
+//   CARELESS_HIP_LANE=0         every shape off the lane-per-observation kernel (elbo_lane.hip)
+//   CARELESS_HIP_NARROW=0       every shape off elbo_narrow.hip
+//   CARELESS_HIP_LANE_W12=0     widths 11, 12 off the lane kernel (the narrow kernel they ran on until round 6)
+//   CARELESS_HIP_LANE_DEPTHS=0  depths other than the default off the lane kernel (until round 5)
+//   CARELESS_HIP_LANE_BLOCKS=0  the head-less blocks of a chain off the lane kernel (the chain unit of this file)
+struct RouteSwitches { bool lane, narrow, w12, depths, blocks; };
+static bool switch_on(const char* name) { const char* e = getenv(name); return !(e != nullptr && e[0] == '0'); }
+static const RouteSwitches& route_switches() {
+    static const RouteSwitches s{switch_on("CARELESS_HIP_LANE"), switch_on("CARELESS_HIP_NARROW"), switch_on("CARELESS_HIP_LANE_W12"),
+                                 switch_on("CARELESS_HIP_LANE_DEPTHS"), switch_on("CARELESS_HIP_LANE_BLOCKS")};
+    return s;
 }
-static bool narrow_enabled() {          // CARELESS_HIP_NARROW=0 keeps narrow scalers on the eight-wave instance of this file (A/B runs)
-    static const bool on = [] { const char* e = getenv("CARELESS_HIP_NARROW"); return !(e != nullptr && e[0] == '0'); }();
-    return on;
+
+// Which launcher takes the launch: the one routing decision of the scaler launches (cl_launch_mlp, cl_mlp_kernel_name_of, cl_mlp_route).
+// Shape, optional buffers and mode only: n_pad and the grid are argument checks of the callers.
+cl_route mlp_route(const cl_mlp_args& a, int mode) {
+    const RouteSwitches& sw = route_switches();
+    const bool lane_depth = sw.depths || a.L == CL_MLP_LMAX_W16;
+    const bool lane = mode == 0 && sw.lane && lane_depth && (sw.w12 || a.w <= CL_LANE_WMAX) && cl_lane_supports(a);
+    const bool narrow = mode == 0 && sw.narrow && cl_narrow_supports(a);
+    const bool lane_imgl = mode == 0 && a.n_imgl > 0 && sw.lane && lane_depth && cl_lane_imgl_supports(a);
+    cl_route r;
+    if (a.dzf_obs != nullptr && (mode == 0 || (a.act_out == nullptr && a.dH_ext == nullptr))) {
+        // deterministic mode: full steps only, with the Evans-2011 gradients in their per-wave slots.  The default scaler's shapes keep their
+        // own kernels (round 4: elbo_lane.hip / elbo_narrow.hip store per observation when dzf_obs is given), per-image layers the lane
+        // kernel's instances only (round 6: one wave per image; the IMGL instances of this file keep their float atomics), every other width
+        // <= 64 runs the deterministic compilations of this file.  (The forward-only and backward-only launches of a layer-block chain have
+        // no float atomics: they take the chain unit.)
+        if (mode != 0 || (a.ev11 != nullptr && a.ev11_part == nullptr)) return CL_ROUTE_NONE;
+        if (a.n_imgl > 0) r = lane_imgl ? CL_ROUTE_LANE_IMGL : CL_ROUTE_NONE;
+        else if (a.dX_out != nullptr) r = (a.row_map != nullptr || a.act_out != nullptr || a.dH_ext != nullptr) ? CL_ROUTE_NONE : CL_ROUTE_MLP_CHAIN_DET;
+        else if (lane) r = CL_ROUTE_LANE;
+        else if (narrow) r = CL_ROUTE_NARROW;
+        else if (a.row_map != nullptr && a.n_imgl == 0) r = CL_ROUTE_MLP_PACKED_DET;            // single-pass Laue, wider than 15
+        else r = (a.row_map != nullptr || a.act_out != nullptr || a.dH_ext != nullptr) ? CL_ROUTE_NONE : CL_ROUTE_MLP_DET;
+    } else if ((a.act_out != nullptr || a.dH_ext != nullptr) && sw.lane && sw.blocks && cl_lane_block_supports(a, mode)) {
+        r = CL_ROUTE_LANE_BLOCK;              // the first block of a chained narrow scaler: the lane kernel's forward-only / external-gradient instances (round 6)
+    } else if (a.act_out != nullptr || a.dH_ext != nullptr || a.dX_out != nullptr) {
+        r = (a.row_map != nullptr || a.n_imgl > 0) ? CL_ROUTE_NONE : CL_ROUTE_MLP_CHAIN;        // (chains use the plain layout)
+    } else if (a.n_imgl > 0) {
+        r = lane_imgl ? CL_ROUTE_LANE_IMGL : CL_ROUTE_MLP_IMGL;       // packed layout + per-image layers: the default scaler's shapes on the lane kernel (round 5)
+    } else if (lane) {
+        r = CL_ROUTE_LANE;                    // the default scaler's shape: lane = observation
+    } else if (narrow) {
+        r = CL_ROUTE_NARROW;                  // hidden width <= 15: one wave per SIMD
+    } else {
+        r = a.row_map != nullptr ? CL_ROUTE_MLP_PACKED : CL_ROUTE_MLP;
+    }
+    // dZ0_out (the launch behind a peeled first layer, elbo_peel.hip) is stored by the default scaler's kernels only: a launch elsewhere
+    // would ignore it and leave the peeled layer a zero gradient without any error
+    if (a.dZ0_out != nullptr && r != CL_ROUTE_LANE && r != CL_ROUTE_NARROW && r != CL_ROUTE_LANE_IMGL) return CL_ROUTE_NONE;
+    if (r >= CL_ROUTE_MLP && mlp_geom(a, mode, r == CL_ROUTE_MLP_IMGL).WP == 0) return CL_ROUTE_NONE;     // wider / deeper than this file's instances
+    return r;
 }
 #endif
 
@@ -1401,40 +1467,22 @@ int cl_launch_mlp_imgl(const cl_mlp_args& a, int mode, int grid, hipStream_t st)
     if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
 #else
 int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    // per-image layers on the lane kernel: ONE predicate for the dZ0_out guard below and for the dispatch (a launch that fell through
-    // to the IMGL instances of this file would ignore dZ0_out and leave the peeled layer a zero gradient without any error)
-    const bool lane_imgl_route = a.n_imgl > 0 && mode == 0 && cl_lane_imgl_supports(a) && lane_enabled() && a.n_pad > 0 && a.n_pad % CL_TILE == 0 && grid >= 1;
-    // dZ0_out (the launch behind a peeled first layer, elbo_peel.hip) is stored by the default scaler's kernels only
-    if (a.dZ0_out != nullptr && !(mode == 0 && a.act_out == nullptr && a.dH_ext == nullptr && a.dX_out == nullptr &&
-                                  (a.dzf_obs == nullptr || a.ev11 == nullptr || a.ev11_part != nullptr) &&
-                                  ((a.n_imgl == 0 && ((cl_lane_supports(a) && lane_enabled()) || (cl_narrow_supports(a) && narrow_enabled()))) || lane_imgl_route)))
-        return -2;
-    if (a.dzf_obs != nullptr && (mode == 0 || (a.act_out == nullptr && a.dH_ext == nullptr))) {
-        // deterministic mode: the default scaler's shapes keep their own kernels (round 4: elbo_lane.hip / elbo_narrow.hip store per
-        // observation when dzf_obs is given), every other width <= 64 runs the deterministic compilation of this file.  (The forward-only
-        // and backward-only launches of a layer-block chain have no float atomics: they take the chain unit below.)
-        // per-image layers (round 6): the lane kernel's instances only (one wave per image); the IMGL instances of this file keep their float atomics
-        if (a.n_imgl > 0) return lane_imgl_route ? cl_launch_lane_imgl(a, grid > a.n_pad / CL_TILE ? a.n_pad / CL_TILE : grid, st) : -2;
-        if (mode == 0 && a.dX_out != nullptr) return cl_launch_mlp_chain_det(a, mode, grid, st);       // the chain's last block: the one with the epilogue
-        if (mode == 0 && (a.ev11 == nullptr || a.ev11_part != nullptr) && a.n_pad > 0 && a.n_pad % CL_TILE == 0 && grid >= 1) {
-            const int g = grid > a.n_pad / CL_TILE ? a.n_pad / CL_TILE : grid;
-            if (cl_lane_supports(a) && lane_enabled()) return cl_launch_lane(a, g, st);
-            if (cl_narrow_supports(a) && narrow_enabled()) return cl_launch_narrow(a, g, st);
-        }
-        if (a.row_map != nullptr && a.n_imgl == 0) return cl_launch_mlp_packed_det(a, mode, grid, st);      // single-pass Laue, wider than 15
-        return cl_launch_mlp_det(a, mode, grid, st);
+    if (a.n_pad % CL_TILE != 0 || a.n_pad <= 0 || grid < 1) return -1;
+    if (grid > a.n_pad / CL_TILE) grid = a.n_pad / CL_TILE;
+    switch (mlp_route(a, mode)) {
+        case CL_ROUTE_NONE: return -2;
+        case CL_ROUTE_LANE: return cl_launch_lane(a, grid, st);
+        case CL_ROUTE_LANE_IMGL: return cl_launch_lane_imgl(a, grid, st);
+        case CL_ROUTE_LANE_BLOCK: return cl_launch_lane_block(a, mode, grid, st);
+        case CL_ROUTE_NARROW: return cl_launch_narrow(a, grid, st);
+        case CL_ROUTE_MLP: break;                                               // this compilation's instances, below
+        case CL_ROUTE_MLP_PACKED: return cl_launch_mlp_packed(a, mode, grid, st);
+        case CL_ROUTE_MLP_IMGL: return cl_launch_mlp_imgl(a, mode, grid, st);
+        case CL_ROUTE_MLP_CHAIN: return cl_launch_mlp_chain(a, mode, grid, st);
+        case CL_ROUTE_MLP_DET: return cl_launch_mlp_det(a, mode, grid, st);
+        case CL_ROUTE_MLP_PACKED_DET: return cl_launch_mlp_packed_det(a, mode, grid, st);
+        case CL_ROUTE_MLP_CHAIN_DET: return cl_launch_mlp_chain_det(a, mode, grid, st);
     }
-    // the first block of a chained narrow scaler: the lane kernel's forward-only / external-gradient instances (round 6)
-    if ((a.act_out != nullptr || a.dH_ext != nullptr) && cl_lane_block_supports(a, mode) && lane_enabled() && a.n_pad > 0 && a.n_pad % CL_TILE == 0 && grid >= 1)
-        return cl_launch_lane_block(a, mode, grid > a.n_pad / CL_TILE ? a.n_pad / CL_TILE : grid, st);
-    if (a.act_out != nullptr || a.dH_ext != nullptr || a.dX_out != nullptr) return cl_launch_mlp_chain(a, mode, grid, st);
-    if (a.n_imgl > 0) {                                                        // packed layout + per-image layers
-        // the default scaler's depth and width with one or two per-image layers: the lane-per-observation kernel (elbo_lane.hip, round 5)
-        if (lane_imgl_route) return cl_launch_lane_imgl(a, grid > a.n_pad / CL_TILE ? a.n_pad / CL_TILE : grid, st);
-        return cl_launch_mlp_imgl(a, mode, grid, st);
-    }
-    if (a.row_map != nullptr && !(mode == 0 && ((cl_narrow_supports(a) && narrow_enabled()) || (cl_lane_supports(a) && lane_enabled()))))
-        return cl_launch_mlp_packed(a, mode, grid, st);                          // packed layout (single-pass Laue)
 #endif
     if (a.n_pad % CL_TILE != 0 || a.n_pad <= 0) return -1;
     // 32-bit byte offsets / buffer sizes inside the kernel: metadata image < 4 GiB, z_f < 4 GiB (shard further across GPUs otherwise)
@@ -1443,12 +1491,6 @@ int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
     const int ntiles = a.n_pad / CL_TILE;
     if (grid > ntiles) grid = ntiles;
     if (grid < 1) return -1;
-#if !CL_IMGL && !CL_CHAIN && !CL_DET
-    // hidden width <= 15 (the careless CLI default): the full step runs on the one-wave-per-SIMD kernel of elbo_narrow.hip
-    // (CARELESS_HIP_NARROW=0 keeps the eight-wave instance below: A/B measurements)
-    if (mode == 0 && cl_lane_supports(a) && lane_enabled()) return cl_launch_lane(a, grid, st);      // the default scaler's shape: lane = observation (elbo_lane.hip)
-    if (mode == 0 && cl_narrow_supports(a) && narrow_enabled()) return cl_launch_narrow(a, grid, st);
-#endif
     switch (mode) {
         case 0: return launch_mode<0>(a, grid, st);
         case 1: return launch_mode<1>(a, grid, st);
@@ -1458,35 +1500,27 @@ int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
 }
 
 #if !CL_IMGL && !CL_CHAIN && !CL_DET
-// Name of the kernel instance cl_launch_mlp(a, mode, ...) runs -- the same routing, restated once, here, next to it (bench.py and the
-// profiling scripts label their rows with it instead of guessing).  Returns the length written (snprintf semantics).
+// Name of the kernel instance cl_launch_mlp(a, mode, ...) runs, from the same route (bench.py and the profiling scripts label their rows
+// with it instead of guessing).  Returns the length written (snprintf semantics).
 int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n) {
+    const cl_route r = mlp_route(a, mode);
     const char* unit = "";
-    bool packed = false;
-    if (a.dzf_obs != nullptr && (mode == 0 || (a.act_out == nullptr && a.dH_ext == nullptr))) {
-        if (a.n_imgl > 0) return (mode == 0 && cl_lane_imgl_supports(a) && lane_enabled()) ? cl_lane_imgl_kernel_name(a, out, n) : snprintf(out, n, "(unsupported)");
-        if (mode == 0 && (a.ev11 == nullptr || a.ev11_part != nullptr) && cl_lane_supports(a) && lane_enabled()) return cl_lane_kernel_name(a, out, n);
-        if (mode == 0 && (a.ev11 == nullptr || a.ev11_part != nullptr) && cl_narrow_supports(a) && narrow_enabled()) return cl_narrow_kernel_name(a, out, n);
-        unit = (mode == 0 && a.dX_out != nullptr) ? ", chain deterministic" : ((a.row_map != nullptr && a.n_imgl == 0) ? ", packed deterministic" : ", deterministic");
-    } else if (a.act_out != nullptr || a.dH_ext != nullptr || a.dX_out != nullptr) unit = ", chain";
-    else if (a.n_imgl > 0) {
-        if (mode == 0 && cl_lane_imgl_supports(a) && lane_enabled())
-            return cl_lane_imgl_kernel_name(a, out, n);
-        unit = ", image layers";
-    } else if (a.row_map != nullptr) { unit = ", packed"; packed = true; }
-    if (a.dzf_obs == nullptr && (unit[0] == 0 || packed)) {
-        if (mode == 0 && cl_lane_supports(a) && lane_enabled()) return cl_lane_kernel_name(a, out, n);
-        if (mode == 0 && cl_narrow_supports(a) && narrow_enabled()) return cl_narrow_kernel_name(a, out, n);
+    switch (r) {
+        case CL_ROUTE_NONE: return snprintf(out, n, "(unsupported)");
+        case CL_ROUTE_LANE: return cl_lane_kernel_name(a, out, n);
+        case CL_ROUTE_LANE_IMGL: return cl_lane_imgl_kernel_name(a, out, n);
+        case CL_ROUTE_NARROW: return cl_narrow_kernel_name(a, out, n);
+        case CL_ROUTE_LANE_BLOCK:             // (still labelled with the chain instance it replaced in round 6: the lane kernel has no name for its block launches)
+        case CL_ROUTE_MLP_CHAIN: unit = ", chain"; break;
+        case CL_ROUTE_MLP: break;
+        case CL_ROUTE_MLP_PACKED: unit = ", packed"; break;
+        case CL_ROUTE_MLP_IMGL: unit = ", image layers"; break;
+        case CL_ROUTE_MLP_DET: unit = ", deterministic"; break;
+        case CL_ROUTE_MLP_PACKED_DET: unit = ", packed deterministic"; break;
+        case CL_ROUTE_MLP_CHAIN_DET: unit = ", chain deterministic"; break;
     }
-    if (a.w < 1 || a.w > 64 || a.d < 1 || a.d > 64) return snprintf(out, n, "(unsupported)");
-    const int imgl = a.n_imgl > 0 ? a.n_imgl : 0;
-    const bool w16 = a.w == 16 && imgl == 0;                     // width exactly 16: the 16-wide instance without the constant-one feature (KS = 5)
-    const bool imgl_d64 = imgl > 0 && mode != 1 && a.d > 32;     // (launch_mode: these shapes take the 32-wide instance)
-    const int WP = ((a.w <= 15 && !imgl_d64) || w16) ? 16 : (a.w <= 32 ? 32 : 64);
-    const int DP = a.d <= 8 ? 8 : (a.d <= 32 ? 32 : 64);
-    const int LM = WP == 16 ? (imgl ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16) : (WP == 32 ? (a.L + imgl <= 5 ? 5 : CL_MLP_LMAX_W32) : CL_MLP_LMAX_W64);
-    const int KS = w16 ? 5 : ((WP == 16 && mode != 1) ? (a.w <= 8 ? 2 : (a.w <= 12 ? 3 : 4)) : 4);
-    return snprintf(out, n, "elbo_mlp_kernel<%d, %d, %d, %d%s, KS=%d>", WP, DP, LM, mode, unit, KS);
+    const MlpGeom g = mlp_geom(a, mode, r == CL_ROUTE_MLP_IMGL);
+    return snprintf(out, n, "elbo_mlp_kernel<%d, %d, %d, %d%s, KS=%d>", g.WP, g.DP, g.LMAX, mode, unit, g.KS);
 }
 
 int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st) {

@@ -153,6 +153,55 @@ def chain_plan(d: int, w: int, L: int, max_layers: int, last: int = 0) -> List[L
     return blocks
 
 
+@dataclass
+class ScalerPlan:
+    wide: bool                             # layer by layer (careless_amd/wide.py): no fused launch holds the scaler
+    peel: bool                             # the first Dense layer runs in front of the training launch (csrc/elbo_peel.hip)
+    blocks: Optional[List[LayerBlock]]     # a chain of layer blocks: deeper than one launch holds
+    chain_lane: bool                       # ... whose last block runs on the lane kernel (dZ_0 out, then cl_chain_dx)
+    route: int                             # cl_mlp_route of the training launch (`ElboEngine.training_launch`); CL_ROUTE_NONE when wide
+
+
+def plan_scaler(lib, d: int, w: int, L: int, K: int = 0, laue: bool = False, two_pass: bool = False, gmax: int = 1, ev11: bool = False,
+                deterministic: bool = False) -> ScalerPlan:
+    """How `ElboEngine` runs L Dense layers of width w on d columns with K per-image layers (`gmax`: the largest harmonic group): the plan
+    chooses the launches -- peel the first layer, cut a deep scaler into blocks, go layer by layer --, the library's routes decide."""
+    NONE, LANE, NARROW, LANE_IMGL = _lib.CL_ROUTE_NONE, _lib.CL_ROUTE_LANE, _lib.CL_ROUTE_NARROW, _lib.CL_ROUTE_LANE_IMGL
+    proto = dict(d=d, w=w, L=L, S=1, refl_id=1, meta_t=1, iobs=1, sig=1, mlp=1, z_f=1, dz_f=1, partials=1, scalars=1, stop_flag=1,
+                 ev11=int(ev11), d_ev11=int(ev11))
+    det = dict(dzf_obs=1, dimg_obs=1, nll_part=1, det_slot=1, ev11_part=int(ev11)) if deterministic else {}
+    route = lambda mode, **kw: _lib.mlp_route(lib, mode, **{**proto, **kw})
+    if w > 64 or d > 64:        # a layer's activations no longer fit a wave's registers next to the weight-gradient blocks
+        return ScalerPlan(True, False, None, False, NONE)
+    max_plain = int(lib.cl_mlp_max_layers(w))
+    if K == 0 and L > max_plain:
+        # a chain of layer blocks, activations exchanged through HBM.  The LAST 20 layers (widths 11, 12: 19, the deepest twelve-wide instance
+        # without spilled registers) and the head on the lane kernel where it takes them, dZ_0 out, `cl_chain_dx` turns it into the gradient
+        # of the block's input (round 6: 24 x 10 at 4 M observations 3.13 -> 1.4 ms per step).  Laue data: the two-pass path.
+        last = 19 if w in (11, 12) else 20
+        chain_lane = not laue and route(0, d=w, L=last, dZ0_out=1) == LANE
+        blocks = chain_plan(d, w, L, min(max_plain, last) if chain_lane else max_plain, last=last if chain_lane else 0)
+        last_block = dict(d=w, L=blocks[-1].l1 - blocks[-1].l0, **({"dZ0_out": 1} if chain_lane else {"dX_out": 1}))
+        return ScalerPlan(False, False, blocks, chain_lane, route(0, **last_block, **det))
+    # Laue rows the fused kernel cannot take as harmonic groups: the two-pass path, cl_mlp_forward + cl_mlp_backward_ext on the scaler itself
+    two_pass = laue and (two_pass or gmax > GRANULE)
+    layout = dict(dict(row_map=1, tile_img=1, imgl=1, d_imgl=1, n_imgl=K, n_images=1) if K else {},
+                  **(dict(row_map=1, gmeta=1, tile_gmax=1) if laue and not two_pass else {}))
+    unpeeled, peeled = route(0, **layout), route(0, **layout, d=w, dZ0_out=1)
+    if K:       # (the lane kernel's per-image-layer instances behind the peeled layer)
+        peel = unpeeled != LANE_IMGL and peeled == LANE_IMGL
+    else:
+        # more columns than the lane / narrow kernel holds: cl_peel_forward computes the first layer's pre-activations, the fused kernel runs
+        # on them (w "metadata columns") with an identity first layer and hands back dZ_0 for cl_peel_backward (DESIGN 4.4).  (Widths 13 .. 15
+        # are no faster on the narrow kernel than on elbo_mlp.hip's 16-wide instance: profiles/r5_envelope.txt, 20 x 15 on 37 columns 2.02 vs 2.19 ms.)
+        peel = unpeeled not in (LANE, NARROW) and peeled in (LANE, NARROW) and w <= 12
+    peel = peel and bool(lib.cl_peel_supported(d, w, L))
+    train = dict(layout, d=w, dZ0_out=1) if peel else layout          # (the two-pass path has no peeled launch)
+    launches = [route(1, **layout, loc_out=1, sig_out=1), route(2, **layout, dO_ext=1)] if two_pass else [route(0, **train)]
+    if NONE in launches:
+        return ScalerPlan(True, False, None, False, NONE)
+    return ScalerPlan(False, peel, None, False, launches[-1] if two_pass else route(0, **train, **det))
+
 
 # ------------------------------------------------------------------------------------------------------------
 # the engine
@@ -238,65 +287,21 @@ class ElboEngine(WidePath):
         self.ev11 = bool(getattr(lik, "ev11", False))
         self.dw_trainable = self.double_wilson and prior.r_raw is not None
         n_dwr = int(prior.r_raw.numel()) if self.dw_trainable else 0
-        self.blocks = None
-        self.chain_lane = False                      # (a chained scaler whose last 20 layers run on the lane kernel: set with the plan below)
-        # hidden or metadata width beyond 64: the activations of a layer no longer fit a wave's registers next to the weight-gradient
-        # blocks, so the scaler runs unfused -- one fp32-MFMA GEMM launch (csrc/wide_gemm.hip) per layer and direction, activations
-        # through HBM -- around the same HIP likelihood kernels (_data_term_wide)
-        self.wide = self.w > 64 or self.d > 64
-        if imgl is not None and not self.wide and self.L + imgl.n_image_layers > self._imgl_layer_cap(imgl.n_image_layers):
-            self.wide = True        # more hidden layers (Dense + per-image) than one fused launch holds: layer by layer as well
-        max_plain = 1 if self.wide else int(self.lib.cl_mlp_max_layers(self.w))
-        if not self.wide and imgl is None and self.L > max_plain:
-            # deeper than one launch holds in registers: a chain of layer blocks, activations exchanged through HBM
-            # width <= 10 (round 6): the LAST 20 layers and the head run on the lane-per-observation kernel -- the default scaler's own, with its
-            # input = the activations of the block in front (w "metadata columns") and dZ_0 out; `cl_chain_dx` turns dZ_0 into the gradient
-            # of those activations.  24 x 10 at 4 M observations: 3.13 -> 1.4 ms per step (two blocks of the 16-wide kernel before).
-            # (widths 11, 12: the last NINETEEN layers -- the deepest twelve-wide instance without spilled registers -- and blocks of at most 19 in front)
-            self.chain_lane = (self.w <= 12 and not self.laue and max_plain == 20 and os.environ.get("CARELESS_HIP_LANE", "1") != "0" and
-                               os.environ.get("CARELESS_HIP_CHAIN_LANE", "1") != "0" and
-                               (self.w <= 10 or os.environ.get("CARELESS_HIP_LANE_W12", "1") != "0"))
-            last = (20 if self.w <= 10 else 19) if self.chain_lane else 0
-            self.blocks = chain_plan(self.d, self.w, self.L, max_plain if last != 19 else 19, last=last)
-        # The careless default scaler (20 layers, hidden width <= 10) on more metadata columns than its lane-per-observation kernel holds
-        # (31; four positionally encoded keys give 37): the first Dense layer is "peeled" -- its pre-activations come from
-        # cl_peel_forward, the fused kernel runs the same scaler with an identity first layer on them (w "metadata columns": the shape it
-        # is fastest at) and hands back dZ_0, cl_peel_backward takes W_0's and b_0's gradient (csrc/elbo_peel.hip).  Training
-        # launches only: forward-only / external-gradient launches (predictions, two-pass Laue) keep the original scaler.
-        # The same for every other scaler of hidden width <= 15 on more than 15 columns: elbo_narrow.hip holds <= 15 of them.
-        lane_shape = self.L == 20 and self.w <= 10 and os.environ.get("CARELESS_HIP_LANE", "1") != "0"
-        # (widths 13 .. 15 -- the narrow kernel's four-step instance, ~90 spilled registers -- are no faster there than on the 16-wide
-        #  instance of elbo_mlp.hip, which takes up to 64 columns itself: profiles/r5_envelope.txt, 20 x 15 on 37 columns 2.02 against 2.19 ms)
-        self.peel = (not self.wide and self.blocks is None and imgl is None and self.w <= 12 and self.L <= 20 and
-                     self.d > (31 if lane_shape else 15) and self.d > self.w and bool(self.lib.cl_peel_supported(self.d, self.w, self.L)) and
-                     os.environ.get("CARELESS_HIP_NARROW", "1") != "0")
-        # ... and (round 5) the default scaler with one or two per-image layers on more than the 15 columns its lane instances hold
-        # (`--image-layers 2 --positional-encoding-keys X,Y`: 21): the peeled layer's w pre-activations are the lane kernel's "metadata"
-        # (round 6: Laue data too -- the per-image-layer instances are packed-layout kernels either way, and their dZ_0-storing form is back)
-        # (... and at 2 .. 19 Dense layers of width 5 .. 10: the per-depth units carry the per-image-layer instances as well)
-        lane_imgl_shape = lane_shape or (2 <= self.L < 20 and 5 <= self.w <= 10 and os.environ.get("CARELESS_HIP_LANE", "1") != "0" and
-                                         os.environ.get("CARELESS_HIP_LANE_DEPTHS", "1") != "0")
-        lane_imgl_max = 2 if self.L == 19 else 3          # (csrc/elbo_lane.hip: CL_LANE_IMGL_MAX_NL, CL_LANE_IMGL3_DEPTH_MAX)
-        if (not self.wide and imgl is not None and lane_imgl_shape and imgl.n_image_layers <= lane_imgl_max and self.d > 15 and self.d > self.w and
-                bool(self.lib.cl_peel_supported(self.d, self.w, self.L))):
-            self.peel = True
-        if imgl is not None:
-            imgl.build(self.d)
-            max_l = self._imgl_layer_cap(imgl.n_image_layers)
-            if not self.wide and self.L + imgl.n_image_layers > max_l:
-                raise NotImplementedError(f"{self.L} Dense + {imgl.n_image_layers} image layers of width {self.w}: the HIP engine "
-                                          f"supports {max_l} hidden layers in total at this width")
         # Deterministic mode (`model.deterministic = True` or CARELESS_HIP_DETERMINISTIC=1): no float atomics anywhere in the step --
         # per-observation stores + fixed-order sums (cl_det_reduce) -- so two runs give bit-identical gradients and parameters
         self.deterministic = bool(getattr(model, "deterministic", False)) or os.environ.get("CARELESS_HIP_DETERMINISTIC", "0") == "1"
         two_pass = self.laue and bool(getattr(model, "laue_two_pass", False))
+        gmax = int(np.bincount(_np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64)).max()) if self.laue else 1
+        self.plan = plan_scaler(self.lib, self.d, self.w, self.L, imgl.n_image_layers if imgl is not None else 0, laue=self.laue,
+                                two_pass=two_pass, gmax=gmax, ev11=self.ev11, deterministic=self.deterministic)
+        self.wide, self.peel, self.blocks, self.chain_lane = self.plan.wide, self.plan.peel, self.plan.blocks, self.plan.chain_lane
+        if imgl is not None:
+            imgl.build(self.d)
         # (wide scalers: monochromatic rows only -- they are their own slots and one kernel holds every float atomic of the path --, with a
         #  sample count that divides 64, so that a row's samples sit inside one wave)
         wide_det_ok = self.wide and not self.laue and 64 % int(model.mc_sample_size) == 0
-        # (per-image layers, round 6: where the step runs the lane kernel's per-image-layer instances -- one or two of them on 2 .. 20 Dense
-        #  layers of width <= 10, up to 15 columns or behind the peeled first layer -- one wave holds all tiles of an image in this mode)
-        imgl_det_ok = (imgl is not None and not self.wide and imgl.n_image_layers <= lane_imgl_max and lane_imgl_shape and (self.d <= 15 or self.peel) and
-                       os.environ.get("CARELESS_HIP_LANE", "1") != "0")
+        # (per-image layers: where the training launch has a route with the deterministic stores -- the lane kernel's instances, one wave per image)
+        imgl_det_ok = self.plan.route != _lib.CL_ROUTE_NONE
         if self.deterministic and (two_pass or (self.wide and not wide_det_ok) or (imgl is not None and not imgl_det_ok) or
                                    (self.blocks is not None and self.laue) or (self.double_wilson and prior.r_raw is not None)):
             raise NotImplementedError("deterministic mode covers monochromatic and single-pass Laue data, the Wilson and the double-Wilson prior "
@@ -491,18 +496,6 @@ class ElboEngine(WidePath):
         for k, p in enumerate(pieces):
             p.det_parent, p.det_index = obs, k
 
-    def _imgl_layer_cap(self, K: int) -> int:
-        """Hidden layers (Dense + per-image) one fused training launch holds at this width.  Width <= 15 on more than 32 metadata columns
-        takes the 32-wide instance (`cl_launch_mlp`: the 16-wide <16, 64, 24, image layers> instance is withdrawn -- csrc/elbo_mlp.hip,
-        launch_mode) unless the step runs the lane kernel's per-image-layer instances behind a peeled first layer."""
-        lane = os.environ.get("CARELESS_HIP_LANE", "1") != "0"
-        depths = lane and os.environ.get("CARELESS_HIP_LANE_DEPTHS", "1") != "0"
-        lane_route = ((self.L == 20 and self.w <= 10 and K <= 3 and lane) or
-                      (2 <= self.L <= 19 and 5 <= self.w <= 10 and K <= (2 if self.L == 19 else 3) and depths))
-        if self.w <= 15 and self.d > 32 and not lane_route:
-            return int(self.lib.cl_mlp_max_layers_imgl(32))
-        return int(self.lib.cl_mlp_max_layers_imgl(self.w))
-
     def _max_images(self):
         if self.img is not None:
             return self.img.max_images
@@ -651,6 +644,12 @@ class ElboEngine(WidePath):
             sq = 65 <= self.w <= 128 and self.d <= 128          # (square layers of the streaming kernel's widths: cl_wide_head_bwd_supported's range)
             return (("wide_sq_kernel + wide_gemm_kernel" if sq else "wide_gemm_kernel (+ wide_stream_kernel)") +
                     (" (slot likelihood: deterministic stores)" if self.deterministic else ""))
+        ma, mode = self.training_launch(mode)
+        buf = C.create_string_buffer(128)
+        check(min(0, self.lib.cl_mlp_kernel_name(C.byref(ma), mode, buf, 128)), "cl_mlp_kernel_name")
+        return buf.value.decode()
+
+    def training_launch(self, mode: int = 0):         # (arguments, mode) of the launch kernel_name names; plan.route is its cl_mlp_route
         obs = self.obs.children[0] if isinstance(self.obs, ObsChunks) else self.obs
         ma = self._mlp_args(0, None, None, obs)
         if self.blocks is not None:
@@ -664,9 +663,7 @@ class ElboEngine(WidePath):
             ma.dO_ext = ptr(obs.laue_dO)
         elif self.peel and mode == 0:
             ma = self._peel_args(ma, obs)
-        buf = C.create_string_buffer(128)
-        check(min(0, self.lib.cl_mlp_kernel_name(C.byref(ma), mode, buf, 128)), "cl_mlp_kernel_name")
-        return buf.value.decode()
+        return ma, mode
 
     def _w_ll(self, obs: ObsData) -> float:
         """Weight of one log-likelihood term: sum / S, or with `kl_weight` the mean over the S x N terms of the observation set
@@ -1412,8 +1409,11 @@ def scaler_forward(mlp, metadata, imgl=None, image_id=None):
     mlp.build(d)
     if mlp.flat.device != dev:
         mlp.flat = mlp.flat.to(dev)
-    too_deep = imgl is not None and mlp.n_layers + imgl.n_image_layers > int(lib.cl_mlp_max_layers_imgl(mlp.width))
-    if mlp.width > 64 or d > 64 or too_deep:
+    # no route for the forward-only launch on the whole scaler: a chain of layer blocks (Dense layers only) or layer by layer
+    fwd = _lib.mlp_route(lib, 1, d=d, w=mlp.width, L=mlp.n_layers, S=1, meta_t=1, mlp=1, loc_out=1, sig_out=1, **(
+        dict(row_map=1, tile_img=1, imgl=1, n_imgl=imgl.n_image_layers, n_images=imgl.max_images) if imgl is not None else {}))
+    chain = fwd == _lib.CL_ROUTE_NONE and imgl is None and mlp.width <= 64 and d <= 64
+    if fwd == _lib.CL_ROUTE_NONE and not chain:
         # wider (or, with per-image layers, deeper) than the fused kernel holds: the layer-by-layer GEMM kernels (see
         # ElboEngine._data_term_wide), forward only; per-image layers run grouped on the rows sorted by image
         w, L, st = mlp.width, mlp.n_layers, _stream()
@@ -1511,10 +1511,9 @@ def scaler_forward(mlp, metadata, imgl=None, image_id=None):
         a.imgl, a.n_imgl, a.n_images = ptr(imgl.flat), imgl.n_image_layers, imgl.max_images
         a.tile_img, a.row_map = ptr(keep[0]), ptr(keep[1])
     grid = min(max(1, int(lib.cl_mlp_default_grid())), n_pad // TILE)
-    max_plain = int(lib.cl_mlp_max_layers(mlp.width))
-    if imgl is None and mlp.n_layers > max_plain:
+    if chain:
         # deeper than one launch: chain of layer blocks (see ElboEngine._data_term_chain)
-        blocks = chain_plan(d, mlp.width, mlp.n_layers, max_plain)
+        blocks = chain_plan(d, mlp.width, mlp.n_layers, int(lib.cl_mlp_max_layers(mlp.width)))
         rows = int(lib.cl_mlp_meta_rows(mlp.width))
         x = meta_t
         for b in blocks:

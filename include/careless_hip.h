@@ -212,16 +212,36 @@ enum { CL_BIJ_EXP_ = 0, CL_BIJ_SOFTPLUS_ = 1 };
 
 int cl_mlp_default_grid(void);                       /* workgroups of a persistent launch = CUs of the current device */
 size_t cl_mlp_param_count(int d, int w, int L);      /* P */
-int cl_mlp_max_layers_imgl(int w);                   /* hidden layers (Dense + per-image) one launch holds with n_imgl > 0         */
-int cl_mlp_max_layers(int w);                        /* Dense layers ONE launch holds at hidden width w (0: width unsupported); deeper
-                                                      * scalers are chained (act_out / dH_ext / dX_out)                          */
+int cl_mlp_max_layers(int w);                        /* Dense layers ONE Dense-only launch holds at hidden width w (0: width unsupported);
+                                                      * deeper scalers are chained (act_out / dH_ext / dX_out).  With per-image layers
+                                                      * ask cl_mlp_route: the limit then depends on the metadata width and the mode   */
 int cl_mlp_meta_rows(int d);                         /* rows of meta_t: d rounded up to a multiple of 4 (one MFMA k-step) */
 int cl_elbo_mono_fwd_bwd(const cl_mlp_args* args, int grid, void* stream);
 int cl_mlp_forward(const cl_mlp_args* args, int grid, void* stream);
 int cl_mlp_backward_ext(const cl_mlp_args* args, int grid, void* stream);
-/* Diagnostics: the name of the kernel instance the three calls above run for these arguments (mode 0 = cl_elbo_mono_fwd_bwd,
- * 1 = cl_mlp_forward, 2 = cl_mlp_backward_ext), e.g. "elbo_lane_kernel<10, 0, false>": what a rocprofv3 kernel trace lists.
- * Writes at most n bytes (NUL-terminated), returns the length of the name or < 0 for bad arguments.  No reference counterpart. */
+/* Which launcher the three calls above hand these arguments to (mode 0 = cl_elbo_mono_fwd_bwd, 1 = cl_mlp_forward,
+ * 2 = cl_mlp_backward_ext): the library's one routing decision.  It depends on the shape, the optional buffers set and the mode
+ * only (pointer fields count as set / NULL, n_pad and the grid are not looked at), and on the A/B switches CARELESS_HIP_LANE,
+ * _NARROW, _LANE_W12, _LANE_DEPTHS and _LANE_BLOCKS.  CL_ROUTE_NONE: no kernel takes the launch -- the call returns -2.
+ * Returns < 0 for bad arguments.  Needs no device. */
+typedef enum cl_route {
+    CL_ROUTE_NONE = 0,
+    CL_ROUTE_LANE,               /* elbo_lane.hip: lane = observation, full step                               */
+    CL_ROUTE_LANE_IMGL,          /* ... with per-image layers                                                  */
+    CL_ROUTE_LANE_BLOCK,         /* ... a head-less layer block's forward / backward launch                     */
+    CL_ROUTE_NARROW,             /* elbo_narrow.hip                                                            */
+    CL_ROUTE_MLP,                /* elbo_mlp.hip: plain layout                                                 */
+    CL_ROUTE_MLP_PACKED,         /* ... packed layout (single-pass Laue)                                       */
+    CL_ROUTE_MLP_IMGL,           /* ... per-image layers                                                       */
+    CL_ROUTE_MLP_CHAIN,          /* ... a block of a layer-block chain                                         */
+    CL_ROUTE_MLP_DET,            /* ... deterministic mode: plain layout                                       */
+    CL_ROUTE_MLP_PACKED_DET,     /* ... deterministic mode: packed layout                                      */
+    CL_ROUTE_MLP_CHAIN_DET       /* ... deterministic mode: the last block of a chain                          */
+} cl_route;
+int cl_mlp_route(const cl_mlp_args* args, int mode);
+/* Diagnostics: the name of the kernel instance the launch cl_mlp_route chose runs, e.g. "elbo_lane_kernel<10, 0, false>": what a
+ * rocprofv3 kernel trace lists; "(unsupported)" for CL_ROUTE_NONE.  Writes at most n bytes (NUL-terminated), returns the length of
+ * the name or < 0 for bad arguments.  No reference counterpart. */
 int cl_mlp_kernel_name(const cl_mlp_args* args, int mode, char* out, size_t n);
 /* grad_mlp[P] += sum over the `nparts` workgroup partials, in index order (deterministic) */
 int cl_reduce_partials(const float* partials, int nparts, int P, float* grad_mlp, const int* stop_flag, void* stream);

@@ -165,6 +165,9 @@ CASES = {
     "laue_two_pass_2x32_S3": dict(N=400, R=40, L=2, w=32, S=3, laue=True, two_pass=True),
     "laue_two_pass_ev11_studentt_S5": dict(N=500, R=40, L=2, w=32, S=5, laue=True, ev11=True, likelihood="studentt", dof=6.0, two_pass=True),
     "laue_two_pass_image_layers1": dict(N=600, R=60, L=2, w=32, S=3, laue=True, n_images=4, image_layers=1, two_pass=True),
+    # (two-pass Laue, per-image layers, more than 32 columns: cl_mlp_backward_ext has no route for 20 + 2 layers there -- layer by layer)
+    "laue_two_pass_image_layers2_20x10_d36": dict(N=600, R=40, L=20, w=10, S=2, laue=True, n_images=5, image_layers=2, extra_meta=30, two_pass=True,
+                                                  perturb=0.02),
     "laue_two_pass_narrow_12x10": dict(N=600, R=40, L=12, w=10, S=2, laue=True, two_pass=True, perturb=0.02),
     "laue_single_pass_narrow_20x10": dict(N=900, R=40, L=20, w=10, S=3, laue=True, perturb=0.02, grid=2),
     "laue_ev11_studentt_S5": dict(N=500, R=40, L=2, w=32, S=5, laue=True, ev11=True, likelihood="studentt", dof=6.0),
@@ -306,6 +309,8 @@ def _assert_grads(g_hip, grads, prob, name=""):
 @pytest.mark.parametrize("name", list(CASES))
 def test_loss_and_gradients_match_oracle(name):
     out, grads, ipred, terms, g_hip, eng, prob = _run_case(CASES[name])
+    if name == "laue_two_pass_image_layers2_20x10_d36":
+        assert eng.d > 32
     assert abs(terms["nll"] - float(out["nll"])) <= RTOL_LOSS * abs(float(out["nll"])), (terms, float(out["nll"]))
     assert abs(terms["kl"] - float(out["kl"])) <= RTOL_LOSS * max(abs(float(out["kl"])), 1.0), (terms, float(out["kl"]))
     assert abs(terms["loss"] - float(out["loss"])) <= RTOL_LOSS * abs(float(out["loss"]))

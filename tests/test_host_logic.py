@@ -277,8 +277,13 @@ def test_kernel_name_follows_the_librarys_routing():
     CLI-default scaler runs lane-per-observation up to 31 metadata columns and any number of MC samples, other depths / widths 11-15
     on the narrow kernel, everything else on the 16- / 32- / 64-wide fused instances.  Host function: no GPU needed."""
     import ctypes as C
+    import itertools
     from careless_amd import _lib
     lib = _lib.get_lib()
+    # the family of the name of every route ("elbo_mlp_kernel<" for the others; the lane kernel's layer-block launches keep the label of
+    # the chain instance they replaced)
+    family = {_lib.CL_ROUTE_NONE: "(unsupported)", _lib.CL_ROUTE_LANE: "elbo_lane_kernel<", _lib.CL_ROUTE_LANE_IMGL: "elbo_lane_kernel<",
+              _lib.CL_ROUTE_NARROW: "elbo_narrow_kernel<"}
 
     def name(mode=0, **kw):
         a = _lib.MlpArgs()
@@ -287,7 +292,12 @@ def test_kernel_name_follows_the_librarys_routing():
         buf = C.create_string_buffer(128)
         n = lib.cl_mlp_kernel_name(C.byref(a), mode, buf, 128)
         assert n == len(buf.value)
+        r = _lib.mlp_route(lib, mode, **kw)
+        assert buf.value.decode().startswith(family.get(r, "elbo_mlp_kernel<")), (r, buf.value)
         return buf.value.decode()
+
+    def route(mode=0, **kw):
+        return _lib.mlp_route(lib, mode, **kw)
 
     # (last argument: the instance with / without the optional inputs and outputs -- injected noise, ipred_out, Ev11)
     assert name(d=5, w=10, L=20, S=1) == "elbo_lane_kernel<10, 8, false, false>"
@@ -332,6 +342,69 @@ def test_kernel_name_follows_the_librarys_routing():
     assert name(d=21, w=64, L=5, S=8, mode=1) == "elbo_mlp_kernel<64, 32, 5, 1, KS=4>"
     assert name(d=5, w=10, L=20, S=1, act_out=1, mode=1).startswith("elbo_mlp_kernel<16, 8, 20, 1, chain")
     assert lib.cl_mlp_kernel_name(None, 0, C.create_string_buffer(8), 8) < 0
+    # the route beside the name (cl_mlp_route: the launcher cl_launch_mlp hands the launch to)
+    assert route(d=5, w=10, L=20, S=1) == route(d=31, w=4, L=20, S=40, row_map=1) == route(d=6, w=9, L=19, S=1, row_map=1) == _lib.CL_ROUTE_LANE
+    assert route(d=5, w=13, L=12, S=8) == route(d=5, w=4, L=12, S=1) == route(d=5, w=10, L=1, S=1) == _lib.CL_ROUTE_NARROW
+    assert route(d=32, w=10, L=20, S=1) == route(d=21, w=64, L=5, S=8) == route(d=21, w=64, L=5, S=8, mode=1) == _lib.CL_ROUTE_MLP
+    assert route(d=5, w=10, L=20, S=2, **imgl) == route(d=5, w=10, L=7, S=2, dzf_obs=1, **imgl) == _lib.CL_ROUTE_LANE_IMGL
+    assert route(d=5, w=4, L=10, S=2, **imgl) == route(d=36, w=11, L=2, S=2, **imgl) == _lib.CL_ROUTE_MLP_IMGL
+    assert route(d=5, w=10, L=20, S=1, act_out=1, mode=1) == _lib.CL_ROUTE_LANE_BLOCK
+    assert route(d=5, w=14, L=20, S=1, act_out=1, mode=1) == route(d=14, w=14, L=4, S=1, dH_ext=1, dX_out=1, mode=2) == _lib.CL_ROUTE_MLP_CHAIN
+    assert route(d=40, w=20, L=10, S=1, row_map=1) == _lib.CL_ROUTE_MLP_PACKED
+    assert route(d=40, w=20, L=10, S=1, dzf_obs=1) == _lib.CL_ROUTE_MLP_DET
+    assert route(d=40, w=20, L=10, S=1, dzf_obs=1, row_map=1) == _lib.CL_ROUTE_MLP_PACKED_DET
+    assert route(d=10, w=10, L=10, S=1, dzf_obs=1, dX_out=1) == _lib.CL_ROUTE_MLP_CHAIN_DET
+    assert route(d=5, w=32, L=2, S=2, dzf_obs=1, **imgl) == _lib.CL_ROUTE_NONE
+    assert lib.cl_mlp_route(None, 0) < 0 and route(d=5, w=10, L=20, S=1, mode=3) < 0
+    # no route -- "(unsupported)" -- where the call returns -2: wider than 64, deeper than the instance, dZ_0 out off the default scaler's kernels
+    assert name(d=5, w=65, L=2, S=1) == name(d=5, w=10, L=25, S=1) == name(d=36, w=10, L=20, S=2, mode=2, **imgl) == "(unsupported)"
+    assert name(d=5, w=13, L=30, S=1, dZ0_out=1) == name(d=21, w=64, L=5, S=8, dZ0_out=1) == "(unsupported)"
+    # ... and over a grid of shapes, optional buffers and modes: the name's family follows the route, "(unsupported)" iff no route
+    flags = ("row_map", "gmeta", "dZ0_out", "act_out", "dH_ext", "dX_out", "dO_ext", "dzf_obs", "ev11")
+    seen = set()
+    for L, w, d, K, mode, f in itertools.product((1, 2, 12, 19, 20, 24), (4, 10, 12, 15, 16, 32, 64, 65), (5, 12, 21, 36, 65), (0, 2, 3), (0, 1, 2),
+                                                (None,) + flags):
+        kw = dict(dict(imgl, n_imgl=K) if K else {}, d=d, w=w, L=L, S=2)
+        if f:
+            kw[f] = 1
+        name(mode, **kw)
+        seen.add(route(mode, **kw))
+    assert seen == set(range(_lib.CL_ROUTE_MLP_CHAIN_DET + 1)) - {_lib.CL_ROUTE_MLP_PACKED_DET, _lib.CL_ROUTE_MLP_CHAIN_DET}   # (two flags each: above)
+
+
+def test_scaler_plan_follows_the_routing_tables():
+    """`plan_scaler` (host side, no GPU): the peel / chain / layer-by-layer plan of every row of tests/test_routing.py's tables, from the
+    library's routes alone -- and the shapes where a launch of the plan would have no route."""
+    import subprocess
+    import sys
+    from careless_amd.engine import plan_scaler
+    from tests.test_routing import IMGL_TABLE, TABLE
+    lib = _lib.get_lib()
+    for L, w, d, frag, peel, blocks, wide in TABLE:
+        p = plan_scaler(lib, d, w, L)
+        assert (p.peel, None if p.blocks is None else len(p.blocks), p.wide) == (peel, blocks, wide), (L, w, d, p)
+        assert p.route == (_lib.CL_ROUTE_NONE if wide else (_lib.CL_ROUTE_LANE if frag.startswith("elbo_lane") else p.route))
+    for L, w, d, K, laue, frag, peel in IMGL_TABLE:
+        if laue:            # (the Laue generator's own metadata columns)
+            d = BaseModel.get_metadata(reference_inputs(util.make_problem(N=600, R=30, L=L, w=w, S=1, laue=True, image_layers=K, n_images=5)[0])).shape[1]
+        p = plan_scaler(lib, d, w, L, K, laue=laue)
+        assert (p.peel, p.blocks, p.wide) == (peel, None, frag.startswith("wide")), (L, w, d, K, p)
+        assert (p.route == _lib.CL_ROUTE_LANE_IMGL) == frag.startswith("elbo_lane")
+    # two-pass Laue, `--image-layers 2`, 20 x 10 on more than 32 columns: cl_mlp_backward_ext has no route there (the 32-wide instance holds
+    # 10 layers) -- layer by layer; single pass, the same shape runs the lane kernel behind the peeled layer
+    assert plan_scaler(lib, 36, 10, 20, 2, laue=True, two_pass=True).wide
+    assert plan_scaler(lib, 36, 10, 20, 2, laue=True, gmax=17).wide
+    p = plan_scaler(lib, 36, 10, 20, 2, laue=True)
+    assert p.peel and not p.wide and p.route == _lib.CL_ROUTE_LANE_IMGL
+    # 24 x 12 with the per-depth lane instances switched off: the last block is no lane launch, the chain stays on the 16-wide kernel
+    # (a subprocess: the library reads its switches once per process)
+    code = ("from careless_amd import _lib; from careless_amd.engine import plan_scaler; "
+            "p = plan_scaler(_lib.get_lib(), 5, 12, 24); print(p.chain_lane, [b.l1 - b.l0 for b in p.blocks])")
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CARELESS_HIP_LANE_DEPTHS="0"), cwd=ROOT, capture_output=True,
+                         text=True, check=True).stdout.split()
+    assert out == ["False", "[12,", "12]"]
+    p = plan_scaler(lib, 5, 12, 24)
+    assert p.chain_lane and [b.l1 - b.l0 for b in p.blocks] == [5, 19]
 
 
 def test_wide_path_envelope_queries():

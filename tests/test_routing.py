@@ -47,8 +47,16 @@ def test_training_step_runs_on_the_kernel_the_design_names(L, w, d, frag, peel, 
     assert frag in name, name
     assert bool(eng.peel) == peel and eng.wide == wide
     assert (eng.blocks is None) == (blocks is None) and (blocks is None or len(eng.blocks) == blocks)
+    _assert_planned_route(eng)
     eng.alloc_history(1)
     eng.train_step(0)                                           # ... and the step it names runs
+
+
+def _assert_planned_route(eng):
+    """the plan's route is the library's route of the engine's real training launch"""
+    import ctypes as C
+    ma, mode = eng.training_launch()
+    assert eng.plan.route == eng.lib.cl_mlp_route(C.byref(ma), mode)
 
 
 #              L   w   d   K  laue   kernel-name fragment                                                  peel
@@ -86,6 +94,7 @@ def test_per_image_layers_run_on_the_kernel_the_design_names(L, w, d, K, laue, f
     name = eng.kernel_name()
     assert frag in name, name
     assert bool(eng.peel) == peel
+    _assert_planned_route(eng)
     eng.alloc_history(1)
     eng.train_step(0)
 
