@@ -18,7 +18,8 @@ LIB = os.path.join(LIBDIR, "libcareless_hip.so")
 # The fused scaler kernels' LeakyReLU is fmaxf(x, leak x); with NaNs honoured hipcc puts a canonicalising v_max_f32 x, x in front of
 # every one of them, without it emits the one v_max_f32 -- an instruction it KNOWS, so that its hazard recognizer pads the two wait
 # states gfx950 wants in front of an MFMA that reads the result (until round 6 the bare instruction was inline assembly, which it does
-# not see: NOTEBOOK R6.1).  Nothing in these units tests for NaN (the non-finite stop is taken on the gradient norm, in elbo_elem.hip).
+# not see: NOTEBOOK R6.1).  The units must still CARRY a NaN from a poisoned observation to the gradient entries it touches (the non-finite
+# stop is taken on the gradient norm, in elbo_elem.hip): tests/test_nonfinite.py holds every route to the oracle's non-finite mask.
 NNAN = ["-fno-honor-nans"]
 # (source, object stem, extra flags): elbo_mlp.hip is compiled twice -- Dense-only scalers and the per-image-layer variant
 UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=0"] + NNAN), ("elbo_mlp.hip", "elbo_mlp_imgl", ["-DCL_IMGL=1"] + NNAN),

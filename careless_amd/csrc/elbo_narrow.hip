@@ -341,19 +341,20 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
             }
         }
         NSTAMP(1);
-        // Dense(2) head: group g's two outputs land in rows 4g, 4g+1; two accumulator chains (even / odd groups)
+        // Dense(2) head: group g's two outputs land in rows 4g, 4g+1 -- the rows of lane quarter q == g; one accumulator chain per group.
+        // The other rows of group g's product are (zero weight) x (activation): exact zeros UNLESS an activation is non-finite, and column
+        // j of those rows belongs to observation 16 g' + j of another group.  So every quarter SELECTS its own group's product (adding
+        // the groups up carried the NaN of one poisoned observation into its partner's (loc, sigma): tests/test_nonfinite.py).
         f32x4 acc_h = *reinterpret_cast<const f32x4*>(sB + NL * 16 + 4 * q);
-        f32x4 acc_h2 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const f32x4 wh = *reinterpret_cast<const f32x4*>(wrow + (NL + g) * 16 * NPW);
+            f32x4 acc_g = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-            for (int t = 0; t < KS; ++t) {
-                if (g & 1) acc_h2 = mfma4(wh[t], top[g][t], acc_h2);
-                else acc_h = mfma4(wh[t], top[g][t], acc_h);
-            }
+            for (int t = 0; t < KS; ++t) acc_g = mfma4(wh[t], top[g][t], acc_g);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc_h[i] += (q == g) ? acc_g[i] : 0.0f;
         }
-        acc_h += acc_h2;
 
         // ================= epilogue: lane = observation; sample, predict, likelihood, dL/d(loc, raw) ==========================
         cl_args_p E = kernargs_again();              // the epilogue's and the prefetch's arguments, loaded here (see kernargs_again)
