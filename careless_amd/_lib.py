@@ -160,6 +160,7 @@ EXPORTS = {
     "cl_mlp_backward_ext": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
     "cl_mlp_route": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
     "cl_mlp_kernel_name": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_char_p, C.c_size_t]),
+    "cl_mlp_check": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_int]),
     "cl_wide_ld": (C.c_int, [C.c_int]),
     "cl_wide_dense_forward": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_longlong, C.c_int, C.c_int, C.c_float, C.c_int, _vp, C.c_int, _vp, _vp]),
     "cl_wide_dense_forward_head": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_longlong, C.c_int, C.c_int, C.c_float, _vp, C.c_int, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp]),

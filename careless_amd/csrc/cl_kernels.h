@@ -1,35 +1,48 @@
-// Internal launch interface between the C-ABI layer (cl_api.hip) and the kernels.  The argument structs are the
-// public ones of include/careless_hip.h.
+// Internal launch interface between the C-ABI layer (cl_api.hip) and the kernels (the argument structs are the public ones of
+// include/careless_hip.h), the one launch helper of the kernels with dynamic LDS, and the device helpers the kernel files share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <cstdio>
 #include "../../include/careless_hip.h"
 
+// What a lane / narrow launch path hands down to the leaf that picks the kernel instance.  With a name sink the leaf prints the
+// instance's own template parameters there and returns the length (cl_mlp_kernel_name: the name comes from the code that selects
+// the instance) without touching the runtime; without one it launches on `grid` workgroups of stream `st`.
+struct cl_launch_ctx {
+    int grid;
+    hipStream_t st;
+    char* name = nullptr;
+    size_t name_n = 0;
+};
+
+// A scaler launch: route, argument check, grid clamp, dispatch (elbo_mlp.hip).  The launchers below it check nothing.
 int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st);
-int cl_launch_mlp_imgl(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // elbo_mlp.hip compiled with -DCL_IMGL=1
-int cl_launch_mlp_packed(const cl_mlp_args& a, int mode, int grid, hipStream_t st); // elbo_mlp.hip compiled with -DCL_IMGL=2
-int cl_launch_mlp_chain(const cl_mlp_args& a, int mode, int grid, hipStream_t st);  // elbo_mlp.hip compiled with -DCL_CHAIN=1
-int cl_launch_mlp_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // elbo_mlp.hip compiled with -DCL_DET=1 (no atomics)
-int cl_launch_mlp_packed_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // ... with -DCL_IMGL=2 -DCL_DET=1 (single-pass Laue, no atomics)
-int cl_launch_mlp_chain_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // ... with -DCL_CHAIN=1 -DCL_DET=1 (a chain's last block, no atomics)
+cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // the launcher cl_launch_mlp hands a launch to
+int mlp_check(const cl_mlp_args& a, int mode, int grid, cl_route r);                 // 0, or the negative code of the launch (every argument check of every route)
+int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // the name of the instance the launch runs
+// the eight compilations of elbo_mlp.hip (build.py), one launcher each
+int cl_launch_mlp_plain(const cl_mlp_args& a, int mode, int grid, hipStream_t st);  // -DCL_IMGL=0
+int cl_launch_mlp_imgl(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // -DCL_IMGL=1: per-image layers
+int cl_launch_mlp_packed(const cl_mlp_args& a, int mode, int grid, hipStream_t st); // -DCL_IMGL=2: packed layout (single-pass Laue)
+int cl_launch_mlp_chain(const cl_mlp_args& a, int mode, int grid, hipStream_t st);  // -DCL_CHAIN=1: a block of a layer-block chain
+int cl_launch_mlp_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // -DCL_DET=1: deterministic mode (no atomics), plain layout, full step
+int cl_launch_mlp_packed_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // -DCL_IMGL=2 -DCL_DET=1
+int cl_launch_mlp_chain_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // -DCL_CHAIN=1 -DCL_DET=1: a chain's LAST block (the forward-only and backward-only launches have no atomics and keep the chain unit)
 int cl_launch_det_reduce(const cl_det_args& a, hipStream_t st);                     // elbo_elem.hip: fixed-order sums of the deterministic mode
-cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // elbo_mlp.hip: the launcher cl_launch_mlp hands a launch to
-int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // ... and the name of the instance it runs
 // The *_supports functions describe the shapes a kernel family holds; the A/B switches that keep shapes off a family are read by mlp_route only.
 int cl_narrow_supports(const cl_mlp_args& a);                                       // elbo_narrow.hip: width <= 15, metadata <= 15, plain layout
-int cl_launch_narrow(const cl_mlp_args& a, int grid, hipStream_t st);               // ... the full ELBO step on that kernel
+int cl_launch_narrow(const cl_mlp_args& a, const cl_launch_ctx& c);                 // ... the full ELBO step on that kernel
 int cl_lane_supports(const cl_mlp_args& a);                                         // elbo_lane.hip: lane = observation; 20 layers, width <= 10, metadata <= 31 columns
 #ifndef CL_LANE_WMAX
 #define CL_LANE_WMAX 10                                                             // ... widest instance of every form (11, 12: twelve-wide register instances)
 #endif
-int cl_lane_kernel_name(const cl_mlp_args& a, char* out, size_t n);
-int cl_narrow_kernel_name(const cl_mlp_args& a, char* out, size_t n);
 int cl_lane_imgl_supports(const cl_mlp_args& a);                                    // ... with one or two per-image layers on top (round 5)
-int cl_launch_lane_imgl(const cl_mlp_args& a, int grid, hipStream_t st);
-int cl_lane_imgl_kernel_name(const cl_mlp_args& a, char* out, size_t n);
+int cl_launch_lane_imgl(const cl_mlp_args& a, const cl_launch_ctx& c);
 int cl_lane_block_supports(const cl_mlp_args& a, int mode);                          // ... a head-less layer block's forward / backward launch (round 6)
-int cl_launch_lane_block(const cl_mlp_args& a, int mode, int grid, hipStream_t st);
-int cl_launch_lane(const cl_mlp_args& a, int grid, hipStream_t st);                 // ... the full ELBO step on that kernel
+int cl_launch_lane_block(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
+int cl_launch_lane(const cl_mlp_args& a, const cl_launch_ctx& c);                   // ... the full ELBO step on that kernel
 int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st);
 int cl_launch_tn_forward(const cl_tn_args& a, hipStream_t st);
 int cl_launch_tn_backward(const cl_tn_args& a, hipStream_t st);
@@ -52,6 +65,108 @@ int cl_launch_laue_likelihood(const cl_laue_args& a, hipStream_t st);
 int cl_launch_laue_backward(const cl_laue_args& a, hipStream_t st);
 int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st);
 int cl_launch_frozen_rows(const cl_frozen_args& a, hipStream_t st);      // elbo_frozen.hip (round 6)
+
+// Launch of a kernel instance with `sm` bytes of dynamic LDS: -3 above the 160 KB of a gfx950 workgroup, else 0 or the hipError_t.
+// The kernel is a template ARGUMENT, so the mark below -- the largest dynamic-LDS size the instance has been configured for -- is one
+// per instance: the lane, narrow and 16/32/64-wide kernels share one function-pointer type, and a mark keyed by type would publish
+// one instance's size for another.  One process drives one device; host threads may race here: setting the attribute twice is
+// harmless, publishing a size that was not set is not, hence set first, then raise the mark.
+template <auto Kern, class... A>
+static inline int cl_launch_lds(dim3 grid, dim3 block, size_t sm, hipStream_t st, const A&... args) {
+    if (sm > 160 * 1024) return -3;
+    static std::atomic<size_t> configured{0};
+    size_t have = configured.load(std::memory_order_acquire);
+    if (have < sm) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+        if (e != hipSuccess) return (int)e;
+        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
+    }
+    (void)hipGetLastError();   // drop any stale error of an unrelated earlier runtime call
+    hipLaunchKernelGGL(Kern, grid, block, sm, st, args...);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Device helpers the kernel files share (one copy of each)
+// ---------------------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Full scheduling fence: pins the order of a hand-interleaved instruction stream, the scheduler may not move anything across it.
+// Used to pin software-prefetched LDS operand reads ABOVE the MFMA group that runs while they are in flight: a wave issues in order
+// and an MFMA issue blocks until the matrix pipe accepts it, so reads placed after a group of MFMAs only start when that group has
+// drained; hipcc by itself keeps one operand buffer and emits exactly that order.
+#define CL_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+
+// Diagnostic build only (-DCL_STAMPS, `python -m careless_amd.build --stamps`, scripts/stamps*.py): per-wave cycle shares of the phases
+// of a tile, accumulated in the kernel's st_acc[] / st_last.  The shipped library is built without it and executes no stamp.
+#ifdef CL_STAMPS
+#define STAMP(k)                                                                                   \
+    do {                                                                                           \
+        unsigned long long t_;                                                                     \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                 \
+        st_acc[k] += t_ - st_last;                                                                 \
+        st_last = t_;                                                                              \
+    } while (0)
+#define STAMP_VM(k)                                                                                \
+    do {                                                                                           \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                           \
+        STAMP(k);                                                                                  \
+    } while (0)
+#else
+#define STAMP(k)
+#define STAMP_VM(k)
+#endif
+
+// (wave-uniform base pointer) + (32-bit per-lane BYTE offset): the form hipcc lowers to `global_* v, v_off, s[base:base+1]`
+// with no 64-bit per-lane address arithmetic (and nothing to keep live or spill across the tile loop)
+template <class T>
+__device__ __forceinline__ T ld_uo(const T* base, unsigned byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+template <class T>
+__device__ __forceinline__ T* ptr_uo(T* base, unsigned byte_off) {
+    return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off);
+}
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// make a wave-uniform int opaque to loop-strength reduction (keeps per-tile base pointers in SGPRs, recomputed per tile)
+__device__ __forceinline__ int opaque_uniform(int v) {
+    v = __builtin_amdgcn_readfirstlane(v);
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// LeakyReLU as max(x, leak x) with a bare v_max_f32: fmaxf() makes hipcc canonicalise x first (a second v_max per element) -- unless
+// the unit is compiled with -fno-honor-nans, so A UNIT THAT CALLS THIS MUST BE BUILT WITH THAT FLAG (build.py: NNAN; every fused scaler
+// unit is, since round 6).  Before that the bare instruction was inline assembly: opaque to hipcc's hazard recognizer, while its result
+// is an MFMA operand of the next layer and gfx950 wants two wait states between a vector-ALU write and an MFMA reading it -- hipcc pads
+// them only between instructions it knows (NOTEBOOK R6.1; scripts/check_lane_isa.py holds the library to the rule).  -DCL_LRELU_ASM
+// rebuilds the old form.
+__device__ __forceinline__ float lrelu(float x, float leak) {
+    const float m = leak * x;
+#ifdef CL_LRELU_ASM
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
+    return r;
+#else
+    return __builtin_fmaxf(x, m);
+#endif
+}
+// dZ = dH * lrelu'(h): dH where h > 0, leak dH otherwise (h == 0 takes the leak branch, like `h > 0 ? ... : ...`; -0.0 cannot
+// occur: h = max(x, leak x)).  A compare / conditional-move pair; the multiply + sign mask + bit select form the issue-time probe
+// (scripts/probe/coissue_probe.hip) suggested was measured slower -- hipcc makes five instructions of it
+// (scripts/patches/r2_narrow_closed_switches.diff, with the start stagger and the static priority of the second wave: no effect).
+__device__ __forceinline__ float lrelu_bwd(float h, float dh, float leak) {
+    return (h > 0.0f) ? dh : leak * dh;
+}
+
+// sum over the 64 lanes of a wave in double precision, left in every lane
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
 
 // The kernel arguments, re-read from the kernarg segment behind an opaque pointer.  hipcc loads every field of a by-value argument
 // struct at kernel entry and keeps it in SGPRs for the whole kernel (more than the ~100 there are: it then parks them in VGPR lanes

@@ -394,6 +394,12 @@ CL_HD float cl_dw_log_prob(float z, float z_parent, bool has_parent, float r, bo
 // Returns log p(ipred) and d/d ipred (through the location AND the scale) plus d/d(Sdfac, SdB, Sdadd).
 // ---------------------------------------------------------------------------------------------------------
 struct cl_ev11 { float sdfac, sdb, sdadd; };
+// ... from the raw trainable triple (Sdfac, Sdadd, SdB), in the reference's order (mono.py:51-59)
+CL_HD cl_ev11 cl_ev11_from_raw(const float* raw) {
+    cl_ev11 p;
+    p.sdfac = cl_softplus(raw[0]); p.sdadd = cl_softplus(raw[1]); p.sdb = cl_softplus(raw[2]);
+    return p;
+}
 CL_HD float cl_lik_ev11(float ipred, float iobs, float sig, int kind, float dof, float lik_const, cl_ev11 p, float* dll,
                         float* g_fac, float* g_b, float* g_add) {
     const float sp = cl_softplus(ipred);

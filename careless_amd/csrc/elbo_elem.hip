@@ -18,11 +18,6 @@ namespace {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // block-wide double sum -> one atomic per block
 __device__ __forceinline__ void block_atomic_add_d(double v, double* dst) {

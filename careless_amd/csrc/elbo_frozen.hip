@@ -32,11 +32,6 @@ constexpr int FB = 256;                 // threads of a workgroup = rows of a ch
 // budget, twice the waves per SIMD), 8 otherwise
 constexpr int THROUGH = 1 << 30;        // edge_rid flag: the wave is ONE run that continues on both sides
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 }  // namespace
 
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(FB) void frozen_rows_kernel(const cl_frozen_args A)
     float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     const bool use_ev11 = A.ev11 != nullptr;
-    if (use_ev11) { ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]); }
+    if (use_ev11) { ev = cl_ev11_from_raw(A.ev11); }
     const float inv_dof = (A.lik_kind == CL_LIK_STUDENTT) ? 1.0f / A.dof : 0.0f;
 
     // a row's seven numbers + the two reflection ids beside its wave, requested one chunk ahead: the chain row -> reflection -> amplitude is
@@ -228,7 +223,7 @@ __global__ __launch_bounds__(FB) void frozen_laue_kernel(const cl_frozen_args A)
     float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     const bool use_ev11 = A.ev11 != nullptr;
-    if (use_ev11) { ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]); }
+    if (use_ev11) { ev = cl_ev11_from_raw(A.ev11); }
     const float inv_dof = (A.lik_kind == CL_LIK_STUDENTT) ? 1.0f / A.dof : 0.0f;
     for (long long c = blockIdx.x; c < chunks; c += gridDim.x) {
         const long long row = c * FB + threadIdx.x;

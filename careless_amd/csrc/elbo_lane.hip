@@ -35,7 +35,6 @@
 #include "cl_kernels.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef CL_LANE_COALESCE
 #define CL_LANE_COALESCE 2      /* smallest number of MC samples whose amplitude gradients leave through LDS (0: never) */
@@ -117,25 +116,6 @@ __device__ __forceinline__ float lrelu2(float x, float lx) {
 #endif
 }
 
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <class T>
-__device__ __forceinline__ T ld_uo(const T* base, unsigned byte_off) {       // (wave-uniform pointer)[32-bit per-lane byte offset]
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-#define LFENCE() __builtin_amdgcn_sched_barrier(0)
-
-#ifdef CL_STAMPS
-#define LSTAMP(k)                                                                                  \
-    do {                                                                                           \
-        unsigned long long t_;                                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                 \
-        st_acc[k] += t_ - st_last;                                                                 \
-        st_last = t_;                                                                              \
-    } while (0)
-#else
-#define LSTAMP(k)
-#endif
 
 // LX: the metadata of a wave tile do not pass through registers at all (16 .. 31 columns: with every column a register of the lane,
 // twice with the prefetch, the 512-register file is over).  The next tile's rows are copied global -> LDS by the DMA path
@@ -360,7 +340,7 @@ void elbo_lane_kernel(const cl_mlp_args A) {
     // dL/d(pre-activations of layer 0) out (round 5: the launch behind a peeled first layer, cl_peel_*: a row per feature,
     // [cl_mlp_meta_rows(w)][n_pad] like meta_t)
     const bool has_dxo = (FULL || DXO) && A.dZ0_out != nullptr;
-    if (use_ev11) { ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]); }
+    if (use_ev11) { ev = cl_ev11_from_raw(A.ev11); }
 
     const int n_wt = (A.n_obs + WT - 1) / WT;                        // wave tiles
     const int wt_step = (int)gridDim.x * NWV;
@@ -562,7 +542,7 @@ void elbo_lane_kernel(const cl_mlp_args A) {
         // row is its position, a packed one's comes from row_map (rme), both known here for in-range rows only
         int dslot_raw = 0;
         if (det && A.det_slot != nullptr && !PACKED) dslot_raw = ld_uo(A.det_slot, 4u * (unsigned)min(wt * WT + lane, A.n_obs - 1));
-        LSTAMP(0);
+        STAMP(0);
         // ================= forward ==========================================================================================
         // (activations and dZ in aligned register pairs: the packed fp32 instructions of the backward pass take them as they stand)
         static_assert(W % 2 == 0, "feature pairs");
@@ -675,7 +655,7 @@ void elbo_lane_kernel(const cl_mlp_args A) {
             }
         }
 #define TOP(k) HS(NLT - 1, k)                            /* the head's input */
-        LSTAMP(1);
+        STAMP(1);
         float dloc = 0.0f, draw = 0.0f;
         if constexpr (MODE == 1) {
             // a head-less block, forward only: the top layer's activations out (feature-major like meta_t: the next block's "metadata")
@@ -854,10 +834,10 @@ void elbo_lane_kernel(const cl_mlp_args A) {
         draw = pds * dsig_draw;              // zero for padding observations
         }   // MODE == 0
 
-        LSTAMP(2);
+        STAMP(2);
         // next tile's inputs: their latency hides under the backward pass
         if (wt + wt_inc < wt_end) prefetch(wt + wt_inc, xcur ^ 1);
-        LSTAMP(3);
+        STAMP(3);
 
         // ================= backward =========================================================================================
         // NI: a parked layer's activations come back from LDS right before their first use on the way down (through an offset the
@@ -902,7 +882,7 @@ void elbo_lane_kernel(const cl_mlp_args A) {
             dH[c] = a;
         }
         }
-        LSTAMP(4);
+        STAMP(4);
             // dZ of a layer: dH where the activation is positive, leak dH otherwise.  As the compiler writes the select (compare
             // into VCC, wait states, select, per element) a lone wave pays ~9 cycles per instruction; compares into scalar
             // register pairs first and the selects after them issue back to back (scripts/probe/pkfma_probe.hip: 5.4 cycles).
@@ -983,7 +963,7 @@ void elbo_lane_kernel(const cl_mlp_args A) {
                         });
                     }
                 }
-                LFENCE();
+                CL_SCHED_FENCE();
                 // weight gradient of layer l; in the shadow of its MFMAs (two LDS instructions each are free for a lone wave) the
                 // staging writes, operand reads and dgrad weights of layer l - 1
                 static_for<0, 16>([&](auto ic_) {
@@ -1004,7 +984,7 @@ void elbo_lane_kernel(const cl_mlp_args A) {
                         // MFMAs into the operand registers of the other layer parity (layer 1 is done with them)
                         pb[1][i] = *reinterpret_cast<const f32x4*>(rdX + xoff + 16 * PIT + 16 * i);
                     }
-                    LFENCE();
+                    CL_SCHED_FENCE();
                 });
                 static_assert(NOPS + NC <= 32, "LDS operations of a layer fit the shadow of sixteen MFMAs");
                 if constexpr (LX && l == 0) {
@@ -1012,11 +992,11 @@ void elbo_lane_kernel(const cl_mlp_args A) {
                         constexpr int i = decltype(ic_)::value, c = (i >> 3) * 2, t = (i >> 1) & 3;
                         if constexpr ((i & 1) == 0) mfma16_acc(wacc0b, pa[0][c][t], pb[1][c][t]);
                         else mfma16_acc(wacd0b, pa[0][c + 1][t], pb[1][c + 1][t]);
-                        LFENCE();
+                        CL_SCHED_FENCE();
                     });
                 }
             });
-        LSTAMP(5);
+        STAMP(5);
     }
     if constexpr (MODE == 1) return;                             // (forward only: nothing accumulated)
     // ================= flush: sum the waves' accumulators, scatter into the flat W^T layout of this workgroup's partial ====
@@ -1132,36 +1112,34 @@ void elbo_lane_kernel(const cl_mlp_args A) {
 #define CL_LANE_PART 0
 #endif
 
+// The leaf of the launch path: with a name sink it prints this instance's template parameters (the default depth and NI = 0 in the
+// short forms the profiles have always used), without one it launches
 template <int W, int DMAX, bool PACKED, bool FULL, bool DXO = false, int NI = 0, int MODE = 0>
-static int launch_lane_inst(const cl_mlp_args& a, int grid, hipStream_t st) {
-    using SM = LSmem<W, DMAX == 0, NI>;
-    const size_t sm = (size_t)SM::total(a.d) * sizeof(float);
-    if (sm > 160 * 1024) return -3;
-    auto kern = elbo_lane_kernel<W, DMAX, PACKED, FULL, DXO, NI, NL, MODE>;
-    static std::atomic<size_t> configured{0};
-    size_t have = configured.load(std::memory_order_acquire);
-    if (have < sm) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
+static int launch_lane_inst(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if (c.name != nullptr) {
+        const char* const pk = PACKED ? "true" : "false", * const fu = FULL ? "true" : "false", * const dx = DXO ? "true" : "false";
+        const char* const det = a.dzf_obs != nullptr ? " (deterministic stores)" : "";
+        if (NI > 0 && NL != CL_MLP_LMAX_W16) return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s, %s, %d, %d> (image layers)%s", W, DMAX, pk, fu, dx, NI, NL, det);
+        if (NI > 0) return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s, %s, %d> (image layers)%s", W, DMAX, pk, fu, dx, NI, det);
+        if (NL != CL_MLP_LMAX_W16) return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s, %s, 0, %d>%s", W, DMAX, pk, fu, dx, NL, det);
+        return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s%s>%s", W, DMAX, pk, fu, DXO ? ", true" : "", det);
     }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), sm, st, a);
-    return (int)hipGetLastError();
+    const size_t sm = (size_t)LSmem<W, DMAX == 0, NI>::total(a.d) * sizeof(float);
+    return cl_launch_lds<elbo_lane_kernel<W, DMAX, PACKED, FULL, DXO, NI, NL, MODE>>(dim3(c.grid), dim3(NT), sm, c.st, a);
 }
 
 // the plain layout has a second instance without the optional inputs / outputs (the training step of a production run); the packed
 // layout (single-pass Laue) keeps the one full instance
 static inline bool lane_wants_full(const cl_mlp_args& a) { return a.eta != nullptr || a.ipred_out != nullptr || a.ev11 != nullptr || a.dzf_obs != nullptr; }
 template <int W, int DMAX, bool PACKED>
-static int launch_lane_one(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if constexpr (PACKED) return launch_lane_inst<W, DMAX, true, true>(a, grid, st);
+static int launch_lane_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if constexpr (PACKED) return launch_lane_inst<W, DMAX, true, true>(a, c);
     else {
-        if (lane_wants_full(a)) return launch_lane_inst<W, DMAX, false, true>(a, grid, st);
+        if (lane_wants_full(a)) return launch_lane_inst<W, DMAX, false, true>(a, c);
         // the production step behind a peeled first layer: metadata = the peeled layer's w pre-activations, in registers (DMAX = 8 or 15)
-        if constexpr (DMAX != 0) { if (a.dZ0_out != nullptr) return launch_lane_inst<W, DMAX, false, false, true>(a, grid, st); }
-        else if (a.dZ0_out != nullptr) return launch_lane_inst<W, DMAX, false, true>(a, grid, st);
-        return launch_lane_inst<W, DMAX, false, false>(a, grid, st);
+        if constexpr (DMAX != 0) { if (a.dZ0_out != nullptr) return launch_lane_inst<W, DMAX, false, false, true>(a, c); }
+        else if (a.dZ0_out != nullptr) return launch_lane_inst<W, DMAX, false, true>(a, c);
+        return launch_lane_inst<W, DMAX, false, false>(a, c);
     }
 }
 
@@ -1188,24 +1166,24 @@ static int launch_lane_one(const cl_mlp_args& a, int grid, hipStream_t st) {
     if (a.w <= 10) return CASE(10); \
     return CASE(CL_LANE_W12);
 
-int cl_launch_lane_plain_reg(const cl_mlp_args& a, int grid, hipStream_t st);
-int cl_launch_lane_packed_reg(const cl_mlp_args& a, int grid, hipStream_t st);
-int cl_launch_lane_plain_rows(const cl_mlp_args& a, int grid, hipStream_t st);
-int cl_launch_lane_packed_rows(const cl_mlp_args& a, int grid, hipStream_t st);
-int cl_launch_lane_imgl_inst(const cl_mlp_args& a, int grid, hipStream_t st);
-int cl_launch_lane_imgl3(const cl_mlp_args& a, int grid, hipStream_t st);
+int cl_launch_lane_plain_reg(const cl_mlp_args& a, const cl_launch_ctx& c);
+int cl_launch_lane_packed_reg(const cl_mlp_args& a, const cl_launch_ctx& c);
+int cl_launch_lane_plain_rows(const cl_mlp_args& a, const cl_launch_ctx& c);
+int cl_launch_lane_packed_rows(const cl_mlp_args& a, const cl_launch_ctx& c);
+int cl_launch_lane_imgl_inst(const cl_mlp_args& a, const cl_launch_ctx& c);
+int cl_launch_lane_imgl3(const cl_mlp_args& a, const cl_launch_ctx& c);
 // other depths than the default (round 6): one compilation per depth, CL_LANE_PART = 7
 #define CL_LANE_DEPTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
-#define CL_LANE_DEPTH_DECL(D) int cl_launch_lane_depth##D(const cl_mlp_args& a, int grid, hipStream_t st);
+#define CL_LANE_DEPTH_DECL(D) int cl_launch_lane_depth##D(const cl_mlp_args& a, const cl_launch_ctx& c);
 CL_LANE_DEPTHS(CL_LANE_DEPTH_DECL)
 #undef CL_LANE_DEPTH_DECL
 // ... and the two launches of a head-less layer block (MODE 1 / 2) at every depth 2 .. 20: the blocks in front of the last one of a chained scaler
-#define CL_LANE_BLOCK_DECL(D) int cl_launch_lane_block##D(const cl_mlp_args& a, int mode, int grid, hipStream_t st);
+#define CL_LANE_BLOCK_DECL(D) int cl_launch_lane_block##D(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
 CL_LANE_DEPTHS(CL_LANE_BLOCK_DECL)
 CL_LANE_BLOCK_DECL(20)
 #undef CL_LANE_BLOCK_DECL
 // ... and the per-image-layer instances at every depth 2 .. 19 (round 6; CL_LANE_PART = 9, one compilation per depth)
-#define CL_LANE_IMGLD_DECL(D) int cl_launch_lane_imgl_depth##D(const cl_mlp_args& a, int grid, hipStream_t st);
+#define CL_LANE_IMGLD_DECL(D) int cl_launch_lane_imgl_depth##D(const cl_mlp_args& a, const cl_launch_ctx& c);
 CL_LANE_DEPTHS(CL_LANE_IMGLD_DECL)
 #undef CL_LANE_IMGLD_DECL
 static inline bool lane_has_depth(int L) {
@@ -1216,8 +1194,8 @@ static inline bool lane_has_depth(int L) {
 }
 
 #if CL_LANE_PART == 0
-int cl_launch_lane_plain_reg(const cl_mlp_args& a, int grid, hipStream_t st) {
-#define CL_LANE_CASE(WW) (a.d <= 8 ? launch_lane_one<WW, 8, false>(a, grid, st) : (WW <= CL_LANE_WMAX ? launch_lane_one<(WW <= CL_LANE_WMAX ? WW : 4), DMAX_ALL, false>(a, grid, st) : -2))
+int cl_launch_lane_plain_reg(const cl_mlp_args& a, const cl_launch_ctx& c) {
+#define CL_LANE_CASE(WW) (a.d <= 8 ? launch_lane_one<WW, 8, false>(a, c) : (WW <= CL_LANE_WMAX ? launch_lane_one<(WW <= CL_LANE_WMAX ? WW : 4), DMAX_ALL, false>(a, c) : -2))
     CL_LANE_WIDTHS_REG(CL_LANE_CASE)
 #undef CL_LANE_CASE
 }
@@ -1269,100 +1247,45 @@ int cl_lane_block_supports(const cl_mlp_args& a, int mode) {
     return a.dH_ext != nullptr && a.act_out == nullptr && a.partials != nullptr;
 }
 
-int cl_launch_lane_block(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    if (!cl_lane_block_supports(a, mode)) return -2;
-    if (a.n_pad % CL_MLP_TILE != 0 || a.n_pad <= 0 || grid < 1) return -1;
-    if (4ull * (unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad >= (1ull << 32)) return -4;
-#define CL_LANE_BLOCK_CALL(D) if (a.L == D) return cl_launch_lane_block##D(a, mode, grid, st);
+int cl_launch_lane_block(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) {
+#define CL_LANE_BLOCK_CALL(D) if (a.L == D) return cl_launch_lane_block##D(a, mode, c);
     CL_LANE_DEPTHS(CL_LANE_BLOCK_CALL)
     CL_LANE_BLOCK_CALL(20)
 #undef CL_LANE_BLOCK_CALL
     return -2;
 }
 
-int cl_launch_lane_imgl(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (!cl_lane_imgl_supports(a)) return -2;
-    if (a.n_pad % CL_MLP_TILE != 0 || a.n_pad <= 0 || a.n_obs != a.n_pad) return -1;
-    if (4ull * (unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad >= (1ull << 32) ||
-        4ull * (unsigned long long)a.R * (unsigned long long)a.S >= (1ull << 32))
-        return -4;
-    if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-    if (grid < 1) return -1;
-    if (a.dzf_obs != nullptr) {          // deterministic mode (round 6), as cl_launch_lane; the per-image gradients: one wave per image (elbo_lane_kernel)
-        if (a.ev11 != nullptr && a.ev11_part == nullptr) return -2;
-        if (a.nll_part == nullptr) return -1;
-        if (4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-    }
-#define CL_LANE_IMGLD_CALL(D) if (a.L == D) return cl_launch_lane_imgl_depth##D(a, grid, st);
+// (deterministic mode -- dzf_obs given --: as cl_launch_lane; the per-image gradients: one wave per image, elbo_lane_kernel)
+int cl_launch_lane_imgl(const cl_mlp_args& a, const cl_launch_ctx& c) {
+#define CL_LANE_IMGLD_CALL(D) if (a.L == D) return cl_launch_lane_imgl_depth##D(a, c);
     CL_LANE_DEPTHS(CL_LANE_IMGLD_CALL)
 #undef CL_LANE_IMGLD_CALL
-    if (a.n_imgl == CL_LANE_IMGL_MAX_NL) return cl_launch_lane_imgl3(a, grid, st);
-    return cl_launch_lane_imgl_inst(a, grid, st);
+    if (a.n_imgl == CL_LANE_IMGL_MAX_NL) return cl_launch_lane_imgl3(a, c);
+    return cl_launch_lane_imgl_inst(a, c);
 }
 
-// name of the instance cl_launch_lane_imgl runs (cl_mlp_kernel_name)
-int cl_lane_imgl_kernel_name(const cl_mlp_args& a, char* out, size_t n) {
-    const bool full = lane_wants_full(a) || (a.n_imgl > CL_LANE_IMGL_MAX && a.dZ0_out != nullptr);       // (three layers + dZ_0 out: the full instance)
-    const char* dxo = (!full && a.dZ0_out != nullptr) ? "true" : "false";
-    const char* det = a.dzf_obs != nullptr ? " (deterministic stores)" : "";
-    if (a.L != NL) return snprintf(out, n, "elbo_lane_kernel<%d, %d, true, %s, %s, %d, %d> (image layers)%s", CL_LANE_WMAX, DMAX_ALL, full ? "true" : "false", dxo, a.n_imgl, a.L, det);
-    return snprintf(out, n, "elbo_lane_kernel<%d, %d, true, %s, %s, %d> (image layers)%s", CL_LANE_WMAX, (a.d <= 8 && a.n_imgl <= CL_LANE_IMGL_MAX) ? 8 : DMAX_ALL,
-                    full ? "true" : "false", dxo, a.n_imgl, det);
-}
-
-// name of the instance cl_launch_lane runs (cl_mlp_kernel_name)
-int cl_lane_kernel_name(const cl_mlp_args& a, char* out, size_t n) {
-    const int W = a.w <= 4 ? 4 : (a.w <= 6 ? 6 : (a.w <= 8 ? 8 : (a.w <= 10 ? 10 : CL_LANE_W12)));
-    const int DM = (a.d <= 8 && a.L == NL) ? 8 : (a.d <= DMAX_ALL ? DMAX_ALL : 0);       // (the other depths: one metadata capacity)
-    const bool packed = a.row_map != nullptr;
-    const bool full = packed || lane_wants_full(a) || (DM == 0 && a.dZ0_out != nullptr);
-    if (a.L != NL)
-        return snprintf(out, n, "elbo_lane_kernel<%d, %d, %s, %s, %s, 0, %d>%s", a.w <= 8 ? 8 : (a.w <= 10 ? CL_LANE_WMAX : CL_LANE_W12), DM, packed ? "true" : "false", full ? "true" : "false",
-                        (!full && a.dZ0_out != nullptr) ? "true" : "false", a.L, a.dzf_obs != nullptr ? " (deterministic stores)" : "");
-    return snprintf(out, n, "elbo_lane_kernel<%d, %d, %s, %s%s>%s", W, DM, packed ? "true" : "false", full ? "true" : "false",
-                    (!full && a.dZ0_out != nullptr) ? ", true" : "", a.dzf_obs != nullptr ? " (deterministic stores)" : "");
-}
-
-int cl_launch_lane(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (!cl_lane_supports(a)) return -2;
-    if (a.n_pad % CL_MLP_TILE != 0 || a.n_pad <= 0) return -1;
-    if (4ull * (unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad >= (1ull << 32) ||
-        4ull * (unsigned long long)a.R * (unsigned long long)a.S >= (1ull << 32))
-        return -4;
-    if (grid < 1) return -1;
-    if (a.dzf_obs != nullptr) {          // deterministic mode: stores per (observation, sample) / observation / workgroup / wave (Evans-2011 terms)
-        if (a.ev11 != nullptr && a.ev11_part == nullptr) return -2;      // (the Evans-2011 gradients need their per-wave slots)
-        if (a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr)) return -1;
-        if (4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-    }
+// (deterministic mode -- dzf_obs given --: stores per (observation, sample) / observation / workgroup / wave (Evans-2011 terms))
+int cl_launch_lane(const cl_mlp_args& a, const cl_launch_ctx& c) {
     if (a.L != NL) {
-        if (a.row_map != nullptr) {
-            if (a.n_obs != a.n_pad || (a.gmeta != nullptr && a.tile_gmax == nullptr)) return -1;
-            if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-        }
-#define CL_LANE_DEPTH_CALL(D) if (a.L == D) return cl_launch_lane_depth##D(a, grid, st);
+#define CL_LANE_DEPTH_CALL(D) if (a.L == D) return cl_launch_lane_depth##D(a, c);
         CL_LANE_DEPTHS(CL_LANE_DEPTH_CALL)
 #undef CL_LANE_DEPTH_CALL
         return -2;
     }
     // metadata as LDS rows from DMAX_ALL + 1 columns on (from 9 on it measured slower than the register instances, round 3)
     const bool rows = a.d > DMAX_ALL;
-    if (a.row_map != nullptr) {
-        if (a.n_obs != a.n_pad || (a.gmeta != nullptr && a.tile_gmax == nullptr)) return -1;
-        if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-        return rows ? cl_launch_lane_packed_rows(a, grid, st) : cl_launch_lane_packed_reg(a, grid, st);
-    }
-    return rows ? cl_launch_lane_plain_rows(a, grid, st) : cl_launch_lane_plain_reg(a, grid, st);
+    if (a.row_map != nullptr) return rows ? cl_launch_lane_packed_rows(a, c) : cl_launch_lane_packed_reg(a, c);
+    return rows ? cl_launch_lane_plain_rows(a, c) : cl_launch_lane_plain_reg(a, c);
 }
 #elif CL_LANE_PART == 1
-int cl_launch_lane_packed_reg(const cl_mlp_args& a, int grid, hipStream_t st) {
-#define CL_LANE_CASE(WW) (a.d <= 8 ? launch_lane_one<WW, 8, true>(a, grid, st) : (WW <= CL_LANE_WMAX ? launch_lane_one<(WW <= CL_LANE_WMAX ? WW : 4), DMAX_ALL, true>(a, grid, st) : -2))
+int cl_launch_lane_packed_reg(const cl_mlp_args& a, const cl_launch_ctx& c) {
+#define CL_LANE_CASE(WW) (a.d <= 8 ? launch_lane_one<WW, 8, true>(a, c) : (WW <= CL_LANE_WMAX ? launch_lane_one<(WW <= CL_LANE_WMAX ? WW : 4), DMAX_ALL, true>(a, c) : -2))
     CL_LANE_WIDTHS_REG(CL_LANE_CASE)
 #undef CL_LANE_CASE
 }
 #elif CL_LANE_PART == 2
-int cl_launch_lane_plain_rows(const cl_mlp_args& a, int grid, hipStream_t st) {
-#define CL_LANE_CASE(WW) launch_lane_one<WW, 0, false>(a, grid, st)
+int cl_launch_lane_plain_rows(const cl_mlp_args& a, const cl_launch_ctx& c) {
+#define CL_LANE_CASE(WW) launch_lane_one<WW, 0, false>(a, c)
     CL_LANE_WIDTHS(CL_LANE_CASE)
 #undef CL_LANE_CASE
 }
@@ -1373,33 +1296,33 @@ int cl_launch_lane_plain_rows(const cl_mlp_args& a, int grid, hipStream_t st) {
 // (one metadata capacity -- 15 columns in registers -- for every depth below the default: the eight-column instances of the default depth buy
 //  back registers the shallower units do not miss, and would double the 19 units' compile time)
 template <int WW>
-static int launch_lane_depth_w(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (a.row_map != nullptr) return launch_lane_inst<WW, DMAX_ALL, true, true>(a, grid, st);
-    if (lane_wants_full(a)) return launch_lane_inst<WW, DMAX_ALL, false, true>(a, grid, st);
+static int launch_lane_depth_w(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if (a.row_map != nullptr) return launch_lane_inst<WW, DMAX_ALL, true, true>(a, c);
+    if (lane_wants_full(a)) return launch_lane_inst<WW, DMAX_ALL, false, true>(a, c);
     // behind a peeled first layer (more than 15 metadata columns: the engine hands over the layer's w pre-activations): dZ_0 out
-    if (a.dZ0_out != nullptr) return launch_lane_inst<WW, DMAX_ALL, false, false, true>(a, grid, st);
-    return launch_lane_inst<WW, DMAX_ALL, false, false>(a, grid, st);
+    if (a.dZ0_out != nullptr) return launch_lane_inst<WW, DMAX_ALL, false, false, true>(a, c);
+    return launch_lane_inst<WW, DMAX_ALL, false, false>(a, c);
 }
-int CL_LANE_DEPTH_FN(CL_LANE_NL)(const cl_mlp_args& a, int grid, hipStream_t st) {
-    return a.w <= 8 ? launch_lane_depth_w<8>(a, grid, st) : (a.w <= 10 ? launch_lane_depth_w<CL_LANE_WMAX>(a, grid, st) : launch_lane_depth_w<CL_LANE_W12>(a, grid, st));
+int CL_LANE_DEPTH_FN(CL_LANE_NL)(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    return a.w <= 8 ? launch_lane_depth_w<8>(a, c) : (a.w <= 10 ? launch_lane_depth_w<CL_LANE_WMAX>(a, c) : launch_lane_depth_w<CL_LANE_W12>(a, c));
 }
 #endif
 #if CL_LANE_PART == 7 || CL_LANE_PART == 8
 // the two launches of a head-less layer block of this depth (part 8: the default depth)
 template <int WW, int MODE>
-static int launch_lane_block_w(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if constexpr (NL == CL_MLP_LMAX_W16) return a.d <= 8 ? launch_lane_inst<WW, 8, false, false, false, 0, MODE>(a, grid, st) : launch_lane_inst<WW, DMAX_ALL, false, false, false, 0, MODE>(a, grid, st);
-    else return launch_lane_inst<WW, DMAX_ALL, false, false, false, 0, MODE>(a, grid, st);
+static int launch_lane_block_w(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if constexpr (NL == CL_MLP_LMAX_W16) return a.d <= 8 ? launch_lane_inst<WW, 8, false, false, false, 0, MODE>(a, c) : launch_lane_inst<WW, DMAX_ALL, false, false, false, 0, MODE>(a, c);
+    else return launch_lane_inst<WW, DMAX_ALL, false, false, false, 0, MODE>(a, c);
 }
 #define CL_LANE_BLOCK_FN2(D) cl_launch_lane_block##D
 #define CL_LANE_BLOCK_FN(D) CL_LANE_BLOCK_FN2(D)
-int CL_LANE_BLOCK_FN(CL_LANE_NL)(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
+int CL_LANE_BLOCK_FN(CL_LANE_NL)(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) {
     // (widths 11, 12: the per-depth units only -- at the default depth twelve activations per layer spill)
     if constexpr (NL != CL_MLP_LMAX_W16) {
-        if (a.w > CL_LANE_WMAX) return mode == 1 ? launch_lane_block_w<CL_LANE_W12, 1>(a, grid, st) : launch_lane_block_w<CL_LANE_W12, 2>(a, grid, st);
+        if (a.w > CL_LANE_WMAX) return mode == 1 ? launch_lane_block_w<CL_LANE_W12, 1>(a, c) : launch_lane_block_w<CL_LANE_W12, 2>(a, c);
     } else if (a.w > CL_LANE_WMAX) return -2;
-    if (mode == 1) return a.w <= 8 ? launch_lane_block_w<8, 1>(a, grid, st) : launch_lane_block_w<CL_LANE_WMAX, 1>(a, grid, st);
-    return a.w <= 8 ? launch_lane_block_w<8, 2>(a, grid, st) : launch_lane_block_w<CL_LANE_WMAX, 2>(a, grid, st);
+    if (mode == 1) return a.w <= 8 ? launch_lane_block_w<8, 1>(a, c) : launch_lane_block_w<CL_LANE_WMAX, 1>(a, c);
+    return a.w <= 8 ? launch_lane_block_w<8, 2>(a, c) : launch_lane_block_w<CL_LANE_WMAX, 2>(a, c);
 }
 #endif
 #if CL_LANE_PART == 5
@@ -1409,28 +1332,28 @@ int CL_LANE_BLOCK_FN(CL_LANE_NL)(const cl_mlp_args& a, int mode, int grid, hipSt
 // instance of elbo_mlp.hip these scalers ran on.  One metadata capacity; behind a peeled first layer (dZ_0 out) the FULL instance: without
 // the option the dZ_0-storing production instance comes out with accumulator-register copies one instruction in front of the inline-assembly
 // MFMAs that read them (the build's wait-state scan refuses it: scripts/check_lane_isa.py, rule R1).
-int cl_launch_lane_imgl3(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (lane_wants_full(a) || a.dZ0_out != nullptr) return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, CL_LANE_IMGL_MAX_NL>(a, grid, st);
-    return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, CL_LANE_IMGL_MAX_NL>(a, grid, st);
+int cl_launch_lane_imgl3(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if (lane_wants_full(a) || a.dZ0_out != nullptr) return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, CL_LANE_IMGL_MAX_NL>(a, c);
+    return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, CL_LANE_IMGL_MAX_NL>(a, c);
 }
 #endif
 #if CL_LANE_PART == 9
 // per-image layers on another depth than the default (-DCL_LANE_NL=D): the widest instance, one metadata capacity, as the Dense-only units
 #define CL_LANE_IMGLD_FN2(D) cl_launch_lane_imgl_depth##D
 #define CL_LANE_IMGLD_FN(D) CL_LANE_IMGLD_FN2(D)
-int CL_LANE_IMGLD_FN(CL_LANE_NL)(const cl_mlp_args& a, int grid, hipStream_t st) {
+int CL_LANE_IMGLD_FN(CL_LANE_NL)(const cl_mlp_args& a, const cl_launch_ctx& c) {
     const bool full = lane_wants_full(a);
-#define CL_LANE_IMGL_CASE(NI_) (full ? launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, NI_>(a, grid, st) : \
-                                (a.dZ0_out != nullptr ? launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, true, NI_>(a, grid, st) : \
-                                                        launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, NI_>(a, grid, st)))
+#define CL_LANE_IMGL_CASE(NI_) (full ? launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, NI_>(a, c) : \
+                                (a.dZ0_out != nullptr ? launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, true, NI_>(a, c) : \
+                                                        launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, NI_>(a, c)))
     if (a.n_imgl == 1) return CL_LANE_IMGL_CASE(1);
     if (a.n_imgl == 2) return CL_LANE_IMGL_CASE(2);
 #undef CL_LANE_IMGL_CASE
     // three per-image layers: production and full instance (behind a peeled first layer the full one, as at the default depth) -- up to
     // CL_LANE_IMGL3_DEPTH_MAX Dense layers: on 19 the full instance (22 layers) crashes the compiler pass named at CL_LANE_PART 5
 #if CL_LANE_NL <= CL_LANE_IMGL3_DEPTH_MAX
-    if (full || a.dZ0_out != nullptr) return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, CL_LANE_IMGL_MAX_NL>(a, grid, st);
-    return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, CL_LANE_IMGL_MAX_NL>(a, grid, st);
+    if (full || a.dZ0_out != nullptr) return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, CL_LANE_IMGL_MAX_NL>(a, c);
+    return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, CL_LANE_IMGL_MAX_NL>(a, c);
 #else
     return -2;
 #endif
@@ -1439,22 +1362,22 @@ int CL_LANE_IMGLD_FN(CL_LANE_NL)(const cl_mlp_args& a, int grid, hipStream_t st)
 #if CL_LANE_PART == 4
 // per-image layers: the widest instance serves every w <= 10 (a narrower scaler pays the padded MFMA steps: --image-layers on a
 // non-default width is rare); with and without the optional inputs / outputs, as the plain layout
-int cl_launch_lane_imgl_inst(const cl_mlp_args& a, int grid, hipStream_t st) {
+int cl_launch_lane_imgl_inst(const cl_mlp_args& a, const cl_launch_ctx& c) {
     // Behind a peeled first layer (more than 15 metadata columns) the launch stores dZ_0: the production instance <.., false, true, NI>.
     // (Round 5 built it, saw results that moved from run to run and withdrew it for the FULL instance; round 6 found the cause -- the
     //  inline-assembly LeakyReLU one wait state in front of an MFMA, NOTEBOOK R6.1 -- and it is back: 4.44 -> 4.0 ms per step at 10 M
     //  observations and 8 samples.)
     const bool full = lane_wants_full(a);
-#define CL_LANE_IMGL_CASE(DM, NI_) (full ? launch_lane_inst<CL_LANE_WMAX, DM, true, true, false, NI_>(a, grid, st) : \
-                                    (a.dZ0_out != nullptr ? launch_lane_inst<CL_LANE_WMAX, DM, true, false, true, NI_>(a, grid, st) : \
-                                                            launch_lane_inst<CL_LANE_WMAX, DM, true, false, false, NI_>(a, grid, st)))
+#define CL_LANE_IMGL_CASE(DM, NI_) (full ? launch_lane_inst<CL_LANE_WMAX, DM, true, true, false, NI_>(a, c) : \
+                                    (a.dZ0_out != nullptr ? launch_lane_inst<CL_LANE_WMAX, DM, true, false, true, NI_>(a, c) : \
+                                                            launch_lane_inst<CL_LANE_WMAX, DM, true, false, false, NI_>(a, c)))
     if (a.n_imgl == 1) return a.d <= 8 ? CL_LANE_IMGL_CASE(8, 1) : CL_LANE_IMGL_CASE(DMAX_ALL, 1);
     return a.d <= 8 ? CL_LANE_IMGL_CASE(8, 2) : CL_LANE_IMGL_CASE(DMAX_ALL, 2);
 #undef CL_LANE_IMGL_CASE
 }
 #elif CL_LANE_PART == 3
-int cl_launch_lane_packed_rows(const cl_mlp_args& a, int grid, hipStream_t st) {
-#define CL_LANE_CASE(WW) launch_lane_one<WW, 0, true>(a, grid, st)
+int cl_launch_lane_packed_rows(const cl_mlp_args& a, const cl_launch_ctx& c) {
+#define CL_LANE_CASE(WW) launch_lane_one<WW, 0, true>(a, c)
     CL_LANE_WIDTHS(CL_LANE_CASE)
 #undef CL_LANE_CASE
 }

@@ -22,11 +22,6 @@ __device__ __forceinline__ float laue_eta(const cl_laue_args& A, int i, int s) {
     const uint64_t gidx = A.row_index ? (uint64_t)A.row_index[i] : (uint64_t)(A.obs_offset + i);
     return cl_noise_normal(A.seed, A.step, (uint32_t)s, gidx);
 }
-__device__ __forceinline__ double wave_sum_d2(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void laue_predict_kernel(const cl_laue_args A) {
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void laue_likelihood_kernel(const cl_laue_args
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     float sg0 = 0.0f, sg1 = 0.0f, sg2 = 0.0f;
     if (A.ev11 != nullptr) {
-        ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]);
+        ev = cl_ev11_from_raw(A.ev11);
         sg0 = cl_sigmoid(A.ev11[0]); sg1 = cl_sigmoid(A.ev11[1]); sg2 = cl_sigmoid(A.ev11[2]);
     }
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x) {
@@ -74,7 +69,7 @@ __global__ __launch_bounds__(256) void laue_likelihood_kernel(const cl_laue_args
         A.iconv[p] = -dll * A.w_ll;                  // dNLL / d iconv[g][s]
     }
     __shared__ double sh[4];
-    nll = wave_sum_d2(nll);
+    nll = wave_sum_d(nll);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = nll;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(256) void slot_rows_kernel(const cl_laue_args A, in
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     float sg0 = 0.0f, sg1 = 0.0f, sg2 = 0.0f;
     if (A.ev11 != nullptr) {
-        ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]);
+        ev = cl_ev11_from_raw(A.ev11);
         sg0 = cl_sigmoid(A.ev11[0]); sg1 = cl_sigmoid(A.ev11[1]); sg2 = cl_sigmoid(A.ev11[2]);
     }
     // everything a pair reads, requested for TWO rounds before the first one is worked on: the kernel is a chain of dependent loads (row ->
@@ -263,7 +258,7 @@ __global__ __launch_bounds__(256) void slot_rows_kernel(const cl_laue_args A, in
         work(Pb, pb);
     }
     __shared__ double sh[4];
-    nll = wave_sum_d2(nll);
+    nll = wave_sum_d(nll);
     if (lane == 0) sh[threadIdx.x >> 6] = nll;
     __syncthreads();
     if (threadIdx.x == 0) {

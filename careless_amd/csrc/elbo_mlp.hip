@@ -38,7 +38,6 @@
 #include "cl_math.h"
 #include "cl_kernels.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef CL_META_RANGE
@@ -59,30 +58,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // compiler-level fence for memory operations: keeps hipcc from hoisting a whole layer of LDS operand reads
 // above the MFMAs that consume them
 #define CL_PIN() asm volatile("" ::: "memory")
-// Full scheduling fence.  Used to pin software-prefetched LDS operand reads ABOVE the MFMA group that runs while they are in
-// flight: a wave issues in order and an MFMA issue blocks until the matrix pipe accepts it, so reads placed after a group of
-// MFMAs only start when that group has drained; hipcc by itself keeps one operand buffer and emits exactly that order.
-#define CL_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-// Diagnostic build only (-DCL_STAMPS, scripts/stamps.py): per-wave cycle shares of the phases of a tile.  The shipped
-// library is built without it and executes no stamp.
 #ifdef CL_STAMPS
-#define CL_NPH 16
-#define STAMP(k)                                                                                   \
-    do {                                                                                           \
-        unsigned long long t_;                                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                 \
-        st_acc[k] += t_ - st_last;                                                                 \
-        st_last = t_;                                                                              \
-    } while (0)
-#define STAMP_VM(k)                                                                                \
-    do {                                                                                           \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                           \
-        STAMP(k);                                                                                  \
-    } while (0)
-#else
-#define STAMP(k)
-#define STAMP_VM(k)
+#define CL_NPH 16          // phases of a tile the -DCL_STAMPS build times (STAMP, cl_kernels.h)
 #endif
 
 namespace {
@@ -97,41 +75,6 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// (wave-uniform base pointer) + (32-bit per-lane BYTE offset): the form hipcc lowers to `global_* v, v_off, s[base:base+1]`
-// with no 64-bit per-lane address arithmetic (and nothing to keep live or spill across the tile loop)
-template <class T>
-__device__ __forceinline__ T ld_uo(const T* base, unsigned byte_off) {
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-template <class T>
-__device__ __forceinline__ T* ptr_uo(T* base, unsigned byte_off) {
-    return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off);
-}
-// make a wave-uniform int opaque to loop-strength reduction (keeps per-tile base pointers in SGPRs, recomputed per tile)
-__device__ __forceinline__ int opaque_uniform(int v) {
-    v = __builtin_amdgcn_readfirstlane(v);
-    asm volatile("" : "+s"(v));
-    return v;
-}
-
-// LeakyReLU as max(x, leak x) with a bare v_max_f32: fmaxf() makes hipcc canonicalise x first (a second v_max per element) -- unless
-// the unit is compiled with -fno-honor-nans (build.py), which it is since round 6.  Before that the bare instruction was inline assembly:
-// opaque to hipcc's hazard recognizer, while its result is an MFMA operand of the next layer and gfx950 wants two wait states between a
-// vector-ALU write and an MFMA reading it (NOTEBOOK R6.1; scripts/check_lane_isa.py holds the library to the rule).
-__device__ __forceinline__ float lrelu(float x, float leak) {
-    const float m = leak * x;
-#ifdef CL_LRELU_ASM
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
-    return r;
-#else
-    return __builtin_fmaxf(x, m);
-#endif
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 template <int WP, int DP, int LMAX>
 struct SmemLayout {
@@ -330,7 +273,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     float ev_g0 = 0.0f, ev_g1 = 0.0f, ev_g2 = 0.0f;
     const bool use_ev11 = (MODE == 0) && (A.ev11 != nullptr);
-    if (use_ev11) { ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]); }
+    if (use_ev11) { ev = cl_ev11_from_raw(A.ev11); }
 
     const int ntiles = A.n_pad / CL_TILE;
     const int S = A.S;
@@ -1299,20 +1242,7 @@ static int launch_one(const cl_mlp_args& a, int grid, hipStream_t st) {
     if (MODE != 1 && flush > sm) sm = flush;
     using AP = AccPlan<WP, DP, LMAX, MODE, (CL_IMGL == 1)>;
     if (AP::NACC > 0) sm = (size_t)AP::total * sizeof(float);                                       // + LDS-resident accumulators
-    if (sm > 160 * 1024) return -3;
-    auto kern = elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0)>;
-    // largest dynamic-LDS size this instance has been configured for (one process drives one device; host threads may race here:
-    // setting the attribute twice is harmless, publishing a size that was not set is not, hence set first, then raise the mark)
-    static std::atomic<size_t> configured{0};
-    size_t have = configured.load(std::memory_order_acquire);
-    if (have < sm) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
-    }
-    (void)hipGetLastError();   // drop any stale error of an unrelated earlier runtime call
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), sm, st, a);
-    return (int)hipGetLastError();
+    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0)>>(dim3(grid), dim3(512), sm, st, a);
 }
 
 // Instantiated geometries: the padded width WP fixes how many layers of activations + weight-gradient blocks fit in the
@@ -1368,6 +1298,31 @@ static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
     return launch_dp<64, CL_MLP_LMAX_W64, MODE>(a, g.DP, grid, st);
 }
 
+// This compilation's launcher (cl_kernels.h lists the eight; cl_launch_mlp has checked the arguments and clamped the grid)
+#if CL_DET && CL_IMGL == 2
+#define CL_MLP_UNIT cl_launch_mlp_packed_det
+#elif CL_DET && CL_CHAIN
+#define CL_MLP_UNIT cl_launch_mlp_chain_det
+#elif CL_DET
+#define CL_MLP_UNIT cl_launch_mlp_det
+#elif CL_CHAIN
+#define CL_MLP_UNIT cl_launch_mlp_chain
+#elif CL_IMGL == 2
+#define CL_MLP_UNIT cl_launch_mlp_packed
+#elif CL_IMGL
+#define CL_MLP_UNIT cl_launch_mlp_imgl
+#else
+#define CL_MLP_UNIT cl_launch_mlp_plain
+#endif
+int CL_MLP_UNIT(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
+    switch (mode) {
+        case 0: return launch_mode<0>(a, grid, st);
+        case 1: return launch_mode<1>(a, grid, st);
+        case 2: return launch_mode<2>(a, grid, st);
+    }
+    return -1;
+}
+
 #if !CL_IMGL && !CL_CHAIN && !CL_DET
 // The A/B switches (bisection and measurement runs; unset or anything but "0" = on), read here and nowhere else.  Each keeps shapes off
 // a kernel family, which then go to the next kernel down mlp_route's order:
@@ -1385,7 +1340,7 @@ static const RouteSwitches& route_switches() {
 }
 
 // Which launcher takes the launch: the one routing decision of the scaler launches (cl_launch_mlp, cl_mlp_kernel_name_of, cl_mlp_route).
-// Shape, optional buffers and mode only: n_pad and the grid are argument checks of the callers.
+// Shape, optional buffers and mode only: n_pad, the grid and the buffers a route requires are mlp_check's.
 cl_route mlp_route(const cl_mlp_args& a, int mode) {
     const RouteSwitches& sw = route_switches();
     const bool lane_depth = sw.depths || a.L == CL_MLP_LMAX_W16;
@@ -1425,91 +1380,78 @@ cl_route mlp_route(const cl_mlp_args& a, int mode) {
     if (r >= CL_ROUTE_MLP && mlp_geom(a, mode, r == CL_ROUTE_MLP_IMGL).WP == 0) return CL_ROUTE_NONE;     // wider / deeper than this file's instances
     return r;
 }
-#endif
+// Every argument check of a scaler launch, in one place: what cl_launch_mlp tests between the route and the dispatch (and what
+// cl_mlp_check answers without launching).  Precedence: -1 tile / grid, -2 no route, the route's own -1 clauses, the -4 bounds.
+// The kernels address with 32-bit byte offsets: a float array of `elems` elements must stay below 4 GiB (shard further across GPUs otherwise).
+static inline bool over_4gib(unsigned long long elems) { return 4ull * elems >= (1ull << 32); }
+static inline bool meta_over(const cl_mlp_args& a) { return over_4gib((unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad); }   // meta_t
+static inline bool refl_over(const cl_mlp_args& a) { return over_4gib((unsigned long long)a.R * (unsigned long long)a.S); }                     // z_f, dz_f
+static inline bool obs_over(const cl_mlp_args& a) { return over_4gib((unsigned long long)a.n_pad * (unsigned long long)a.S); }                  // eta, ipred_out, dzf_obs
 
-#if CL_DET && CL_IMGL == 2
-// packed layout (single-pass Laue) without float atomics: the seventh compilation of this file (build.py: elbo_mlp_packed_det)
-int cl_launch_mlp_packed_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    if (mode != 0 || a.row_map == nullptr || a.n_obs != a.n_pad || a.n_imgl != 0 || (a.ev11 != nullptr && a.ev11_part == nullptr)) return -2;
-    if (a.gmeta != nullptr && a.tile_gmax == nullptr) return -1;
-    if (a.dzf_obs == nullptr || a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr)) return -1;
-    if (4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-#elif CL_DET && CL_CHAIN
-// the LAST block of a layer-block chain (the one launch of a chained scaler with an epilogue) without float atomics: the eighth compilation
-// of this file (build.py: elbo_mlp_chain_det).  The chain's forward-only and backward-only launches have no atomics and keep the chain unit.
-int cl_launch_mlp_chain_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    if (mode != 0 || a.row_map != nullptr || a.n_imgl > 0 || a.act_out != nullptr || a.dH_ext != nullptr || a.dX_out == nullptr || (a.ev11 != nullptr && a.ev11_part == nullptr)) return -2;
-    if (a.dzf_obs == nullptr || a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr)) return -1;
-    if (4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-#elif CL_DET
-int cl_launch_mlp_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    // plain layout, full step, every store target present (with the Evans-2011 terms: their per-wave slots)
-    if (mode != 0 || a.row_map != nullptr || a.n_imgl > 0 || a.act_out != nullptr || a.dH_ext != nullptr || a.dX_out != nullptr || (a.ev11 != nullptr && a.ev11_part == nullptr)) return -2;
-    if (a.dzf_obs == nullptr || a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr)) return -1;
-    if (4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-#elif CL_CHAIN
-int cl_launch_mlp_chain(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    if (a.row_map != nullptr || a.n_imgl > 0) return -2;                       // chains use the plain layout
-    if (a.act_out != nullptr && mode != 1) return -1;
-    if (a.dH_ext != nullptr && mode != 2) return -1;
-#elif CL_IMGL == 2
-int cl_launch_mlp_packed(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    if (a.row_map == nullptr || a.n_obs != a.n_pad || a.n_imgl != 0) return -1;
-    if (a.gmeta != nullptr && (a.tile_gmax == nullptr || mode != 0)) return -1;
-    if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-#elif CL_IMGL
-int cl_launch_mlp_imgl(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    if (a.row_map == nullptr || a.n_obs != a.n_pad || a.n_imgl < 0) return -1;
-    if (a.n_imgl > 0 && (a.imgl == nullptr || a.tile_img == nullptr || a.n_images < 1 || a.use_img)) return -1;
-    if (a.n_imgl > 0 && mode != 1 && a.d_imgl == nullptr) return -1;
-    if (a.gmeta != nullptr && (a.tile_gmax == nullptr || mode != 0)) return -1;
-    // eta / ipred_out are addressed with 32-bit byte offsets from their base in this variant
-    if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-#else
-int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
+int mlp_check(const cl_mlp_args& a, int mode, int grid, cl_route r) {
     if (a.n_pad % CL_TILE != 0 || a.n_pad <= 0 || grid < 1) return -1;
-    if (grid > a.n_pad / CL_TILE) grid = a.n_pad / CL_TILE;
-    switch (mlp_route(a, mode)) {
-        case CL_ROUTE_NONE: return -2;
-        case CL_ROUTE_LANE: return cl_launch_lane(a, grid, st);
-        case CL_ROUTE_LANE_IMGL: return cl_launch_lane_imgl(a, grid, st);
-        case CL_ROUTE_LANE_BLOCK: return cl_launch_lane_block(a, mode, grid, st);
-        case CL_ROUTE_NARROW: return cl_launch_narrow(a, grid, st);
-        case CL_ROUTE_MLP: break;                                               // this compilation's instances, below
-        case CL_ROUTE_MLP_PACKED: return cl_launch_mlp_packed(a, mode, grid, st);
-        case CL_ROUTE_MLP_IMGL: return cl_launch_mlp_imgl(a, mode, grid, st);
-        case CL_ROUTE_MLP_CHAIN: return cl_launch_mlp_chain(a, mode, grid, st);
-        case CL_ROUTE_MLP_DET: return cl_launch_mlp_det(a, mode, grid, st);
-        case CL_ROUTE_MLP_PACKED_DET: return cl_launch_mlp_packed_det(a, mode, grid, st);
-        case CL_ROUTE_MLP_CHAIN_DET: return cl_launch_mlp_chain_det(a, mode, grid, st);
+    if (r == CL_ROUTE_NONE) return -2;
+    const bool packed = a.row_map != nullptr || r == CL_ROUTE_MLP_IMGL;      // (the route keeps row_map off the plain-layout launchers)
+    // deterministic mode: the routes with per-observation stores (the lane and narrow kernels store when dzf_obs is given)
+    const bool det = r == CL_ROUTE_MLP_DET || r == CL_ROUTE_MLP_PACKED_DET || r == CL_ROUTE_MLP_CHAIN_DET ||
+                     (a.dzf_obs != nullptr && (r == CL_ROUTE_LANE || r == CL_ROUTE_LANE_IMGL || r == CL_ROUTE_NARROW));
+    if (r == CL_ROUTE_MLP_PACKED_DET && a.n_obs != a.n_pad) return -2;      // (this unit's answer to a padded packed layout has always been -2)
+    if (packed) {                                                           // packed layout: no padding rows behind n_obs, group sizes with their tile maxima, full step only
+        if (a.row_map == nullptr || a.n_obs != a.n_pad || a.n_imgl < 0) return -1;
+        if (a.gmeta != nullptr && (a.tile_gmax == nullptr || mode != 0)) return -1;
     }
-#endif
-    if (a.n_pad % CL_TILE != 0 || a.n_pad <= 0) return -1;
-    // 32-bit byte offsets / buffer sizes inside the kernel: metadata image < 4 GiB, z_f < 4 GiB (shard further across GPUs otherwise)
-    const unsigned long long meta_bytes = 4ull * (unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad;
-    if (meta_bytes >= (1ull << 32) || 4ull * (unsigned long long)a.R * (unsigned long long)a.S >= (1ull << 32)) return -4;
-    const int ntiles = a.n_pad / CL_TILE;
-    if (grid > ntiles) grid = ntiles;
-    if (grid < 1) return -1;
-    switch (mode) {
-        case 0: return launch_mode<0>(a, grid, st);
-        case 1: return launch_mode<1>(a, grid, st);
-        case 2: return launch_mode<2>(a, grid, st);
+    if (r == CL_ROUTE_MLP_IMGL) {                                           // per-image layers: their weights, the tiles' images, and no image scale beside them
+        if (a.imgl == nullptr || a.tile_img == nullptr || a.n_images < 1 || a.use_img) return -1;
+        if (mode != 1 && a.d_imgl == nullptr) return -1;
     }
-    return -1;
+    if (r == CL_ROUTE_MLP_CHAIN) {                                          // a block's activations leave the forward launch, its gradient enters the backward one
+        if (a.act_out != nullptr && mode != 1) return -1;
+        if (a.dH_ext != nullptr && mode != 2) return -1;
+    }
+    if (det && (a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr))) return -1;      // the store targets
+    if (meta_over(a)) return -4;
+    if (r != CL_ROUTE_LANE_BLOCK && refl_over(a)) return -4;                 // (a head-less block reads no reflection)
+    if ((det || (packed && (a.eta != nullptr || a.ipred_out != nullptr))) && obs_over(a)) return -4;
+    return 0;
 }
 
-#if !CL_IMGL && !CL_CHAIN && !CL_DET
-// Name of the kernel instance cl_launch_mlp(a, mode, ...) runs, from the same route (bench.py and the profiling scripts label their rows
-// with it instead of guessing).  Returns the length written (snprintf semantics).
+// The launcher the route names.  With a name sink in `c` (cl_mlp_kernel_name_of) the lane and narrow paths print their instance.
+static int mlp_dispatch(const cl_mlp_args& a, int mode, cl_route r, const cl_launch_ctx& c) {
+    switch (r) {
+        case CL_ROUTE_NONE: break;
+        case CL_ROUTE_LANE: return cl_launch_lane(a, c);
+        case CL_ROUTE_LANE_IMGL: return cl_launch_lane_imgl(a, c);
+        case CL_ROUTE_LANE_BLOCK: return cl_launch_lane_block(a, mode, c);
+        case CL_ROUTE_NARROW: return cl_launch_narrow(a, c);
+        case CL_ROUTE_MLP: return cl_launch_mlp_plain(a, mode, c.grid, c.st);
+        case CL_ROUTE_MLP_PACKED: return cl_launch_mlp_packed(a, mode, c.grid, c.st);
+        case CL_ROUTE_MLP_IMGL: return cl_launch_mlp_imgl(a, mode, c.grid, c.st);
+        case CL_ROUTE_MLP_CHAIN: return cl_launch_mlp_chain(a, mode, c.grid, c.st);
+        case CL_ROUTE_MLP_DET: return cl_launch_mlp_det(a, mode, c.grid, c.st);
+        case CL_ROUTE_MLP_PACKED_DET: return cl_launch_mlp_packed_det(a, mode, c.grid, c.st);
+        case CL_ROUTE_MLP_CHAIN_DET: return cl_launch_mlp_chain_det(a, mode, c.grid, c.st);
+    }
+    return -2;
+}
+
+int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
+    const cl_route r = mlp_route(a, mode);
+    if (int e = mlp_check(a, mode, grid, r)) return e;
+    if (grid > a.n_pad / CL_TILE) grid = a.n_pad / CL_TILE;
+    return mlp_dispatch(a, mode, r, {grid, st});
+}
+
+// Name of the kernel instance cl_launch_mlp(a, mode, ...) runs (bench.py and the profiling scripts label their rows with it instead of
+// guessing): for shapes, not for valid buffers -- the same dispatch without mlp_check.  The lane and narrow paths print the name at the
+// leaf that picks the instance; this file's instances share mlp_geom between launch and name.  Returns the length written (snprintf semantics).
 int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n) {
     const cl_route r = mlp_route(a, mode);
     const char* unit = "";
     switch (r) {
         case CL_ROUTE_NONE: return snprintf(out, n, "(unsupported)");
-        case CL_ROUTE_LANE: return cl_lane_kernel_name(a, out, n);
-        case CL_ROUTE_LANE_IMGL: return cl_lane_imgl_kernel_name(a, out, n);
-        case CL_ROUTE_NARROW: return cl_narrow_kernel_name(a, out, n);
+        case CL_ROUTE_LANE:
+        case CL_ROUTE_LANE_IMGL:
+        case CL_ROUTE_NARROW: return mlp_dispatch(a, mode, r, {0, nullptr, out, n});
         case CL_ROUTE_LANE_BLOCK:             // (still labelled with the chain instance it replaced in round 6: the lane kernel has no name for its block launches)
         case CL_ROUTE_MLP_CHAIN: unit = ", chain"; break;
         case CL_ROUTE_MLP: break;

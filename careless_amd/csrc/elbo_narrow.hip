@@ -28,10 +28,6 @@
 #include "cl_math.h"
 #include "cl_kernels.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-
-
 namespace {
 
 constexpr int NL = CL_MLP_LMAX_W16;   // Dense layers one launch holds
@@ -39,34 +35,6 @@ constexpr int NPW = 20;               // row pitch of a 16 x 16 weight image
 
 __device__ __forceinline__ int slot_of(int f) { return ((f & 3) << 2) | (f >> 2); }   // feature <-> slot (involution on 0..15)
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// (one v_max_f32 the compiler knows: -fno-honor-nans, see elbo_mlp.hip)
-__device__ __forceinline__ float lrelu(float x, float leak) {
-    const float m = leak * x;
-#ifdef CL_LRELU_ASM
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
-    return r;
-#else
-    return __builtin_fmaxf(x, m);
-#endif
-}
-
-// dZ = dH * lrelu'(h): dH where h > 0, leak dH otherwise (h == 0 takes the leak branch, like `h > 0 ? ... : ...`; -0.0 cannot
-// occur: h = max(x, leak x)).  A compare / conditional-move pair; the multiply + sign mask + bit select form the issue-time probe
-// (scripts/probe/coissue_probe.hip) suggested was measured slower -- hipcc makes five instructions of it
-// (scripts/patches/r2_narrow_closed_switches.diff, with the start stagger and the static priority of the second wave: no effect).
-__device__ __forceinline__ float lrelu_bwd(float h, float dh, float leak) {
-    return (h > 0.0f) ? dh : leak * dh;
-}
-
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int opaque_uniform(int v) {
-    v = __builtin_amdgcn_readfirstlane(v);
-    asm volatile("" : "+s"(v));
-    return v;
-}
 // "Is layer l the top layer?" as a bit test on an opaque SGPR mask (1 << (L - 1)).  Written as `l == Lt - 1` hipcc replaces the
 // unrolled layer number l inside the guarded block by the run-time value Lt - 1, finds the twenty blocks identical, merges them
 // into one that indexes `hs` at run time -- and the activations land in scratch memory.
@@ -75,26 +43,6 @@ __device__ __forceinline__ unsigned top_layer_mask(int L) {
     asm volatile("" : "+s"(m));
     return m;
 }
-template <class T>
-__device__ __forceinline__ T ld_uo(const T* base, unsigned byte_off) {       // (wave-uniform pointer)[32-bit per-lane byte offset]
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-// pins the order of the hand-interleaved instruction stream: the scheduler may not move anything across it
-#define NFENCE() __builtin_amdgcn_sched_barrier(0)
-
-// Diagnostic build only (-DCL_STAMPS): per-wave cycle shares of the phases of a wave tile; the shipped library executes no stamp
-#ifdef CL_STAMPS
-#define NSTAMP(k)                                                                                  \
-    do {                                                                                           \
-        unsigned long long t_;                                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                 \
-        st_acc[k] += t_ - st_last;                                                                 \
-        st_last = t_;                                                                              \
-    } while (0)
-#else
-#define NSTAMP(k)
-#endif
 
 template <int G, int NWAVES>
 struct NSmem {
@@ -215,7 +163,7 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     float ev_g0 = 0.0f, ev_g1 = 0.0f, ev_g2 = 0.0f;
     const bool use_ev11 = A.ev11 != nullptr;
-    if (use_ev11) { ev.sdfac = cl_softplus(A.ev11[0]); ev.sdadd = cl_softplus(A.ev11[1]); ev.sdb = cl_softplus(A.ev11[2]); }
+    if (use_ev11) { ev = cl_ev11_from_raw(A.ev11); }
 
     const int n_wt = (A.n_obs + WT - 1) / WT;                        // wave tiles
     const int wt_step = (int)gridDim.x * NWAVES;
@@ -301,7 +249,7 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                 }
             }
         }
-        NSTAMP(0);
+        STAMP(0);
         // ================= forward ==========================================================================================
         // `top` = the top layer's activations (the head's input), copied out where the depth puts them.
         float hs[NL][G][KS];
@@ -326,12 +274,12 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                         acc[g] = mfma4(wf[t], b, t == 0 ? bias : acc[g]);
                     }
                 }
-                NFENCE();
+                CL_SCHED_FENCE();
 #pragma unroll
                 for (int g = 0; g < G; ++g)
 #pragma unroll
                     for (int t = 0; t < KS; ++t) hs[l][g][t] = lrelu(acc[g][t], leak);
-                NFENCE();
+                CL_SCHED_FENCE();
                 if (topm & (1u << l)) {
 #pragma unroll
                     for (int g = 0; g < G; ++g)
@@ -340,7 +288,7 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                 }
             }
         }
-        NSTAMP(1);
+        STAMP(1);
         // Dense(2) head: group g's two outputs land in rows 4g, 4g+1 -- the rows of lane quarter q == g; one accumulator chain per group.
         // The other rows of group g's product are (zero weight) x (activation): exact zeros UNLESS an activation is non-finite, and column
         // j of those rows belongs to observation 16 g' + j of another group.  So every quarter SELECTS its own group's product (adding
@@ -470,10 +418,10 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
             sD[PBW + lane] = draw;
         }
 
-        NSTAMP(2);
+        STAMP(2);
         // next tile's inputs: their latency hides under the backward pass
         if (wt + wt_step < n_wt) prefetch(wt + wt_step, E);
-        NSTAMP(3);
+        STAMP(3);
 
         // ================= backward =========================================================================================
         // The weight gradient of a layer is issued one layer late: its operands (the staged dZ_l and the layer's input, read
@@ -500,7 +448,7 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
             a = mfma4(wcol[(NL + g) * 16 * NPW + NPW], draw, a);
             dH[g] = a;
         }
-        NFENCE();
+        CL_SCHED_FENCE();
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -516,7 +464,7 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
         f32x4 paccb[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
         if (SM::NACC > 0) { paccb[0] = acc_slot(Lt < NL ? Lt : NL - 1); paccb[1] = paccb[0]; }     // (run-time slot; unused when Lt < LREG or Lt == NL)
 
-        NSTAMP(4);
+        STAMP(4);
         float wdb[2][KS];
         {
             const int lt1 = Lt > 1 ? Lt - 1 : 1;
@@ -542,7 +490,7 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                 for (int g = 0; g < G; ++g) {
                     float dzn[KS];
                     f32x4 accd = {0.0f, 0.0f, 0.0f, 0.0f};
-                    NFENCE();
+                    CL_SCHED_FENCE();
                     // MFMAs of group g: the pending wgrad (layer l+1) and this layer's dgrad, alternating chains
                     wa = mfma4(pa[g][0], pb[g][0], wa);
                     if (l > 0) accd = mfma4(wd[0], dz[0], accd);
@@ -562,12 +510,12 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                                 if (4 * t + q < w) p0[(size_t)(4 * t + q) * np] = dz[t];
                         }
                     }
-                    NFENCE();
+                    CL_SCHED_FENCE();
                     wa = mfma4(pa[g][1], pb[g][1], wa);
                     if (l > 0) accd = mfma4(wd[1], dz[1], accd);
 #pragma unroll
                     for (int t = 0; t < KS; ++t) (stw + TH)[t * PBW + 16 * g] = (l == 0) ? x0[g][t] : hs[l > 0 ? l - 1 : 0][g][t];   // stage the layer's input
-                    NFENCE();
+                    CL_SCHED_FENCE();
                     wa = mfma4(pa[g][2], pb[g][2], wa);
                     if (l > 0 && KS > 2) accd = mfma4(wd[KS > 2 ? 2 : 0], dz[KS > 2 ? 2 : 0], accd);
                     // dZ of the group that comes next in this layer
@@ -576,12 +524,12 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                         for (int t = 0; t < KS; ++t)
                             dzn[t] = lrelu_bwd(hs[l][g + 1 < G ? g + 1 : 0][t], dH[g + 1 < G ? g + 1 : 0][t], leak);
                     }
-                    NFENCE();
+                    CL_SCHED_FENCE();
                     wa = mfma4(pa[g][3], pb[g][3], wa);
                     if (l > 0 && KS > 3) accd = mfma4(wd[KS > 3 ? 3 : 0], dz[KS > 3 ? 3 : 0], accd);
                     pa[g] = *reinterpret_cast<const f32x4*>(strd + 16 * g);                                  // operands of this layer's wgrad
                     pb[g] = *reinterpret_cast<const f32x4*>(strd + TH + 16 * g);
-                    NFENCE();
+                    CL_SCHED_FENCE();
                     dHn[g] = accd;
                     if (g + 1 < G) {
 #pragma unroll
@@ -598,13 +546,13 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
                 for (int g = 0; g < G; ++g) dH[g] = dHn[g];
             }
         }
-        NSTAMP(5);
+        STAMP(5);
         // the last pending weight gradient: layer 0
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int t = 0; t < 4; ++t) wacc[0] = mfma4(pa[g][t], pb[g][t], wacc[0]);
-        NSTAMP(6);
+        STAMP(6);
     }
 #ifdef CL_STAMPS
     if (A.loc_out != nullptr && lane == 0) {
@@ -695,22 +643,13 @@ void elbo_narrow_kernel(const cl_mlp_args A) {
     }
 }
 
+// The leaf of the launch path: with a name sink it prints this instance's template parameters, without one it launches
 template <int G, int KS, int NWAVES, bool PACKED>
-static int launch_narrow_one(const cl_mlp_args& a, int grid, hipStream_t st) {
-    using SM = NSmem<G, NWAVES>;
-    const size_t sm = (size_t)SM::total * sizeof(float);
-    if (sm > 160 * 1024) return -3;
-    auto kern = elbo_narrow_kernel<G, KS, NWAVES, PACKED>;
-    static std::atomic<size_t> configured{0};
-    size_t have = configured.load(std::memory_order_acquire);
-    if (have < sm) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
-    }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), sm, st, a);
-    return (int)hipGetLastError();
+static int launch_narrow_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if (c.name != nullptr)
+        return snprintf(c.name, c.name_n, "elbo_narrow_kernel<%d, %d, %d, %s>%s", G, KS, NWAVES, PACKED ? "true" : "false",
+                        a.dzf_obs != nullptr ? " (deterministic stores)" : "");
+    return cl_launch_lds<elbo_narrow_kernel<G, KS, NWAVES, PACKED>>(dim3(c.grid), dim3(64 * NWAVES), (size_t)NSmem<G, NWAVES>::total * sizeof(float), c.st, a);
 }
 
 // 1 = this geometry runs on the narrow kernel (full ELBO step; plain observation layout, or the packed one of single-pass Laue)
@@ -719,39 +658,17 @@ int cl_narrow_supports(const cl_mlp_args& a) {
            a.dH_ext == nullptr && a.dX_out == nullptr && (a.row_map != nullptr || a.gmeta == nullptr);
 }
 
-// name of the instance cl_launch_narrow runs (cl_mlp_kernel_name)
-int cl_narrow_kernel_name(const cl_mlp_args& a, char* out, size_t n) {
-    const int m = a.w > a.d ? a.w : a.d;
-    return snprintf(out, n, "elbo_narrow_kernel<2, %d, 8, %s>%s", m <= 8 ? 2 : (m <= 12 ? 3 : 4), a.row_map != nullptr ? "true" : "false",
-                    a.dzf_obs != nullptr ? " (deterministic stores)" : "");
-}
-
 template <bool PACKED>
-static int launch_narrow_ks(const cl_mlp_args& a, int grid, hipStream_t st) {
+static int launch_narrow_ks(const cl_mlp_args& a, const cl_launch_ctx& c) {
     const int m = a.w > a.d ? a.w : a.d;               // the metadata layer takes the same number of k-steps as the hidden ones
-    if (m <= 8) return launch_narrow_one<2, 2, 8, PACKED>(a, grid, st);
-    if (m <= 12) return launch_narrow_one<2, 3, 8, PACKED>(a, grid, st);
+    if (m <= 8) return launch_narrow_one<2, 2, 8, PACKED>(a, c);
+    if (m <= 12) return launch_narrow_one<2, 3, 8, PACKED>(a, c);
     // widths 13 .. 15: four k-steps.  Two waves per SIMD spill ~90 registers at that size; a one-wave-per-SIMD instance (<2, 4, 4>: no spill)
     // measured no faster in round 3 (DESIGN / NOTEBOOK: 20 x 13 1.60 vs 1.56 ms) and is not instantiated any more
-    return launch_narrow_one<2, 4, 8, PACKED>(a, grid, st);
+    return launch_narrow_one<2, 4, 8, PACKED>(a, c);
 }
 
-int cl_launch_narrow(const cl_mlp_args& a, int grid, hipStream_t st) {
-    if (!cl_narrow_supports(a)) return -2;
-    if (a.n_pad % CL_MLP_TILE != 0 || a.n_pad <= 0) return -1;
-    if (4ull * (unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad >= (1ull << 32) ||
-        4ull * (unsigned long long)a.R * (unsigned long long)a.S >= (1ull << 32))
-        return -4;
-    if (grid < 1) return -1;
-    if (a.dzf_obs != nullptr) {          // deterministic mode: stores per (observation, sample) / observation / workgroup / wave (Evans-2011 terms)
-        if (a.ev11 != nullptr && a.ev11_part == nullptr) return -2;      // (the Evans-2011 gradients need their per-wave slots)
-        if (a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr)) return -1;
-        if (4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-    }
-    if (a.row_map != nullptr) {
-        if (a.n_obs != a.n_pad || (a.gmeta != nullptr && a.tile_gmax == nullptr)) return -1;
-        if ((a.eta != nullptr || a.ipred_out != nullptr) && 4ull * (unsigned long long)a.n_pad * (unsigned long long)a.S >= (1ull << 32)) return -4;
-        return launch_narrow_ks<true>(a, grid, st);
-    }
-    return launch_narrow_ks<false>(a, grid, st);
+// (deterministic mode -- dzf_obs given --: stores per (observation, sample) / observation / workgroup / wave (Evans-2011 terms))
+int cl_launch_narrow(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    return a.row_map != nullptr ? launch_narrow_ks<true>(a, c) : launch_narrow_ks<false>(a, c);
 }

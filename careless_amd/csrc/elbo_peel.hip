@@ -16,7 +16,6 @@
 #include <hip/hip_runtime.h>
 #include "cl_kernels.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 

@@ -37,7 +37,6 @@
 #include "cl_math.h"
 #include "cl_kernels.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef CL_WIDE_DIAG
 #define CL_WIDE_DIAG 0      /* diagnostic builds only (WRONG results): 1 = the stream kernels read no row operand from global memory, 2 = they store no
@@ -103,7 +102,6 @@ struct GemmArgs {
     float* hd_part;                                                 // [z][2 M + 2] partial sums of (dWo | dbo)
 };
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // global -> registers: one tile of an operand (ROWS x BK), zero outside [0, rows_lim) x [0, k_lim)
 template <int ROWS, bool KMAJOR>
@@ -954,23 +952,13 @@ template <int NA>
 int launch_stream2(const Stream2Args& s, hipStream_t st) {
     constexpr int NA0 = NA, NA1 = NA;
     const size_t sm = (size_t)(16 * NA1 * SKP + 3 * 16 * NA1 + 16 * NA0 * (S0P + 1)) * sizeof(float);
-    auto kern = wide_stream2_kernel<NA>;
-    static std::atomic<size_t> configured{0};
-    size_t have = configured.load(std::memory_order_acquire);
-    if (have < sm) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
-    }
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const long long nblk = (s.n + 15) >> 4;
     long long grid = (nblk + 7) / 8;
     if (grid > 2LL * cus) grid = 2LL * cus;
     if (grid < 1) grid = 1;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), sm, st, s);
-    return (int)hipGetLastError();
+    return cl_launch_lds<wide_stream2_kernel<NA>>(dim3((unsigned)grid), dim3(512), sm, st, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1347,18 +1335,8 @@ static long long sq_grid(long long n) {
 template <bool WKM, int EPI, int NA, bool PRE, bool WG0 = false, bool HEADB = false, bool LIK = false>
 int launch_sq_n(const StreamArgs& s, hipStream_t st) {
     const size_t sm = (size_t)(16 * NA * SKP + 3 * 16 * NA + (PRE ? 16 * NA * (S0P + 1) : 0)) * sizeof(float);
-    auto kern = wide_sq_kernel<WKM, EPI, NA, PRE, WG0, HEADB, LIK>;
-    static std::atomic<size_t> configured{0};
-    size_t have = configured.load(std::memory_order_acquire);
-    if (have < sm) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
-    }
     const long long grid = sq_grid(s.n);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), sm, st, s);
-    return (int)hipGetLastError();
+    return cl_launch_lds<wide_sq_kernel<WKM, EPI, NA, PRE, WG0, HEADB, LIK>>(dim3((unsigned)grid), dim3(512), sm, st, s);
 }
 
 template <bool WKM, int EPI, bool PRE, bool WG0 = false, bool HEADB = false, bool LIK = false>
@@ -1376,23 +1354,13 @@ int launch_stream_n(const StreamArgs& s, hipStream_t st) {
     const int NA = (s.N + 15) >> 4;
     // weights, bias, the fused head's two rows; the dgrad with a recomputed mask adds the first layer's image and bias
     const size_t sm = (size_t)(16 * NA * SKP + 3 * 16 * NA + (PRE ? 16 * NA * (S0P + 1) : 0)) * sizeof(float);
-    auto kern = wide_stream_kernel<WKM, EPI, NAT, GRP, PRE>;
-    static std::atomic<size_t> configured{0};
-    size_t have = configured.load(std::memory_order_acquire);
-    if (have < sm) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        while (have < sm && !configured.compare_exchange_weak(have, sm, std::memory_order_release, std::memory_order_acquire)) {}
-    }
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const long long nblk = (s.n + 15) >> 4;
     long long grid = s.seg != nullptr ? (long long)s.n_groups : (nblk + 7) / 8;
     if (grid > 2LL * cus) grid = 2LL * cus;          // two 8-wave workgroups per CU (2 x 67.6 KB of LDS at 128 x 128)
     if (grid < 1) grid = 1;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), sm, st, s);
-    return (int)hipGetLastError();
+    return cl_launch_lds<wide_stream_kernel<WKM, EPI, NAT, GRP, PRE>>(dim3((unsigned)grid), dim3(512), sm, st, s);
 }
 
 template <bool WKM, int EPI>

@@ -12,7 +12,9 @@
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); every call only enqueues;
  *   - return value: 0 = ok, < 0 = invalid argument (-1 shape, -2 unsupported scaler geometry, -3 LDS budget, -4 shard >= 4 GiB),
  *     > 0 = hipError_t from the launch;  nothing throws, nothing allocates persistent device memory;
- *   - no global mutable state besides the loaded code object: calls are re-entrant across streams;
+ *   - no global mutable state besides the loaded code object, with two exceptions, both monotonic and safe to race on: the
+ *     per-kernel-instance mark of the largest dynamic-LDS size configured so far (csrc/cl_kernels.h: cl_launch_lds) and the
+ *     occupancy cache of cl_frozen_rows (csrc/elbo_frozen.hip: frozen_blocks); calls are re-entrant across streams;
  *   - a NULL noise pointer (u_f / eta) selects the in-kernel counter-based generator keyed by
  *     (seed, step, sample, global element index), so results are independent of the number of GPUs.
  *
@@ -243,6 +245,10 @@ int cl_mlp_route(const cl_mlp_args* args, int mode);
  * rocprofv3 kernel trace lists; "(unsupported)" for CL_ROUTE_NONE.  Writes at most n bytes (NUL-terminated), returns the length of
  * the name or < 0 for bad arguments.  No reference counterpart. */
 int cl_mlp_kernel_name(const cl_mlp_args* args, int mode, char* out, size_t n);
+/* Diagnostics: the return code the call of `mode` would give for these arguments and this grid WITHOUT launching -- 0 where it would
+ * reach the launch, else its negative code (-1, -2, -4; -3 is found at the launch itself).  The entry checks of that call, the route
+ * and the one argument check every route shares; pointers are only tested against NULL.  Needs no device.  No reference counterpart. */
+int cl_mlp_check(const cl_mlp_args* args, int mode, int grid);
 /* grad_mlp[P] += sum over the `nparts` workgroup partials, in index order (deterministic) */
 int cl_reduce_partials(const float* partials, int nparts, int P, float* grad_mlp, const int* stop_flag, void* stream);
 

@@ -1,0 +1,87 @@
+"""Are the gfx950 kernels of two builds of libcareless_hip.so the same, instruction for instruction?  (No GPU needed.)
+
+    python scripts/diff_device_code.py OLD.so NEW.so
+
+A change that touches host code only -- or moves a device helper from one file to another -- must leave every kernel as it was: then the
+speed of the kernels is the parent's by construction.  Both libraries are unbundled and disassembled (the tools of
+scripts/check_lane_isa.py); kernels are matched by name (demangled where llvm-cxxfilt is installed), without the suffix the compiler
+derives from the source path for kernels with internal linkage.  Compared per kernel: the instruction sequence (mnemonic and operands; addresses and the comments
+derived from them are dropped) and the kernel descriptor's resources (register counts, scratch and LDS size).  Exit code 1 and one
+line per kernel that is missing, extra or different.
+"""
+from __future__ import annotations
+
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from collections import defaultdict
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_lane_isa import OBJDUMP, demangle, parse_objdump, unbundle  # noqa: E402
+
+READELF = os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf")
+RESOURCES = (".sgpr_count", ".vgpr_count", ".agpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size",
+             ".group_segment_fixed_size", ".kernarg_segment_size", ".max_flat_workgroup_size", ".wavefront_size")
+_UNIQUE = re.compile(r"\.(intern|static|anon)\.[0-9A-Za-z_]+|__[0-9a-f]{8,}(?=\b)")
+
+
+def resources(co: str) -> dict:
+    """mangled kernel name -> the resource fields of its entry in the code object's metadata note"""
+    txt = subprocess.run([READELF, "--notes", co], stdout=subprocess.PIPE, text=True, check=True).stdout
+    out, cur = {}, {}
+    for ln in txt.split("\n"):
+        m = re.match(r"\s*(?:- )?(\.[a-z_]+):\s*(\S+)\s*$", ln)
+        if not m:
+            continue
+        if ln.lstrip().startswith("- ") and cur.get(".symbol"):      # the next kernel's record begins
+            out[cur[".symbol"][:-len(".kd")]] = cur
+            cur = {}
+        cur[m.group(1)] = m.group(2).strip("'\"")
+    if cur.get(".symbol"):
+        out[cur[".symbol"][:-len(".kd")]] = cur
+    return {k: tuple(v.get(f) for f in RESOURCES) for k, v in out.items()}
+
+
+def kernels_of(lib: str) -> dict:
+    """demangled name (path-derived suffix stripped) -> sorted list of (resources, instruction texts), one per code object that holds it"""
+    out = defaultdict(list)
+    with tempfile.TemporaryDirectory() as d:
+        for co in unbundle(lib, d):
+            txt = subprocess.run([OBJDUMP, "-d", co], stdout=subprocess.PIPE, text=True, check=True).stdout
+            ks = {k: v for k, v in parse_objdump(txt).items() if v[1]}
+            res = resources(co)
+            for k, name in demangle(list(ks)).items():
+                out[_UNIQUE.sub("", name)].append((res.get(k), tuple(i.text for i in ks[k][1])))
+    return {k: sorted(v, key=repr) for k, v in out.items()}
+
+
+def main() -> int:
+    if len(sys.argv) != 3:
+        print(__doc__)
+        return 2
+    old, new = kernels_of(sys.argv[1]), kernels_of(sys.argv[2])
+    bad = [f"only in {sys.argv[1]}: {k}" for k in sorted(set(old) - set(new))] + [f"only in {sys.argv[2]}: {k}" for k in sorted(set(new) - set(old))]
+    for k in sorted(set(old) & set(new)):
+        if old[k] == new[k]:
+            continue
+        if len(old[k]) != len(new[k]):
+            bad.append(f"{k}: {len(old[k])} copies against {len(new[k])}")
+            continue
+        for (r0, i0), (r1, i1) in zip(old[k], new[k]):
+            if r0 != r1:
+                bad.append(f"{k}: resources {dict(zip(RESOURCES, r0 or ()))} against {dict(zip(RESOURCES, r1 or ()))}")
+            if i0 != i1:
+                at = next((n for n, (a, b) in enumerate(zip(i0, i1)) if a != b), min(len(i0), len(i1)))
+                bad.append(f"{k}: {len(i0)} against {len(i1)} instructions, first difference at #{at}: "
+                           f"`{i0[at] if at < len(i0) else '(end)'}` against `{i1[at] if at < len(i1) else '(end)'}`")
+    for b in bad:
+        print(b)
+    n0, n1 = sum(len(v) for v in old.values()), sum(len(v) for v in new.values())
+    print(f"{n0} kernels against {n1}: {len(bad)} differ")
+    return 1 if bad or n0 != n1 else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

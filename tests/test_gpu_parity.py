@@ -404,6 +404,19 @@ def test_random_shapes_on_the_lane_kernel(name):
     _assert_grads(g_hip, grads, prob, name)
 
 
+def test_dynamic_lds_mark_is_kept_per_kernel_instance():
+    """The launch helper (csrc/cl_kernels.h: cl_launch_lds) remembers, per kernel INSTANCE, the largest dynamic-LDS size it has
+    configured.  In one process and in this order: the LDS-row lane instance of width 10 at its smallest need (16 metadata columns),
+    the same instance at its largest (31 columns: the mark has to rise), then another instance of the same function-pointer type
+    (width 4 on 31 columns: it has to be configured on its own account).  A mark that did not rise, or one shared between instances,
+    shows as a launch error code; each step is held to the oracle like every other lane shape."""
+    for w, d in ((10, 16), (10, 31), (4, 31)):
+        out, grads, ipred, terms, g_hip, eng, prob = _run_case(dict(N=256, R=32, d0=d, L=20, w=w, S=1, perturb=0.02))
+        # (the run above injects noise: the FULL form of the instance the production step is named after)
+        assert eng.d == d and eng.kernel_name().startswith(f"elbo_lane_kernel<{w}, 0, false, "), (eng.d, eng.kernel_name())
+        _assert_grads(g_hip, grads, prob, f"lds_mark_20x{w}_d{d}")
+
+
 def _random_engine_cases(n=12, seed=11):
     """Seeded random draws over everything the engine routes: widths 1 .. 100 (lane / narrow / 32- and 64-wide fused instances,
     chains of launches for deep scalers, the own GEMM kernels of csrc/wide_gemm.hip beyond width 64), depths 1 .. 24, 1 .. 40 metadata columns, 1 .. 12 MC samples,

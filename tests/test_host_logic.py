@@ -273,7 +273,8 @@ def test_pack_by_image_and_pack_laue_layouts():
 
 
 def test_kernel_name_follows_the_librarys_routing():
-    """`cl_mlp_kernel_name` restates `cl_launch_mlp`'s routing inside the library (bench.py labels its roofline row with it): the
+    """`cl_mlp_kernel_name` is printed by the code that selects the instance: it runs `cl_launch_mlp`'s own dispatch with a name sink,
+    and the leaf that would launch prints its template parameters instead (bench.py labels its roofline row with it): the
     CLI-default scaler runs lane-per-observation up to 31 metadata columns and any number of MC samples, other depths / widths 11-15
     on the narrow kernel, everything else on the 16- / 32- / 64-wide fused instances.  Host function: no GPU needed."""
     import ctypes as C
@@ -370,6 +371,137 @@ def test_kernel_name_follows_the_librarys_routing():
         name(mode, **kw)
         seen.add(route(mode, **kw))
     assert seen == set(range(_lib.CL_ROUTE_MLP_CHAIN_DET + 1)) - {_lib.CL_ROUTE_MLP_PACKED_DET, _lib.CL_ROUTE_MLP_CHAIN_DET}   # (two flags each: above)
+
+
+def test_one_argument_check_answers_for_every_route():
+    """`cl_mlp_check`: the return code a scaler launch would give, without the launch -- the entry checks of the call, the route, and
+    `mlp_check`, the one table of argument checks every route shares (csrc/elbo_mlp.hip).  For each of the twelve routes an accepted
+    launch and a rejected one per clause that applies to it, with the exact code; precedence: -1 tile / grid, -2 no route, the route's
+    -1 clauses, the -4 bounds.  Pointer fields are only tested against NULL and nothing is launched: holds with or without a GPU."""
+    import ctypes as C
+    from careless_amd import _lib
+    lib = _lib.get_lib()
+    mode_base = {0: dict(refl_id=1, iobs=1, sig=1, z_f=1, dz_f=1, partials=1, scalars=1), 1: dict(loc_out=1, sig_out=1), 2: dict(dO_ext=1, partials=1)}
+    drop = object()
+
+    def check(route, code, mode=0, grid=4, **kw):
+        f = dict(mode_base[mode], meta_t=1, mlp=1, n_obs=256, n_pad=256, S=2, R=50)
+        f.update(kw)
+        f = {k: v for k, v in f.items() if v is not drop}
+        assert _lib.mlp_route(lib, mode, **f) == route, (route, mode, kw)
+        assert lib.cl_mlp_check(C.byref(_lib.MlpArgs(**f)), mode, grid) == code, (route, code, mode, kw)
+
+    BIG_S = 1 << 22                     # n_pad * S * 4 = 2^32 at n_pad = 256: the per-(observation, sample) arrays
+    BIG_R = 1 << 29                     # R * S * 4 = 2^32 at S = 2: z_f / dz_f
+    BIG_N = 128 << 20                   # n_pad * 8 metadata rows * 4 = 2^32 (a multiple of the tile; R * S and n_pad * S stay below)
+    big_n = dict(n_obs=BIG_N, n_pad=BIG_N, S=1)
+    imgl = dict(n_imgl=2, row_map=1, imgl=1, d_imgl=1, tile_img=1, n_images=7, use_img=0)
+    det = dict(dzf_obs=1, nll_part=1)
+    lane, narrow, mlp = dict(d=5, w=10, L=20), dict(d=5, w=13, L=12), dict(d=40, w=20, L=10)
+
+    assert lib.cl_mlp_check(None, 0, 4) < 0
+    assert lib.cl_mlp_check(C.byref(_lib.MlpArgs(meta_t=1, mlp=1, n_obs=256, n_pad=256, d=5, w=10, L=20)), 3, 4) == -1       # no such mode
+    # the entry checks and tile / grid validity come first: -1 whatever the route, CL_ROUTE_NONE included
+    check(_lib.CL_ROUTE_LANE, -1, z_f=drop, **lane)
+    check(_lib.CL_ROUTE_LANE, -1, n_pad=300, **lane)
+    check(_lib.CL_ROUTE_LANE, -1, n_obs=0, **lane)
+    check(_lib.CL_ROUTE_LANE, -1, grid=0, **lane)
+    check(_lib.CL_ROUTE_NONE, -1, grid=0, d=5, w=65, L=2)
+    check(_lib.CL_ROUTE_NONE, -2, d=5, w=65, L=2)
+    check(_lib.CL_ROUTE_NONE, -2, S=BIG_S, d=5, w=65, L=2)
+    check(_lib.CL_ROUTE_NONE, -2, ev11=1, **det, **lane)             # (the Evans-2011 gradients need their per-wave slots: no route)
+    # the lane and the narrow kernel: plain and packed layout, deterministic stores
+    for route, shape in ((_lib.CL_ROUTE_LANE, lane), (_lib.CL_ROUTE_NARROW, narrow)):
+        check(route, 0, **shape)
+        check(route, 0, grid=1000, **shape)                        # (a grid larger than the tiles is clamped, not refused)
+        check(route, 0, row_map=1, gmeta=1, tile_gmax=1, eta=1, **shape)
+        check(route, 0, use_img=1, image_id=1, img=1, d_img=1, dimg_obs=1, ev11=1, ev11_part=1, **det, **shape)
+        check(route, -1, row_map=1, n_obs=200, **shape)
+        check(route, -1, row_map=1, gmeta=1, **shape)
+        check(route, -1, dzf_obs=1, **shape)                       # no nll_part
+        check(route, -1, use_img=1, image_id=1, img=1, d_img=1, **det, **shape)       # no dimg_obs
+        check(route, -4, **big_n, **shape)
+        check(route, -4, R=BIG_R, **shape)
+        check(route, 0, S=BIG_S, R=1, **shape)                     # plain layout, atomics: no array of n_pad * S elements is addressed
+        check(route, 0, S=BIG_S, R=1, row_map=1, **shape)
+        check(route, -4, S=BIG_S, R=1, row_map=1, eta=1, **shape)
+        check(route, -4, S=BIG_S, R=1, row_map=1, ipred_out=1, **shape)
+        check(route, -4, S=BIG_S, R=1, **det, **shape)
+        check(route, -1, S=BIG_S, R=1, dzf_obs=1, **shape)         # precedence: a bound crossed AND nll_part missing -> -1
+        check(route, -1, R=BIG_R, dzf_obs=1, **shape)
+        check(route, -1, R=BIG_R, row_map=1, n_obs=200, **shape)    # ... the same for a packed-layout clause
+    # ... with per-image layers
+    check(_lib.CL_ROUTE_LANE_IMGL, 0, eta=1, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, 0, **det, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -1, n_obs=200, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -1, dzf_obs=1, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -4, **big_n, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -4, R=BIG_R, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, 0, S=BIG_S, R=1, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -4, S=BIG_S, R=1, ipred_out=1, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -4, S=BIG_S, R=1, **det, **lane, **imgl)
+    check(_lib.CL_ROUTE_LANE_IMGL, -1, S=BIG_S, R=1, dzf_obs=1, **lane, **imgl)
+    # ... a head-less layer block: forward (act_out) and backward (dH_ext); it reads no reflection, so R * S is no bound of it
+    check(_lib.CL_ROUTE_LANE_BLOCK, 0, mode=1, act_out=1, loc_out=drop, sig_out=drop, **lane)
+    check(_lib.CL_ROUTE_LANE_BLOCK, 0, mode=2, dH_ext=1, dO_ext=drop, **lane)
+    check(_lib.CL_ROUTE_LANE_BLOCK, 0, mode=2, dH_ext=1, dO_ext=drop, R=BIG_R, **lane)
+    check(_lib.CL_ROUTE_LANE_BLOCK, -1, mode=1, grid=0, act_out=1, loc_out=drop, sig_out=drop, **lane)
+    check(_lib.CL_ROUTE_LANE_BLOCK, -4, mode=1, act_out=1, loc_out=drop, sig_out=drop, **big_n, **lane)
+    # the 16- / 32- / 64-wide units: plain layout
+    for mode in (0, 1, 2):
+        check(_lib.CL_ROUTE_MLP, 0, mode=mode, **mlp)
+        check(_lib.CL_ROUTE_MLP, -1, mode=mode, n_pad=300, **mlp)
+        check(_lib.CL_ROUTE_MLP, -4, mode=mode, R=BIG_R, **mlp)
+        check(_lib.CL_ROUTE_MLP, -4, mode=mode, **big_n, **dict(mlp, d=5))
+    check(_lib.CL_ROUTE_MLP, 0, S=BIG_S, R=1, eta=1, **mlp)
+    # ... packed layout
+    check(_lib.CL_ROUTE_MLP_PACKED, 0, row_map=1, gmeta=1, tile_gmax=1, ipred_out=1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, 0, mode=1, row_map=1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -1, row_map=1, n_obs=200, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -1, row_map=1, n_imgl=-1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -1, row_map=1, gmeta=1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -1, mode=1, row_map=1, gmeta=1, tile_gmax=1, **mlp)      # group sizes: the full step only
+    check(_lib.CL_ROUTE_MLP_PACKED, 0, S=BIG_S, R=1, row_map=1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -4, S=BIG_S, R=1, row_map=1, eta=1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -4, R=BIG_R, row_map=1, **mlp)
+    check(_lib.CL_ROUTE_MLP_PACKED, -4, row_map=1, **big_n, **dict(mlp, d=5))
+    # ... per-image layers
+    wide_imgl = dict(imgl, **dict(mlp, L=4))
+    check(_lib.CL_ROUTE_MLP_IMGL, 0, gmeta=1, tile_gmax=1, **wide_imgl)
+    check(_lib.CL_ROUTE_MLP_IMGL, 0, mode=1, **dict(wide_imgl, d_imgl=0))
+    check(_lib.CL_ROUTE_MLP_IMGL, -1, **dict(wide_imgl, row_map=0))
+    check(_lib.CL_ROUTE_MLP_IMGL, -1, n_obs=200, **wide_imgl)
+    for missing in (dict(imgl=0), dict(tile_img=0), dict(n_images=0), dict(use_img=1, image_id=1, img=1, d_img=1), dict(d_imgl=0)):
+        check(_lib.CL_ROUTE_MLP_IMGL, -1, **dict(wide_imgl, **missing))
+    check(_lib.CL_ROUTE_MLP_IMGL, -1, gmeta=1, **wide_imgl)
+    check(_lib.CL_ROUTE_MLP_IMGL, -1, mode=1, gmeta=1, tile_gmax=1, **wide_imgl)
+    check(_lib.CL_ROUTE_MLP_IMGL, -4, S=BIG_S, R=1, ipred_out=1, **wide_imgl)
+    check(_lib.CL_ROUTE_MLP_IMGL, -4, R=BIG_R, **wide_imgl)
+    check(_lib.CL_ROUTE_MLP_IMGL, -4, **big_n, **dict(wide_imgl, d=5))
+    # ... a block of a layer-block chain: activations leave the forward launch, the gradient enters the backward one
+    chain = dict(d=5, w=14, L=20)
+    check(_lib.CL_ROUTE_MLP_CHAIN, 0, mode=1, act_out=1, loc_out=drop, sig_out=drop, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, 0, mode=2, dH_ext=1, dX_out=1, dO_ext=drop, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, 0, dX_out=1, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, -1, mode=0, act_out=1, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, -1, mode=2, act_out=1, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, -1, mode=0, dH_ext=1, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, -1, mode=1, dH_ext=1, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, -4, dX_out=1, R=BIG_R, **chain)
+    check(_lib.CL_ROUTE_MLP_CHAIN, -4, dX_out=1, **big_n, **chain)
+    # ... the deterministic compilations: every store target, and the per-(observation, sample) records below 4 GiB
+    for route, kw in ((_lib.CL_ROUTE_MLP_DET, mlp), (_lib.CL_ROUTE_MLP_PACKED_DET, dict(mlp, row_map=1)), (_lib.CL_ROUTE_MLP_CHAIN_DET, dict(d=10, w=10, L=10, dX_out=1))):
+        check(route, 0, **det, **kw)
+        check(route, 0, use_img=1, image_id=1, img=1, d_img=1, dimg_obs=1, ev11=1, ev11_part=1, **det, **kw)
+        check(route, -1, dzf_obs=1, **kw)
+        check(route, -1, use_img=1, image_id=1, img=1, d_img=1, **det, **kw)
+        check(route, -4, S=BIG_S, R=1, **det, **kw)
+        check(route, -1, S=BIG_S, R=1, dzf_obs=1, **kw)            # precedence again
+        check(route, -4, R=BIG_R, **det, **kw)
+        check(route, -4, **det, **big_n, **dict(kw, d=5) if route != _lib.CL_ROUTE_MLP_CHAIN_DET else dict(kw, d=5, w=14, L=20))
+    check(_lib.CL_ROUTE_MLP_PACKED_DET, -2, n_obs=200, **det, **dict(mlp, row_map=1))     # (this unit has always answered -2 to padding rows)
+    check(_lib.CL_ROUTE_MLP_PACKED_DET, -1, gmeta=1, **det, **dict(mlp, row_map=1))
+    check(_lib.CL_ROUTE_MLP_PACKED_DET, 0, gmeta=1, tile_gmax=1, **det, **dict(mlp, row_map=1))
 
 
 def test_scaler_plan_follows_the_routing_tables():
