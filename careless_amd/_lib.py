@@ -24,6 +24,9 @@ CL_EV11_WAVES = 8               # wave slots per workgroup in ev11_part (include
 (CL_ROUTE_NONE, CL_ROUTE_LANE, CL_ROUTE_LANE_IMGL, CL_ROUTE_LANE_BLOCK, CL_ROUTE_NARROW, CL_ROUTE_MLP, CL_ROUTE_MLP_PACKED, CL_ROUTE_MLP_IMGL,
  CL_ROUTE_MLP_CHAIN, CL_ROUTE_MLP_DET, CL_ROUTE_MLP_PACKED_DET, CL_ROUTE_MLP_CHAIN_DET) = range(12)
 
+# cl_mlp_epilogue: the sampling epilogue of the instance a scaler launch runs (enum cl_epilogue)
+CL_EPI_GENERIC, CL_EPI_PLAIN_NORMAL, CL_EPI_PLAIN_STUDENTT = range(3)
+
 _vp = C.c_void_p
 
 
@@ -159,6 +162,7 @@ EXPORTS = {
     "cl_mlp_forward": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
     "cl_mlp_backward_ext": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
     "cl_mlp_route": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
+    "cl_mlp_epilogue": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
     "cl_mlp_kernel_name": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_char_p, C.c_size_t]),
     "cl_mlp_check": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_int]),
     "cl_wide_ld": (C.c_int, [C.c_int]),
@@ -281,6 +285,12 @@ def mlp_route(lib, mode: int, **fields) -> int:
     """`cl_mlp_route` of a launch with these `cl_mlp_args` fields (pointer fields: non-zero = a buffer is given); no device needed."""
     a = MlpArgs(**fields)
     return int(lib.cl_mlp_route(C.byref(a), mode))
+
+
+def mlp_epilogue(lib, mode: int, **fields) -> int:
+    """`cl_mlp_epilogue` of a launch with these `cl_mlp_args` fields (as `mlp_route`); no device needed."""
+    a = MlpArgs(**fields)
+    return int(lib.cl_mlp_epilogue(C.byref(a), mode))
 
 
 def ptr(t) -> Optional[int]:

@@ -97,6 +97,11 @@ int cl_mlp_route(const cl_mlp_args* a, int mode) {
     return (int)mlp_route(*a, mode);
 }
 
+int cl_mlp_epilogue(const cl_mlp_args* a, int mode) {
+    if (a == nullptr || mode < 0 || mode > 2) return -1;
+    return (int)mlp_epilogue(*a, mode, mlp_route(*a, mode));
+}
+
 int cl_mlp_kernel_name(const cl_mlp_args* a, int mode, char* out, size_t n) {
     if (a == nullptr || out == nullptr || n == 0 || mode < 0 || mode > 2) return -1;
     return cl_mlp_kernel_name_of(*a, mode, out, n);

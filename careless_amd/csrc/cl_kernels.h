@@ -20,6 +20,7 @@ struct cl_launch_ctx {
 // A scaler launch: route, argument check, grid clamp, dispatch (elbo_mlp.hip).  The launchers below it check nothing.
 int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st);
 cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // the launcher cl_launch_mlp hands a launch to
+cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r);                // the epilogue of the instance that launcher runs (cl_mlp_epilogue)
 int mlp_check(const cl_mlp_args& a, int mode, int grid, cl_route r);                 // 0, or the negative code of the launch (every argument check of every route)
 int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // the name of the instance the launch runs
 // the eight compilations of elbo_mlp.hip (build.py), one launcher each

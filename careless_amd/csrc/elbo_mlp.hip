@@ -142,9 +142,15 @@ struct AccPlan {
 //     in absolute time and no faster than width 32 (profiles/r5_envelope_widths_16_64.txt).
 // DET: names the deterministic compilation's instances (their bodies differ by preprocessor: without a template argument of their own
 // they would be the same symbols as the plain unit's and the linker would keep one of the two)
-template <int WP, int DP, int LMAX, int MODE, bool IMGL, bool CHAIN = false, bool ILAY = IMGL, int KS = 4, bool DET = (CL_DET != 0)>
+// EPI: the sampling epilogue (enum cl_epilogue).  CL_EPI_GENERIC decides per MC sample what is uniform for the whole launch (likelihood
+//     kind, Evans-2011 model, injected noise or Philox, noise_row, ipred_out, any S); the two plain values compile the common launch --
+//     in-kernel noise keyed by the row, none of the optional buffers, S <= 8 (epi_plain, below), the likelihood kind a constant -- as
+//     straight-line code for the lane's two samples.  64-wide full-step instances of the plain unit only.
+template <int WP, int DP, int LMAX, int MODE, bool IMGL, bool CHAIN = false, bool ILAY = IMGL, int KS = 4, bool DET = (CL_DET != 0),
+          int EPI = CL_EPI_GENERIC>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void elbo_mlp_kernel(const cl_mlp_args A) {
+    static_assert(EPI == CL_EPI_GENERIC || (WP == 64 && MODE == 0 && !IMGL && !CHAIN && !DET), "plain epilogue: 64-wide full step of the plain unit");
     using SL = SmemLayout<WP, DP, LMAX>;
     constexpr int FB = WP / 16;          // 16-feature blocks of a hidden layer
     constexpr int KS1 = DP / 4;          // MFMA k-steps of the first layer (4 metadata features per step)
@@ -272,7 +278,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
     // Evans-2011 error model: Sd* = softplus(raw); per-lane gradient accumulators
     cl_ev11 ev = {1.0f, 0.0f, 0.0f};
     float ev_g0 = 0.0f, ev_g1 = 0.0f, ev_g2 = 0.0f;
-    const bool use_ev11 = (MODE == 0) && (A.ev11 != nullptr);
+    const bool use_ev11 = (EPI == CL_EPI_GENERIC) && (MODE == 0) && (A.ev11 != nullptr);
     if (use_ev11) { ev = cl_ev11_from_raw(A.ev11); }
 
     const int ntiles = A.n_pad / CL_TILE;
@@ -448,8 +454,9 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
         unsigned dzo = 4u * (unsigned)drow * (unsigned)S;
         if (MODE == 0 && rid >= 0 && E0->det_slot != nullptr) dzo = 4u * (unsigned)E0->det_slot[drow] * (unsigned)S;
 #endif
-        const float* __restrict__ eta_t = E0->eta ? (IMGL ? E0->eta : E0->eta + (size_t)tile_u * CL_TILE * S) : nullptr;
-        float* __restrict__ ipred_t = E0->ipred_out ? (IMGL ? E0->ipred_out : E0->ipred_out + (size_t)tile_u * CL_TILE * S) : nullptr;
+        // (plain epilogue: the launch has neither, and the tile's gathers are the image scale and the two z_f values)
+        const float* __restrict__ eta_t = (EPI == CL_EPI_GENERIC && E0->eta) ? (IMGL ? E0->eta : E0->eta + (size_t)tile_u * CL_TILE * S) : nullptr;
+        float* __restrict__ ipred_t = (EPI == CL_EPI_GENERIC && E0->ipred_out) ? (IMGL ? E0->ipred_out : E0->ipred_out + (size_t)tile_u * CL_TILE * S) : nullptr;
         if (MODE == 0 && rid >= 0) {
             if (E0->use_img && img > 0) aim = ld_uo(E0->img, 4u * (unsigned)(img - 1));
             if (qe < S) zf0 = ld_uo(E0->z_f, zoff + 4u * qe);
@@ -457,7 +464,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
             if (eta_t != nullptr) {
                 if (qe < S) et0 = ld_uo(eta_t, eoff + 4u * qe);
                 if (qe + 4 < S) et1 = ld_uo(eta_t, eoff + 4u * (qe + 4));
-            } else if (!IMGL && E0->noise_row != nullptr) {
+            } else if (EPI == CL_EPI_GENERIC && !IMGL && E0->noise_row != nullptr) {
                 // plain layout over rows that are not a contiguous range of the caller's (a rank that owns a reflection range takes
                 // every observation of those reflections): the row's GLOBAL number, the key of the in-kernel noise, rides in the
                 // register the injected noise would use
@@ -649,6 +656,46 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                         pds += dt * eta;
                         pda += dzs * tq;
                     }
+                }
+            } else if (EPI != CL_EPI_GENERIC) {
+                // ---- plain epilogue: a lane's samples are s = qe and s = qe + 4 (S <= 8), straight-line, the same expressions in the same
+                //      order as the loop below.  Both z_f values came with the tile-start gathers, so the sample code holds no load and no
+                //      vmcnt wait; the scalar arguments are read once, in front of the first sample; both dz_f atomics leave after both
+                //      samples' arithmetic (on the loop latch the next sample's first wait also waited for the atomic's acknowledgement).
+                // The tile-start gathers are awaited HERE, on every path.  Waited for only inside the branch below, they stay outstanding on
+                // the path around it, their registers get reused behind the join, and hipcc puts an s_waitcnt vmcnt(0) there -- which on
+                // the path through the branch waits for the acknowledgement of the two atomics just issued.
+                asm volatile("" ::"v"(aim), "v"(zf0), "v"(zf1));
+                if (rid >= 0 && qe < S) {
+                    constexpr int KIND = (EPI == CL_EPI_PLAIN_NORMAL) ? CL_LIK_NORMAL : CL_LIK_STUDENTT;
+                    const float shift = E->shift, w_ll = E->w_ll, dof = E->dof, lik_const = E->lik_const;
+                    float* __restrict__ const dzf = E->dz_f;
+                    // hardware reciprocal and logarithm (1 ulp): sigma is an input, its log enters the NLL additively
+                    const float inv_sg = 1.0f / sg;
+                    const float log_sg = logf(sg);
+                    float eta0, eta1;                 // one Philox block + Box-Muller pair serves samples qe and qe + 4
+                    cl_noise_normal_pair(E->seed, E->step, (uint32_t)qe, (uint64_t)(E->obs_offset + gobs_e), &eta0, &eta1);
+                    auto sample = [&](float eta, float zf) -> float {          // returns dNLL / d z_f[rid][s]
+                        const float tq = o0e + sige * eta + shift;
+                        const float zs = aim * tq;
+                        const float ipred = zs * zf * zf;
+                        float dll;
+                        const float ll = cl_lik_log_prob2(ipred, io, inv_sg, log_sg, KIND, dof, lik_const, &dll);
+                        nll_acc -= ll * w_ll;
+                        const float gi = -dll * w_ll;                    // dNLL / d ipred
+                        const float dzs = gi * zf * zf;
+                        const float dt = dzs * aim;
+                        pdl += dt;
+                        pds += dt * eta;
+                        pda += dzs * tq;
+                        return gi * zs * 2.0f * zf;
+                    };
+                    const bool two = qe + 4 < S;
+                    const float g0 = sample(eta0, zf0);
+                    float g1 = 0.0f;
+                    if (two) g1 = sample(eta1, zf1);
+                    atomicAdd(ptr_uo(dzf, zoff + 4u * qe), g0);
+                    if (two) atomicAdd(ptr_uo(dzf, zoff + 4u * (qe + 4)), g1);
                 }
             } else if (rid >= 0) {
                 // hardware reciprocal and logarithm (1 ulp): sigma is an input, its log enters the NLL additively
@@ -1232,7 +1279,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
 #define CL_CHAIN 0
 #endif
 
-template <int WP, int DP, int LMAX, int MODE, int KS = 4>
+template <int WP, int DP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC>
 static int launch_one(const cl_mlp_args& a, int grid, hipStream_t st) {
     using SL = SmemLayout<WP, DP, LMAX>;
     const size_t sm_tiles = (size_t)SL::total * sizeof(float);
@@ -1242,7 +1289,7 @@ static int launch_one(const cl_mlp_args& a, int grid, hipStream_t st) {
     if (MODE != 1 && flush > sm) sm = flush;
     using AP = AccPlan<WP, DP, LMAX, MODE, (CL_IMGL == 1)>;
     if (AP::NACC > 0) sm = (size_t)AP::total * sizeof(float);                                       // + LDS-resident accumulators
-    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0)>>(dim3(grid), dim3(512), sm, st, a);
+    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0), EPI>>(dim3(grid), dim3(512), sm, st, a);
 }
 
 // Instantiated geometries: the padded width WP fixes how many layers of activations + weight-gradient blocks fit in the
@@ -1273,13 +1320,48 @@ static inline MlpGeom mlp_geom(const cl_mlp_args& a, int mode, bool imgl_unit) {
     if (a.L + imgl > g.LMAX) g.WP = 0;
     return g;
 }
-
-template <int WP, int LMAX, int MODE, int KS = 4>
-static int launch_dp(const cl_mlp_args& a, int dp, int grid, hipStream_t st) {
-    if (dp == 8) return launch_one<WP, 8, LMAX, MODE, KS>(a, grid, st);
-    if (dp == 32) return launch_one<WP, 32, LMAX, MODE, KS>(a, grid, st);
-    return launch_one<WP, 64, LMAX, MODE, KS>(a, grid, st);
+// The launches the plain epilogue is compiled for (template parameter EPI): a full step that draws its noise in the kernel keyed by the
+// row itself, returns no predictions, has no Evans-2011 error model and at most two MC samples per epilogue lane.  Arguments only: which
+// instances HAVE a plain epilogue (the 64-wide ones of the plain unit) and the A/B switch are mlp_epilogue's.
+static inline cl_epilogue epi_plain(const cl_mlp_args& a, int mode) {
+    if (mode != 0 || a.eta != nullptr || a.noise_row != nullptr || a.ipred_out != nullptr || a.S > 8) return CL_EPI_GENERIC;
+    if (a.ev11 != nullptr || a.d_ev11 != nullptr || a.ev11_part != nullptr) return CL_EPI_GENERIC;
+    if (a.lik_kind == CL_LIK_NORMAL) return CL_EPI_PLAIN_NORMAL;
+    return a.lik_kind == CL_LIK_STUDENTT ? CL_EPI_PLAIN_STUDENTT : CL_EPI_GENERIC;
 }
+
+template <int WP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC>
+static int launch_dp(const cl_mlp_args& a, int dp, int grid, hipStream_t st) {
+    if (dp == 8) return launch_one<WP, 8, LMAX, MODE, KS, EPI>(a, grid, st);
+    if (dp == 32) return launch_one<WP, 32, LMAX, MODE, KS, EPI>(a, grid, st);
+    return launch_one<WP, 64, LMAX, MODE, KS, EPI>(a, grid, st);
+}
+
+#define CL_PLAIN_UNIT (!CL_IMGL && !CL_CHAIN && !CL_DET)
+#if CL_PLAIN_UNIT
+// The A/B switches (bisection and measurement runs; unset or anything but "0" = on), read here and nowhere else.  Each keeps shapes off
+// a kernel family, which then go to the next kernel down mlp_route's order:
+//   CARELESS_HIP_LANE=0         every shape off the lane-per-observation kernel (elbo_lane.hip)
+//   CARELESS_HIP_NARROW=0       every shape off elbo_narrow.hip
+//   CARELESS_HIP_LANE_W12=0     widths 11, 12 off the lane kernel (the narrow kernel they ran on until round 6)
+//   CARELESS_HIP_LANE_DEPTHS=0  depths other than the default off the lane kernel (until round 5)
+//   CARELESS_HIP_LANE_BLOCKS=0  the head-less blocks of a chain off the lane kernel (the chain unit of this file)
+// and one keeps launches off an instance of the kernel the route names:
+//   CARELESS_HIP_EPI=0          the 64-wide instances off their plain epilogue (the generic one: every launch until this switch came)
+struct RouteSwitches { bool lane, narrow, w12, depths, blocks, epi; };
+static bool switch_on(const char* name) { const char* e = getenv(name); return !(e != nullptr && e[0] == '0'); }
+static const RouteSwitches& route_switches() {
+    static const RouteSwitches s{switch_on("CARELESS_HIP_LANE"), switch_on("CARELESS_HIP_NARROW"), switch_on("CARELESS_HIP_LANE_W12"),
+                                 switch_on("CARELESS_HIP_LANE_DEPTHS"), switch_on("CARELESS_HIP_LANE_BLOCKS"), switch_on("CARELESS_HIP_EPI")};
+    return s;
+}
+// The epilogue of the instance a launch on route `r` runs (cl_mlp_epilogue; launch_mode picks the instance by it).
+cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r) {
+    if (r != CL_ROUTE_MLP || !route_switches().epi || mlp_geom(a, mode, false).WP != 64) return CL_EPI_GENERIC;
+    return epi_plain(a, mode);
+}
+#endif
+
 
 template <int MODE>
 static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
@@ -1295,6 +1377,13 @@ static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
         return launch_dp<16, L16, MODE, 4>(a, g.DP, grid, st);
     }
     if (g.WP == 32) return g.LMAX == 5 ? launch_dp<32, 5, MODE>(a, g.DP, grid, st) : launch_dp<32, CL_MLP_LMAX_W32, MODE>(a, g.DP, grid, st);
+#if CL_PLAIN_UNIT
+    if constexpr (MODE == 0) {
+        const cl_epilogue e = mlp_epilogue(a, MODE, CL_ROUTE_MLP);
+        if (e == CL_EPI_PLAIN_NORMAL) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_NORMAL>(a, g.DP, grid, st);
+        if (e == CL_EPI_PLAIN_STUDENTT) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_STUDENTT>(a, g.DP, grid, st);
+    }
+#endif
     return launch_dp<64, CL_MLP_LMAX_W64, MODE>(a, g.DP, grid, st);
 }
 
@@ -1323,22 +1412,7 @@ int CL_MLP_UNIT(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
     return -1;
 }
 
-#if !CL_IMGL && !CL_CHAIN && !CL_DET
-// The A/B switches (bisection and measurement runs; unset or anything but "0" = on), read here and nowhere else.  Each keeps shapes off
-// a kernel family, which then go to the next kernel down mlp_route's order:
-//   CARELESS_HIP_LANE=0         every shape off the lane-per-observation kernel (elbo_lane.hip)
-//   CARELESS_HIP_NARROW=0       every shape off elbo_narrow.hip
-//   CARELESS_HIP_LANE_W12=0     widths 11, 12 off the lane kernel (the narrow kernel they ran on until round 6)
-//   CARELESS_HIP_LANE_DEPTHS=0  depths other than the default off the lane kernel (until round 5)
-//   CARELESS_HIP_LANE_BLOCKS=0  the head-less blocks of a chain off the lane kernel (the chain unit of this file)
-struct RouteSwitches { bool lane, narrow, w12, depths, blocks; };
-static bool switch_on(const char* name) { const char* e = getenv(name); return !(e != nullptr && e[0] == '0'); }
-static const RouteSwitches& route_switches() {
-    static const RouteSwitches s{switch_on("CARELESS_HIP_LANE"), switch_on("CARELESS_HIP_NARROW"), switch_on("CARELESS_HIP_LANE_W12"),
-                                 switch_on("CARELESS_HIP_LANE_DEPTHS"), switch_on("CARELESS_HIP_LANE_BLOCKS")};
-    return s;
-}
-
+#if CL_PLAIN_UNIT
 // Which launcher takes the launch: the one routing decision of the scaler launches (cl_launch_mlp, cl_mlp_kernel_name_of, cl_mlp_route).
 // Shape, optional buffers and mode only: n_pad, the grid and the buffers a route requires are mlp_check's.
 cl_route mlp_route(const cl_mlp_args& a, int mode) {

@@ -224,7 +224,7 @@ int cl_mlp_backward_ext(const cl_mlp_args* args, int grid, void* stream);
 /* Which launcher the three calls above hand these arguments to (mode 0 = cl_elbo_mono_fwd_bwd, 1 = cl_mlp_forward,
  * 2 = cl_mlp_backward_ext): the library's one routing decision.  It depends on the shape, the optional buffers set and the mode
  * only (pointer fields count as set / NULL, n_pad and the grid are not looked at), and on the A/B switches CARELESS_HIP_LANE,
- * _NARROW, _LANE_W12, _LANE_DEPTHS and _LANE_BLOCKS.  CL_ROUTE_NONE: no kernel takes the launch -- the call returns -2.
+ * _NARROW, _LANE_W12, _LANE_DEPTHS and _LANE_BLOCKS (CARELESS_HIP_EPI picks an instance, not a route: cl_mlp_epilogue).  CL_ROUTE_NONE: no kernel takes the launch -- the call returns -2.
  * Returns < 0 for bad arguments.  Needs no device. */
 typedef enum cl_route {
     CL_ROUTE_NONE = 0,
@@ -241,6 +241,17 @@ typedef enum cl_route {
     CL_ROUTE_MLP_CHAIN_DET       /* ... deterministic mode: the last block of a chain                          */
 } cl_route;
 int cl_mlp_route(const cl_mlp_args* args, int mode);
+/* The sampling epilogue of the kernel instance that launch runs.  The 64-wide instances of CL_ROUTE_MLP have, beside the generic
+ * epilogue (every option decided per MC sample), one compiled for the common full step: mode 0, noise drawn in the kernel and keyed
+ * by the row itself (eta and noise_row NULL), ipred_out NULL, no Evans-2011 buffers (ev11, d_ev11, ev11_part NULL), S <= 8, a Normal
+ * or Student-T likelihood.  Same results up to the order of the float atomics.  CARELESS_HIP_EPI=0 keeps every launch on the generic
+ * epilogue (A/B runs).  Every other route, width and mode answers CL_EPI_GENERIC; < 0 for bad arguments.  Needs no device. */
+typedef enum cl_epilogue {
+    CL_EPI_GENERIC = 0,
+    CL_EPI_PLAIN_NORMAL,         /* plain epilogue, Normal likelihood    */
+    CL_EPI_PLAIN_STUDENTT        /* plain epilogue, Student-T likelihood */
+} cl_epilogue;
+int cl_mlp_epilogue(const cl_mlp_args* args, int mode);
 /* Diagnostics: the name of the kernel instance the launch cl_mlp_route chose runs, e.g. "elbo_lane_kernel<10, 0, false>": what a
  * rocprofv3 kernel trace lists; "(unsupported)" for CL_ROUTE_NONE.  Writes at most n bytes (NUL-terminated), returns the length of
  * the name or < 0 for bad arguments.  No reference counterpart. */
