@@ -54,6 +54,12 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _copy_args(ma: MlpArgs) -> MlpArgs:
+    a = MlpArgs()
+    C.memmove(C.byref(a), C.byref(ma), C.sizeof(MlpArgs))
+    return a
+
+
 # ------------------------------------------------------------------------------------------------------------
 # layout of the flat parameter vector
 # ------------------------------------------------------------------------------------------------------------
@@ -210,6 +216,9 @@ class ElboEngine(WidePath):
     FROZEN_LAUE_PACKED = True        # ... harmonic groups: packed order + the two-call form of `cl_frozen_rows` (tests flip it to compare with the three slot launches)
     FROZEN_SORTED_ROWS = True        # a frozen scaler's monochromatic rows: sorted by reflection, `cl_frozen_rows` (round 6; tests flip it to compare with `cl_slot_rows`)
     SLOT_ROWS_ONE_LAUNCH = True      # rows that are their own slot: predict + log-prob + gradient in one `cl_slot_rows` launch (tests flip it)
+    local_only = False               # test hook: a rank shard on one device, the per-rank partial gradient stays in place (no collective call)
+    force_allreduce = False          # CARELESS_FORCE_DIST=1: a one-rank run makes every collective call of the multi-GPU step
+
     def __init__(self, model, inputs, seed: int = 1234, shard: Optional[Shard] = None, process_group=None,
                  grid: Optional[int] = None):
         self.device = require_gpu("ElboEngine")
@@ -217,7 +226,9 @@ class ElboEngine(WidePath):
         self.model = model
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.process_group = process_group
-        # CARELESS_FORCE_DIST=1 (careless.py: _data_parallel): a one-rank run makes every collective call of the multi-GPU step
+        self.peel_params = self.peel_grad = None    # the peeled scaler's parameters and reduced gradient (`_peel_bufs`)
+        self._wide = None                           # work buffers of the layer-by-layer path (`_wide_setup`)
+        self._pending_reduce = None                 # a partial reduction left to the step's cl_tn_backward launch (`_data_term`)
         if os.environ.get("CARELESS_FORCE_DIST", "0") == "1":
             import torch.distributed as dist
             self.force_allreduce = dist.is_available() and dist.is_initialized()
@@ -384,7 +395,7 @@ class ElboEngine(WidePath):
         self.scaler_frozen = False
         self.obs = self._build_obs(inputs, self.shard.start, self.shard.stop, grid, self.laue_groups, rows=self.shard.rows if self.owner else None)
         if self.blocks is not None:
-            self.obs.alloc_chain(self.lib, self.blocks, self.w, dev)
+            self.obs.alloc_chain(self.lib, self.blocks, self.w, dev, self.chain_lane)
         RS = self.R * self.S
         o_dz = 0
         # the buffer a step all-reduces starts on a 16-byte boundary: the flat gradient (row split), or -- reflection-owner split -- what
@@ -421,7 +432,7 @@ class ElboEngine(WidePath):
         kw = dict(grid=grid, n_refl=self.R, n_images=self._max_images(), laue_groups=laue_groups, pack_images=self.imgl is not None and not self.wide,
                   sort_images=self.imgl is not None and self.wide,
                   laue_single_pass=not getattr(self.model, "laue_two_pass", False) and self.blocks is None and not self.wide, wide=self.wide)
-        if getattr(self, "_frozen_layout", False):
+        if self._frozen_layout:
             # plain rows for a frozen scaler (its output is a constant: no tile / image constraint) -- except Laue data, which keeps the packed
             # order of the single-pass kernels (a group inside a 16-row granule) for `cl_frozen_rows`' group sums (round 6)
             kw.update(pack_images=False, sort_images=False,
@@ -433,7 +444,7 @@ class ElboEngine(WidePath):
             start, stop = 0, len(rows)
         if self.laue or self.imgl is not None or self.wide or stop - start <= per:
             o = ObsData(self.lib, inputs, start, stop, self.S, self.layout.P, self.device, rows=rows, **kw)
-            o.host_inputs = inputs                        # (a reference: the frozen-scaler path reads the rows' metadata once per training)
+            o.host_inputs = inputs
             if self.deterministic:
                 self._det_attach(o, [o])
             return o
@@ -441,8 +452,6 @@ class ElboEngine(WidePath):
         for a in range(start, stop, per):
             b = min(stop, a + per)
             pieces.append(ObsData(self.lib, inputs, a, b, self.S, self.layout.P, self.device, rows=None if rows is None else rows[a:b], **kw))
-            pieces[-1].row0 = a - start                   # first row of the piece inside the shard's eta / ipred arrays
-            pieces[-1].is_piece = True                    # (several launches share dz_f: `cl_frozen_rows` adds instead of storing)
             pieces[-1].host_inputs = inputs
             kw["n_refl"] = kw["n_images"] = None          # (the id ranges were checked over the whole input by the first piece)
             if len(pieces) > 1:
@@ -501,16 +510,10 @@ class ElboEngine(WidePath):
             return self.img.max_images
         return self.imgl.max_images if self.imgl is not None else None
 
-    # the training shard's arrays under their old names
+    # the training shard's sizes under their old names (bench.py, tests, scripts/stamps*.py)
     N = property(lambda self: self.obs.N)
     n_pad = property(lambda self: self.obs.n_pad)
     grid = property(lambda self: self.obs.grid)
-    refl_id = property(lambda self: self.obs.refl_id)
-    image_id = property(lambda self: self.obs.image_id)
-    meta_t = property(lambda self: self.obs.meta_t)
-    iobs = property(lambda self: self.obs.iobs)
-    sig = property(lambda self: self.obs.sig)
-    partials = property(lambda self: self.obs.partials)
 
     # ------------------------------------------------------------------------------------------------------
     def refresh_config(self):
@@ -533,7 +536,7 @@ class ElboEngine(WidePath):
             self.obs = self._build_obs(first.host_inputs, self.shard.start, self.shard.stop, self._grid_arg, self.laue_groups,
                                        rows=self.shard.rows if self.owner else None)
             if self.blocks is not None:
-                self.obs.alloc_chain(self.lib, self.blocks, self.w, self.device)
+                self.obs.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         opt = m.optimizer
         self.opt = opt
         S, N, R = self.S, self.N_total, self.R
@@ -581,10 +584,37 @@ class ElboEngine(WidePath):
                 a.asu_ids, a.n_asu = ptr(self.asu_ids), lay.n_dwr
         return a
 
+    def _step_fields(self, a, obs: ObsData, step: int):
+        """The per-step constants `cl_mlp_args`, `cl_laue_args` and `cl_frozen_args` name alike, on whichever of the three `a` is."""
+        lay = self.layout
+        a.R, a.S = self.R, self.S
+        a.z_f, a.dz_f = ptr(self.z_f), ptr(self.dz_f)
+        a.lik_kind, a.dof, a.lik_const = self.lik_kind, self.dof, self.lik_const
+        a.shift = self.mlp.scale_multiplier or 0.0
+        a.w_ll = self._w_ll(obs)
+        a.seed, a.step = self.seed, step & 0xFFFFFFFF
+        a.scalars, a.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
+        if self.ev11:
+            a.ev11 = self.params.data_ptr() + 4 * lay.off_ev11
+            a.d_ev11 = self.grads.data_ptr() + 4 * lay.off_ev11
+        return a
+
+    def _shard_rows(self, obs: ObsData, t) -> Optional[int]:
+        """Pointer to the rows of `obs` inside a per-(row, sample) array of its whole shard (eta, ipred_out): a piece of a chunked shard starts at row0."""
+        return None if t is None else t.data_ptr() + 4 * self.S * obs.row0
+
+    def _det_parts(self, obs: ObsData, k: int):
+        """(nll_part, ev11_part) of part k of the shard `obs` belongs to (deterministic mode): the fused launches of its pieces store into parts
+        0 .. pieces - 1 -- det["grid"] NLL slots, CL_EV11_WAVES Evans-2011 slots of three floats per workgroup --, the slot / padded-slot
+        likelihood launch behind them (k = det["pieces"])."""
+        det = obs.det_parent.det
+        return (det["nll"].data_ptr() + 8 * det["grid"] * k,
+                det["ev11"].data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det["grid"] * k if self.ev11 else None)
+
     def _mlp_args(self, step: int, eta, ipred_out=None, obs: Optional[ObsData] = None) -> MlpArgs:
         lay = self.layout
         obs = self.obs if obs is None else obs
-        a = MlpArgs()
+        a = self._step_fields(MlpArgs(), obs, step)
         a.refl_id = ptr(obs.refl_id); a.image_id = ptr(obs.image_id); a.meta_t = ptr(obs.meta_t)
         a.iobs = ptr(obs.iobs); a.sig = ptr(obs.sig)
         a.n_obs, a.n_pad = obs.N, obs.n_pad
@@ -594,8 +624,7 @@ class ElboEngine(WidePath):
             a.row_map = ptr(obs.row_map)
         if obs.fused_laue:
             a.gmeta, a.tile_gmax = ptr(obs.gmeta), ptr(obs.tile_gmax)
-        if getattr(obs, "noise_row", None) is not None:
-            a.noise_row = ptr(obs.noise_row)
+        a.noise_row = ptr(obs.noise_row)
         if self.imgl is not None:
             a.imgl = self.params.data_ptr() + 4 * lay.off_imgl
             a.d_imgl = self.grads.data_ptr() + 4 * lay.off_imgl
@@ -606,36 +635,39 @@ class ElboEngine(WidePath):
         a.leak = self.mlp.leakiness
         a.use_img = 1 if lay.n_img > 0 else 0
         a.img = (self.params.data_ptr() + 4 * lay.off_img) if lay.n_img > 0 else None
-        a.z_f = ptr(self.z_f)
-        a.R, a.S = self.R, self.S
-        a.lik_kind, a.dof, a.lik_const = self.lik_kind, self.dof, self.lik_const
         a.bij_kind, a.eps = self.bij_kind, self.mlp.epsilon
-        a.shift = self.mlp.scale_multiplier or 0.0
-        a.w_ll = self._w_ll(obs)
-        row0 = getattr(obs, "row0", 0)                  # piece of a chunked shard: its rows inside the shard's eta / ipred arrays
-        a.eta = ptr(eta) + 4 * self.S * row0 if eta is not None else None
-        a.seed, a.step = self.seed, step & 0xFFFFFFFF
-        a.dz_f = ptr(self.dz_f)
+        a.eta, a.ipred_out = self._shard_rows(obs, eta), self._shard_rows(obs, ipred_out)
         a.d_img = (self.grads.data_ptr() + 4 * lay.off_img) if lay.n_img > 0 else None
         a.partials = ptr(obs.partials)
-        a.scalars = ptr(self.scalars)
-        a.ipred_out = ptr(ipred_out) + 4 * self.S * row0 if ipred_out is not None else None
-        a.stop_flag = ptr(self.stop_flag)
-        if self.ev11:
-            a.ev11 = self.params.data_ptr() + 4 * lay.off_ev11
-            a.d_ev11 = self.grads.data_ptr() + 4 * lay.off_ev11
         if self.deterministic:
             det = obs.det_parent.det
             if det["slot"] is not None:
                 a.dzf_obs = det["dzf"].data_ptr()                  # (records by slot: positions inside the whole shard, not the piece)
-                a.det_slot = det["slot"].data_ptr() + 4 * row0
+                a.det_slot = det["slot"].data_ptr() + 4 * obs.row0
             else:
-                a.dzf_obs = det["dzf"].data_ptr() + 4 * self.S * row0
-            a.dimg_obs = det["dimg"].data_ptr() + 4 * row0
-            a.nll_part = det["nll"].data_ptr() + 8 * det["grid"] * obs.det_index
-            if self.ev11:
-                a.ev11_part = det["ev11"].data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det["grid"] * obs.det_index
+                a.dzf_obs = det["dzf"].data_ptr() + 4 * self.S * obs.row0
+            a.dimg_obs = det["dimg"].data_ptr() + 4 * obs.row0
+            a.nll_part, a.ev11_part = self._det_parts(obs, obs.det_index)
         return a
+
+    def _likelihood_args(self, ma: MlpArgs, obs: ObsData, mode: int = 0):
+        """From `_mlp_args` of `obs`: (arguments, mode) of the scaler launch that computes the likelihood -- the launch `plan.route` is the
+        route of: the last block of a chain with its dZ_0 (lane kernel) or dX out, the backward launch of the two-pass Laue path (mode 2,
+        dL/d(loc, sigma) in), the launch behind a peeled first layer, else the fused launch on the scaler itself.  The data term launches
+        with it, `training_launch` asks about it."""
+        if self.blocks is not None:
+            K = len(self.blocks)
+            ma = self._block_args(ma, obs, K - 1)
+            if self.chain_lane:
+                ma.dZ0_out = ptr(obs.chain_dz0)       # dZ_0 of the block's first layer; `cl_chain_dx` turns it into the gradient of the block's input
+            else:
+                ma.dX_out = ptr(obs.chain_dact[K - 2])
+        elif self.laue and not obs.fused_laue:
+            mode = 2 if mode == 0 else mode
+            ma.dO_ext = ptr(obs.laue_dO)
+        elif self.peel and mode == 0:
+            ma = self._peel_args(ma, obs)
+        return ma, mode
 
     def kernel_name(self, mode: int = 0) -> str:
         """Name of the kernel instance the scaler launches of this engine run (`cl_mlp_kernel_name`: the library's own routing):
@@ -651,19 +683,7 @@ class ElboEngine(WidePath):
 
     def training_launch(self, mode: int = 0):         # (arguments, mode) of the launch kernel_name names; plan.route is its cl_mlp_route
         obs = self.obs.children[0] if isinstance(self.obs, ObsChunks) else self.obs
-        ma = self._mlp_args(0, None, None, obs)
-        if self.blocks is not None:
-            ma = self._block_args(ma, obs, len(self.blocks) - 1)
-            if getattr(self, "chain_lane", False):
-                ma.dZ0_out = ptr(obs.chain_dact[len(self.blocks) - 2])
-            else:
-                ma.dX_out = ptr(obs.chain_dact[len(self.blocks) - 2])
-        elif self.laue and not obs.fused_laue:
-            mode = 2 if mode == 0 else mode
-            ma.dO_ext = ptr(obs.laue_dO)
-        elif self.peel and mode == 0:
-            ma = self._peel_args(ma, obs)
-        return ma, mode
+        return self._likelihood_args(self._mlp_args(0, None, None, obs), obs, mode)
 
     def _w_ll(self, obs: ObsData) -> float:
         """Weight of one log-likelihood term: sum / S, or with `kl_weight` the mean over the S x N terms of the observation set
@@ -704,7 +724,7 @@ class ElboEngine(WidePath):
         if self.double_wilson:
             check(lib.cl_dw_prior_forward(C.byref(tn), st), "cl_dw_prior_forward")
         self._pending_reduce = None
-        dist_on = (self.shard.world > 1 and not getattr(self, "local_only", False)) or getattr(self, "force_allreduce", False)
+        dist_on = (self.shard.world > 1 and not self.local_only) or self.force_allreduce
         # Row split, two-piece message (`model.split_message = True` / CARELESS_HIP_SPLIT_MESSAGE=1; measured in DESIGN 5.2): everything
         # behind a and b in the flat gradient -- the scaler's, the image scales', Ev11's part -- is final once the fused kernel and the
         # partial reduction are through, so its all-reduce starts then (asynchronously, on the communicator's stream) and runs beside
@@ -766,90 +786,82 @@ class ElboEngine(WidePath):
             a.ev11_part, a.n_ev11, a.d_ev11 = ptr(det["ev11"]), int(det["ev11"].numel()) // 3, self.grads.data_ptr() + 4 * lay.off_ev11
         check(self.lib.cl_det_reduce(C.byref(a), st), "cl_det_reduce")
 
-    def _data_term(self, obs: ObsData, step: int, eta, ipred_out, st, _piece: bool = False, defer_reduce: bool = False):
-        """NLL of `obs` into scalars[NLL] and its gradient into dz_f / the flat gradient (scaler + image scales).  `defer_reduce`:
-        a single fused launch leaves its partial reduction to the caller (`self._pending_reduce`: forward_backward hands it to the
-        step's cl_tn_backward launch)."""
+    def _data_term(self, obs, step: int, eta, ipred_out, st, defer_reduce: bool = False):
+        """NLL of `obs` into scalars[NLL] and its gradient into dz_f / the flat gradient (scaler + image scales): one launch sequence per
+        piece of the set, then -- deterministic mode -- the fixed-order sums over the whole set.  `defer_reduce`: a single fused launch
+        leaves its partial reduction to the caller (`self._pending_reduce`: forward_backward hands it to the step's cl_tn_backward launch)."""
+        if obs.empty:
+            return
+        chunked = isinstance(obs, ObsChunks)
+        for piece in (obs.children if chunked else [obs]):
+            self._data_term_launch(piece, step, eta, ipred_out, st, defer_reduce and not chunked)
+        if self.deterministic:
+            self._det_reduce(obs, st)
+
+    def _data_term_launch(self, obs: ObsData, step: int, eta, ipred_out, st, defer_reduce: bool):
+        """The data term of one `ObsData`: exactly one path, then the reduction of the weight-gradient partials that goes with it."""
         lib, lay = self.lib, self.layout
-        if getattr(obs, "empty", False):
-            return
-        if isinstance(obs, ObsChunks):
-            for piece in obs.children:
-                self._data_term(piece, step, eta, ipred_out, st, _piece=True)
-            if self.deterministic:
-                self._det_reduce(obs, st)
-            return
         if self.scaler_frozen and self.frozen_fast and self._frozen_ok(obs):
-            self._data_term_frozen(obs, step, eta, ipred_out, st)
-            if self.deterministic and not _piece:
-                self._det_reduce(obs, st)
+            self._data_term_frozen(obs, step, eta, ipred_out, st)             # (no scaler gradient: nothing to reduce)
             return
         if self.wide:
-            self._data_term_wide(obs, step, eta, ipred_out, st)
-            if self.deterministic and not _piece:
-                self._det_reduce(obs, st)
+            self._data_term_wide(obs, step, eta, ipred_out, st)               # (reduces layer by layer)
             return
         ma = self._mlp_args(step, eta, ipred_out, obs)
         if self.blocks is not None:
-            self._data_term_chain(ma, obs, step, eta, ipred_out, st)
-            if self.deterministic and not _piece:
-                self._det_reduce(obs, st)
+            self._data_term_chain(ma, obs, step, eta, ipred_out, st)          # (reduces block by block)
             return
-        if self.laue and obs.fused_laue:
-            # single pass: the harmonic group sums happen inside the fused kernel; the padded slots (no rows, iconv = 0,
-            # reference formatter.py:637-640 / laue.py:24) only add their constant -- and, with Ev11, its gradient
-            self._fused_step_launch(ma, obs, st)
-            self._laue_pad_slots(ma, obs, st)
-        elif self.laue:
-            self._laue_passes(ma, obs, step, eta, ipred_out, st)
+        a, mode = self._likelihood_args(ma, obs)
+        if mode == 2:
+            self._laue_passes(a, obs, step, eta, ipred_out, st)
         else:
             # (deterministic mode: every workgroup of the launch STORES its NLL slot, det["grid"] slots per piece -- nothing to clear;
             #  the slots a short last piece leaves unwritten were zero-initialised and are never touched)
-            self._fused_step_launch(ma, obs, st)
-        if self.peel and not (self.laue and not obs.fused_laue):
-            self._peel_reduce(obs, st, ma.n_obs)
-        elif defer_reduce and not _piece and not self.deterministic:
+            self._fused_step_launch(a, obs, st)
+            if obs.fused_laue:
+                # single pass: the harmonic group sums happen inside the fused kernel; the padded slots (no rows, iconv = 0,
+                # reference formatter.py:637-640 / laue.py:24) only add their constant -- and, with Ev11, its gradient
+                self._laue_pad_slots(a, obs, st)
+        if self.peel and mode == 0:
+            self._peel_reduce(obs, st, a.n_obs)
+        elif defer_reduce and not self.deterministic:
             self._pending_reduce = (ptr(obs.partials), obs.grid, lay.P, self.grads.data_ptr() + 4 * lay.off_mlp)
         else:
             check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, lay.P, self.grads.data_ptr() + 4 * lay.off_mlp,
                                          ptr(self.stop_flag), st), "cl_reduce_partials")
-        if self.deterministic and not _piece:
-            self._det_reduce(obs, st)
 
-    def _laue_pad_slots(self, ma: MlpArgs, obs: ObsData, st):
+    def _laue_pad_slots(self, ma, obs: ObsData, st):
         """The padded slots of a packed Laue observation set (no rows, iconv = 0: reference formatter.py:637-640 / laue.py:24) add their
-        constant to the NLL -- and, with Ev11, its gradient -- through one small `cl_laue_likelihood` launch."""
+        constant to the NLL -- and, with Ev11, its gradient -- through one small `cl_laue_likelihood` launch.  `ma`: the arguments of the
+        rows' own launch (`cl_mlp_args` or `cl_frozen_args`: its w_ll, ev11, d_ev11).  (Of the per-step constants this launch reads the
+        likelihood's alone: the other shared fields stay zero.)"""
         lib = self.lib
         npad = int(obs.pad_iobs.numel())
         if npad <= 0:
             return
-        uniform = getattr(obs, "pad_uniform", False)            # all padded slots alike: one slot, weight x their number
-        nslot = 1 if uniform else npad
+        nslot = 1 if obs.pad_uniform else npad                  # all padded slots alike: one slot, weight x their number
         obs.pad_iconv[: nslot * self.S].zero_()
         la = LaueArgs()
         la.iobs, la.sig, la.iconv = ptr(obs.pad_iobs), ptr(obs.pad_sig), ptr(obs.pad_iconv)
         la.n_obs, la.S = nslot, self.S
         la.lik_kind, la.dof, la.lik_const = self.lik_kind, self.dof, self.lik_const
-        la.w_ll = ma.w_ll * (npad if uniform else 1)
+        la.w_ll = ma.w_ll * (npad if obs.pad_uniform else 1)
         la.scalars, la.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
         la.ev11, la.d_ev11 = ma.ev11, ma.d_ev11
         if self.deterministic:      # the padded slots' workgroups store their NLL behind the fused launch's parts
-            det = obs.det_parent.det
-            la.nll_part = det["nll"].data_ptr() + 8 * det["pieces"] * det["grid"]
-            if self.ev11:
-                la.ev11_part = det["ev11"].data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det["pieces"] * det["grid"]
+            la.nll_part, la.ev11_part = self._det_parts(obs, obs.det_parent.det["pieces"])
         check(lib.cl_laue_likelihood(C.byref(la), st), "cl_laue_likelihood")
 
     def _frozen_ok(self, obs: ObsData) -> bool:
         """The sampling / likelihood kernels take this observation image as it is: rows in the caller's order (not packed by image or
         harmonic group, not sorted by image), and -- deterministic mode -- rows that are their own slot."""
-        if getattr(obs, "host_inputs", None) is None:
+        if obs.host_inputs is None:
             return False
         if obs.fused_laue:
             # harmonic groups in the packed order of the single-pass kernels (round 6): `cl_frozen_rows` in its two-call form -- an engine
             # built around a frozen scaler keeps that layout for Laue data (_build_obs)
             return self._frozen_layout and self.FROZEN_LAUE_PACKED and not self.deterministic and obs.tile_img is None
-        if obs.row_map is not None or getattr(obs, "perm", None) is not None:
+        if obs.row_map is not None or obs.perm is not None:
             return False
         if self.imgl is not None and not self._frozen_layout:
             return False
@@ -861,84 +873,83 @@ class ElboEngine(WidePath):
         predict, log-prob and its gradient to dz_f (and the Evans-2011 terms) on the slot kernels of the two-pass path
         (`cl_slot_rows`, or `cl_laue_predict / _likelihood / _backward` for harmonic groups).  The scaler's own gradient is not computed at
         all: the reference takes gradients of `trainable_variables` only (variational.py:201), so its "Grad Norm" does not see it either."""
-        if getattr(obs, "locsig_epoch", None) != self._frozen_epoch:
+        if obs.locsig_epoch != self._frozen_epoch:
             sl = obs.rows if obs.rows is not None else slice(obs.start, obs.start + obs.N)
             md = _np(BaseModel.get_metadata(obs.host_inputs))
             md = md.reshape(md.shape[0], -1)[sl]
             ids = _np(BaseModel.get_image_id(obs.host_inputs)).reshape(-1)[sl] if self.imgl is not None else None
             obs.laue_loc, obs.laue_sig = scaler_forward(self.mlp, md, self.imgl, ids)
-            if getattr(obs, "laue_dO", None) is None:
+            if obs.laue_dO is None:
                 obs.laue_dO = torch.empty(obs.N * 2, dtype=torch.float32, device=self.device)
-            if not hasattr(obs, "harmonic_id") and not obs.fused_laue:
-                obs.harmonic_id = None
-            if getattr(obs, "laue_iconv", None) is None and not obs.fused_laue:      # (rows that are their own slot never touch it; the entry point wants a pointer)
+            if obs.laue_iconv is None and not obs.fused_laue:      # (rows that are their own slot never touch it; the entry point wants a pointer)
                 obs.laue_iconv = torch.empty(obs.N * self.S if obs.harmonic_id is not None else 4, dtype=torch.float32, device=self.device)
-            if obs.rows is not None and getattr(obs, "row_index", None) is None:
+            if obs.rows is not None and obs.row_index is None:
                 obs.row_index = torch.as_tensor(np.asarray(obs.rows, dtype=np.int64), device=self.device)     # the noise key of every row
             obs.locsig_epoch = self._frozen_epoch
-        ma = self._mlp_args(step, eta, ipred_out, obs)
         if obs.fused_laue:
-            self._frozen_laue(ma, obs, step, eta, ipred_out, st)
+            self._frozen_laue(obs, step, eta, ipred_out, st)
             return
-        keyed = getattr(obs, "row_index", None) is not None and (eta is not None or ipred_out is not None)      # (injected noise on rows that are not a contiguous range: the slot kernels index it by local row)
+        keyed = obs.row_index is not None and (eta is not None or ipred_out is not None)      # (injected noise on rows that are not a contiguous range: the slot kernels index it by local row)
         if obs.harmonic_id is None and not self.deterministic and self.FROZEN_SORTED_ROWS and not keyed:
-            self._frozen_rows(ma, obs, step, eta, ipred_out, st)
+            self._frozen_rows(obs, step, eta, ipred_out, st)
             return
-        self._slot_likelihood(ma, obs, step, eta, ipred_out, st, frozen=True)
+        self._slot_likelihood(self._mlp_args(step, eta, ipred_out, obs), obs, step, eta, ipred_out, st, frozen=True)
 
-    def _frozen_rows(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
+    def _row_image_scales(self, image_id: torch.Tensor) -> Optional[torch.Tensor]:
+        """The image scale of every row of `image_id` (image 0 is pinned to 1: image.py:23-25); None without image scales."""
+        lay = self.layout
+        if lay.n_img <= 0:
+            return None
+        scales = torch.cat([torch.ones(1, dtype=torch.float32, device=self.device), self.params[lay.off_img: lay.off_img + lay.n_img].detach()])
+        return scales.index_select(0, image_id)
+
+    def _frozen_args(self, obs: ObsData, step: int, eta, ipred_out) -> FrozenArgs:
+        """What the row-per-thread launches of `cl_frozen_rows` share: (loc, sigma), image scale and noise key of every row from
+        `obs.frozen_sorted`, the step's constants, the set's rows of eta / ipred_out.  The caller adds the row arrays, `n` and the fields of
+        its form (`edge_*` and `accumulate`, or `gmeta` / `gbuf` / `src`)."""
+        fz = obs.frozen_sorted
+        fa = self._step_fields(FrozenArgs(), obs, step)
+        fa.loc, fa.sigma, fa.aim, fa.key = ptr(fz["loc"]), ptr(fz["sigma"]), ptr(fz["aim"]), ptr(fz["key"])
+        fa.obs_offset = int(obs.start)
+        fa.eta, fa.ipred_out = self._shard_rows(obs, eta), self._shard_rows(obs, ipred_out)
+        return fa
+
+    def _frozen_rows(self, obs: ObsData, step: int, eta, ipred_out, st):
         """Monochromatic rows behind a frozen scaler (round 6, `cl_frozen_rows`): the rows sorted by reflection ONCE per training -- the
         scaler's output is a constant, so no layout constraint binds their order -- with (loc, sigma), the image scale and the global row
         number (the noise key) of every row beside them; per step one row-per-thread launch that sums the amplitude gradients of a
         reflection's rows inside the wave and stores them (no float atomics into dz_f), plus the small launch for the runs that cross a
         wave border.  The image scales are part of the frozen scaling model: their gradient is not computed either."""
-        fz = getattr(obs, "frozen_sorted", None)
+        fz = obs.frozen_sorted
         if fz is None or fz["epoch"] != self._frozen_epoch:
             dev = self.device
             rid = obs.refl_id[: obs.N]
             order = torch.argsort(rid, stable=True)
             take = lambda t: t[: obs.N].index_select(0, order).contiguous()
-            if ma.use_img:
-                img_id = obs.image_id[: obs.N].long()
-                scales = torch.cat([torch.ones(1, dtype=torch.float32, device=dev), self.params[self.layout.off_img: self.layout.off_img + self.layout.n_img].detach()])
-                aim = scales.index_select(0, img_id).index_select(0, order).contiguous()      # (image 0 is pinned to 1: image.py:23-25)
-            else:
-                aim = None
-            if getattr(obs, "row_index", None) is not None:
+            aim = self._row_image_scales(obs.image_id[: obs.N].long())
+            if obs.row_index is not None:
                 key = obs.row_index[: obs.N].index_select(0, order).to(torch.int32).contiguous()
             else:
                 key = (order + int(obs.start)).to(torch.int32).contiguous()
             n_waves = (obs.N + 63) // 64
             fz = obs.frozen_sorted = dict(
-                epoch=self._frozen_epoch, refl=take(rid).to(torch.int32), loc=take(obs.laue_loc), sigma=take(obs.laue_sig), aim=aim,
-                iobs=take(obs.iobs), sig=take(obs.sig), key=key,
+                epoch=self._frozen_epoch, refl=take(rid).to(torch.int32), loc=take(obs.laue_loc), sigma=take(obs.laue_sig),
+                aim=None if aim is None else take(aim), iobs=take(obs.iobs), sig=take(obs.sig), key=key,
                 edge_rid=torch.empty(2 * n_waves, dtype=torch.int32, device=dev),
                 edge_val=torch.empty(max(int(self.lib.cl_frozen_edge_floats(obs.N, self.S)), 1), dtype=torch.float32, device=dev))
-        fa = FrozenArgs()
-        fa.refl_id, fa.loc, fa.sigma, fa.aim = ptr(fz["refl"]), ptr(fz["loc"]), ptr(fz["sigma"]), ptr(fz["aim"])
-        fa.iobs, fa.sig, fa.key = ptr(fz["iobs"]), ptr(fz["sig"]), ptr(fz["key"])
-        fa.obs_offset, fa.n = int(obs.start), int(obs.N)
-        fa.R, fa.S = self.R, self.S
-        fa.z_f, fa.dz_f = ptr(self.z_f), ptr(self.dz_f)
+        fa = self._frozen_args(obs, step, eta, ipred_out)
+        fa.refl_id, fa.iobs, fa.sig, fa.n = ptr(fz["refl"]), ptr(fz["iobs"]), ptr(fz["sig"]), int(obs.N)
         # (several launches into one dz_f -- the pieces of a chunked shard -- and the double-Wilson prior, whose dlog p / dz is in dz_f
         #  before the data term: add with atomics instead of storing)
-        fa.accumulate = 1 if (getattr(obs, "is_piece", False) or self.double_wilson) else 0
-        fa.lik_kind, fa.dof, fa.lik_const = self.lik_kind, self.dof, self.lik_const
-        fa.shift, fa.w_ll = ma.shift, ma.w_ll
-        row0 = getattr(obs, "row0", 0)                  # piece of a chunked shard: its rows inside the shard's eta / ipred arrays
-        fa.eta = None if eta is None else eta.data_ptr() + 4 * self.S * row0
-        fa.seed, fa.step = self.seed, step & 0xFFFFFFFF
-        fa.scalars, fa.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
-        fa.ipred_out = None if ipred_out is None else ipred_out.data_ptr() + 4 * self.S * row0
-        fa.ev11, fa.d_ev11 = ma.ev11, ma.d_ev11
+        fa.accumulate = 1 if (obs.is_piece or self.double_wilson) else 0
         fa.edge_rid, fa.edge_val = ptr(fz["edge_rid"]), ptr(fz["edge_val"])
         check(self.lib.cl_frozen_rows(C.byref(fa), st), "cl_frozen_rows")
 
-    def _frozen_laue(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
+    def _frozen_laue(self, obs: ObsData, step: int, eta, ipred_out, st):
         """Harmonic groups behind a frozen scaler (round 6): `cl_frozen_rows` twice -- in the packed order of the single-pass kernels the group
         sums, the likelihood and every row's amplitude gradient (stored per row: the rows of a group belong to different reflections), then
         the same rows in reflection order, gathered and summed per reflection like monochromatic rows -- and the padded slots' constant."""
-        fz = getattr(obs, "frozen_sorted", None)
+        fz = obs.frozen_sorted
         dev = self.device
         if obs.noise_row is not None and (eta is not None or ipred_out is not None):
             raise NotImplementedError("injected noise / ipred_out on a shard of harmonic groups behind a frozen scaler (a parity-test input: "
@@ -949,11 +960,7 @@ class ElboEngine(WidePath):
             rmc = rm.clamp(min=0)
             loc_p = obs.laue_loc.index_select(0, rmc).contiguous()
             sig_p = obs.laue_sig.index_select(0, rmc).contiguous()
-            if ma.use_img:
-                scales = torch.cat([torch.ones(1, dtype=torch.float32, device=dev), self.params[self.layout.off_img: self.layout.off_img + self.layout.n_img].detach()])
-                aim = scales.index_select(0, obs.image_id.long().clamp(min=0)).contiguous()
-            else:
-                aim = None
+            aim = self._row_image_scales(obs.image_id.long().clamp(min=0))
             key = obs.noise_row if obs.noise_row is not None else (rmc + int(obs.start)).to(torch.int32).contiguous()
             active = torch.nonzero(valid & (obs.refl_id >= 0)).flatten()
             order = torch.argsort(obs.refl_id.index_select(0, active), stable=True)
@@ -968,65 +975,48 @@ class ElboEngine(WidePath):
                 gbuf=torch.zeros(max(n2, 1) * self.S, dtype=torch.float32, device=dev),
                 edge_rid=torch.empty(2 * ((n2 + 63) // 64) + 2, dtype=torch.int32, device=dev),
                 edge_val=torch.empty(max(int(self.lib.cl_frozen_edge_floats(n2, self.S)), 1), dtype=torch.float32, device=dev))
-        row0 = getattr(obs, "row0", 0)
-        fa = FrozenArgs()
-        fa.refl_id, fa.loc, fa.sigma, fa.aim = ptr(obs.refl_id), ptr(fz["loc"]), ptr(fz["sigma"]), ptr(fz["aim"])
-        fa.iobs, fa.sig, fa.key = ptr(obs.iobs), ptr(obs.sig), ptr(fz["key"])
-        fa.obs_offset, fa.n = int(obs.start), int(obs.n_pad)
-        fa.R, fa.S = self.R, self.S
-        fa.z_f, fa.dz_f = ptr(self.z_f), ptr(self.dz_f)
-        fa.lik_kind, fa.dof, fa.lik_const = self.lik_kind, self.dof, self.lik_const
-        fa.shift, fa.w_ll = ma.shift, ma.w_ll
-        fa.eta = None if eta is None else eta.data_ptr() + 4 * self.S * row0
-        fa.seed, fa.step = self.seed, step & 0xFFFFFFFF
-        fa.scalars, fa.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
-        fa.ipred_out = None if ipred_out is None else ipred_out.data_ptr() + 4 * self.S * row0
-        fa.ev11, fa.d_ev11 = ma.ev11, ma.d_ev11
+        fa = self._frozen_args(obs, step, eta, ipred_out)
+        fa.refl_id, fa.iobs, fa.sig, fa.n = ptr(obs.refl_id), ptr(obs.iobs), ptr(obs.sig), int(obs.n_pad)
         fa.gmeta, fa.gbuf, fa.src = ptr(obs.gmeta), ptr(fz["gbuf"]), ptr(fz["dst"])
         check(self.lib.cl_frozen_rows(C.byref(fa), st), "cl_frozen_rows (harmonic groups)")
-        if fz["n2"] > 0:
+        if fz["n2"] > 0:            # (the second call reads the first one's gradients and nothing else of the step: a handful of fields)
             fb = FrozenArgs()
             fb.refl_id, fb.gbuf = ptr(fz["refl_sorted"]), ptr(fz["gbuf"])
             fb.n, fb.R, fb.S = fz["n2"], self.R, self.S
             fb.dz_f, fb.stop_flag = ptr(self.dz_f), ptr(self.stop_flag)
-            fb.accumulate = 1 if (getattr(obs, "is_piece", False) or self.double_wilson) else 0
+            fb.accumulate = 1 if (obs.is_piece or self.double_wilson) else 0
             fb.edge_rid, fb.edge_val = ptr(fz["edge_rid"]), ptr(fz["edge_val"])
             check(self.lib.cl_frozen_rows(C.byref(fb), st), "cl_frozen_rows (per-reflection sums)")
-        self._laue_pad_slots(ma, obs, st)
+        self._laue_pad_slots(fa, obs, st)
 
     def _peel_bufs(self, obs: ObsData):
         """Buffers of the peeled first layer for one observation set: its pre-activations and dZ_0 (feature-major, like meta_t), the
         weight-gradient partials; per engine: the peeled scaler's parameters and reduced gradient."""
-        pb = getattr(obs, "peel", None)
-        if pb is None:
+        if obs.peel is None:
             rows = int(self.lib.cl_mlp_meta_rows(self.w))
             nparts = int(self.lib.cl_peel_parts(obs.n_pad))     # (packed layouts: every row of the padded axis may be a real one)
-            pb = obs.peel = dict(u=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
-                                 dz0=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
-                                 parts=torch.empty(nparts * (self.w * self.d + self.w), dtype=torch.float32, device=self.device), nparts=nparts)
-        if getattr(self, "peel_params", None) is None:
+            obs.peel = dict(u=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
+                            dz0=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
+                            parts=torch.empty(nparts * (self.w * self.d + self.w), dtype=torch.float32, device=self.device), nparts=nparts)
+        if self.peel_params is None:
             Pp = int(self.lib.cl_mlp_param_count(self.w, self.w, self.L))
             self.peel_params = torch.zeros(Pp, dtype=torch.float32, device=self.device)
             self.peel_grad = torch.zeros(Pp, dtype=torch.float32, device=self.device)
-        return pb
+        return obs.peel
 
     def _peel_args(self, ma: MlpArgs, obs: ObsData) -> MlpArgs:
         """The fused launch behind the peeled first layer: the layer's pre-activations as metadata, identity first layer, dZ_0 out."""
         pb = self._peel_bufs(obs)
-        a = MlpArgs()
-        C.memmove(C.byref(a), C.byref(ma), C.sizeof(MlpArgs))
+        a = _copy_args(ma)
         a.meta_t, a.d, a.mlp, a.dZ0_out = ptr(pb["u"]), self.w, ptr(self.peel_params), ptr(pb["dz0"])
         return a
 
-    def _fused_step_launch(self, ma: MlpArgs, obs: ObsData, st):
-        """cl_elbo_mono_fwd_bwd, behind cl_peel_forward when the first layer is peeled (self.peel)."""
-        if not self.peel:
-            check(self.lib.cl_elbo_mono_fwd_bwd(C.byref(ma), obs.grid, st), "cl_elbo_mono_fwd_bwd")
-            return
-        pb, lay = self._peel_bufs(obs), self.layout
-        check(self.lib.cl_peel_forward(ptr(obs.meta_t), ma.n_obs, obs.n_pad, self.d, self.w, self.L, self.params.data_ptr() + 4 * lay.off_mlp, ptr(pb["u"]),
-                                       ptr(self.peel_params), ptr(self.peel_grad), int(self.peel_grad.numel()), ptr(self.stop_flag), st), "cl_peel_forward")
-        a = self._peel_args(ma, obs)
+    def _fused_step_launch(self, a: MlpArgs, obs: ObsData, st):
+        """cl_elbo_mono_fwd_bwd on `_likelihood_args`' arguments, behind cl_peel_forward when the first layer is peeled (self.peel)."""
+        if self.peel:
+            pb, lay = obs.peel, self.layout
+            check(self.lib.cl_peel_forward(ptr(obs.meta_t), a.n_obs, obs.n_pad, self.d, self.w, self.L, self.params.data_ptr() + 4 * lay.off_mlp, ptr(pb["u"]),
+                                           ptr(self.peel_params), ptr(self.peel_grad), int(self.peel_grad.numel()), ptr(self.stop_flag), st), "cl_peel_forward")
         check(self.lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
 
     def _peel_reduce(self, obs: ObsData, st, n_obs: int):
@@ -1041,8 +1031,7 @@ class ElboEngine(WidePath):
     def _block_args(self, ma: MlpArgs, obs: ObsData, k: int) -> MlpArgs:
         """Arguments of block k of the chain: its slice of the parameters, its input (metadata or the previous block's output)."""
         lay, b = self.layout, self.blocks[k]
-        a = MlpArgs()
-        C.memmove(C.byref(a), C.byref(ma), C.sizeof(MlpArgs))
+        a = _copy_args(ma)
         a.mlp = self.params.data_ptr() + 4 * (lay.off_mlp + b.off)
         a.d, a.L = b.d_in, b.l1 - b.l0
         a.meta_t = ptr(obs.meta_t) if k == 0 else ptr(obs.chain_act[k - 1])
@@ -1058,20 +1047,14 @@ class ElboEngine(WidePath):
             a = self._block_args(ma, obs, k)
             a.act_out = ptr(obs.chain_act[k])
             check(lib.cl_mlp_forward(C.byref(a), obs.grid, st), "cl_mlp_forward")
-        a = self._block_args(ma, obs, K - 1)
-        if getattr(self, "chain_lane", False):
-            # the last block on the lane kernel: dZ_0 of its first layer out (into a buffer of the boundary's shape), then dX = W_0^T dZ_0
-            if getattr(obs, "chain_dz0", None) is None:
-                obs.chain_dz0 = torch.zeros_like(obs.chain_dact[K - 2])
-            a.dZ0_out = ptr(obs.chain_dz0)
-            check(lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
-            check(lib.cl_chain_dx(ptr(obs.chain_dz0), a.mlp, a.n_obs, obs.n_pad, self.w, self.w, ptr(obs.chain_dact[K - 2]), ptr(self.stop_flag), st), "cl_chain_dx")
+        a, _ = self._likelihood_args(ma, obs)
+        if self.laue:
+            a.dO_ext = ptr(obs.laue_dO)
+            self._laue_passes(a, obs, step, eta, ipred_out, st)
         else:
-            a.dX_out = ptr(obs.chain_dact[K - 2])
-            if self.laue:
-                self._laue_passes(a, obs, step, eta, ipred_out, st)
-            else:
-                check(lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
+            check(lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
+            if self.chain_lane:     # the last block on the lane kernel handed back dZ_0 of its first layer: dX = W_0^T dZ_0
+                check(lib.cl_chain_dx(ptr(obs.chain_dz0), a.mlp, a.n_obs, obs.n_pad, self.w, self.w, ptr(obs.chain_dact[K - 2]), ptr(self.stop_flag), st), "cl_chain_dx")
         check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, self.blocks[K - 1].P, gptr(K - 1), ptr(self.stop_flag), st),
               "cl_reduce_partials")
         for k in range(K - 2, -1, -1):
@@ -1092,7 +1075,7 @@ class ElboEngine(WidePath):
         tn = self._tn_args(key, u_f)
         check(lib.cl_tn_forward(C.byref(tn), st), "cl_tn_forward")
         self._data_term(obs, key, eta, None, st)
-        if self.owner and self.shard.world > 1 and not getattr(self, "local_only", False):
+        if self.owner and self.shard.world > 1 and not self.local_only:
             # an owner-mode rank holds the validation rows of ITS reflections (make_obs): the set's NLL is the sum over the ranks
             import torch.distributed as dist
             t = self.scalars[0:1].clone()
@@ -1117,36 +1100,32 @@ class ElboEngine(WidePath):
         if o.d != self.d:
             raise ValueError("validation metadata width differs from the training data")
         if self.blocks is not None:
-            o.alloc_chain(self.lib, self.blocks, self.w, self.device)
+            o.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         return o
 
     def _laue_passes(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
         """Harmonic deconvolution (reference likelihoods/laue.py:9-47): scaler forward, predict + group sums, likelihood on
-        the slots, gradient broadcast back to the rows, scaler backward from dL/d(loc, sigma)."""
+        the slots, gradient broadcast back to the rows, scaler backward from dL/d(loc, sigma).  `ma`: the backward launch's arguments
+        (`dO_ext` set: `_likelihood_args`); the forward launch runs on a copy without it."""
         lib = self.lib
         ma.loc_out, ma.sig_out = ptr(obs.laue_loc), ptr(obs.laue_sig)
-        check(lib.cl_mlp_forward(C.byref(ma), obs.grid, st), "cl_mlp_forward")
+        fwd = _copy_args(ma)
+        fwd.dO_ext = None
+        check(lib.cl_mlp_forward(C.byref(fwd), obs.grid, st), "cl_mlp_forward")
         self._slot_likelihood(ma, obs, step, eta, ipred_out, st)
-        ma.dO_ext = ptr(obs.laue_dO)
         check(lib.cl_mlp_backward_ext(C.byref(ma), obs.grid, st), "cl_mlp_backward_ext")
 
     def _slot_args(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, a: int = 0, n: Optional[int] = None) -> LaueArgs:
         """Arguments of the slot likelihood kernels for the rows [a, a + n) of `obs` (default: all of them)."""
-        la = LaueArgs()
+        la = self._step_fields(LaueArgs(), obs, step)
         n = obs.N - a if n is None else n
         off = lambda t, size: None if t is None else t.data_ptr() + size * a
         la.refl_id, la.image_id, la.harmonic_id = off(obs.refl_id, 4), off(obs.image_id, 4), off(obs.harmonic_id, 4)
         la.loc, la.sigma, la.iobs, la.sig = off(obs.laue_loc, 4), off(obs.laue_sig, 4), off(obs.iobs, 4), off(obs.sig, 4)
         la.n_obs, la.obs_offset = n, obs.start + a
-        la.img, la.use_img = ma.img, ma.use_img
-        la.z_f, la.R, la.S = ptr(self.z_f), self.R, self.S
-        la.lik_kind, la.dof, la.lik_const = self.lik_kind, self.dof, self.lik_const
-        la.shift, la.w_ll = ma.shift, ma.w_ll
-        la.eta = off(eta, 4 * self.S)
-        la.seed, la.step = self.seed, step & 0xFFFFFFFF
-        la.iconv, la.dz_f, la.d_img, la.dO = off(obs.laue_iconv, 4 * self.S), ptr(self.dz_f), ma.d_img, off(obs.laue_dO, 8)
-        la.scalars, la.ipred_out, la.stop_flag = ptr(self.scalars), off(ipred_out, 4 * self.S), ptr(self.stop_flag)
-        la.ev11, la.d_ev11 = ma.ev11, ma.d_ev11
+        la.img, la.use_img, la.d_img = ma.img, ma.use_img, ma.d_img
+        la.eta, la.ipred_out = off(eta, 4 * self.S), off(ipred_out, 4 * self.S)
+        la.iconv, la.dO = off(obs.laue_iconv, 4 * self.S), off(obs.laue_dO, 8)
         la.row_index = off(obs.row_index, 8)
         return la
 
@@ -1162,9 +1141,7 @@ class ElboEngine(WidePath):
             # reflection order: det_slot), every workgroup stores its NLL; cl_det_reduce sums them in a fixed order after the backward pass
             det = obs.det_parent.det
             la.dzf_obs, la.dimg_obs, la.det_slot = ptr(det["dzf"]), ptr(det["dimg"]), ptr(det["slot"])
-            la.nll_part = det["nll"].data_ptr() + 8 * det["pieces"] * det["grid"]
-            if self.ev11:
-                la.ev11_part = det["ev11"].data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det["pieces"] * det["grid"]
+            la.nll_part, la.ev11_part = self._det_parts(obs, det["pieces"])
             check(lib.cl_slot_rows(C.byref(la), st), "cl_slot_rows")
             return
         if obs.harmonic_id is None and self.SLOT_ROWS_ONE_LAUNCH:
@@ -1187,7 +1164,7 @@ class ElboEngine(WidePath):
         them (the output step, saved weights, a later `train_model` call).  One sum all-reduce of a vector that is zero outside the
         rank's own ranges -- once per training run, not per step.  Adam's moments stay with the owner (ownership is fixed for the
         engine's lifetime)."""
-        if not self.owner or self.shard.world <= 1 or getattr(self, "local_only", False):
+        if not self.owner or self.shard.world <= 1 or self.local_only:
             return
         import torch.distributed as dist
         if not dist.is_initialized():
@@ -1270,7 +1247,7 @@ class ElboEngine(WidePath):
         """Synchronise and convert the device history to the reference's dict of lists (variational.py:262-268).
         Steps after the first non-finite gradient norm were skipped on the device and are dropped, which reproduces
         the reference's early `break` (:271-274)."""
-        if self.shard.world > 1 and not getattr(self, "local_only", False) and not self._hist_reduced:
+        if self.shard.world > 1 and not self.local_only and not self._hist_reduced:
             self._hist_reduced = True
             # the records hold this rank's partial NLL / KL: summed over the ranks once, in fp64 (careless_amd/distributed.py)
             from careless_amd.distributed import allreduce_history_

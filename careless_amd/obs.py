@@ -216,6 +216,21 @@ class ObsData:
         stop = self.N_total if stop is None else stop
         self.laue = BaseModel.is_laue(inputs)
         self.rows = None                      # explicit row list when the shard is not a contiguous range
+        self.empty = False
+        # what the engine attaches later (careless_amd/engine.py, wide.py); None / 0 / False until then
+        self.host_inputs = None               # the caller's inputs (a reference: the frozen-scaler path reads the rows' metadata once per training)
+        self.row0, self.is_piece = 0, False   # piece of a chunked shard (`ObsChunks`): its first row inside the shard's eta / ipred arrays
+        self.det = self.det_parent = None     # deterministic mode: the shard's buffers (on the set `cl_det_reduce` runs on), the set a piece stores into
+        self.det_index = 0                    # ... and the piece's part of its NLL / Evans-2011 slots
+        self.peel = None                      # buffers of a peeled first layer
+        self.frozen_sorted = self.locsig_epoch = None         # frozen scaler: the per-training row arrays, the `train_model` call (loc, sigma) are of
+        self.chain_act = self.chain_dact = self.chain_dz0 = None      # chained scaler: activations / their gradients at the block boundaries, dZ_0 of a lane-kernel last block
+        self.wide_chunks = self.wide_tiles = self.wide_full = self.wide_dsd = None     # layer-by-layer path: row chunks, tile lists, kept activations, d sigma / d raw
+        self.harmonic_id = self.laue_loc = self.laue_sig = self.laue_iconv = self.laue_dO = None      # slot kernels' inputs and work buffers
+        self.pad_iobs = self.pad_sig = self.pad_iconv = None          # single-pass Laue: the padded slots' own arrays
+        self.pad_uniform = False
+        self.perm = self.img_seg = self.meta_rm = None                # layer-by-layer path: image order of the rows, row-major metadata [rows][meta_ld]
+        self.meta_ld = 0
         if self.laue and laue_groups is not None:
             hid_all = _np(BaseModel.get_harmonic_id(inputs)).reshape(-1)
             g0, g1, pad0, pad1 = laue_groups
@@ -308,7 +323,6 @@ class ObsData:
             self.meta_ld = int(lib.cl_wide_ld(self.d))                 # [rows][ld]: the features, zero padding to a multiple of four
             rm = np.zeros((self.N, self.meta_ld), dtype=np.float32)
             rm[:, : self.d] = metadata[sl]
-            self.perm = None
             if sort_images:
                 # per-image layers on this path: the rows of an image must be consecutive (grouped GEMM kernels); everything per row
                 # is stored in image order, `perm` maps the local order back to the caller's
@@ -342,9 +356,9 @@ class ObsData:
                 self.row_index = torch.as_tensor(self.rows.astype(np.int64), device=device)
         if wide and not self.laue:
             hl = None                          # every row its own "harmonic group" (harmonic_id NULL): the slot kernels then ARE the mono likelihood
-        elif wide and getattr(self, "perm", None) is not None:
+        elif wide and self.perm is not None:
             hl = hl[self.perm]
-        if wide and getattr(self, "perm", None) is not None:
+        if wide and self.perm is not None:
             # global rows in the stored (image) order: the noise key of every row, and which columns of an injected eta are its
             base_rows = self.rows if self.rows is not None else np.arange(self.start, self.start + self.N)
             self.rows = np.asarray(base_rows)[self.perm]
@@ -358,13 +372,14 @@ class ObsData:
         g = int(grid) if grid is not None else max(1, int(lib.cl_mlp_default_grid()))
         self.grid = min(g, self.n_pad // TILE)
         self.partials = torch.empty(0 if wide else self.grid * P, dtype=torch.float32, device=device)
-        self.chain_act = self.chain_dact = None       # activations / their gradients at the block boundaries of a chained scaler
 
-    def alloc_chain(self, lib, blocks, w, device):
+    def alloc_chain(self, lib, blocks, w, device, lane: bool = False):
+        """Buffers of a chained scaler; `lane`: the last block runs on the lane kernel, which hands back dZ_0 of its first layer."""
         rows = int(lib.cl_mlp_meta_rows(w))
         n = len(blocks) - 1
         self.chain_act = [torch.zeros(rows, self.n_pad, dtype=torch.float32, device=device) for _ in range(n)]
         self.chain_dact = [torch.zeros(rows, self.n_pad, dtype=torch.float32, device=device) for _ in range(n)]
+        self.chain_dz0 = torch.zeros_like(self.chain_dact[-1]) if lane else None      # (a buffer of the last boundary's shape)
 
 
 class ObsChunks:
@@ -379,15 +394,19 @@ class ObsChunks:
         c0 = children[0]
         self.start, self.N, self.N_total, self.d = c0.start, sum(c.N for c in children), c0.N_total, c0.d
         self.n_pad, self.grid, self.partials = sum(c.n_pad for c in children), c0.grid, c0.partials
-        self.laue, self.fused_laue, self.rows, self.row_map, self.row0 = False, False, None, None, 0
+        self.laue, self.fused_laue, self.rows, self.row_map, self.perm, self.empty = False, False, None, None, None, False
+        self.det = None                             # deterministic mode: the shard's buffers (ElboEngine._det_attach)
+        row0 = 0
         for c in children:
-            if getattr(c, "rows", None) is None:
-                c.row0 = c.start - self.start       # first row of the piece inside the shard's eta / ipred arrays
+            c.row0, c.is_piece = row0, True         # first row of the piece inside the shard's eta / ipred arrays; several launches share dz_f
+            row0 += c.N
 
-    def alloc_chain(self, lib, blocks, w, device):
-        self.children[0].alloc_chain(lib, blocks, w, device)         # the pieces run one after the other: one set of buffers
+    def alloc_chain(self, lib, blocks, w, device, lane: bool = False):
+        c0 = self.children[0]
+        c0.alloc_chain(lib, blocks, w, device, lane)                 # the pieces run one after the other: one set of buffers
         for c in self.children[1:]:
-            c.chain_act, c.chain_dact = self.children[0].chain_act, self.children[0].chain_dact
+            c.chain_act, c.chain_dact = c0.chain_act, c0.chain_dact
+            c.chain_dz0 = torch.zeros_like(c0.chain_dz0) if lane else None
 
 
 class _EmptyObs:

@@ -34,7 +34,7 @@ class WidePath:
         """Work buffers of the unfused path (csrc/wide_gemm.hip): one activation buffer per hidden layer (Dense + per-image) + two
         gradient buffers of `chunk` rows, the per-layer weight-gradient partials.  The chunk is sized from the layer count and
         width so the buffers stay inside WIDE_BUDGET (and, with it, inside the device memory next to the shard)."""
-        if getattr(self, "_wide", None) is not None:
+        if self._wide is not None:
             return self._wide
         lib, dev = self.lib, self.device
         ldw = int(lib.cl_wide_ld(self.w))
@@ -66,7 +66,7 @@ class WidePath:
     def _wide_chunks(self, obs: ObsData):
         """Row chunks [a, b) of `obs` for the layer-by-layer path.  With per-image layers a chunk holds whole images (their rows are
         consecutive: ObsData sort_images) and carries (first image, device array of the images' row starts relative to a)."""
-        if getattr(obs, "wide_chunks", None) is not None:
+        if obs.wide_chunks is not None:
             return obs.wide_chunks
         W = self._wide_setup()
         chunks = []
@@ -83,7 +83,7 @@ class WidePath:
                     rel = torch.as_tensor((seg[m0:m1 + 1] - seg[m0]).astype(np.int32), device=self.device)
                     chunks.append((int(seg[m0]), int(seg[m1]), m0, rel))
                     if self.w > 128:            # wider than the grouped streaming kernel holds: the tiled kernel's list of row pieces
-                        if getattr(obs, "wide_tiles", None) is None:
+                        if obs.wide_tiles is None:
                             obs.wide_tiles = {}
                         obs.wide_tiles[int(seg[m0])] = image_tiles(seg[m0:m1 + 1] - seg[m0], self.device)
                 m0 = m1
@@ -133,9 +133,8 @@ class WidePath:
         recomputes each chunk's forward into the chunk-sized buffers."""
         W = self._wide_setup()
         need = 4 * (W["nh"] - (1 if self._wide_pre() else 0)) * W["ldw"] * obs.N
-        have = getattr(obs, "wide_full", None)
-        if have is not None:
-            return have
+        if obs.wide_full is not None:
+            return obs.wide_full
         free = torch.cuda.mem_get_info(self.device)[0]
         if need > min(self.WIDE_KEEP_BUDGET, free // 4):
             return None
@@ -228,7 +227,7 @@ class WidePath:
         full = self._wide_keep_all(obs)
         kept = []
         headb = self._wide_head_bwd()
-        if headb and getattr(obs, "wide_dsd", None) is None:
+        if headb and obs.wide_dsd is None:
             obs.wide_dsd = torch.empty(obs.N, dtype=torch.float32, device=self.device)
         # The slot likelihood rides in the top layer's forward epilogue when a production step asks for nothing else of it (rows that are
         # their own slot, in-kernel noise, no predictions out, no Evans-2011 terms, not the deterministic mode); the library decides by

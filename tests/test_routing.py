@@ -98,3 +98,46 @@ def test_per_image_layers_run_on_the_kernel_the_design_names(L, w, d, K, laue, f
     eng.alloc_history(1)
     eng.train_step(0)
 
+
+
+def _table_kw(row):
+    if isinstance(row[3], str):                             # a row of TABLE (its fourth column is the name fragment)
+        L, w, d = row[:3]
+        return dict(N=300, R=30, d0=d, L=L, w=w, S=1, perturb=0.02)
+    L, w, d, K, laue = row[:5]                              # a row of IMGL_TABLE
+    kw = dict(N=600, R=30, L=L, w=w, S=1, perturb=0.02, image_layers=K, n_images=5)
+    kw.update(dict(laue=True) if laue else dict(d0=d))
+    return kw
+
+
+@pytest.mark.parametrize("row", TABLE + IMGL_TABLE, ids=[f"{r[0]}x{r[1]}_d{r[2]}" for r in TABLE] +
+                         [f"{r[0]}x{r[1]}_d{r[2]}_K{r[3]}{'_laue' if r[4] else ''}" for r in IMGL_TABLE])
+def test_training_launch_is_the_launch_a_step_issues(row, monkeypatch):
+    """`plan.route` and `training_launch()` against the step itself: the three scaler entry points are wrapped, one `forward_backward` runs,
+    and the launch that computes the likelihood -- the last `cl_elbo_mono_fwd_bwd`; on the two-pass Laue path the first `cl_mlp_backward_ext`
+    with `dO_ext` -- is asked for its own `cl_mlp_route`.  Layer-by-layer rows issue none of the three."""
+    import ctypes as C
+
+    import torch
+
+    from careless_amd import _lib
+    from careless_amd.engine import ElboEngine
+    kw = _table_kw(row)
+    data, cfg, params, x, u_f, eta = util.make_problem(**kw)
+    eng = ElboEngine(util.build_model(data, cfg, params, kw["L"], kw["w"]), util.reference_inputs(data), seed=1)
+    lib, seen = eng.lib, []
+    for mode, entry in enumerate(("cl_elbo_mono_fwd_bwd", "cl_mlp_forward", "cl_mlp_backward_ext")):
+        def wrapped(a, grid, stream, _mode=mode, _fn=getattr(lib, entry)):
+            seen.append((_mode, bool(a._obj.dO_ext), int(lib.cl_mlp_route(a, _mode))))
+            return _fn(a, grid, stream)
+        monkeypatch.setattr(lib, entry, wrapped)
+    eng.forward_backward(0)
+    torch.cuda.synchronize()
+    if eng.wide:
+        assert eng.plan.route == _lib.CL_ROUTE_NONE and not seen
+        return
+    fused = [s for s in seen if s[0] == 0]
+    mode, _, route = fused[-1] if fused else next(s for s in seen if s[0] == 2 and s[1])
+    ma, want_mode = eng.training_launch()
+    assert route == eng.plan.route, (seen, eng.plan)
+    assert (mode, route) == (want_mode, eng.lib.cl_mlp_route(C.byref(ma), want_mode)), seen
