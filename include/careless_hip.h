@@ -281,6 +281,11 @@ int cl_det_reduce(const cl_det_args* args, void* stream);
  *           (careless/models/merging/variational.py:197-202) when the hidden or the metadata width exceeds what the fused kernels
  *           hold (64): one fp32-MFMA GEMM per layer and direction, activations in HBM, in row chunks chosen by the caller.
  * Activation buffers are row-major [rows][ld], ld = cl_wide_ld(width) = the width rounded up to 4.
+ * Padding columns: the columns [width, ld) of every row buffer passed in are ZERO, and every cl_wide_* call leaves the padding columns of
+ * its outputs zero (the square-layer kernels and the head's backward pass read and write whole float4 quads of a row, padding included:
+ * that is what keeps the next layer correct).  ld % 4 == 0 and 16-byte aligned buffers are what the engine passes; any other pitch or
+ * alignment takes the kernels' element-wise (scalar) loads and stores where the entry point accepts it (cl_wide_dense_forward / _dgrad /
+ * _wgrad and the per-image forms), and is refused (-1 / -2) by the entry points that say so below.
  * Weights in the W^T layout of the flat parameter vector (Wt[out][in], then b[out]).
  * Call order per row chunk, generic form (any width): cl_wide_dense_forward x L -> cl_wide_head_forward -> [likelihood: cl_slot_rows when
  * every row is its own slot, cl_laue_predict / _likelihood / _backward otherwise] -> cl_wide_dense_forward x L again unless the activations

@@ -564,6 +564,29 @@ def test_wide_path_envelope_queries():
     assert lib.cl_wide_dense_dgrad_pre_wgrad0(None, 128, None, 100, 128, 128, None, 8, 5, None, None, 0.01, None, None, None) == -1
 
 
+def test_wide_entry_points_answer_without_a_launch():
+    """The -2 (shape outside the kernel's envelope) and -1 (bad layout) answers of the layer-by-layer entry points that are given before
+    anything is launched or dereferenced: the pointers below are made-up addresses.  That is safe only while each of these checks stays
+    ahead of the launch in csrc/wide_gemm.hip (every call below was read against it: all return before hipLaunchKernelGGL) -- whoever
+    reorders an entry check must keep it so, or this test launches on a bogus pointer where a device is present."""
+    lib = _lib.get_lib()
+    p, off = 0x10000, 0x10004                        # 16-byte aligned / 4 bytes off
+    # the top layer with the head in its epilogue: layers up to 128 x 128
+    for n_in, n_out in ((129, 64), (64, 129)):
+        assert lib.cl_wide_dense_forward_head(p, 132, p, p, 100, n_in, n_out, 0.01, p, 132, p, 0, 1e-7, p, p, None, None, None) == -2
+    # the head's backward pass inside the top layer's dgrad: the square-layer envelope (65 .. 128, same number of 16-column blocks)
+    for n_out, n_in in ((96, 128), (64, 64), (129, 129), (128, 60)):
+        assert lib.cl_wide_dense_dgrad_head(p, 132, p, p, p, p, 100, n_out, n_in, p, 132, 0.01, p, 132, None, None) == -2
+    # the recomputed first layer takes at most 15 metadata columns
+    assert lib.cl_wide_dense_wgrad_pre(p, 128, p, 16, 16, p, p, 0.01, 100, 128, 128, p, 1, None, None) == -2
+    assert lib.cl_wide_dense_wgrad_pre(p, 128, off, 16, 15, p, p, 0.01, 100, 128, 128, p, 1, None, None) == -1      # (X0 off 16-byte alignment)
+    # the head's backward pass reads H and writes dZ as float4: pitch a multiple of 4, 16-byte aligned, width at most 1024
+    assert lib.cl_wide_head_backward(p, 128, p, p, 100, 128, 0, 1e-7, 0.01, off, 128, p, 1, None, None) == -1
+    assert lib.cl_wide_head_backward(off, 128, p, p, 100, 128, 0, 1e-7, 0.01, p, 128, p, 1, None, None) == -1
+    assert lib.cl_wide_head_backward(p, 128, p, p, 100, 126, 0, 1e-7, 0.01, p, 126, p, 1, None, None) == -1
+    assert lib.cl_wide_head_backward(p, 1028, p, p, 100, 1025, 0, 1e-7, 0.01, p, 1028, p, 1, None, None) == -2
+
+
 def test_round6_entry_points_host_side():
     """`cl_frozen_rows` / `cl_chain_dx` (round 6): workspace queries and argument checks answer without a device."""
     import ctypes as C
