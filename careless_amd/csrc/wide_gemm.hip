@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 #include "cl_math.h"
 #include "cl_kernels.h"
 
@@ -948,19 +949,6 @@ void wide_stream2_kernel(const Stream2Args S) {
     }
 }
 
-template <int NA>
-int launch_stream2(const Stream2Args& s, hipStream_t st) {
-    constexpr int NA0 = NA, NA1 = NA;
-    const size_t sm = (size_t)(16 * NA1 * SKP + 3 * 16 * NA1 + 16 * NA0 * (S0P + 1)) * sizeof(float);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const long long nblk = (s.n + 15) >> 4;
-    long long grid = (nblk + 7) / 8;
-    if (grid > 2LL * cus) grid = 2LL * cus;
-    if (grid < 1) grid = 1;
-    return cl_launch_lds<wide_stream2_kernel<NA>>(dim3((unsigned)grid), dim3(512), sm, st, s);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // square layers (hidden -> hidden: N and K span the same number NA of 16-column blocks), round 4
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1312,79 +1300,169 @@ void wide_sq_kernel(const StreamArgs S) {
     }
 }
 
-// 1: the square-layer kernel takes this call (same block count on both sides, row buffers laid out as cl_wide_ld says, 16-byte aligned)
-static bool sq_ok(const StreamArgs& s) {
+// ---------------------------------------------------------------------------------------------------------------------------
+// host side: the one launch layer under the cl_wide_* entry points -- grid and LDS sizing, argument builders, the launchers that
+// turn run-time widths into kernel instances.  Every launch of this file is a cl_launch_lds call (cl_kernels.h).
+// ---------------------------------------------------------------------------------------------------------------------------
+int cu_count() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+
+// workgroups of a streaming launch that wants `want` of them: two 8-wave workgroups per CU at most (2 x 67.6 KB of LDS at 128 x 128)
+long long stream_grid(long long want) {
+    const long long most = 2LL * cu_count();
+    if (want > most) want = most;
+    return want < 1 ? 1 : want;
+}
+// ... one per eight 16-row blocks of n rows
+long long row_grid(long long n) { return stream_grid((((n + 15) >> 4) + 7) / 8); }
+
+// dynamic LDS of a streaming kernel of NA 16-column blocks: weights, bias, the fused head's two rows; a recomputed first layer (the
+// dgrad with a recomputed mask, the two-layer forward) adds that layer's image and bias
+constexpr size_t stream_lds(int NA, bool pre) { return (size_t)(16 * NA * SKP + 3 * 16 * NA + (pre ? 16 * NA * (S0P + 1) : 0)) * sizeof(float); }
+
+// what the entry checks repeat
+bool rows_ok(long long n) { return n >= 1 && n <= 0x7fffffffLL; }        // (a row count the kernels' 32-bit row indices hold)
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <class... P>
+bool any_null(const P*... p) { return ((p == nullptr) || ...); }
+
+// f(std::integral_constant<int, NA>) for the run-time block count na = LO .. 7; every other count takes the 8-block instance
+template <int LO, class F>
+int with_blocks(int na, F f) {
+    if constexpr (LO < 8) return na == LO ? f(std::integral_constant<int, LO>{}) : with_blocks<LO + 1>(na, f);
+    else return f(std::integral_constant<int, 8>{});
+}
+
+// the fields every streaming launch shares: rows X [n][ldx] (K columns) against W (pitch ldw) -> Y [n][ldy] (N columns)
+StreamArgs stream_args(const float* X, int ldx, const float* W, int ldw, float* Y, int ldy, long long n, int N, int K, float leak, const int* stop_flag) {
+    StreamArgs s = {};
+    s.X = X; s.ldx = ldx; s.W = W; s.ldw = ldw; s.Y = Y; s.ldy = ldy; s.n = n; s.N = N; s.K = K;
+    s.leak = leak; s.stop_flag = stop_flag;
+    return s;
+}
+
+PreArgs pre_args(const float* X0, int ldx0, int n_in0, const float* Wt0, const float* b0, int w) {
+    PreArgs p = {};
+    p.X0 = X0; p.ldx0 = ldx0; p.K0 = n_in0; p.W0 = Wt0; p.b0 = b0; p.N0 = w;
+    return p;
+}
+
+// the fields every tiled launch shares: C [M][N] (pitch ldc) from A (pitch lda) and B (pitch ldb), contraction K
+GemmArgs gemm_args(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float leak, const int* stop_flag) {
+    GemmArgs g = {};
+    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.leak = leak; g.stop_flag = stop_flag;
+    return g;
+}
+
+// ... of a per-image layer's forward / dgrad on the list of row pieces `tiles`: one w x w kernel per image
+GemmArgs tile_args(const float* A, int lda, const float* W, int w, float* C, int ldc, const int* seg, const int* tiles, float leak, const int* stop_flag) {
+    GemmArgs g = gemm_args(A, lda, W, w, C, ldc, 0, w, w, leak, stop_flag);
+    g.seg = seg; g.tiles = tiles; g.bgs = (long long)w * w;
+    return g;
+}
+
+// ... of a Dense layer's weight gradient split over `nsplit` row ranges (whole BK chunks each): partial s of [dWt (n_out x n_in) | db (n_out)]
+// at partials + s * pstride
+GemmArgs wgrad_args(const float* A, int lda, const float* B, int ldb, float* partials, long long n, int n_out, int n_in, int nsplit, float leak,
+                    const int* stop_flag) {
+    GemmArgs g = gemm_args(A, lda, B, ldb, partials, 0, n_out, n_in, (int)n, leak, stop_flag);
+    g.n_in = n_in;
+    g.ksplit = ((int)((n + nsplit - 1) / nsplit) + BK - 1) / BK * BK;
+    g.pstride = (long long)n_out * n_in + n_out;
+    return g;
+}
+
+// 1: the square-layer kernel takes this call (same block count on both sides, row buffers laid out as cl_wide_ld says, 16-byte aligned);
+// `stores_rows` = false: a launch that writes no row output (s.Y stays null), so only its operands are judged
+bool sq_ok(const StreamArgs& s, bool stores_rows = true) {
     if (s.seg != nullptr) return false;
     const int NA = (s.N + 15) >> 4, KA = (s.K + 15) >> 4;
     if (NA != KA || NA < 5) return false;                      // (up to 64 the generic instance is as good; 65 .. 128 is what this path is for)
-    if (s.ldx % 4 != 0 || s.ldy % 4 != 0 || s.ldx < s.K || s.ldy < s.N || s.ldx > 16 * NA || s.ldy > 16 * NA) return false;
-    if ((reinterpret_cast<uintptr_t>(s.X) & 15) != 0 || (reinterpret_cast<uintptr_t>(s.Y) & 15) != 0) return false;
-    if (s.H != nullptr && (s.ldh % 4 != 0 || s.ldh > 16 * NA || (reinterpret_cast<uintptr_t>(s.H) & 15) != 0)) return false;
+    if (s.ldx % 4 != 0 || s.ldx < s.K || s.ldx > 16 * NA || !aligned16(s.X)) return false;
+    if (stores_rows && (s.ldy % 4 != 0 || s.ldy < s.N || s.ldy > 16 * NA || !aligned16(s.Y))) return false;
+    if (s.H != nullptr && (s.ldh % 4 != 0 || s.ldh > 16 * NA || !aligned16(s.H))) return false;
     return true;
-}
-
-static long long sq_grid(long long n) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const long long nblk = (n + 15) >> 4;
-    long long grid = (nblk + 7) / 8;
-    if (grid > 2LL * cus) grid = 2LL * cus;
-    return grid < 1 ? 1 : grid;
-}
-
-template <bool WKM, int EPI, int NA, bool PRE, bool WG0 = false, bool HEADB = false, bool LIK = false>
-int launch_sq_n(const StreamArgs& s, hipStream_t st) {
-    const size_t sm = (size_t)(16 * NA * SKP + 3 * 16 * NA + (PRE ? 16 * NA * (S0P + 1) : 0)) * sizeof(float);
-    const long long grid = sq_grid(s.n);
-    return cl_launch_lds<wide_sq_kernel<WKM, EPI, NA, PRE, WG0, HEADB, LIK>>(dim3((unsigned)grid), dim3(512), sm, st, s);
 }
 
 template <bool WKM, int EPI, bool PRE, bool WG0 = false, bool HEADB = false, bool LIK = false>
 int launch_sq(const StreamArgs& s, hipStream_t st) {
-    switch ((s.N + 15) >> 4) {
-        case 5: return launch_sq_n<WKM, EPI, 5, PRE, WG0, HEADB, LIK>(s, st);
-        case 6: return launch_sq_n<WKM, EPI, 6, PRE, WG0, HEADB, LIK>(s, st);
-        case 7: return launch_sq_n<WKM, EPI, 7, PRE, WG0, HEADB, LIK>(s, st);
-        default: return launch_sq_n<WKM, EPI, 8, PRE, WG0, HEADB, LIK>(s, st);
-    }
+    return with_blocks<5>((s.N + 15) >> 4, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        return cl_launch_lds<wide_sq_kernel<WKM, EPI, NA, PRE, WG0, HEADB, LIK>>(dim3((unsigned)row_grid(s.n)), dim3(512), stream_lds(NA, PRE), st, s);
+    });
 }
 
-template <bool WKM, int EPI, int NAT, bool GRP, bool PRE = false>
+// the generic streaming kernel: the 4-block instance up to 64 output columns, the 8-block one above; grouped (per-image layers): a
+// workgroup per image at most
+template <bool WKM, int EPI, int NAT, bool GRP, bool PRE>
 int launch_stream_n(const StreamArgs& s, hipStream_t st) {
-    const int NA = (s.N + 15) >> 4;
-    // weights, bias, the fused head's two rows; the dgrad with a recomputed mask adds the first layer's image and bias
-    const size_t sm = (size_t)(16 * NA * SKP + 3 * 16 * NA + (PRE ? 16 * NA * (S0P + 1) : 0)) * sizeof(float);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const long long nblk = (s.n + 15) >> 4;
-    long long grid = s.seg != nullptr ? (long long)s.n_groups : (nblk + 7) / 8;
-    if (grid > 2LL * cus) grid = 2LL * cus;          // two 8-wave workgroups per CU (2 x 67.6 KB of LDS at 128 x 128)
-    if (grid < 1) grid = 1;
-    return cl_launch_lds<wide_stream_kernel<WKM, EPI, NAT, GRP, PRE>>(dim3((unsigned)grid), dim3(512), sm, st, s);
+    const long long grid = s.seg != nullptr ? stream_grid(s.n_groups) : row_grid(s.n);
+    return cl_launch_lds<wide_stream_kernel<WKM, EPI, NAT, GRP, PRE>>(dim3((unsigned)grid), dim3(512), stream_lds((s.N + 15) >> 4, PRE), st, s);
 }
 
-template <bool WKM, int EPI>
+template <bool WKM, int EPI, bool PRE = false>
 int launch_stream(const StreamArgs& s, hipStream_t st) {
-    if (s.seg != nullptr) return s.N <= 64 ? launch_stream_n<WKM, EPI, 4, true>(s, st) : launch_stream_n<WKM, EPI, 8, true>(s, st);
-    if (s.N <= 64) return launch_stream_n<WKM, EPI, 4, false>(s, st);
-    return launch_stream_n<WKM, EPI, 8, false>(s, st);
+    if constexpr (!PRE) {                                       // (no grouped instance recomputes a first layer)
+        if (s.seg != nullptr) return s.N <= 64 ? launch_stream_n<WKM, EPI, 4, true, false>(s, st) : launch_stream_n<WKM, EPI, 8, true, false>(s, st);
+    }
+    return s.N <= 64 ? launch_stream_n<WKM, EPI, 4, false, PRE>(s, st) : launch_stream_n<WKM, EPI, 8, false, PRE>(s, st);
+}
+
+// a layer inside the streaming kernels' envelope: the square-layer kernel where it takes the call, else the generic one
+template <bool WKM, int EPI, bool PRE = false>
+int launch_layer(const StreamArgs& s, hipStream_t st) {
+    return sq_ok(s) ? launch_sq<WKM, EPI, PRE>(s, st) : launch_stream<WKM, EPI, PRE>(s, st);
+}
+
+int launch_stream2(const Stream2Args& s, hipStream_t st) {
+    // exact block count: zero-padded blocks would cost real MFMAs
+    return with_blocks<1>(((s.pre.N0 > s.N1 ? s.pre.N0 : s.N1) + 15) >> 4, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        return cl_launch_lds<wide_stream2_kernel<NA>>(dim3((unsigned)row_grid(s.n)), dim3(512), stream_lds(NA, true), st, s);
+    });
 }
 
 template <bool AK, bool BK_, int EPI>
 int launch_gemm_tiles(const GemmArgs& g, int n_tiles, hipStream_t st) {
     if (n_tiles <= 0 || g.N <= 0 || g.K <= 0 || g.tiles == nullptr || g.seg == nullptr) return -1;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((wide_gemm_kernel<AK, BK_, EPI, 128>), dim3(n_tiles, (g.N + 127) / 128, 1), dim3(256), 0, st, g);
-    return (int)hipGetLastError();
+    return cl_launch_lds<wide_gemm_kernel<AK, BK_, EPI, 128>>(dim3(n_tiles, (g.N + 127) / 128, 1), dim3(256), 0, st, g);
 }
 
 template <bool AK, bool BK_, int EPI>
 int launch_gemm(const GemmArgs& g, int zsplit, hipStream_t st) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return -1;
-    (void)hipGetLastError();
-    if (g.N > 64) hipLaunchKernelGGL((wide_gemm_kernel<AK, BK_, EPI, 128>), dim3((g.M + BM - 1) / BM, (g.N + 127) / 128, zsplit), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((wide_gemm_kernel<AK, BK_, EPI, 64>), dim3((g.M + BM - 1) / BM, 1, zsplit), dim3(256), 0, st, g);
-    return (int)hipGetLastError();
+    if (g.N > 64) return cl_launch_lds<wide_gemm_kernel<AK, BK_, EPI, 128>>(dim3((g.M + BM - 1) / BM, (g.N + 127) / 128, zsplit), dim3(256), 0, st, g);
+    return cl_launch_lds<wide_gemm_kernel<AK, BK_, EPI, 64>>(dim3((g.M + BM - 1) / BM, 1, zsplit), dim3(256), 0, st, g);
+}
+
+// the weight gradient of a layer up to 128 x 128 with the head's backward pass (HEADW) or the recomputed first layer (PREM) in its loader:
+// one 128-column tile of a 128-row output per split
+template <bool HEADW, bool PREM>
+int launch_wgrad_fused(const GemmArgs& g, int nsplit, hipStream_t st) {
+    return cl_launch_lds<wide_gemm_kernel<true, true, EPI_WGRAD, 128, HEADW, PREM>>(dim3(1, 1, nsplit), dim3(256), 0, st, g);
+}
+
+// the check of the recomputed first layer's arguments (w = the width it feeds): 0, or the call's answer
+int pre_check(const float* X0, int ldx0, int n_in0, const float* Wt0, const float* b0, int w) {
+    if (any_null(X0, Wt0, b0)) return -1;
+    if (!cl_wide_pre_supported(n_in0, w)) return -2;
+    if (ldx0 < n_in0 || ldx0 % 4 != 0 || ldx0 > K0MAX || !aligned16(X0)) return -1;
+    return 0;
+}
+
+// the check and the argument fill cl_wide_dense_forward_head and _forward_head_lik share: 0 and `s` filled, or the call's answer
+int forward_head_args(StreamArgs& s, const float* X, int ldx, const float* Wt, const float* b, long long n, int n_in, int n_out, float leak, float* Y,
+                      int ldy, const float* head, int bij_kind, float eps, float* loc_out, float* sig_out, float* dsig_draw_out, const int* stop_flag) {
+    if (any_null(X, Wt, b, Y, head, loc_out, sig_out) || !rows_ok(n) || n_in < 1 || n_out < 1 || ldx < n_in || ldy < n_out) return -1;
+    if (n_in > SMAX || n_out > SMAX) return -2;
+    s = stream_args(X, ldx, Wt, n_in, Y, ldy, n, n_out, n_in, leak, stop_flag);
+    s.bias = b; s.act = 1;
+    s.head_W = head; s.bij_kind = bij_kind; s.eps = eps; s.loc_out = loc_out; s.sig_out = sig_out; s.dsd_out = dsig_draw_out;
+    return 0;
 }
 
 }  // namespace
@@ -1395,17 +1473,14 @@ int cl_wide_ld(int width) { return width < 1 ? 0 : ((width + 3) & ~3); }
 
 int cl_wide_dense_forward(const float* X, int ldx, const float* Wt, const float* b, long long n, int n_in, int n_out, float leak, int act,
                           float* Y, int ldy, const int* stop_flag, void* stream) {
-    if (X == nullptr || Wt == nullptr || b == nullptr || Y == nullptr || n < 1 || n > 0x7fffffffLL || n_in < 1 || n_out < 1 || ldx < n_in || ldy < n_out) return -1;
+    if (any_null(X, Wt, b, Y) || !rows_ok(n) || n_in < 1 || n_out < 1 || ldx < n_in || ldy < n_out) return -1;
     if (n_in <= SMAX && n_out <= SMAX) {
-        StreamArgs s = {};
-        s.X = X; s.ldx = ldx; s.W = Wt; s.ldw = n_in; s.Y = Y; s.ldy = ldy; s.n = n; s.N = n_out; s.K = n_in;
-        s.bias = b; s.leak = leak; s.act = act; s.stop_flag = stop_flag;
-        if (sq_ok(s)) return launch_sq<false, EPI_BIAS_LRELU, false>(s, (hipStream_t)stream);
-        return launch_stream<false, EPI_BIAS_LRELU>(s, (hipStream_t)stream);
+        StreamArgs s = stream_args(X, ldx, Wt, n_in, Y, ldy, n, n_out, n_in, leak, stop_flag);
+        s.bias = b; s.act = act;
+        return launch_layer<false, EPI_BIAS_LRELU>(s, (hipStream_t)stream);
     }
-    GemmArgs g = {};
-    g.A = X; g.lda = ldx; g.B = Wt; g.ldb = n_in; g.C = Y; g.ldc = ldy;
-    g.M = (int)n; g.N = n_out; g.K = n_in; g.bias = b; g.leak = leak; g.act = act; g.stop_flag = stop_flag;
+    GemmArgs g = gemm_args(X, ldx, Wt, n_in, Y, ldy, (int)n, n_out, n_in, leak, stop_flag);
+    g.bias = b; g.act = act;
     return launch_gemm<false, false, EPI_BIAS_LRELU>(g, 1, (hipStream_t)stream);
 }
 
@@ -1415,16 +1490,9 @@ int cl_wide_dense_forward(const float* X, int ldx, const float* Wt, const float*
 int cl_wide_dense_forward_head(const float* X, int ldx, const float* Wt, const float* b, long long n, int n_in, int n_out, float leak,
                                float* Y, int ldy, const float* head, int bij_kind, float eps, float* loc_out, float* sig_out, float* dsig_draw_out,
                                const int* stop_flag, void* stream) {
-    if (X == nullptr || Wt == nullptr || b == nullptr || Y == nullptr || head == nullptr || loc_out == nullptr || sig_out == nullptr || n < 1 ||
-        n > 0x7fffffffLL || n_in < 1 || n_out < 1 || ldx < n_in || ldy < n_out)
-        return -1;
-    if (n_in > SMAX || n_out > SMAX) return -2;
     StreamArgs s = {};
-    s.X = X; s.ldx = ldx; s.W = Wt; s.ldw = n_in; s.Y = Y; s.ldy = ldy; s.n = n; s.N = n_out; s.K = n_in;
-    s.bias = b; s.leak = leak; s.act = 1; s.stop_flag = stop_flag;
-    s.head_W = head; s.bij_kind = bij_kind; s.eps = eps; s.loc_out = loc_out; s.sig_out = sig_out; s.dsd_out = dsig_draw_out;
-    if (sq_ok(s)) return launch_sq<false, EPI_BIAS_LRELU, false>(s, (hipStream_t)stream);
-    return launch_stream<false, EPI_BIAS_LRELU>(s, (hipStream_t)stream);
+    if (int e = forward_head_args(s, X, ldx, Wt, b, n, n_in, n_out, leak, Y, ldy, head, bij_kind, eps, loc_out, sig_out, dsig_draw_out, stop_flag)) return e;
+    return launch_layer<false, EPI_BIAS_LRELU>(s, (hipStream_t)stream);
 }
 
 /* cl_wide_dense_forward_head with the slot likelihood of the call's rows in the same epilogue (round 4): what cl_slot_rows computes from
@@ -1435,19 +1503,14 @@ int cl_wide_dense_forward_head(const float* X, int ldx, const float* Wt, const f
 int cl_wide_dense_forward_head_lik(const float* X, int ldx, const float* Wt, const float* b, long long n, int n_in, int n_out, float leak,
                                    float* Y, int ldy, const float* head, int bij_kind, float eps, float* loc_out, float* sig_out, float* dsig_draw_out,
                                    const cl_laue_args* lik, const int* stop_flag, void* stream) {
-    if (X == nullptr || Wt == nullptr || b == nullptr || Y == nullptr || head == nullptr || loc_out == nullptr || sig_out == nullptr || lik == nullptr ||
-        n < 1 || n > 0x7fffffffLL || n_in < 1 || n_out < 1 || ldx < n_in || ldy < n_out)
-        return -1;
-    if (n_in > SMAX || n_out > SMAX) return -2;
+    if (lik == nullptr) return -1;
+    StreamArgs s = {};
+    if (int e = forward_head_args(s, X, ldx, Wt, b, n, n_in, n_out, leak, Y, ldy, head, bij_kind, eps, loc_out, sig_out, dsig_draw_out, stop_flag)) return e;
     const cl_laue_args& a = *lik;
     if (a.harmonic_id != nullptr || a.eta != nullptr || a.ipred_out != nullptr || a.ev11 != nullptr || a.dzf_obs != nullptr || a.nll_part != nullptr) return -2;
-    if (a.refl_id == nullptr || a.iobs == nullptr || a.sig == nullptr || a.z_f == nullptr || a.dz_f == nullptr || a.dO == nullptr || a.scalars == nullptr ||
-        a.S < 1 || a.n_obs != (int)n || (a.use_img && (a.image_id == nullptr || a.img == nullptr || a.d_img == nullptr)))
+    if (any_null(a.refl_id, a.iobs, a.sig, a.z_f, a.dz_f, a.dO, a.scalars) || a.S < 1 || a.n_obs != (int)n ||
+        (a.use_img && any_null(a.image_id, a.img, a.d_img)))
         return -1;
-    StreamArgs s = {};
-    s.X = X; s.ldx = ldx; s.W = Wt; s.ldw = n_in; s.Y = Y; s.ldy = ldy; s.n = n; s.N = n_out; s.K = n_in;
-    s.bias = b; s.leak = leak; s.act = 1; s.stop_flag = stop_flag;
-    s.head_W = head; s.bij_kind = bij_kind; s.eps = eps; s.loc_out = loc_out; s.sig_out = sig_out; s.dsd_out = dsig_draw_out;
     if (!sq_ok(s)) return -2;
     s.lik.refl_id = a.refl_id; s.lik.image_id = a.image_id; s.lik.iobs = a.iobs; s.lik.sig = a.sig;
     s.lik.row_index = a.row_index; s.lik.obs_offset = a.obs_offset;
@@ -1469,13 +1532,10 @@ int cl_wide_head_bwd_supported(int n_out, int n_in) {
 
 int cl_wide_dense_dgrad_head(const float* Htop, int ldt, const float* head, const float* dO, const float* dsig_draw, const float* Wt, long long n,
                              int n_out, int n_in, const float* Hprev, int ldh, float leak, float* dX, int ldo, const int* stop_flag, void* stream) {
-    if (Htop == nullptr || head == nullptr || dO == nullptr || dsig_draw == nullptr || Wt == nullptr || dX == nullptr || n < 1 || n > 0x7fffffffLL ||
-        n_in < 1 || n_out < 1 || ldt < n_out || ldo < n_in)
-        return -1;
+    if (any_null(Htop, head, dO, dsig_draw, Wt, dX) || !rows_ok(n) || n_in < 1 || n_out < 1 || ldt < n_out || ldo < n_in) return -1;
     if (!cl_wide_head_bwd_supported(n_out, n_in)) return -2;
-    StreamArgs s = {};
-    s.X = Htop; s.ldx = ldt; s.W = Wt; s.ldw = n_in; s.Y = dX; s.ldy = ldo; s.n = n; s.N = n_in; s.K = n_out;
-    s.H = Hprev; s.ldh = ldh; s.leak = leak; s.stop_flag = stop_flag;
+    StreamArgs s = stream_args(Htop, ldt, Wt, n_in, dX, ldo, n, n_in, n_out, leak, stop_flag);
+    s.H = Hprev; s.ldh = ldh;
     s.head_W = head; s.dO = dO; s.dsd = dsig_draw;
     if (!sq_ok(s)) return -2;
     return launch_sq<true, EPI_DLRELU, false, false, true>(s, (hipStream_t)stream);
@@ -1483,17 +1543,14 @@ int cl_wide_dense_dgrad_head(const float* Htop, int ldt, const float* head, cons
 
 int cl_wide_dense_dgrad(const float* dZ, int lddz, const float* Wt, long long n, int n_out, int n_in, const float* Hprev, int ldh, float leak,
                         float* dX, int ldo, const int* stop_flag, void* stream) {
-    if (dZ == nullptr || Wt == nullptr || dX == nullptr || n < 1 || n > 0x7fffffffLL || n_in < 1 || n_out < 1 || lddz < n_out || ldo < n_in) return -1;
+    if (any_null(dZ, Wt, dX) || !rows_ok(n) || n_in < 1 || n_out < 1 || lddz < n_out || ldo < n_in) return -1;
     if (n_in <= SMAX && n_out <= SMAX) {
-        StreamArgs s = {};
-        s.X = dZ; s.ldx = lddz; s.W = Wt; s.ldw = n_in; s.Y = dX; s.ldy = ldo; s.n = n; s.N = n_in; s.K = n_out;
-        s.H = Hprev; s.ldh = ldh; s.leak = leak; s.stop_flag = stop_flag;
-        if (sq_ok(s)) return launch_sq<true, EPI_DLRELU, false>(s, (hipStream_t)stream);
-        return launch_stream<true, EPI_DLRELU>(s, (hipStream_t)stream);
+        StreamArgs s = stream_args(dZ, lddz, Wt, n_in, dX, ldo, n, n_in, n_out, leak, stop_flag);
+        s.H = Hprev; s.ldh = ldh;
+        return launch_layer<true, EPI_DLRELU>(s, (hipStream_t)stream);
     }
-    GemmArgs g = {};
-    g.A = dZ; g.lda = lddz; g.B = Wt; g.ldb = n_in; g.C = dX; g.ldc = ldo;
-    g.M = (int)n; g.N = n_in; g.K = n_out; g.H = Hprev; g.ldh = ldh; g.leak = leak; g.stop_flag = stop_flag;
+    GemmArgs g = gemm_args(dZ, lddz, Wt, n_in, dX, ldo, (int)n, n_in, n_out, leak, stop_flag);
+    g.H = Hprev; g.ldh = ldh;
     return launch_gemm<false, true, EPI_DLRELU>(g, 1, (hipStream_t)stream);
 }
 
@@ -1501,48 +1558,28 @@ int cl_wide_dense_dgrad(const float* dZ, int lddz, const float* Wt, long long n,
  * cl_wide_dense_dgrad_pre, cl_wide_dense_wgrad_pre): metadata of at most 15 columns, hidden width at most 128 */
 int cl_wide_pre_supported(int n_in0, int w) { return n_in0 >= 1 && n_in0 <= K0WG && w >= 1 && w <= SMAX; }
 
-static int pre_check(const float* X0, int ldx0, int n_in0, const float* Wt0, const float* b0, int w) {
-    if (X0 == nullptr || Wt0 == nullptr || b0 == nullptr) return -1;
-    if (!cl_wide_pre_supported(n_in0, w)) return -2;
-    if (ldx0 < n_in0 || ldx0 % 4 != 0 || ldx0 > K0MAX || (reinterpret_cast<uintptr_t>(X0) & 15) != 0) return -1;
-    return 0;
-}
-
 int cl_wide_dense2_forward(const float* X0, int ldx0, int n_in0, const float* Wt0, const float* b0, const float* Wt1, const float* b1, long long n,
                            int w0, int w1, float leak, float* Y, int ldy, const float* head, int bij_kind, float eps, float* loc_out, float* sig_out,
                            const int* stop_flag, void* stream) {
     if (int e = pre_check(X0, ldx0, n_in0, Wt0, b0, w0)) return e;
-    if (Wt1 == nullptr || b1 == nullptr || Y == nullptr || n < 1 || n > 0x7fffffffLL || w1 < 1 || ldy < w1) return -1;
+    if (any_null(Wt1, b1, Y) || !rows_ok(n) || w1 < 1 || ldy < w1) return -1;
     if (w1 > SMAX) return -2;
-    if (head != nullptr && (loc_out == nullptr || sig_out == nullptr)) return -1;
+    if (head != nullptr && any_null(loc_out, sig_out)) return -1;
     Stream2Args s = {};
-    s.pre.X0 = X0; s.pre.ldx0 = ldx0; s.pre.K0 = n_in0; s.pre.W0 = Wt0; s.pre.b0 = b0; s.pre.N0 = w0;
+    s.pre = pre_args(X0, ldx0, n_in0, Wt0, b0, w0);
     s.W1 = Wt1; s.b1 = b1; s.N1 = w1; s.Y = Y; s.ldy = ldy; s.n = n; s.leak = leak;
     s.head_W = head; s.bij_kind = bij_kind; s.eps = eps; s.loc_out = loc_out; s.sig_out = sig_out; s.stop_flag = stop_flag;
-    hipStream_t st = (hipStream_t)stream;
-    switch (((w0 > w1 ? w0 : w1) + 15) >> 4) {         // exact block count: zero-padded blocks would cost real MFMAs
-        case 1: return launch_stream2<1>(s, st);
-        case 2: return launch_stream2<2>(s, st);
-        case 3: return launch_stream2<3>(s, st);
-        case 4: return launch_stream2<4>(s, st);
-        case 5: return launch_stream2<5>(s, st);
-        case 6: return launch_stream2<6>(s, st);
-        case 7: return launch_stream2<7>(s, st);
-        default: return launch_stream2<8>(s, st);
-    }
+    return launch_stream2(s, (hipStream_t)stream);
 }
 
 int cl_wide_dense_dgrad_pre(const float* dZ, int lddz, const float* Wt, long long n, int n_out, int n_in, const float* X0, int ldx0, int n_in0,
                             const float* Wt0, const float* b0, float leak, float* dX, int ldo, const int* stop_flag, void* stream) {
     if (int e = pre_check(X0, ldx0, n_in0, Wt0, b0, n_in)) return e;
-    if (dZ == nullptr || Wt == nullptr || dX == nullptr || n < 1 || n > 0x7fffffffLL || n_out < 1 || lddz < n_out || ldo < n_in) return -1;
+    if (any_null(dZ, Wt, dX) || !rows_ok(n) || n_out < 1 || lddz < n_out || ldo < n_in) return -1;
     if (n_out > SMAX) return -2;
-    StreamArgs s = {};
-    s.X = dZ; s.ldx = lddz; s.W = Wt; s.ldw = n_in; s.Y = dX; s.ldy = ldo; s.n = n; s.N = n_in; s.K = n_out;
-    s.leak = leak; s.stop_flag = stop_flag;
-    s.pre.X0 = X0; s.pre.ldx0 = ldx0; s.pre.K0 = n_in0; s.pre.W0 = Wt0; s.pre.b0 = b0; s.pre.N0 = n_in;
-    if (sq_ok(s)) return launch_sq<true, EPI_DLRELU, true>(s, (hipStream_t)stream);
-    return s.N <= 64 ? launch_stream_n<true, EPI_DLRELU, 4, false, true>(s, (hipStream_t)stream) : launch_stream_n<true, EPI_DLRELU, 8, false, true>(s, (hipStream_t)stream);
+    StreamArgs s = stream_args(dZ, lddz, Wt, n_in, dX, ldo, n, n_in, n_out, leak, stop_flag);
+    s.pre = pre_args(X0, ldx0, n_in0, Wt0, b0, n_in);
+    return launch_layer<true, EPI_DLRELU, true>(s, (hipStream_t)stream);
 }
 
 /* The second layer's dgrad and the FIRST layer's weight gradient in one launch (round 4): dZ_0 = (dZ Wt) * LeakyReLU'(h_0) with h_0 recomputed
@@ -1550,40 +1587,32 @@ int cl_wide_dense_dgrad_pre(const float* dZ, int lddz, const float* Wt, long lon
  * cl_wide_dgrad_wgrad0_parts(n) partial sums of [dWt_0 (n_in x n_in0) | db_0 (n_in)] into `partials` (add them with cl_reduce_partials).
  * -2: shape not taken (the square-layer kernel's envelope: 65 .. 128 on both sides, same number of 16-column blocks): the caller then
  * runs cl_wide_dense_dgrad_pre + cl_wide_dense_wgrad.                                                                               */
-int cl_wide_dgrad_wgrad0_parts(long long n) { return n < 1 ? 0 : (int)sq_grid(n); }
+int cl_wide_dgrad_wgrad0_parts(long long n) { return n < 1 ? 0 : (int)row_grid(n); }
 
 int cl_wide_dense_dgrad_pre_wgrad0(const float* dZ, int lddz, const float* Wt, long long n, int n_out, int n_in, const float* X0, int ldx0, int n_in0,
                                    const float* Wt0, const float* b0, float leak, float* partials, const int* stop_flag, void* stream) {
     if (int e = pre_check(X0, ldx0, n_in0, Wt0, b0, n_in)) return e;
-    if (dZ == nullptr || Wt == nullptr || partials == nullptr || n < 1 || n > 0x7fffffffLL || n_out < 1 || lddz < n_out) return -1;
+    if (any_null(dZ, Wt, partials) || !rows_ok(n) || n_out < 1 || lddz < n_out) return -1;
     if (n_out > SMAX) return -2;
-    StreamArgs s = {};
-    s.X = dZ; s.ldx = lddz; s.W = Wt; s.ldw = n_in; s.Y = const_cast<float*>(dZ); s.ldy = lddz; s.n = n; s.N = n_in; s.K = n_out;   /* (Y: never written; set for sq_ok's layout tests) */
-    s.leak = leak; s.stop_flag = stop_flag;
-    s.pre.X0 = X0; s.pre.ldx0 = ldx0; s.pre.K0 = n_in0; s.pre.W0 = Wt0; s.pre.b0 = b0; s.pre.N0 = n_in;
+    StreamArgs s = stream_args(dZ, lddz, Wt, n_in, nullptr, 0, n, n_in, n_out, leak, stop_flag);      // (no row output: dZ_0 is not stored)
+    s.pre = pre_args(X0, ldx0, n_in0, Wt0, b0, n_in);
     s.wg0_part = partials;
-    if (!sq_ok(s)) return -2;
+    // The square-layer kernel or nothing.  The path's row buffers share one pitch, which covers both sides of a layer (cl_wide_ld of the
+    // hidden width): a dZ whose pitch is below n_in is not that layout, although this kernel reads only n_out columns of it
+    if (lddz < n_in || !sq_ok(s, false)) return -2;
     return launch_sq<true, EPI_DLRELU, true, true>(s, (hipStream_t)stream);
 }
 
 int cl_wide_dense_wgrad_pre(const float* dZ, int lddz, const float* X0, int ldx0, int n_in0, const float* Wt0, const float* b0, float leak, long long n,
                             int n_out, int n_in, float* partials, int nsplit, const int* stop_flag, void* stream) {
     if (int e = pre_check(X0, ldx0, n_in0, Wt0, b0, n_in)) return e;
-    if (dZ == nullptr || partials == nullptr || n < 1 || n > 0x7fffffffLL || n_out < 1 || nsplit < 1 || lddz < n_out) return -1;
-    GemmArgs g = {};
-    g.A = dZ; g.lda = lddz; g.B = X0; g.ldb = ldx0; g.C = partials;
-    g.M = n_out; g.N = n_in; g.K = (int)n; g.n_in = n_in;
-    g.ksplit = (int)((n + nsplit - 1) / nsplit);
-    g.ksplit = (g.ksplit + BK - 1) / BK * BK;
-    g.pstride = (long long)n_out * n_in + n_out;
-    g.leak = leak; g.stop_flag = stop_flag;
-    g.pre.X0 = X0; g.pre.ldx0 = ldx0; g.pre.K0 = n_in0; g.pre.W0 = Wt0; g.pre.b0 = b0; g.pre.N0 = n_in;
+    if (any_null(dZ, partials) || !rows_ok(n) || n_out < 1 || nsplit < 1 || lddz < n_out) return -1;
     // the layer's input tile is made by MFMAs where the kernel stages it: one 128-column tile of a 128-row output (cl_wide_pre_supported
     // bounds both widths by 128; a width <= 64 never comes here -- the fused kernels take it)
     if (n_in > 128 || n_out > 128) return -2;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((wide_gemm_kernel<true, true, EPI_WGRAD, 128, false, true>), dim3(1, 1, nsplit), dim3(256), 0, (hipStream_t)stream, g);
-    return (int)hipGetLastError();
+    GemmArgs g = wgrad_args(dZ, lddz, X0, ldx0, partials, n, n_out, n_in, nsplit, leak, stop_flag);
+    g.pre = pre_args(X0, ldx0, n_in0, Wt0, b0, n_in);
+    return launch_wgrad_fused<false, true>(g, nsplit, (hipStream_t)stream);
 }
 
 int cl_wide_wgrad_splits(long long n) {
@@ -1593,59 +1622,39 @@ int cl_wide_wgrad_splits(long long n) {
 
 int cl_wide_dense_wgrad(const float* dZ, int lddz, const float* H, int ldh, long long n, int n_out, int n_in, float* partials, int nsplit,
                         const int* stop_flag, void* stream) {
-    if (dZ == nullptr || H == nullptr || partials == nullptr || n < 1 || n > 0x7fffffffLL || n_in < 1 || n_out < 1 || nsplit < 1 || lddz < n_out ||
-        ldh < n_in)
-        return -1;
-    GemmArgs g = {};
-    g.A = dZ; g.lda = lddz; g.B = H; g.ldb = ldh; g.C = partials;
-    g.M = n_out; g.N = n_in; g.K = (int)n; g.n_in = n_in;
-    g.ksplit = (int)((n + nsplit - 1) / nsplit);
-    g.ksplit = (g.ksplit + BK - 1) / BK * BK;
-    g.pstride = (long long)n_out * n_in + n_out;
-    g.stop_flag = stop_flag;
+    if (any_null(dZ, H, partials) || !rows_ok(n) || n_in < 1 || n_out < 1 || nsplit < 1 || lddz < n_out || ldh < n_in) return -1;
+    const GemmArgs g = wgrad_args(dZ, lddz, H, ldh, partials, n, n_out, n_in, nsplit, 0.0f, stop_flag);
     return launch_gemm<true, true, EPI_WGRAD>(g, nsplit, (hipStream_t)stream);
 }
 
 /* head_partials[s][2 n_out + 2] = (dWo | dbo) over the s-th row range, next to the layer's own partials as cl_wide_dense_wgrad writes them */
 int cl_wide_dense_wgrad_head(const float* Htop, int ldt, const float* head, const float* dO, const float* dsig_draw, float leak, const float* H, int ldh,
                              long long n, int n_out, int n_in, float* partials, float* head_partials, int nsplit, const int* stop_flag, void* stream) {
-    if (Htop == nullptr || head == nullptr || dO == nullptr || dsig_draw == nullptr || H == nullptr || partials == nullptr || head_partials == nullptr ||
-        n < 1 || n > 0x7fffffffLL || n_in < 1 || n_out < 1 || nsplit < 1 || ldt < n_out || ldh < n_in)
+    if (any_null(Htop, head, dO, dsig_draw, H, partials, head_partials) || !rows_ok(n) || n_in < 1 || n_out < 1 || nsplit < 1 || ldt < n_out || ldh < n_in)
         return -1;
     if (!cl_wide_head_bwd_supported(n_out, n_in)) return -2;
-    // (the loader reads dO and dsig_draw as aligned quads of four consecutive rows)
-    if ((reinterpret_cast<uintptr_t>(dO) & 15) != 0 || (reinterpret_cast<uintptr_t>(dsig_draw) & 15) != 0) return -1;
-    GemmArgs g = {};
-    g.A = Htop; g.lda = ldt; g.B = H; g.ldb = ldh; g.C = partials;
-    g.M = n_out; g.N = n_in; g.K = (int)n; g.n_in = n_in;
-    g.ksplit = (int)((n + nsplit - 1) / nsplit);
-    g.ksplit = (g.ksplit + BK - 1) / BK * BK;
-    g.pstride = (long long)n_out * n_in + n_out;
-    g.leak = leak; g.stop_flag = stop_flag;
+    if (!aligned16(dO) || !aligned16(dsig_draw)) return -1;      // (the loader reads dO and dsig_draw as aligned quads of four consecutive rows)
+    GemmArgs g = wgrad_args(Htop, ldt, H, ldh, partials, n, n_out, n_in, nsplit, leak, stop_flag);
     g.hd_dO = dO; g.hd_dsd = dsig_draw; g.hd_W = head; g.hd_part = head_partials;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((wide_gemm_kernel<true, true, EPI_WGRAD, 128, true>), dim3(1, 1, nsplit), dim3(256), 0, (hipStream_t)stream, g);
-    return (int)hipGetLastError();
+    return launch_wgrad_fused<true, false>(g, nsplit, (hipStream_t)stream);
 }
 
 /* per-image layers (grouped): rows sorted by image, seg[g] .. seg[g+1] = rows of image g of this call (n_groups images);
  * W = the layer's kernels [image][out][in] (w x w each), b = its biases [image][w]; both pointers at the call's first image */
 int cl_wide_image_forward(const float* X, int ldx, const float* W, const float* b, const int* seg, int n_groups, long long n, int w, float leak,
                           float* Y, int ldy, const int* stop_flag, void* stream) {
-    if (X == nullptr || W == nullptr || b == nullptr || seg == nullptr || Y == nullptr || n_groups < 1 || n < 1 || w < 1 || w > SMAX || ldx < w || ldy < w) return w > SMAX ? -2 : -1;
-    StreamArgs s = {};
-    s.X = X; s.ldx = ldx; s.W = W; s.ldw = w; s.Y = Y; s.ldy = ldy; s.n = n; s.N = w; s.K = w;
-    s.bias = b; s.leak = leak; s.act = 1; s.stop_flag = stop_flag;
+    if (any_null(X, W, b, seg, Y) || n_groups < 1 || n < 1 || w < 1 || w > SMAX || ldx < w || ldy < w) return w > SMAX ? -2 : -1;
+    StreamArgs s = stream_args(X, ldx, W, w, Y, ldy, n, w, w, leak, stop_flag);
+    s.bias = b; s.act = 1;
     s.seg = seg; s.n_groups = n_groups; s.wstride = (long long)w * w; s.bstride = w;
     return launch_stream<false, EPI_BIAS_LRELU>(s, (hipStream_t)stream);
 }
 
 int cl_wide_image_dgrad(const float* dZ, int lddz, const float* W, const int* seg, int n_groups, long long n, int w, const float* Hprev, int ldh, float leak,
                         float* dX, int ldo, const int* stop_flag, void* stream) {
-    if (dZ == nullptr || W == nullptr || seg == nullptr || dX == nullptr || n_groups < 1 || n < 1 || w < 1 || w > SMAX || lddz < w || ldo < w) return w > SMAX ? -2 : -1;
-    StreamArgs s = {};
-    s.X = dZ; s.ldx = lddz; s.W = W; s.ldw = w; s.Y = dX; s.ldy = ldo; s.n = n; s.N = w; s.K = w;
-    s.H = Hprev; s.ldh = ldh; s.leak = leak; s.stop_flag = stop_flag;
+    if (any_null(dZ, W, seg, dX) || n_groups < 1 || n < 1 || w < 1 || w > SMAX || lddz < w || ldo < w) return w > SMAX ? -2 : -1;
+    StreamArgs s = stream_args(dZ, lddz, W, w, dX, ldo, n, w, w, leak, stop_flag);
+    s.H = Hprev; s.ldh = ldh;
     s.seg = seg; s.n_groups = n_groups; s.wstride = (long long)w * w;
     return launch_stream<true, EPI_DLRELU>(s, (hipStream_t)stream);
 }
@@ -1654,44 +1663,35 @@ int cl_wide_image_dgrad(const float* dZ, int lddz, const float* W, const int* se
  * `tiles` = (group, first row) pairs covering every group's rows in 128-row pieces (the caller builds the list from its row counts) */
 int cl_wide_image_forward_tiles(const float* X, int ldx, const float* W, const float* b, const int* seg, const int* tiles, int n_tiles, int w, float leak,
                                 float* Y, int ldy, const int* stop_flag, void* stream) {
-    if (X == nullptr || W == nullptr || b == nullptr || seg == nullptr || tiles == nullptr || Y == nullptr || n_tiles < 1 || w < 1 || ldx < w || ldy < w) return -1;
-    GemmArgs g = {};
-    g.A = X; g.lda = ldx; g.B = W; g.ldb = w; g.C = Y; g.ldc = ldy;
-    g.M = 0; g.N = w; g.K = w; g.bias = b; g.leak = leak; g.act = 1; g.stop_flag = stop_flag;
-    g.seg = seg; g.tiles = tiles; g.bgs = (long long)w * w; g.biasgs = w;
+    if (any_null(X, W, b, seg, tiles, Y) || n_tiles < 1 || w < 1 || ldx < w || ldy < w) return -1;
+    GemmArgs g = tile_args(X, ldx, W, w, Y, ldy, seg, tiles, leak, stop_flag);
+    g.bias = b; g.act = 1; g.biasgs = w;
     return launch_gemm_tiles<false, false, EPI_BIAS_LRELU>(g, n_tiles, (hipStream_t)stream);
 }
 
 int cl_wide_image_dgrad_tiles(const float* dZ, int lddz, const float* W, const int* seg, const int* tiles, int n_tiles, int w, const float* Hprev, int ldh,
                               float leak, float* dX, int ldo, const int* stop_flag, void* stream) {
-    if (dZ == nullptr || W == nullptr || seg == nullptr || tiles == nullptr || dX == nullptr || n_tiles < 1 || w < 1 || lddz < w || ldo < w) return -1;
-    GemmArgs g = {};
-    g.A = dZ; g.lda = lddz; g.B = W; g.ldb = w; g.C = dX; g.ldc = ldo;
-    g.M = 0; g.N = w; g.K = w; g.H = Hprev; g.ldh = ldh; g.leak = leak; g.stop_flag = stop_flag;
-    g.seg = seg; g.tiles = tiles; g.bgs = (long long)w * w;
+    if (any_null(dZ, W, seg, tiles, dX) || n_tiles < 1 || w < 1 || lddz < w || ldo < w) return -1;
+    GemmArgs g = tile_args(dZ, lddz, W, w, dX, ldo, seg, tiles, leak, stop_flag);
+    g.H = Hprev; g.ldh = ldh;
     return launch_gemm_tiles<false, true, EPI_DLRELU>(g, n_tiles, (hipStream_t)stream);
 }
 
 /* dW[image][out][in] = dZ_rows^T H_rows, db[image][out] = column sums of dZ_rows, written (not added) for the n_groups images of the call */
 int cl_wide_image_wgrad(const float* dZ, int lddz, const float* H, int ldh, const int* seg, int n_groups, long long n, int w, float* dW, float* db,
                         const int* stop_flag, void* stream) {
-    if (dZ == nullptr || H == nullptr || seg == nullptr || dW == nullptr || db == nullptr || n_groups < 1 || n < 1 || n > 0x7fffffffLL || w < 1 || lddz < w || ldh < w)
-        return -1;
-    GemmArgs g = {};
-    g.A = dZ; g.lda = lddz; g.B = H; g.ldb = ldh; g.C = dW;
-    g.M = w; g.N = w; g.K = (int)n; g.n_in = w;
-    g.pstride = (long long)w * w; g.seg = seg; g.Cb = db; g.bstride = w;
-    g.stop_flag = stop_flag;
+    if (any_null(dZ, H, seg, dW, db) || n_groups < 1 || !rows_ok(n) || w < 1 || lddz < w || ldh < w) return -1;
+    // one z-block per image in place of the row splits: the image's rows are its contraction, its kernel and bias its own output
+    GemmArgs g = gemm_args(dZ, lddz, H, ldh, dW, 0, w, w, (int)n, 0.0f, stop_flag);
+    g.n_in = w; g.pstride = (long long)w * w; g.seg = seg; g.Cb = db; g.bstride = w;
     return launch_gemm<true, true, EPI_WGRAD>(g, n_groups, (hipStream_t)stream);
 }
 
 int cl_wide_head_forward(const float* H, int ldh, const float* Wo, long long n, int w, int bij_kind, float eps, float* loc_out, float* sig_out,
                          const int* stop_flag, void* stream) {
-    if (H == nullptr || Wo == nullptr || loc_out == nullptr || sig_out == nullptr || n < 1 || w < 1 || ldh < w) return -1;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(wide_head_forward_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, (hipStream_t)stream, H, ldh, Wo, (int)n, w, bij_kind, eps,
-                       loc_out, sig_out, stop_flag);
-    return (int)hipGetLastError();
+    if (any_null(H, Wo, loc_out, sig_out) || n < 1 || w < 1 || ldh < w) return -1;
+    return cl_launch_lds<wide_head_forward_kernel>(dim3((unsigned)((n + 15) / 16)), dim3(256), 0, (hipStream_t)stream, H, ldh, Wo, (int)n, w, bij_kind, eps,
+                                                   loc_out, sig_out, stop_flag);
 }
 
 int cl_wide_head_blocks(long long n) {
@@ -1701,27 +1701,21 @@ int cl_wide_head_blocks(long long n) {
 
 int cl_wide_head_backward(const float* H, int ldh, const float* Wo, const float* dO, long long n, int w, int bij_kind, float eps, float leak,
                           float* dZ, int lddz, float* partials, int nblocks, const int* stop_flag, void* stream) {
-    if (H == nullptr || Wo == nullptr || dO == nullptr || dZ == nullptr || partials == nullptr || n < 1 || n > 0x7fffffffLL || w < 1 || nblocks < 1 ||
-        ldh < w || lddz < w || ldh % 4 != 0 || lddz % 4 != 0 || (reinterpret_cast<uintptr_t>(H) & 15) != 0 || (reinterpret_cast<uintptr_t>(dZ) & 15) != 0)
+    if (any_null(H, Wo, dO, dZ, partials) || !rows_ok(n) || w < 1 || nblocks < 1 || ldh < w || lddz < w || ldh % 4 != 0 || lddz % 4 != 0 ||
+        !aligned16(H) || !aligned16(dZ))
         return -1;
     if (w > 1024) return -2;
     const size_t sm = (size_t)8 * (2 * w + 2) * sizeof(float);
     const int rpb = (int)((n + nblocks - 1) / nblocks);
     const int rows = (rpb + 7) / 8 * 8;
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipGetLastError();
-#define CL_HEAD_BWD(NP) \
-    hipLaunchKernelGGL(wide_head_backward_kernel<NP>, dim3(nblocks), dim3(256), sm, st, H, ldh, Wo, dO, (int)n, w, bij_kind, eps, leak, rows, dZ, lddz, partials, stop_flag)
-    if (w <= 128) CL_HEAD_BWD(1);
-    else if (w <= 256) CL_HEAD_BWD(2);
-    else if (w <= 512) CL_HEAD_BWD(4);
-    else {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wide_head_backward_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        if (e != hipSuccess) return (int)e;
-        CL_HEAD_BWD(8);
-    }
-#undef CL_HEAD_BWD
-    return (int)hipGetLastError();
+    const auto launch = [&](auto np) {            // np = the instance's 128-column pieces of a row
+        return cl_launch_lds<wide_head_backward_kernel<decltype(np)::value>>(dim3(nblocks), dim3(256), sm, (hipStream_t)stream, H, ldh, Wo, dO, (int)n, w,
+                                                                             bij_kind, eps, leak, rows, dZ, lddz, partials, stop_flag);
+    };
+    if (w <= 128) return launch(std::integral_constant<int, 1>{});
+    if (w <= 256) return launch(std::integral_constant<int, 2>{});
+    if (w <= 512) return launch(std::integral_constant<int, 4>{});
+    return launch(std::integral_constant<int, 8>{});
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ fused launch takes): the layer-by-layer path of the engine on the GEMM kernels o
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -23,6 +24,11 @@ def image_tiles(rel_seg: np.ndarray, device) -> torch.Tensor:
     first = np.repeat(np.concatenate([[0], np.cumsum(n)[:-1]]), n)
     row = rel[:-1][g] + 128 * (np.arange(int(n.sum())) - first)
     return torch.as_tensor(np.stack([g, row], axis=1).astype(np.int32).reshape(-1), device=device)
+
+
+# The Dense(2) head of one row chunk, for the top layer's epilogue: the head's offset in the scaler's flat layout, the device pointers of the
+# chunk's loc / sigma rows and of its d sigma / d raw rows (None unless the head's backward pass is fused into the top layer's backward)
+WideHead = namedtuple("WideHead", "off loc sig dsd")
 
 
 class WidePath:
@@ -145,7 +151,8 @@ class WidePath:
 
     def _wide_forward(self, obs: ObsData, chunk, keep: bool, st, full=None, head=None, lik=None):
         """Hidden layers on one row chunk of `obs`: layer l's output lands in acts[l] when `keep` (else two buffers alternate), or
-        in the chunk's rows of the whole-set buffers `full`; returns the (buffer, ld) pairs of h_0 .. h_(L + K)."""
+        in the chunk's rows of the whole-set buffers `full`.  Returns the (buffer, ld) pairs of h_0 .. h_(L + K), whether `head` (a WideHead)
+        rode in the top layer's epilogue and whether the slot likelihood `lik` did too."""
         a, b, m0, seg = chunk
         lib, W = self.lib, self._wide_setup()
         n, ldw, base = b - a, W["ldw"], self.params.data_ptr() + 4 * self.layout.off_mlp
@@ -153,7 +160,7 @@ class WidePath:
         sf, leak = ptr(self.stop_flag), self.mlp.leakiness
         dst_of = (lambda l: full[l].data_ptr() + 4 * a * ldw) if full is not None else (lambda l: W["acts"][l if keep else l & 1].data_ptr())
         hs = [(obs.meta_rm.data_ptr() + 4 * a * obs.meta_ld, obs.meta_ld)]
-        self._head_fused = self._lik_fused = False
+        head_fused = lik_fused = False
         pre = self._wide_pre()
         for l, (ow, ob, fan_in) in enumerate(layers):
             if pre and l == 0:
@@ -162,33 +169,27 @@ class WidePath:
             dst = dst_of(l)
             if pre and l == 1:
                 (ow0, ob0, d0) = layers[0]
-                with_head = head is not None and self.L == 2 and self.imgl is None
-                off_head, loc_ptr, sig_ptr = head[:3] if with_head else (0, None, None)
-                check(lib.cl_wide_dense2_forward(hs[0][0], hs[0][1], d0, base + 4 * ow0, base + 4 * ob0, base + 4 * ow, base + 4 * ob, n, self.w, self.w,
-                                                 leak, dst, ldw, (base + 4 * off_head) if with_head else None, self.bij_kind, self.mlp.epsilon,
-                                                 loc_ptr, sig_ptr, sf, st), "cl_wide_dense2_forward")
-                self._head_fused = with_head
+                head_fused = head is not None and self.L == 2 and self.imgl is None
+                hd = head if head_fused else WideHead(0, None, None, None)
+                check(lib.cl_wide_dense2_forward(*hs[0], d0, base + 4 * ow0, base + 4 * ob0, base + 4 * ow, base + 4 * ob, n, self.w, self.w,
+                                                 leak, dst, ldw, (base + 4 * hd.off) if head_fused else None, self.bij_kind, self.mlp.epsilon,
+                                                 hd.loc, hd.sig, sf, st), "cl_wide_dense2_forward")
             elif head is not None and l == self.L - 1 and self.imgl is None and fan_in <= 128 and self.w <= 128:
                 # the top layer carries the Dense(2) head in its epilogue: (loc, sigma) come out of the same pass
-                off_head, loc_ptr, sig_ptr = head[:3]
-                dsd_ptr = head[3] if len(head) > 3 else None       # d sigma / d raw per row, for the head backward fused into this layer's backward
+                top = (*hs[-1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, dst, ldw,
+                       base + 4 * head.off, self.bij_kind, self.mlp.epsilon, head.loc, head.sig, head.dsd)
                 rc = -2
                 if lik is not None:
                     # ... and the slot likelihood of the chunk's rows too: (loc, sigma) never wait in memory for a launch of their own
-                    rc = lib.cl_wide_dense_forward_head_lik(hs[-1][0], hs[-1][1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, dst, ldw,
-                                                            base + 4 * off_head, self.bij_kind, self.mlp.epsilon, loc_ptr, sig_ptr, dsd_ptr,
-                                                            C.byref(lik), sf, st)
+                    rc = lib.cl_wide_dense_forward_head_lik(*top, C.byref(lik), sf, st)
                     if rc != -2:
                         check(rc, "cl_wide_dense_forward_head_lik")
-                        self._lik_fused = True
+                        lik_fused = True
                 if rc == -2:
-                    check(lib.cl_wide_dense_forward_head(hs[-1][0], hs[-1][1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, dst, ldw,
-                                                         base + 4 * off_head, self.bij_kind, self.mlp.epsilon, loc_ptr, sig_ptr, dsd_ptr, sf, st),
-                          "cl_wide_dense_forward_head")
-                self._head_fused = True
+                    check(lib.cl_wide_dense_forward_head(*top, sf, st), "cl_wide_dense_forward_head")
+                head_fused = True
             else:
-                check(lib.cl_wide_dense_forward(hs[-1][0], hs[-1][1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, 1,
-                                                dst, ldw, sf, st), "cl_wide_dense_forward")
+                check(lib.cl_wide_dense_forward(*hs[-1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, 1, dst, ldw, sf, st), "cl_wide_dense_forward")
             hs.append((dst, ldw))
         for k in range(self.imgl.n_image_layers if self.imgl is not None else 0):       # image.py:116-125
             l = self.L + k
@@ -196,36 +197,30 @@ class WidePath:
             wk, bk = self._imgl_ptrs(self.params, k, m0)
             if self.w > 128:
                 tl = obs.wide_tiles[a]
-                check(lib.cl_wide_image_forward_tiles(hs[-1][0], hs[-1][1], wk, bk, ptr(seg), ptr(tl), tl.numel() // 2, self.w, leak, dst, ldw, sf, st),
+                check(lib.cl_wide_image_forward_tiles(*hs[-1], wk, bk, ptr(seg), ptr(tl), tl.numel() // 2, self.w, leak, dst, ldw, sf, st),
                       "cl_wide_image_forward_tiles")
             else:
-                check(lib.cl_wide_image_forward(hs[-1][0], hs[-1][1], wk, bk, ptr(seg), seg.numel() - 1, n, self.w, leak, dst, ldw, sf, st),
-                      "cl_wide_image_forward")
+                check(lib.cl_wide_image_forward(*hs[-1], wk, bk, ptr(seg), seg.numel() - 1, n, self.w, leak, dst, ldw, sf, st), "cl_wide_image_forward")
             hs.append((dst, ldw))
-        return hs
+        return hs, head_fused, lik_fused
 
     def _data_term_wide(self, obs: ObsData, step: int, eta, ipred_out, st):
         """Hidden / metadata width > 64 (or more hidden layers with per-image layers than one fused launch holds): unfused scaler on
         the GEMM kernels of csrc/wide_gemm.hip.  Forward (row chunks; the top layer carries the Dense(2) head) -> (loc, sigma) per row ->
         the slot likelihood (one launch when every row is its own slot, the three Laue launches otherwise) -> dL/d(loc, sigma) -> per
-        chunk: forward again unless the activations were kept; the head's backward pass inside the top layer's weight gradient and
-        dgrad (or its own launch outside their envelope), then weight gradient and dgrad layer by layer, top down, the first layer's
-        weight gradient inside the second layer's dgrad when the first layer is recomputed.  6 (activations kept) or 8 P_mm flops per
+        chunk: forward again unless the activations were kept, then _wide_backward_chunk.  6 (activations kept) or 8 P_mm flops per
         observation; every product in exact fp32."""
-        lib, lay, W = self.lib, self.layout, self._wide_setup()
+        lib = self.lib
         chunks = self._wide_chunks(obs)
         ma = self._mlp_args(step, eta, ipred_out, obs)
-        layers, off_head = self._wide_layers()
-        pbase = self.params.data_ptr() + 4 * lay.off_mlp
-        gbase = self.grads.data_ptr() + 4 * lay.off_mlp
-        sf, leak, w, ldw = ptr(self.stop_flag), self.mlp.leakiness, self.w, W["ldw"]
-        K = self.imgl.n_image_layers if self.imgl is not None else 0
+        _, off_head = self._wide_layers()
+        pbase = self.params.data_ptr() + 4 * self.layout.off_mlp
         # The activations of ALL rows are kept by the forward pass when they fit (WIDE_KEEP_BUDGET, a quarter of the free memory at
         # most: 15 GB for 10 M rows of a 3 x 128 scaler on a 288-GB device) and the backward pass starts from them -- 6 P_mm flops per
         # observation.  Otherwise the buffers hold one chunk at a time and each chunk's forward is recomputed when its turn in the
         # backward pass comes (8 P_mm).
         full = self._wide_keep_all(obs)
-        kept = []
+        kept, lik_fused = [], []
         headb = self._wide_head_bwd()
         if headb and obs.wide_dsd is None:
             obs.wide_dsd = torch.empty(obs.N, dtype=torch.float32, device=self.device)
@@ -233,86 +228,90 @@ class WidePath:
         # their own slot, in-kernel noise, no predictions out, no Evans-2011 terms, not the deterministic mode); the library decides by
         # shape (-2), the same for every chunk
         want_lik = (self.FUSE_LIK and obs.harmonic_id is None and eta is None and ipred_out is None and not self.ev11 and not self.deterministic)
-        lik_fused = []
         for ch in chunks:
             a, b = ch[0], ch[1]
-            head = (off_head, obs.laue_loc.data_ptr() + 4 * a, obs.laue_sig.data_ptr() + 4 * a)
-            if headb:
-                head = head + (obs.wide_dsd.data_ptr() + 4 * a,)
+            loc, sig = obs.laue_loc.data_ptr() + 4 * a, obs.laue_sig.data_ptr() + 4 * a
+            head = WideHead(off_head, loc, sig, obs.wide_dsd.data_ptr() + 4 * a if headb else None)
             lik = self._slot_args(ma, obs, step, None, None, a, b - a) if want_lik else None
-            hs = (self._wide_forward(obs, ch, True, st, full=full, head=head, lik=lik) if full is not None
-                  else self._wide_forward(obs, ch, False, st, head=head, lik=lik))
+            hs, head_fused, lf = self._wide_forward(obs, ch, full is not None, st, full=full, head=head, lik=lik)
             kept.append(hs)
-            lik_fused.append(self._lik_fused)
-            if not self._head_fused:
-                check(lib.cl_wide_head_forward(hs[-1][0], hs[-1][1], pbase + 4 * off_head, b - a, w, self.bij_kind, self.mlp.epsilon,
-                                               obs.laue_loc.data_ptr() + 4 * a, obs.laue_sig.data_ptr() + 4 * a, sf, st), "cl_wide_head_forward")
+            lik_fused.append(lf)
+            if not head_fused:
+                check(lib.cl_wide_head_forward(*hs[-1], pbase + 4 * off_head, b - a, self.w, self.bij_kind, self.mlp.epsilon, loc, sig,
+                                               ptr(self.stop_flag), st), "cl_wide_head_forward")
         if not all(lik_fused):
             assert not any(lik_fused)
             self._slot_likelihood(ma, obs, step, eta, ipred_out, st)
         for ic, ch in enumerate(chunks):
-            a, b, m0, seg = ch
-            n = b - a
-            hs = kept[ic] if full is not None else self._wide_forward(obs, ch, True, st)
-            dz, dzn = W["dz"]
-            nsplit = min(W["nsplit"], int(lib.cl_wide_wgrad_splits(n)))
-            if headb:
-                # the head's backward pass rides on the top layer's two backward kernels: dZ_L is made from h_L where they read it
-                l = self.L - 1
-                ow, ob, fan_in = layers[l]
-                hd = (hs[-1][0], hs[-1][1], pbase + 4 * off_head, obs.laue_dO.data_ptr() + 8 * a, obs.wide_dsd.data_ptr() + 4 * a)
-                check(lib.cl_wide_dense_wgrad_head(*hd, leak, hs[l][0], hs[l][1], n, w, fan_in, ptr(W["wpart"]), ptr(W["hpart"]), nsplit, sf, st),
-                      "cl_wide_dense_wgrad_head")
-                check(lib.cl_reduce_partials(ptr(W["wpart"]), nsplit, w * fan_in + w, gbase + 4 * ow, sf, st), "cl_reduce_partials")
-                check(lib.cl_reduce_partials(ptr(W["hpart"]), nsplit, 2 * w + 2, gbase + 4 * off_head, sf, st), "cl_reduce_partials")
-                check(lib.cl_wide_dense_dgrad_head(*hd, pbase + 4 * ow, n, w, fan_in, hs[l][0], hs[l][1], leak, ptr(dz), ldw, sf, st),
-                      "cl_wide_dense_dgrad_head")
+            self._wide_backward_chunk(obs, ch, kept[ic] if full is not None else self._wide_forward(obs, ch, True, st)[0], headb, st)
+
+    def _wide_backward_chunk(self, obs: ObsData, chunk, hs, headb: bool, st):
+        """The backward pass of one row chunk from its activations `hs` (_wide_forward) and the rows' dL/d(loc, sigma): the head's backward
+        pass inside the top Dense layer's weight gradient and dgrad (`headb`; its own launch outside their envelope), then weight gradient
+        and dgrad layer by layer, top down -- the per-image layers, then the Dense layers, the first one's weight gradient inside the
+        second one's dgrad when the first layer is recomputed."""
+        a, b, m0, seg = chunk
+        n = b - a
+        lib, W = self.lib, self._wide_setup()
+        layers, off_head = self._wide_layers()
+        pbase, gbase = (t.data_ptr() + 4 * self.layout.off_mlp for t in (self.params, self.grads))
+        sf, leak, w, ldw = ptr(self.stop_flag), self.mlp.leakiness, self.w, W["ldw"]
+        dz, dzn = W["dz"]
+        nsplit = min(W["nsplit"], int(lib.cl_wide_wgrad_splits(n)))
+
+        def reduce(parts, nparts, size, off):
+            check(lib.cl_reduce_partials(ptr(parts), nparts, size, gbase + 4 * off, sf, st), "cl_reduce_partials")
+
+        if headb:
+            # the head's backward pass rides on the top layer's two backward kernels: dZ_L is made from h_L where they read it
+            l = self.L - 1
+            ow, ob, fan_in = layers[l]
+            hd = (*hs[-1], pbase + 4 * off_head, obs.laue_dO.data_ptr() + 8 * a, obs.wide_dsd.data_ptr() + 4 * a)
+            check(lib.cl_wide_dense_wgrad_head(*hd, leak, *hs[l], n, w, fan_in, ptr(W["wpart"]), ptr(W["hpart"]), nsplit, sf, st), "cl_wide_dense_wgrad_head")
+            reduce(W["wpart"], nsplit, w * fan_in + w, ow)
+            reduce(W["hpart"], nsplit, 2 * w + 2, off_head)
+            check(lib.cl_wide_dense_dgrad_head(*hd, pbase + 4 * ow, n, w, fan_in, *hs[l], leak, ptr(dz), ldw, sf, st), "cl_wide_dense_dgrad_head")
+        else:
+            nblk = min(W["nblk"], int(lib.cl_wide_head_blocks(n)))
+            check(lib.cl_wide_head_backward(*hs[-1], pbase + 4 * off_head, obs.laue_dO.data_ptr() + 8 * a, n, w, self.bij_kind,
+                                            self.mlp.epsilon, leak, ptr(dz), ldw, ptr(W["hpart"]), nblk, sf, st), "cl_wide_head_backward")
+            reduce(W["hpart"], nblk, 2 * w + 2, off_head)
+        K = self.imgl.n_image_layers if self.imgl is not None else 0
+        for k in range(K - 1, -1, -1):          # per-image layers: each image's gradient is written once (its rows sit in one chunk)
+            l = self.L + k
+            gw, gb = self._imgl_ptrs(self.grads, k, m0)
+            wk, _ = self._imgl_ptrs(self.params, k, m0)
+            check(lib.cl_wide_image_wgrad(ptr(dz), ldw, *hs[l], ptr(seg), seg.numel() - 1, n, w, gw, gb, sf, st), "cl_wide_image_wgrad")
+            if w > 128:
+                tl = obs.wide_tiles[a]
+                check(lib.cl_wide_image_dgrad_tiles(ptr(dz), ldw, wk, ptr(seg), ptr(tl), tl.numel() // 2, w, *hs[l], leak, ptr(dzn), ldw, sf, st),
+                      "cl_wide_image_dgrad_tiles")
             else:
-                nblk = min(W["nblk"], int(lib.cl_wide_head_blocks(n)))
-                check(lib.cl_wide_head_backward(hs[-1][0], hs[-1][1], pbase + 4 * off_head, obs.laue_dO.data_ptr() + 8 * a, n, w, self.bij_kind,
-                                                self.mlp.epsilon, leak, ptr(dz), ldw, ptr(W["hpart"]), nblk, sf, st), "cl_wide_head_backward")
-                check(lib.cl_reduce_partials(ptr(W["hpart"]), nblk, 2 * w + 2, gbase + 4 * off_head, sf, st), "cl_reduce_partials")
-            for k in range(K - 1, -1, -1):          # per-image layers: each image's gradient is written once (its rows sit in one chunk)
-                l = self.L + k
-                gw, gb = self._imgl_ptrs(self.grads, k, m0)
-                wk, _ = self._imgl_ptrs(self.params, k, m0)
-                check(lib.cl_wide_image_wgrad(ptr(dz), ldw, hs[l][0], hs[l][1], ptr(seg), seg.numel() - 1, n, w, gw, gb, sf, st), "cl_wide_image_wgrad")
-                if w > 128:
-                    tl = obs.wide_tiles[a]
-                    check(lib.cl_wide_image_dgrad_tiles(ptr(dz), ldw, wk, ptr(seg), ptr(tl), tl.numel() // 2, w, hs[l][0], hs[l][1], leak, ptr(dzn), ldw, sf, st),
-                          "cl_wide_image_dgrad_tiles")
-                else:
-                    check(lib.cl_wide_image_dgrad(ptr(dz), ldw, wk, ptr(seg), seg.numel() - 1, n, w, hs[l][0], hs[l][1], leak, ptr(dzn), ldw, sf, st),
-                          "cl_wide_image_dgrad")
+                check(lib.cl_wide_image_dgrad(ptr(dz), ldw, wk, ptr(seg), seg.numel() - 1, n, w, *hs[l], leak, ptr(dzn), ldw, sf, st), "cl_wide_image_dgrad")
+            dz, dzn = dzn, dz
+        pre = self._wide_pre()
+        for l in range(self.L - (2 if headb else 1), -1, -1):
+            ow, ob, fan_in = layers[l]
+            if pre and l == 1:
+                # the layer's input h_0 is recomputed from the metadata: as the weight gradient's operand and as the dgrad's mask
+                ow0, ob0, d0 = layers[0]
+                x0 = (*hs[0], d0, pbase + 4 * ow0, pbase + 4 * ob0)
+                check(lib.cl_wide_dense_wgrad_pre(ptr(dz), ldw, *x0, leak, n, w, fan_in, ptr(W["wpart"]), nsplit, sf, st), "cl_wide_dense_wgrad_pre")
+                reduce(W["wpart"], nsplit, w * fan_in + w, ow)
+                # layer 1's dgrad with layer 0's weight gradient taken where dZ_0 is produced (it is never stored) ...
+                rc = -2 if not self.FUSE_WG0 else \
+                    lib.cl_wide_dense_dgrad_pre_wgrad0(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *x0, leak, ptr(W["wpart"]), sf, st)
+                if rc != -2:
+                    check(rc, "cl_wide_dense_dgrad_pre_wgrad0")
+                    reduce(W["wpart"], int(lib.cl_wide_dgrad_wgrad0_parts(n)), w * d0 + w, ow0)
+                    break
+                # ... or, outside that kernel's envelope, the two launches
+                check(lib.cl_wide_dense_dgrad_pre(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *x0, leak, ptr(dzn), ldw, sf, st), "cl_wide_dense_dgrad_pre")
                 dz, dzn = dzn, dz
-            pre = self._wide_pre()
-            for l in range(self.L - (2 if headb else 1), -1, -1):
-                ow, ob, fan_in = layers[l]
-                if pre and l == 1:
-                    # the layer's input h_0 is recomputed from the metadata: as the weight gradient's operand and as the dgrad's mask
-                    ow0, ob0, d0 = layers[0]
-                    x0, ld0 = hs[0]
-                    check(lib.cl_wide_dense_wgrad_pre(ptr(dz), ldw, x0, ld0, d0, pbase + 4 * ow0, pbase + 4 * ob0, leak, n, w, fan_in, ptr(W["wpart"]),
-                                                      nsplit, sf, st), "cl_wide_dense_wgrad_pre")
-                    check(lib.cl_reduce_partials(ptr(W["wpart"]), nsplit, w * fan_in + w, gbase + 4 * ow, sf, st), "cl_reduce_partials")
-                    # layer 1's dgrad with layer 0's weight gradient taken where dZ_0 is produced (it is never stored) ...
-                    rc = -2 if not self.FUSE_WG0 else \
-                        lib.cl_wide_dense_dgrad_pre_wgrad0(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, x0, ld0, d0, pbase + 4 * ow0, pbase + 4 * ob0, leak,
-                                                           ptr(W["wpart"]), sf, st)
-                    if rc != -2:
-                        check(rc, "cl_wide_dense_dgrad_pre_wgrad0")
-                        check(lib.cl_reduce_partials(ptr(W["wpart"]), int(lib.cl_wide_dgrad_wgrad0_parts(n)), w * d0 + w, gbase + 4 * ow0, sf, st),
-                              "cl_reduce_partials")
-                        break
-                    # ... or, outside that kernel's envelope, the two launches
-                    check(lib.cl_wide_dense_dgrad_pre(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, x0, ld0, d0, pbase + 4 * ow0, pbase + 4 * ob0, leak,
-                                                      ptr(dzn), ldw, sf, st), "cl_wide_dense_dgrad_pre")
-                    dz, dzn = dzn, dz
-                    continue
-                check(lib.cl_wide_dense_wgrad(ptr(dz), ldw, hs[l][0], hs[l][1], n, w, fan_in, ptr(W["wpart"]), nsplit, sf, st), "cl_wide_dense_wgrad")
-                check(lib.cl_reduce_partials(ptr(W["wpart"]), nsplit, w * fan_in + w, gbase + 4 * ow, sf, st), "cl_reduce_partials")
-                if l > 0:
-                    check(lib.cl_wide_dense_dgrad(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, hs[l][0], hs[l][1], leak, ptr(dzn), ldw, sf, st),
-                          "cl_wide_dense_dgrad")
-                    dz, dzn = dzn, dz
+                continue
+            check(lib.cl_wide_dense_wgrad(ptr(dz), ldw, *hs[l], n, w, fan_in, ptr(W["wpart"]), nsplit, sf, st), "cl_wide_dense_wgrad")
+            reduce(W["wpart"], nsplit, w * fan_in + w, ow)
+            if l > 0:
+                check(lib.cl_wide_dense_dgrad(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *hs[l], leak, ptr(dzn), ldw, sf, st), "cl_wide_dense_dgrad")
+                dz, dzn = dzn, dz
 

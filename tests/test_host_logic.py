@@ -585,6 +585,160 @@ def test_wide_entry_points_answer_without_a_launch():
     assert lib.cl_wide_head_backward(off, 128, p, p, 100, 128, 0, 1e-7, 0.01, p, 128, p, 1, None, None) == -1
     assert lib.cl_wide_head_backward(p, 128, p, p, 100, 126, 0, 1e-7, 0.01, p, 126, p, 1, None, None) == -1
     assert lib.cl_wide_head_backward(p, 1028, p, p, 100, 1025, 0, 1e-7, 0.01, p, 1028, p, 1, None, None) == -2
+    _wide_rejections(lib)
+
+
+def _wide_rejections(lib):
+    """Every launching cl_wide_* entry point, one rejecting call per clause its checks distinguish: a missing pointer, the row-count
+    bounds (n = 0; n = 2^31 where the entry point bounds it -- cl_wide_head_forward, cl_wide_image_forward / _dgrad and the _tiles pair
+    do not, so that call is NOT made for them: it would launch), a pitch below the width, every -2 envelope edge, every alignment /
+    pitch-multiple clause, and which of -1 and -2 answers when both apply.  Per entry point: its parameter names in C order, a call the
+    library would ACCEPT (never made), and (expected answer, what to change in it) pairs."""
+    import ctypes as C
+    p, off, big = 0x10000, 0x10004, 1 << 31
+
+    def rejects(name, params, base, cases):
+        fn, params = getattr(lib, name), params.split()
+        assert sorted(params) == sorted(base), name
+        for want, over in cases:
+            assert set(over) <= set(base), (name, over)
+            a = dict(base, **over)
+            got = fn(*[a[k] for k in params])
+            assert got == want, (name, over, got, want)
+
+    def nulls(*names):
+        return [(-1, {k: None}) for k in names]
+
+    row = [(-1, dict(n=0)), (-1, dict(n=-5)), (-1, dict(n=big))]
+    com = dict(n=100, leak=0.01, stop=None, st=None)
+
+    rejects("cl_wide_dense_forward", "X ldx Wt b n n_in n_out leak act Y ldy stop st",
+            dict(com, X=p, ldx=128, Wt=p, b=p, n_in=128, n_out=128, act=1, Y=p, ldy=128),
+            nulls("X", "Wt", "b", "Y") + row + [(-1, dict(n_in=0)), (-1, dict(n_out=0)), (-1, dict(ldx=127)), (-1, dict(ldy=127)),
+                                              (-1, dict(n_in=200, n_out=200, ldx=200, ldy=199)), (-1, dict(n_in=200, ldx=199))])
+    fh = dict(com, X=p, ldx=128, Wt=p, b=p, n_in=128, n_out=128, Y=p, ldy=128, head=p, bij=0, eps=1e-7, loc=p, sig=p, dsd=None)
+    fh_cases = (nulls("X", "Wt", "b", "Y", "head", "loc", "sig") + row +
+                [(-1, dict(n_in=0)), (-1, dict(n_out=0)), (-1, dict(ldx=127)), (-1, dict(ldy=127)),
+                 (-2, dict(n_in=129, ldx=132)), (-2, dict(n_out=129, ldy=132)), (-2, dict(n_in=129, n_out=129, ldx=132, ldy=132)),
+                 (-1, dict(n_in=129, ldx=132, X=None)), (-1, dict(n_out=129, ldy=128)), (-1, dict(n_in=129, ldx=132, n=0))])
+    rejects("cl_wide_dense_forward_head", "X ldx Wt b n n_in n_out leak Y ldy head bij eps loc sig dsd stop st", fh, fh_cases)
+
+    # ... with the slot likelihood: the host reads the argument block, so a real (zeroed, then filled with made-up addresses) one
+    blocks = []
+
+    def lik(**over):
+        a = _lib.LaueArgs()
+        blocks.append(a)
+        for k in ("refl_id", "iobs", "sig", "z_f", "dz_f", "dO", "scalars"):
+            setattr(a, k, p)
+        a.S, a.n_obs = 4, 100
+        for k, v in over.items():
+            setattr(a, k, v)
+        return C.pointer(a)
+
+    fl = dict(fh, lik=lik())
+    rejects("cl_wide_dense_forward_head_lik", "X ldx Wt b n n_in n_out leak Y ldy head bij eps loc sig dsd lik stop st", fl,
+            fh_cases + [(-1, dict(lik=None)), (-2, dict(n_in=129, ldx=132, lik=lik(S=0)))] +         # the shared check comes first
+            # what the fused epilogue declines: harmonics, injected noise, predictions out, Evans-2011 terms, the deterministic stores
+            [(-2, dict(lik=lik(**{k: p}))) for k in ("harmonic_id", "eta", "ipred_out", "ev11", "dzf_obs", "nll_part")] +
+            [(-2, dict(lik=lik(eta=p, refl_id=None)))] +                                            # (declined before the block is judged)
+            [(-1, dict(lik=lik(**{k: None}))) for k in ("refl_id", "iobs", "sig", "z_f", "dz_f", "dO", "scalars")] +
+            [(-1, dict(lik=lik(S=0))), (-1, dict(lik=lik(n_obs=99))), (-1, dict(lik=lik(use_img=1))),
+             (-1, dict(lik=lik(use_img=1, image_id=p, img=p))), (-1, dict(lik=lik(use_img=1, image_id=p, d_img=p))),
+             (-1, dict(lik=lik(use_img=1, img=p, d_img=p))), (-1, dict(lik=lik(S=0), n_in=64, ldx=64))] +
+            # the square-layer kernel's envelope: 5 .. 8 blocks, the same on both sides, pitches multiples of 4 inside the blocks, aligned
+            [(-2, dict(n_in=64, ldx=64)), (-2, dict(n_out=64, ldy=64)), (-2, dict(n_in=64, n_out=64, ldx=64, ldy=64)),
+             (-2, dict(n_in=96, ldx=96)), (-2, dict(n_in=100, n_out=100, ldx=101, ldy=100)), (-2, dict(n_in=100, n_out=100, ldx=100, ldy=102)),
+             (-2, dict(n_in=100, n_out=100, ldx=116, ldy=100)), (-2, dict(n_in=100, n_out=100, ldx=100, ldy=116)),
+             (-2, dict(ldx=132)), (-2, dict(ldy=132)), (-2, dict(X=off)), (-2, dict(Y=off))])
+
+    w100 = dict(n_out=100, n_in=100, ldt=100, ldo=100, ldh=100)     # (seven blocks a side: row buffers of 100 .. 112 floats)
+    dh = dict(com, Htop=p, ldt=128, head=p, dO=p, dsd=p, Wt=p, n_out=128, n_in=128, Hprev=p, ldh=128, dX=p, ldo=128)
+    rejects("cl_wide_dense_dgrad_head", "Htop ldt head dO dsd Wt n n_out n_in Hprev ldh leak dX ldo stop st", dh,
+            nulls("Htop", "head", "dO", "dsd", "Wt", "dX") + row +
+            [(-1, dict(n_in=0)), (-1, dict(n_out=0)), (-1, dict(ldt=127)), (-1, dict(ldo=127)), (-1, dict(n_out=129, ldt=128)),
+             (-2, dict(n_out=129, ldt=132)), (-2, dict(n_out=64)), (-2, dict(n_out=64, n_in=64)), (-2, dict(n_out=96)), (-2, dict(n_in=96)),
+             (-1, dict(n_out=64, n_in=64, dX=None)),
+             (-2, dict(w100, ldt=101)), (-2, dict(w100, ldo=102)), (-2, dict(w100, ldh=106)), (-2, dict(w100, ldo=116)), (-2, dict(w100, ldt=116)),
+             (-2, dict(w100, ldh=116)), (-2, dict(ldt=132)), (-2, dict(ldo=132)), (-2, dict(ldh=132)), (-2, dict(Htop=off)), (-2, dict(dX=off)),
+             (-2, dict(Hprev=off)), (-2, dict(ldh=126))])
+
+    rejects("cl_wide_dense_dgrad", "dZ lddz Wt n n_out n_in Hprev ldh leak dX ldo stop st",
+            dict(com, dZ=p, lddz=128, Wt=p, n_out=128, n_in=128, Hprev=p, ldh=128, dX=p, ldo=128),
+            nulls("dZ", "Wt", "dX") + row + [(-1, dict(n_in=0)), (-1, dict(n_out=0)), (-1, dict(lddz=127)), (-1, dict(ldo=127)),
+                                            (-1, dict(n_out=200, lddz=199)), (-1, dict(n_in=200, ldo=199))])
+
+    # the recomputed first layer (pre_check): pointers, then the envelope (1 .. 15 metadata columns, width 1 .. 128), then the metadata's layout
+    pre = dict(X0=p, ldx0=8, n_in0=5, Wt0=p, b0=p)
+
+    def pre_cases(width):
+        return (nulls("X0", "Wt0", "b0") +
+                [(-2, dict(n_in0=16, ldx0=16)), (-2, dict(n_in0=0)), (-2, {width: 129}), (-2, {width: 0}), (-1, dict(n_in0=16, ldx0=16, X0=None)),
+                 (-1, dict(ldx0=4)), (-1, dict(n_in0=6, ldx0=7)), (-1, dict(ldx0=20)), (-1, dict(X0=off)), (-2, dict(n_in0=16, ldx0=4, X0=off))])
+
+    rejects("cl_wide_dense2_forward", "X0 ldx0 n_in0 Wt0 b0 Wt1 b1 n w0 w1 leak Y ldy head bij eps loc sig stop st",
+            dict(com, **pre, Wt1=p, b1=p, w0=128, w1=128, Y=p, ldy=128, head=p, bij=0, eps=1e-7, loc=p, sig=p),
+            pre_cases("w0") + nulls("Wt1", "b1", "Y", "loc", "sig") + row +
+            [(-1, dict(w1=0)), (-1, dict(ldy=127)), (-2, dict(w1=129, ldy=132)), (-1, dict(w1=129, ldy=128)), (-1, dict(w1=129, ldy=132, Y=None)),
+             (-2, dict(w1=129, ldy=132, loc=None)), (-2, dict(n_in0=16, ldx0=16, Y=None)), (-2, dict(w0=129, n=0))])
+    rejects("cl_wide_dense_dgrad_pre", "dZ lddz Wt n n_out n_in X0 ldx0 n_in0 Wt0 b0 leak dX ldo stop st",
+            dict(com, **pre, dZ=p, lddz=128, Wt=p, n_out=128, n_in=128, dX=p, ldo=128),
+            pre_cases("n_in") + nulls("dZ", "Wt", "dX") + row +
+            [(-1, dict(n_out=0)), (-1, dict(lddz=127)), (-1, dict(ldo=127)), (-2, dict(n_out=129, lddz=132)), (-1, dict(n_out=129, lddz=128)),
+             (-1, dict(n_out=129, lddz=132, dX=None)), (-2, dict(n_in0=16, ldx0=16, dX=None))])
+    rejects("cl_wide_dense_dgrad_pre_wgrad0", "dZ lddz Wt n n_out n_in X0 ldx0 n_in0 Wt0 b0 leak partials stop st",
+            dict(com, **pre, dZ=p, lddz=128, Wt=p, n_out=128, n_in=128, partials=p),
+            pre_cases("n_in") + nulls("dZ", "Wt", "partials") + row +
+            [(-1, dict(n_out=0)), (-1, dict(lddz=127)), (-2, dict(n_out=129, lddz=132)), (-1, dict(n_out=129, lddz=128)),
+             (-1, dict(n_out=129, lddz=132, partials=None)),
+             # the square-layer envelope; the rows of dZ are read at the width of BOTH sides of the layer: the pitch covers n_in too
+             (-2, dict(n_out=64, n_in=64, lddz=64)), (-2, dict(n_out=64)), (-2, dict(n_in=64)), (-2, dict(n_out=96)), (-2, dict(n_in=96)),
+             (-2, dict(n_out=100, n_in=110, lddz=104)), (-2, dict(n_out=100, n_in=110, lddz=108)), (-2, dict(n_out=100, n_in=100, lddz=101)),
+             (-2, dict(n_out=100, n_in=100, lddz=116)), (-2, dict(lddz=132)), (-2, dict(dZ=off))])
+    rejects("cl_wide_dense_wgrad_pre", "dZ lddz X0 ldx0 n_in0 Wt0 b0 leak n n_out n_in partials nsplit stop st",
+            dict(com, **pre, dZ=p, lddz=128, n_out=128, n_in=128, partials=p, nsplit=1),
+            pre_cases("n_in") + nulls("dZ", "partials") + row +
+            [(-1, dict(n_out=0)), (-1, dict(nsplit=0)), (-1, dict(lddz=127)), (-2, dict(n_out=129, lddz=132)), (-1, dict(n_out=129, lddz=128)),
+             (-1, dict(n_out=129, lddz=132, nsplit=0)), (-2, dict(n_in=129, dZ=None))])
+
+    rejects("cl_wide_dense_wgrad", "dZ lddz H ldh n n_out n_in partials nsplit stop st",
+            dict(n=100, stop=None, st=None, dZ=p, lddz=128, H=p, ldh=128, n_out=128, n_in=128, partials=p, nsplit=1),
+            nulls("dZ", "H", "partials") + row + [(-1, dict(n_in=0)), (-1, dict(n_out=0)), (-1, dict(nsplit=0)), (-1, dict(lddz=127)), (-1, dict(ldh=127))])
+    rejects("cl_wide_dense_wgrad_head", "Htop ldt head dO dsd leak H ldh n n_out n_in partials hpart nsplit stop st",
+            dict(com, Htop=p, ldt=128, head=p, dO=p, dsd=p, H=p, ldh=128, n_out=128, n_in=128, partials=p, hpart=p, nsplit=1),
+            nulls("Htop", "head", "dO", "dsd", "H", "partials", "hpart") + row +
+            [(-1, dict(n_in=0)), (-1, dict(n_out=0)), (-1, dict(nsplit=0)), (-1, dict(ldt=127)), (-1, dict(ldh=127)),
+             (-2, dict(n_out=129, ldt=132)), (-2, dict(n_out=64)), (-2, dict(n_out=64, n_in=64)), (-2, dict(n_in=96)),
+             (-1, dict(n_out=64, n_in=64, nsplit=0)), (-1, dict(dO=off)), (-1, dict(dsd=off)), (-2, dict(n_in=96, dO=off))])
+
+    # per-image layers: the grouped streaming kernel holds widths up to 128 and says so (-2) whatever else is wrong with the call
+    imf = dict(com, X=p, ldx=128, W=p, b=p, seg=p, n_groups=3, w=128, Y=p, ldy=128)
+    rejects("cl_wide_image_forward", "X ldx W b seg n_groups n w leak Y ldy stop st", imf,
+            nulls("X", "W", "b", "seg", "Y") + [(-1, dict(n=0)), (-1, dict(n_groups=0)), (-1, dict(w=0)), (-1, dict(ldx=127)), (-1, dict(ldy=127)),
+                                               (-2, dict(w=129, ldx=132, ldy=132)), (-2, dict(w=129)), (-2, dict(w=129, X=None)), (-2, dict(w=129, n=0))])
+    imd = dict(com, dZ=p, lddz=128, W=p, seg=p, n_groups=3, w=128, Hprev=p, ldh=128, dX=p, ldo=128)
+    rejects("cl_wide_image_dgrad", "dZ lddz W seg n_groups n w Hprev ldh leak dX ldo stop st", imd,
+            nulls("dZ", "W", "seg", "dX") + [(-1, dict(n=0)), (-1, dict(n_groups=0)), (-1, dict(w=0)), (-1, dict(lddz=127)), (-1, dict(ldo=127)),
+                                            (-2, dict(w=129, lddz=132, ldo=132)), (-2, dict(w=129)), (-2, dict(w=129, dZ=None)), (-2, dict(w=129, n=0))])
+    tf = dict(leak=0.01, stop=None, st=None, X=p, ldx=256, W=p, b=p, seg=p, tiles=p, n_tiles=4, w=256, Y=p, ldy=256)
+    rejects("cl_wide_image_forward_tiles", "X ldx W b seg tiles n_tiles w leak Y ldy stop st", tf,
+            nulls("X", "W", "b", "seg", "tiles", "Y") + [(-1, dict(n_tiles=0)), (-1, dict(w=0)), (-1, dict(ldx=255)), (-1, dict(ldy=255))])
+    td = dict(leak=0.01, stop=None, st=None, dZ=p, lddz=256, W=p, seg=p, tiles=p, n_tiles=4, w=256, Hprev=p, ldh=256, dX=p, ldo=256)
+    rejects("cl_wide_image_dgrad_tiles", "dZ lddz W seg tiles n_tiles w Hprev ldh leak dX ldo stop st", td,
+            nulls("dZ", "W", "seg", "tiles", "dX") + [(-1, dict(n_tiles=0)), (-1, dict(w=0)), (-1, dict(lddz=255)), (-1, dict(ldo=255))])
+    rejects("cl_wide_image_wgrad", "dZ lddz H ldh seg n_groups n w dW db stop st",
+            dict(n=100, stop=None, st=None, dZ=p, lddz=128, H=p, ldh=128, seg=p, n_groups=3, w=128, dW=p, db=p),
+            nulls("dZ", "H", "seg", "dW", "db") + row + [(-1, dict(n_groups=0)), (-1, dict(w=0)), (-1, dict(lddz=127)), (-1, dict(ldh=127))])
+
+    rejects("cl_wide_head_forward", "H ldh Wo n w bij eps loc sig stop st",
+            dict(n=100, stop=None, st=None, H=p, ldh=128, Wo=p, w=128, bij=0, eps=1e-7, loc=p, sig=p),
+            nulls("H", "Wo", "loc", "sig") + [(-1, dict(n=0)), (-1, dict(w=0)), (-1, dict(ldh=127))])
+    rejects("cl_wide_head_backward", "H ldh Wo dO n w bij eps leak dZ lddz partials nblocks stop st",
+            dict(com, H=p, ldh=128, Wo=p, dO=p, w=128, bij=0, eps=1e-7, dZ=p, lddz=128, partials=p, nblocks=1),
+            nulls("H", "Wo", "dO", "dZ", "partials") + row +
+            [(-1, dict(w=0)), (-1, dict(nblocks=0)), (-1, dict(ldh=127)), (-1, dict(lddz=127)), (-1, dict(w=126, ldh=126)), (-1, dict(w=126, lddz=126)),
+             (-1, dict(H=off)), (-1, dict(dZ=off)), (-2, dict(w=1025, ldh=1028, lddz=1028)), (-1, dict(w=1025, ldh=1028, lddz=1028, H=off)),
+             (-1, dict(w=1025, ldh=1028, lddz=1024))])
 
 
 def test_round6_entry_points_host_side():

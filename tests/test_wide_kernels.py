@@ -3,16 +3,16 @@ tests/ref_wide.py at their a-priori rounding bounds, on operands carved from one
 bit-identical after the call, every output element written, padding columns of outputs exactly zero, partial slots written).
 
 Shape -> instance, from the dispatch in wide_gemm.hip (shapes are in -> out; N = output columns of the launch, K = contraction):
-  launch_sq (sq_ok: ceil(N / 16) == ceil(K / 16) = NA >= 5, ld % 4 == 0, 16-byte aligned): `switch ((s.N + 15) >> 4) { case 5 .. 7; default: 8 }`
+  launch_sq (sq_ok: ceil(N / 16) == ceil(K / 16) = NA >= 5, ld % 4 == 0, 16-byte aligned): `with_blocks<5>((s.N + 15) >> 4, ..)`, NA = 5 .. 7 by name, else 8
       65 -> 80: wide_sq_kernel<.., NA = 5>; 96 -> 96: NA = 6; 100 -> 112, 112 -> 100, 100 -> 100, 120 -> 120: NA = 7 (never run before);
       113 -> 128, 128 -> 113: NA = 8 with a ragged last block; PRE (dgrad_pre), WG0 (dgrad_pre_wgrad0), HEADB (dgrad_head) forms alike.
-  launch_stream: `s.N <= 64 ? launch_stream_n<.., 4, ..> : launch_stream_n<.., 8, ..>` for the other layers up to 128 x 128:
+  launch_stream: `s.N <= 64 ? launch_stream_n<.., 4, .., PRE> : launch_stream_n<.., 8, .., PRE>` for the other layers up to 128 x 128:
       70 -> 96, 128 -> 65, 16 -> 128, 1 -> 65, 96 -> 70 (dgrad: N = 70), 32 -> 70: wide_stream_kernel<.., NAT = 8>; 70 -> 32, 128 -> 1, 3 -> 64: NAT = 4;
       any layer with ld % 4 != 0 or a pointer off 16-byte alignment: the same kernels on their scalar paths (vec == false).
-  launch_gemm (a side beyond 128; every weight gradient): `g.N > 64 ? wide_gemm_kernel<.., 128> : wide_gemm_kernel<.., 64>`
+  launch_gemm (a side beyond 128; every weight gradient): `if (g.N > 64) .. wide_gemm_kernel<.., 128> ..; .. wide_gemm_kernel<.., 64>`
       130 -> 96, 64 -> 129 (a tile of one column), 200 -> 300 (three column tiles, K > 128): BN = 128; 130 -> 32, 129 -> 64, 300 -> 1: BN = 64.
-  launch_stream2<NA>, NA = ceil(max(w0, w1) / 16): 100, 120 -> wide_stream2_kernel<7>; 65 -> <5>; 128 -> <8>; 20 -> <2>.
-  CL_HEAD_BWD ladder: `w <= 128: NP 1; w <= 256: NP 2; w <= 512: NP 4; else NP 8 (sets the dynamic-LDS attribute)`:
+  launch_stream2: `with_blocks<1>(((s.pre.N0 > s.N1 ? s.pre.N0 : s.N1) + 15) >> 4, ..)`: 100, 120 -> wide_stream2_kernel<7>; 65 -> <5>; 128 -> <8>; 20 -> <2>.
+  cl_wide_head_backward's ladder: `if (w <= 128) return launch(<1>); if (w <= 256) .. <2>; if (w <= 512) .. <4>; return launch(<8>)` (cl_launch_lds sets the dynamic-LDS attribute):
       65, 128 -> 1; 129, 256 -> 2; 300, 512 -> wide_head_backward_kernel<4>; 520, 1024 -> <8>.
   Rows: grids are min(ceil(n / 128), 2 CUs) workgroups of 8 waves, a wave per 16-row block: at n_long = 128 (2 CUs) + 128 * 3 + 5 some waves
   walk two blocks (the prefetch of "the wave's next block"), some one, and the last block is ragged.  Grouped kernels take
@@ -477,7 +477,7 @@ def head_backward(n, w, kind, nblocks, stop=False):
 @pytest.mark.parametrize("n", ROWS)
 @pytest.mark.parametrize("w", HEAD_W)
 def test_head_backward(w, n, blocks, kind):
-    """the CL_HEAD_BWD ladder: NP = 1 (65, 128), 2 (129, 256), 4 (300, 512), 8 (520, 1024: 8 * (2 w + 2) floats of dynamic LDS, past 64 KiB at 1024);
+    """the instance ladder of cl_wide_head_backward: NP = 1 (65, 128), 2 (129, 256), 4 (300, 512), 8 (520, 1024: 8 * (2 w + 2) floats of dynamic LDS, past 64 KiB at 1024);
     blocks without rows (n = 1 in seven blocks) still write their partial slots"""
     nb = {"one": 1, "auto": int(lib().cl_wide_head_blocks(n)), "seven": 7}[blocks]
     head_backward(n, w, kind, nb)
