@@ -21,6 +21,17 @@ LIB = os.path.join(LIBDIR, "libcareless_hip.so")
 # not see: NOTEBOOK R6.1).  The units must still CARRY a NaN from a poisoned observation to the gradient entries it touches (the non-finite
 # stop is taken on the gradient norm, in elbo_elem.hip): tests/test_nonfinite.py holds every route to the oracle's non-finite mask.
 NNAN = ["-fno-honor-nans"]
+# The lane kernel's 4x4x1 MFMA results feed vector code: kept in architectural registers, no accumulator-register detour.  Internal LLVM
+# option (validated on ROCm 7.2.0 / AMD clang 22); probed before use
+LANE_FLAG = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
+# The units of elbo_lane.hip: (object stem, unit kind, depth or None, takes LANE_FLAG) -- the kinds, what each compiles and why it is a unit
+# of its own: the table at the head of the source
+LANE_TABLE = [("elbo_lane0", "DISPATCH", None, True), ("elbo_lane1", "PACKED_REG", None, True), ("elbo_lane2", "PLAIN_ROWS", None, True),
+              ("elbo_lane3", "PACKED_ROWS", None, True), ("elbo_lane4", "IMGL", None, True), ("elbo_lane5", "IMGL3", None, False),
+              *[(f"elbo_lane_d{D}", "DEPTH", D, True) for D in range(2, 20)], *[(f"elbo_lane_i{D}", "IMGL_DEPTH", D, True) for D in range(2, 20)],
+              ("elbo_lane_b20", "BLOCK", None, True)]
+LANE_UNITS = [("elbo_lane.hip", stem, [f"-DCL_LANE_UNIT=CL_LANE_UNIT_{kind}"] + ([f"-DCL_LANE_NL={D}"] if D else []) + (LANE_FLAG if flag else []) + NNAN)
+              for stem, kind, D, flag in LANE_TABLE]
 # (source, object stem, extra flags): elbo_mlp.hip is compiled twice -- Dense-only scalers and the per-image-layer variant
 UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=0"] + NNAN), ("elbo_mlp.hip", "elbo_mlp_imgl", ["-DCL_IMGL=1"] + NNAN),
          ("elbo_mlp.hip", "elbo_mlp_packed", ["-DCL_IMGL=2"] + NNAN),
@@ -29,19 +40,7 @@ UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=
          ("elbo_mlp.hip", "elbo_mlp_packed_det", ["-DCL_IMGL=2", "-DCL_DET=1"] + NNAN),    # ... in the packed layout (single-pass Laue)
          ("elbo_mlp.hip", "elbo_mlp_chain_det", ["-DCL_CHAIN=1", "-DCL_DET=1"] + NNAN),    # ... for the last block of a layer-block chain
          ("elbo_narrow.hip", "elbo_narrow", ["-fno-slp-vectorize"] + NNAN),     # (packed fp32 math costs more than it saves beside MFMAs)
-         # (4x4x1 results feed vector code: no accumulator-register detour); four parts = four groups of instances, compiled in parallel
-         ("elbo_lane.hip", "elbo_lane0", ["-DCL_LANE_PART=0", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN),
-         ("elbo_lane.hip", "elbo_lane1", ["-DCL_LANE_PART=1", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN),
-         ("elbo_lane.hip", "elbo_lane2", ["-DCL_LANE_PART=2", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN),
-         ("elbo_lane.hip", "elbo_lane3", ["-DCL_LANE_PART=3", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN),
-         ("elbo_lane.hip", "elbo_lane4", ["-DCL_LANE_PART=4", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN),      # per-image layers (round 5)
-         # three per-image layers on the default depth: WITHOUT the option above (its AGPR-copy rewrite pass crashes on the 23-layer instances)
-         ("elbo_lane.hip", "elbo_lane5", ["-DCL_LANE_PART=5"] + NNAN),
-         # ... and the widest instances once more per depth below the default (round 6: `--mlp-layers 2 .. 19` at widths 7 .. 10; 16 - 25 s each)
-         *[("elbo_lane.hip", f"elbo_lane_d{D}", ["-DCL_LANE_PART=7", f"-DCL_LANE_NL={D}", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN) for D in range(2, 20)],
-         # ... and the per-image-layer instances per depth (`--mlp-layers D --image-layers 1|2`; 10 - 40 s each)
-         *[("elbo_lane.hip", f"elbo_lane_i{D}", ["-DCL_LANE_PART=9", f"-DCL_LANE_NL={D}", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN) for D in range(2, 20)],
-         ("elbo_lane.hip", "elbo_lane_b20", ["-DCL_LANE_PART=8", "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + NNAN),      # the layer-block launches (act_out / dH_ext) at the default depth
+         *LANE_UNITS,
          ("elbo_elem.hip", "elbo_elem", []), ("elbo_laue.hip", "elbo_laue", []), ("wide_gemm.hip", "wide_gemm", []),
          ("elbo_peel.hip", "elbo_peel", []), ("elbo_frozen.hip", "elbo_frozen", []),
          # host threads, no device code: the formatter's symmetry bookkeeping (exact products kept apart from their sums)
@@ -49,9 +48,6 @@ UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["cl_math.h", "cl_kernels.h", os.path.join("..", "..", "include", "careless_hip.h")]
 ARCH = "gfx950"
-
-
-LANE_FLAG = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]      # internal LLVM option (validated on ROCm 7.2.0 / AMD clang 22); probed before use
 
 
 def _lane_flag_ok(hipcc: str) -> bool:
@@ -126,7 +122,7 @@ def _build(LIB: str, extra, verbose: bool) -> str:
             cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17"] + list(extra) + flags + ["-c", os.path.join(CSRC, s), "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
-            while sum(1 for _, p in procs if p.poll() is None) >= jobs:      # (63 units: not all compilers at once on a small box)
+            while sum(1 for _, p in procs if p.poll() is None) >= jobs:      # (58 units: not all compilers at once on a small box)
                 time.sleep(0.2)
             procs.append((cmd, subprocess.Popen(cmd)))
             objs.append(o)

@@ -35,13 +35,13 @@ int cl_launch_det_reduce(const cl_det_args& a, hipStream_t st);                 
 // The *_supports functions describe the shapes a kernel family holds; the A/B switches that keep shapes off a family are read by mlp_route only.
 int cl_narrow_supports(const cl_mlp_args& a);                                       // elbo_narrow.hip: width <= 15, metadata <= 15, plain layout
 int cl_launch_narrow(const cl_mlp_args& a, const cl_launch_ctx& c);                 // ... the full ELBO step on that kernel
-int cl_lane_supports(const cl_mlp_args& a);                                         // elbo_lane.hip: lane = observation; 20 layers, width <= 10, metadata <= 31 columns
+int cl_lane_supports(const cl_mlp_args& a);                                         // elbo_lane.hip: lane = observation; 2 .. 20 layers, width <= 12, metadata <= 31 columns
 #ifndef CL_LANE_WMAX
-#define CL_LANE_WMAX 10                                                             // ... widest instance of every form (11, 12: twelve-wide register instances)
+#define CL_LANE_WMAX 10                                                             // ... widest instance of every form (11, 12: twelve-wide, metadata in registers)
 #endif
-int cl_lane_imgl_supports(const cl_mlp_args& a);                                    // ... with one or two per-image layers on top (round 5)
+int cl_lane_imgl_supports(const cl_mlp_args& a);                                    // ... with one to three per-image layers on top
 int cl_launch_lane_imgl(const cl_mlp_args& a, const cl_launch_ctx& c);
-int cl_lane_block_supports(const cl_mlp_args& a, int mode);                          // ... a head-less layer block's forward / backward launch (round 6)
+int cl_lane_block_supports(const cl_mlp_args& a, int mode);                          // ... a head-less layer block's forward / backward launch
 int cl_launch_lane_block(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
 int cl_launch_lane(const cl_mlp_args& a, const cl_launch_ctx& c);                   // ... the full ELBO step on that kernel
 int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st);

@@ -2,7 +2,8 @@
 // in registers), metadata width <= 31, any number of MC samples -- the geometry of the careless CLI default (--mlp-layers 20, --mlp-width 10,
 // --mc-samples 1: careless/args/scaling.py:21-31), also with the 16 extra metadata columns of --positional-encoding-keys X,Y
 // (careless/utils/positional_encoding.py:3-17).  The depth is a compile-time constant of the unit: the default build has 20 Dense layers,
-// build.py compiles the file again for every depth 2 .. 19 (round 6: -DCL_LANE_NL); widths 13 - 15 and one-layer scalers run on elbo_narrow.hip.
+// build.py compiles the file again for every depth 2 .. 19 (-DCL_LANE_NL; there from width 5 on); widths 13 - 15 and one-layer scalers run on
+// elbo_narrow.hip.
 //
 // Same arithmetic and the same reference lines as elbo_mlp.hip (scaler forward / sample / predict / likelihood / backward:
 // careless/models/scaling/nn.py:92-120, image.py:53-63, models/merging/variational.py:156-181, 197-202,
@@ -40,10 +41,37 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define CL_LANE_COALESCE 2      /* smallest number of MC samples whose amplitude gradients leave through LDS (0: never) */
 #endif
 
+// The compilation units of this file (build.py: LANE_UNITS): -DCL_LANE_UNIT=<kind>, the per-depth kinds with -DCL_LANE_NL=<depth>.  Every unit
+// sees the whole kernel template and instantiates what its section of the launch layer (the #if chain at the end of the file) names.
+//   kind          compiles                                                                          a unit of its own for
+//   DISPATCH      the *_supports predicates, the dispatch; plain layout, metadata in registers      compile time (25 - 50 s a unit, in parallel)
+//   PACKED_REG    packed layout (single-pass Laue), metadata in registers                           compile time
+//   PLAIN_ROWS    plain layout, metadata as LDS rows                                                compile time
+//   PACKED_ROWS   packed layout, metadata as LDS rows                                               compile time
+//   IMGL          one or two per-image layers on the default depth                                  compile time
+//   IMGL3         three per-image layers on the default depth                                       its flags: built WITHOUT -amdgpu-mfma-vgpr-form=1, whose
+//                                                                                                   AGPR-copy rewrite pass crashes on the 23-layer instances
+//   DEPTH         CL_LANE_NL = 2 .. 19 Dense layers: widths 8, 10, 12, metadata in registers, both  the depth as a compile-time constant (16 - 25 s each)
+//                 layouts; and the layer-block launches (MODE 1 / 2) of that depth
+//   BLOCK         the layer-block launches of the default depth                                     compile time
+//   IMGL_DEPTH    one to three per-image layers on CL_LANE_NL = 2 .. 19 Dense layers                the depth as a compile-time constant (10 - 40 s each)
+#define CL_LANE_UNIT_DISPATCH 1
+#define CL_LANE_UNIT_PACKED_REG 2
+#define CL_LANE_UNIT_PLAIN_ROWS 3
+#define CL_LANE_UNIT_PACKED_ROWS 4
+#define CL_LANE_UNIT_IMGL 5
+#define CL_LANE_UNIT_IMGL3 6
+#define CL_LANE_UNIT_DEPTH 7
+#define CL_LANE_UNIT_BLOCK 8
+#define CL_LANE_UNIT_IMGL_DEPTH 9
+#ifndef CL_LANE_UNIT
+#define CL_LANE_UNIT CL_LANE_UNIT_DISPATCH
+#endif
+
 namespace {
 
 // Dense layers of the scaler: a compile-time constant of the unit.  The default build has the careless default depth (20 = the most one
-// launch holds); round 6 compiles the file again with -DCL_LANE_NL=2 .. 19 (build.py: one part per depth, 16 - 25 s each, the widest
+// launch holds); build.py compiles the file again with -DCL_LANE_NL=2 .. 19 (one unit per depth, 16 - 25 s each, the widest
 // instances only) for `--mlp-layers` below the default -- a run-time depth test per unrolled layer costs this one-wave-per-SIMD kernel its
 // register allocation (NOTEBOOK R6.3: 120 - 380 spilled registers and accumulator copies behind the inline-assembly MFMAs).
 #ifndef CL_LANE_NL
@@ -79,10 +107,10 @@ __device__ __forceinline__ f32x4 mfma_bk(float a, float b, f32x4 c) { return __b
 // wait states between them; the only other reader is the flush, a barrier later.)
 // Diagnostic switches of round 6 (scripts/probe/build_lane_variants.py; NOTEBOOK R6.1): CL_LANE_MFMA_BUILTIN / CL_LANE_SEL_C replace one
 // kind of inline-assembly statement by code the compiler knows, CL_LANE_LRELU_ASM brings the inline-assembly LeakyReLU back; CL_LANE_PAD_PRE / CL_LANE_PAD_POST pad the MFMA statement.
-// (The unit of the three-per-image-layer instances -- CL_LANE_PART 5, compiled WITHOUT -amdgpu-mfma-vgpr-form: see there -- spills accumulator
+// (The unit of the three-per-image-layer instances -- CL_LANE_UNIT_IMGL3, compiled WITHOUT -amdgpu-mfma-vgpr-form: see there -- spills accumulator
 //  registers, and the compiler's reload copies land one instruction in front of the statement whose MFMA reads them: two wait states in front of
 //  every such MFMA, in that unit only.)
-#if !defined(CL_LANE_PAD_PRE) && defined(CL_LANE_PART) && CL_LANE_PART == 5
+#if !defined(CL_LANE_PAD_PRE) && CL_LANE_UNIT == CL_LANE_UNIT_IMGL3
 #define CL_LANE_PAD_PRE "s_nop 1\n\t"
 #endif
 #ifndef CL_LANE_PAD_PRE
@@ -1106,279 +1134,238 @@ void elbo_lane_kernel(const cl_mlp_args A) {
 #endif
 }
 
-// The instances are spread over four compilations of this file (build.py: -DCL_LANE_PART=0 .. 3, in parallel; a part takes 25 - 50 s):
-// part 0 = plain layout, metadata in registers (+ the dispatch); 1 = packed layout, registers; 2 = plain, LDS rows (LX); 3 = packed, LX.
-#ifndef CL_LANE_PART
-#define CL_LANE_PART 0
+// ---------------------------------------------------------------------------------------------------------
+// The launch layer: host code only.  What a launch runs is decided in four steps, each written once: the unit (cl_lane_unit<kind, depth>,
+// one per compilation: the table at the head of the file), the compile-time width (with_lane_width), the form (launch_lane_form), and
+// the leaf (launch_lane_inst), which launches the instance or prints its name.
+// ---------------------------------------------------------------------------------------------------------
+#if CL_LANE_UNIT < CL_LANE_UNIT_DISPATCH || CL_LANE_UNIT > CL_LANE_UNIT_IMGL_DEPTH
+#error "CL_LANE_UNIT: not one of the unit kinds listed at the head of this file"
+#endif
+constexpr int LANE_W12 = 12;               // widest instance with the metadata in registers (three output chunks like width 10, two more activation registers per layer)
+constexpr int LANE_IMGL_MAX = 2;           // per-image layers of the instances with all three forms ...
+constexpr int LANE_IMGL_MAX_NL = 3;        // ... a third one: production and full form
+constexpr int LANE_IMGL3_DEPTH_MAX = 18;   // ... the third one on 2 .. 18 and on 20 Dense layers: on 19 the full instance (22 layers) crashes the compiler pass named at unit IMGL3
+constexpr int LANE_DEPTH_LO = 2;           // the depths with units of their own: LANE_DEPTH_LO .. NL - 1 of the default build
+#ifndef CL_LANE_DEPTH_WMIN
+#define CL_LANE_DEPTH_WMIN 5               /* narrowest scaler the other-depth instances (compiled at widths 8, 10 and 12) take: from here on the padded steps still beat elbo_narrow.hip */
 #endif
 
-// The leaf of the launch path: with a name sink it prints this instance's template parameters (the default depth and NI = 0 in the
-// short forms the profiles have always used), without one it launches
+// The leaf of the launch path: with a name sink it prints this instance's template parameters up to the last one that is off its default
+// (at least four: the short forms the profiles have always used; the depth's default is CL_MLP_LMAX_W16), without one it launches
 template <int W, int DMAX, bool PACKED, bool FULL, bool DXO = false, int NI = 0, int MODE = 0>
 static int launch_lane_inst(const cl_mlp_args& a, const cl_launch_ctx& c) {
     if (c.name != nullptr) {
-        const char* const pk = PACKED ? "true" : "false", * const fu = FULL ? "true" : "false", * const dx = DXO ? "true" : "false";
-        const char* const det = a.dzf_obs != nullptr ? " (deterministic stores)" : "";
-        if (NI > 0 && NL != CL_MLP_LMAX_W16) return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s, %s, %d, %d> (image layers)%s", W, DMAX, pk, fu, dx, NI, NL, det);
-        if (NI > 0) return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s, %s, %d> (image layers)%s", W, DMAX, pk, fu, dx, NI, det);
-        if (NL != CL_MLP_LMAX_W16) return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s, %s, 0, %d>%s", W, DMAX, pk, fu, dx, NL, det);
-        return snprintf(c.name, c.name_n, "elbo_lane_kernel<%d, %d, %s, %s%s>%s", W, DMAX, pk, fu, DXO ? ", true" : "", det);
+        constexpr int shown = MODE != 0 ? 8 : (NL != CL_MLP_LMAX_W16 ? 7 : (NI > 0 ? 6 : (DXO ? 5 : 4)));
+        const char* const tf[2] = {"false", "true"};
+        char p[64];
+        int n = snprintf(p, sizeof p, "%d, %d, %s, %s", W, DMAX, tf[PACKED], tf[FULL]);
+        if (shown >= 5) n += snprintf(p + n, sizeof p - n, ", %s", tf[DXO]);
+        if (shown >= 6) n += snprintf(p + n, sizeof p - n, ", %d", NI);
+        if (shown >= 7) n += snprintf(p + n, sizeof p - n, ", %d", NL);
+        if (shown >= 8) n += snprintf(p + n, sizeof p - n, ", %d", MODE);
+        return snprintf(c.name, c.name_n, "elbo_lane_kernel<%s>%s%s", p, NI > 0 ? " (image layers)" : "",
+                        MODE == 0 && a.dzf_obs != nullptr ? " (deterministic stores)" : "");
     }
     const size_t sm = (size_t)LSmem<W, DMAX == 0, NI>::total(a.d) * sizeof(float);
     return cl_launch_lds<elbo_lane_kernel<W, DMAX, PACKED, FULL, DXO, NI, NL, MODE>>(dim3(c.grid), dim3(NT), sm, c.st, a);
 }
 
-// the plain layout has a second instance without the optional inputs / outputs (the training step of a production run); the packed
-// layout (single-pass Laue) keeps the one full instance
+// The forms of an instance: production (the training step of a production run: none of the optional inputs / outputs), full (with
+// them), and production that stores dZ_0 (the step behind the engine's peeled first layer, which hands over the layer's w pre-activations
+// as metadata).  A unit compiles all three, production and full (dZ_0 asked: the full one), or the full one only.
+enum lane_forms { LANE_FULL_ONLY, LANE_PROD_FULL, LANE_ALL_FORMS };
 static inline bool lane_wants_full(const cl_mlp_args& a) { return a.eta != nullptr || a.ipred_out != nullptr || a.ev11 != nullptr || a.dzf_obs != nullptr; }
-template <int W, int DMAX, bool PACKED>
-static int launch_lane_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    if constexpr (PACKED) return launch_lane_inst<W, DMAX, true, true>(a, c);
-    else {
-        if (lane_wants_full(a)) return launch_lane_inst<W, DMAX, false, true>(a, c);
-        // the production step behind a peeled first layer: metadata = the peeled layer's w pre-activations, in registers (DMAX = 8 or 15)
-        if constexpr (DMAX != 0) { if (a.dZ0_out != nullptr) return launch_lane_inst<W, DMAX, false, false, true>(a, c); }
-        else if (a.dZ0_out != nullptr) return launch_lane_inst<W, DMAX, false, true>(a, c);
-        return launch_lane_inst<W, DMAX, false, false>(a, c);
+template <lane_forms FORMS, int W, int DMAX, bool PACKED, int NI = 0>
+static int launch_lane_form(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if constexpr (FORMS != LANE_FULL_ONLY) {
+        const bool dz0 = a.dZ0_out != nullptr;
+        const bool full = lane_wants_full(a) || (dz0 && FORMS != LANE_ALL_FORMS);
+        if constexpr (FORMS == LANE_ALL_FORMS) {
+            if (dz0 && !full) return launch_lane_inst<W, DMAX, PACKED, false, true, NI>(a, c);
+        }
+        if (!full) return launch_lane_inst<W, DMAX, PACKED, false, false, NI>(a, c);
     }
+    return launch_lane_inst<W, DMAX, PACKED, true, false, NI>(a, c);
 }
 
-#define CL_LANE_IMGL_MAX 2          /* per-image layers of the lane instances with all three forms (production, full, dZ_0 out) ... */
-#define CL_LANE_IMGL_MAX_NL 3       /* ... a third one: production and full form; at the default depth in a unit of its own (CL_LANE_PART = 5) */
-#define CL_LANE_IMGL3_DEPTH_MAX 18  /* ... the third one on 2 .. 18 and on 20 Dense layers (19: see CL_LANE_PART 9) */
-#ifndef CL_LANE_DEPTH_WMIN
-#define CL_LANE_DEPTH_WMIN 5        /* narrowest scaler the other-depth instances (compiled at widths 8 and 10) take */
-#endif
-
-// the instance whose compile-time width is the smallest one that holds the scaler (zero-padded features cost MFMA steps)
-#define CL_LANE_WIDTHS(CASE)      \
-    if (a.w <= 4) return CASE(4); \
-    if (a.w <= 6) return CASE(6); \
-    if (a.w <= 8) return CASE(8); \
-    return CASE(10);
-// ... with the metadata in registers also widths 11 and 12 (round 6: three output chunks like width 10, two more activation registers per
-// layer -- 22 .. 72 spilled registers at the default depth, none from 16 layers down; still ahead of elbo_narrow.hip: profiles/r6_envelope_w12.txt)
-#define CL_LANE_W12 12
-#define CL_LANE_WIDTHS_REG(CASE)   \
-    if (a.w <= 4) return CASE(4);  \
-    if (a.w <= 6) return CASE(6);  \
-    if (a.w <= 8) return CASE(8);  \
-    if (a.w <= 10) return CASE(10); \
-    return CASE(CL_LANE_W12);
-
-int cl_launch_lane_plain_reg(const cl_mlp_args& a, const cl_launch_ctx& c);
-int cl_launch_lane_packed_reg(const cl_mlp_args& a, const cl_launch_ctx& c);
-int cl_launch_lane_plain_rows(const cl_mlp_args& a, const cl_launch_ctx& c);
-int cl_launch_lane_packed_rows(const cl_mlp_args& a, const cl_launch_ctx& c);
-int cl_launch_lane_imgl_inst(const cl_mlp_args& a, const cl_launch_ctx& c);
-int cl_launch_lane_imgl3(const cl_mlp_args& a, const cl_launch_ctx& c);
-// other depths than the default (round 6): one compilation per depth, CL_LANE_PART = 7
-#define CL_LANE_DEPTHS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
-#define CL_LANE_DEPTH_DECL(D) int cl_launch_lane_depth##D(const cl_mlp_args& a, const cl_launch_ctx& c);
-CL_LANE_DEPTHS(CL_LANE_DEPTH_DECL)
-#undef CL_LANE_DEPTH_DECL
-// ... and the two launches of a head-less layer block (MODE 1 / 2) at every depth 2 .. 20: the blocks in front of the last one of a chained scaler
-#define CL_LANE_BLOCK_DECL(D) int cl_launch_lane_block##D(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
-CL_LANE_DEPTHS(CL_LANE_BLOCK_DECL)
-CL_LANE_BLOCK_DECL(20)
-#undef CL_LANE_BLOCK_DECL
-// ... and the per-image-layer instances at every depth 2 .. 19 (round 6; CL_LANE_PART = 9, one compilation per depth)
-#define CL_LANE_IMGLD_DECL(D) int cl_launch_lane_imgl_depth##D(const cl_mlp_args& a, const cl_launch_ctx& c);
-CL_LANE_DEPTHS(CL_LANE_IMGLD_DECL)
-#undef CL_LANE_IMGLD_DECL
-static inline bool lane_has_depth(int L) {
-#define CL_LANE_DEPTH_TEST(D) if (L == D) return true;
-    CL_LANE_DEPTHS(CL_LANE_DEPTH_TEST)
-#undef CL_LANE_DEPTH_TEST
-    return false;
+// f(the compile-time width that holds a scaler of width w): the smallest of the set (zero-padded features cost MFMA steps), its widest
+// for anything above (the *_supports predicates keep wider scalers away)
+enum lane_widths { LANE_W4_10, LANE_W4_12, LANE_W8_12 };
+template <lane_widths SET, class F>
+static int with_lane_width(int w, F f) {
+    if constexpr (SET != LANE_W8_12) {
+        if (w <= 4) return f(std::integral_constant<int, 4>{});
+        if (w <= 6) return f(std::integral_constant<int, 6>{});
+    }
+    if (w <= 8) return f(std::integral_constant<int, 8>{});
+    if constexpr (SET != LANE_W4_10) {
+        if (w > CL_LANE_WMAX) return f(std::integral_constant<int, LANE_W12>{});
+    }
+    return f(std::integral_constant<int, CL_LANE_WMAX>{});
 }
 
-#if CL_LANE_PART == 0
-int cl_launch_lane_plain_reg(const cl_mlp_args& a, const cl_launch_ctx& c) {
-#define CL_LANE_CASE(WW) (a.d <= 8 ? launch_lane_one<WW, 8, false>(a, c) : (WW <= CL_LANE_WMAX ? launch_lane_one<(WW <= CL_LANE_WMAX ? WW : 4), DMAX_ALL, false>(a, c) : -2))
-    CL_LANE_WIDTHS_REG(CL_LANE_CASE)
-#undef CL_LANE_CASE
+// One entry point per unit kind and depth: specialised in the unit that compiles it, called from the dispatch unit (`mode`: block launches)
+template <int KIND, int DEPTH>
+int cl_lane_unit(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
+// ... the entry point of kind KIND for a.L among the depths LO .. HI
+template <int KIND, int LO, int HI>
+static int lane_unit_of_depth(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) {
+    if constexpr (LO > HI) return -2;
+    else return a.L == LO ? cl_lane_unit<KIND, LO>(a, mode, c) : lane_unit_of_depth<KIND, LO + 1, HI>(a, mode, c);
 }
+
+// metadata in registers.  Eight columns or fifteen at the default depth; one capacity in the per-depth units (the eight-column instances buy
+// back registers the shallower units do not miss, and would double their compile time); twelve wide at the default depth: eight columns only
+template <lane_forms FORMS, bool PACKED>
+static int launch_lane_reg(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    return with_lane_width<(NL == CL_MLP_LMAX_W16 ? LANE_W4_12 : LANE_W8_12)>(a.w, [&](auto ww) {
+        constexpr int W = decltype(ww)::value;
+        if constexpr (NL == CL_MLP_LMAX_W16) {
+            if (a.d <= 8) return launch_lane_form<FORMS, W, 8, PACKED>(a, c);
+        }
+        if constexpr (NL == CL_MLP_LMAX_W16 && W > CL_LANE_WMAX) return -2;
+        else return launch_lane_form<FORMS, W, DMAX_ALL, PACKED>(a, c);
+    });
+}
+// metadata as LDS rows
+template <lane_forms FORMS, bool PACKED>
+static int launch_lane_rows(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    return with_lane_width<LANE_W4_10>(a.w, [&](auto ww) { return launch_lane_form<FORMS, decltype(ww)::value, 0, PACKED>(a, c); });
+}
+// NI per-image layers: the widest instance serves every w <= 10 (--image-layers on a non-default width is rare).  Three of them have no
+// dZ_0-storing production instance: without -amdgpu-mfma-vgpr-form it comes out with accumulator-register copies one instruction in front
+// of the inline-assembly MFMAs that read them (the build's wait-state scan refuses it: scripts/check_lane_isa.py, rule R1).
+template <int NI>
+static int launch_lane_imgl_of(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    constexpr lane_forms FORMS = NI <= LANE_IMGL_MAX ? LANE_ALL_FORMS : LANE_PROD_FULL;
+    if constexpr (NL == CL_MLP_LMAX_W16 && NI <= LANE_IMGL_MAX) {
+        if (a.d <= 8) return launch_lane_form<FORMS, CL_LANE_WMAX, 8, true, NI>(a, c);
+    }
+    return launch_lane_form<FORMS, CL_LANE_WMAX, DMAX_ALL, true, NI>(a, c);
+}
+// the launch of a head-less layer block (MODE 1: forward with act_out; 2: backward from dH_ext): widths 8 and 10, in the per-depth units
+// also 12 (at the default depth twelve activations per layer spill)
+template <int MODE>
+static int launch_lane_block(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    return with_lane_width<LANE_W8_12>(a.w, [&](auto ww) {
+        constexpr int W = decltype(ww)::value;
+        if constexpr (NL == CL_MLP_LMAX_W16 && W > CL_LANE_WMAX) return -2;
+        else {
+            if constexpr (NL == CL_MLP_LMAX_W16) {
+                if (a.d <= 8) return launch_lane_inst<W, 8, false, false, false, 0, MODE>(a, c);
+            }
+            return launch_lane_inst<W, DMAX_ALL, false, false, false, 0, MODE>(a, c);
+        }
+    });
+}
+
+#if CL_LANE_UNIT == CL_LANE_UNIT_DISPATCH
+template <>
+int cl_lane_unit<CL_LANE_UNIT_DISPATCH, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) { return launch_lane_reg<LANE_ALL_FORMS, false>(a, c); }
 
 // LDS bytes the LDS-row instance of hidden width w needs for d metadata columns
 static size_t lane_rows_lds(int w, int d) {
-    const int t = w <= 4 ? LSmem<4, true>::total(d) : (w <= 6 ? LSmem<6, true>::total(d) : (w <= 8 ? LSmem<8, true>::total(d) : LSmem<10, true>::total(d)));
-    return (size_t)t * sizeof(float);
+    return sizeof(float) * (size_t)with_lane_width<LANE_W4_10>(w, [&](auto ww) { return LSmem<decltype(ww)::value, true>::total(d); });
 }
 
-// 1 = this geometry runs on the lane-per-observation kernel (full ELBO step of a scaler of exactly NL layers -- the default depth --;
-// plain observation layout, or the packed one of single-pass Laue).  Up to 15 metadata columns are registers of the lane, 16 .. 31
-// are rows of an LDS buffer (LX); any number of MC samples (batches of SPRE).  4 M observations, 20 x 10, Student-T, ms per step
-// here / on elbo_narrow.hip (scripts/narrow_samples.py): S = 1 0.96 / 1.11, 2: 1.01 / 1.12, 4: 1.07 / 1.19, 8: 1.16 / 1.34.
+// The clauses the three predicates below share.  A depth is compiled if it is the default one or has a per-depth unit (whose instances start
+// at width 8: a narrower scaler pays the padded steps); the columns are registers of the lane up to DMAX_ALL of them.
+static inline bool lane_depth_compiled(const cl_mlp_args& a) { return a.L == NL || (a.L >= LANE_DEPTH_LO && a.L < NL && a.w >= CL_LANE_DEPTH_WMIN); }
+static inline bool lane_cols_in_regs(const cl_mlp_args& a) { return a.d >= 1 && a.d <= DMAX_ALL; }
+// ... what every launch on this kernel needs: width and columns inside the window, a compiled depth, no input gradient to hand to an earlier block
+static inline bool lane_envelope(const cl_mlp_args& a, int wmax, int dmax) {
+    return a.w >= 1 && a.w <= wmax && a.d >= 1 && a.d <= dmax && lane_depth_compiled(a) && a.dX_out == nullptr;
+}
+// ... a full ELBO step, not a block of a chain
+static inline bool lane_full_step(const cl_mlp_args& a) { return a.S >= 1 && a.act_out == nullptr && a.dH_ext == nullptr; }
+
+// 1 = this geometry runs on the lane-per-observation kernel (full ELBO step; plain observation layout, or the packed one of single-pass
+// Laue).  Up to 15 metadata columns are registers of the lane, 16 .. 31 are rows of an LDS buffer (LX); any number of MC samples
+// (batches of SPRE).  4 M observations, 20 x 10, Student-T, ms per step here / on elbo_narrow.hip (scripts/narrow_samples.py):
+// S = 1 0.96 / 1.11, 2: 1.01 / 1.12, 4: 1.07 / 1.19, 8: 1.16 / 1.34.
 int cl_lane_supports(const cl_mlp_args& a) {
-    const int wtop = a.d <= DMAX_ALL ? CL_LANE_W12 : CL_LANE_WMAX;
-    if (!(a.w >= 1 && a.w <= wtop && a.S >= 1 && a.d >= 1 && a.d <= DMAX_LX && (a.L == NL || lane_has_depth(a.L)) && a.n_imgl == 0 && a.act_out == nullptr &&
-          a.dH_ext == nullptr && a.dX_out == nullptr && (a.row_map != nullptr || a.gmeta == nullptr)))
-        return 0;
-    // the other depths (round 6): instances at widths 8 and 10 (a narrower scaler pays the padded steps: from width CL_LANE_DEPTH_WMIN on it still
-    // beats elbo_narrow.hip), metadata in registers (more columns: behind the engine's peeled first layer, dZ_0 out in the plain layout)
-    if (a.L != NL) return a.w >= CL_LANE_DEPTH_WMIN && a.d <= DMAX_ALL && (a.dZ0_out == nullptr || a.row_map == nullptr);
+    const bool regs = lane_cols_in_regs(a);
+    if (!(lane_envelope(a, regs ? LANE_W12 : CL_LANE_WMAX, DMAX_LX) && lane_full_step(a) && a.n_imgl == 0 && (a.row_map != nullptr || a.gmeta == nullptr))) return 0;
+    // the other depths: metadata in registers (more columns: behind the engine's peeled first layer, dZ_0 out in the plain layout)
+    if (a.L != NL) return regs && (a.dZ0_out == nullptr || a.row_map == nullptr);
     // widths 11, 12 at the default depth: 22 .. 72 spilled registers -- ahead of the narrow kernel on <= 8 columns (1.05 against 1.11 ms at
     // 4 M observations), behind it on 9 .. 15 (1.17 against 1.12)
     if (a.w > CL_LANE_WMAX) return a.d <= 8;
-    return a.d <= DMAX_ALL || lane_rows_lds(a.w, a.d) <= 160 * 1024;
+    return regs || lane_rows_lds(a.w, a.d) <= 160 * 1024;
 }
 
-// 1 = the training step of a NeuralImageScaler runs on the lane-per-observation kernel (round 5): the default depth and width (NL Dense layers,
-// w <= 10) on up to 15 metadata columns with one or two per-image layers (`careless mono | poly --image-layers 1|2`) in the packed-by-image
-// layout (Laue data: harmonic groups inside 16-row granules, single pass, as without per-image layers); everything else with per-image
-// layers stays on the IMGL instances of elbo_mlp.hip.
-// Round 6: the same at 2 .. 19 Dense layers (`--mlp-layers D --image-layers 1|2`: the instances of the per-depth units, width >= CL_LANE_DEPTH_WMIN).
+// 1 = the training step of a NeuralImageScaler runs on the lane-per-observation kernel: w <= 10 on up to 15 metadata columns with one
+// to three per-image layers (`careless mono | poly [--mlp-layers D] --image-layers K`; three: not on 19 Dense layers) in the
+// packed-by-image layout (Laue data: harmonic groups inside 16-row granules, single pass, as without per-image layers); everything
+// else with per-image layers stays on the IMGL instances of elbo_mlp.hip.
 int cl_lane_imgl_supports(const cl_mlp_args& a) {
-    const bool depth_ok = a.L == NL || (lane_has_depth(a.L) && a.w >= CL_LANE_DEPTH_WMIN);
-    return a.n_imgl >= 1 && a.n_imgl <= ((a.L == NL || a.L <= CL_LANE_IMGL3_DEPTH_MAX) ? CL_LANE_IMGL_MAX_NL : CL_LANE_IMGL_MAX) && a.w >= 1 && a.w <= CL_LANE_WMAX && a.S >= 1 && a.d >= 1 && a.d <= DMAX_ALL && depth_ok &&
-           a.act_out == nullptr && a.dH_ext == nullptr && a.dX_out == nullptr && a.row_map != nullptr &&
+    const int nmax = (a.L == NL || a.L <= LANE_IMGL3_DEPTH_MAX) ? LANE_IMGL_MAX_NL : LANE_IMGL_MAX;
+    return lane_envelope(a, CL_LANE_WMAX, DMAX_ALL) && lane_full_step(a) && a.n_imgl >= 1 && a.n_imgl <= nmax && a.row_map != nullptr &&
            (a.gmeta == nullptr || a.tile_gmax != nullptr) && !a.use_img && a.imgl != nullptr && a.d_imgl != nullptr && a.tile_img != nullptr && a.n_images >= 1;
 }
 
-// 1 = this launch of a head-less layer block (mode 1: forward with act_out; mode 2: backward from dH_ext) runs on the lane kernel (round 6):
-// 2 .. 20 Dense layers of width 5 .. 10 on <= 15 input columns in the plain layout, the FIRST block of a chain (no dX_out)
+// 1 = this launch of a head-less layer block (mode 1: forward with act_out; mode 2: backward from dH_ext) runs on the lane kernel:
+// 2 .. 20 Dense layers of width 5 .. 10 (12 below the default depth) on <= 15 input columns in the plain layout, the FIRST block of a chain
 int cl_lane_block_supports(const cl_mlp_args& a, int mode) {
     if (!(mode == 1 || mode == 2)) return 0;
-    if (!(a.w >= CL_LANE_DEPTH_WMIN && a.w <= (a.L == NL ? CL_LANE_WMAX : CL_LANE_W12) && a.d >= 1 && a.d <= DMAX_ALL && (a.L == NL || lane_has_depth(a.L)) && a.n_imgl == 0 &&
-          a.row_map == nullptr && a.gmeta == nullptr && a.dX_out == nullptr && a.dO_ext == nullptr && a.dZ0_out == nullptr))
+    if (!(lane_envelope(a, a.L == NL ? CL_LANE_WMAX : LANE_W12, DMAX_ALL) && a.w >= CL_LANE_DEPTH_WMIN && a.n_imgl == 0 && a.row_map == nullptr &&
+          a.gmeta == nullptr && a.dO_ext == nullptr && a.dZ0_out == nullptr))
         return 0;
     if (mode == 1) return a.act_out != nullptr && a.dH_ext == nullptr && a.loc_out == nullptr && a.sig_out == nullptr;
     return a.dH_ext != nullptr && a.act_out == nullptr && a.partials != nullptr;
 }
 
-int cl_launch_lane_block(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) {
-#define CL_LANE_BLOCK_CALL(D) if (a.L == D) return cl_launch_lane_block##D(a, mode, c);
-    CL_LANE_DEPTHS(CL_LANE_BLOCK_CALL)
-    CL_LANE_BLOCK_CALL(20)
-#undef CL_LANE_BLOCK_CALL
-    return -2;
-}
+int cl_launch_lane_block(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) { return lane_unit_of_depth<CL_LANE_UNIT_BLOCK, LANE_DEPTH_LO, NL>(a, mode, c); }
 
 // (deterministic mode -- dzf_obs given --: as cl_launch_lane; the per-image gradients: one wave per image, elbo_lane_kernel)
 int cl_launch_lane_imgl(const cl_mlp_args& a, const cl_launch_ctx& c) {
-#define CL_LANE_IMGLD_CALL(D) if (a.L == D) return cl_launch_lane_imgl_depth##D(a, c);
-    CL_LANE_DEPTHS(CL_LANE_IMGLD_CALL)
-#undef CL_LANE_IMGLD_CALL
-    if (a.n_imgl == CL_LANE_IMGL_MAX_NL) return cl_launch_lane_imgl3(a, c);
-    return cl_launch_lane_imgl_inst(a, c);
+    if (a.L != NL) return lane_unit_of_depth<CL_LANE_UNIT_IMGL_DEPTH, LANE_DEPTH_LO, NL - 1>(a, 0, c);
+    return a.n_imgl == LANE_IMGL_MAX_NL ? cl_lane_unit<CL_LANE_UNIT_IMGL3, NL>(a, 0, c) : cl_lane_unit<CL_LANE_UNIT_IMGL, NL>(a, 0, c);
 }
 
 // (deterministic mode -- dzf_obs given --: stores per (observation, sample) / observation / workgroup / wave (Evans-2011 terms))
 int cl_launch_lane(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    if (a.L != NL) {
-#define CL_LANE_DEPTH_CALL(D) if (a.L == D) return cl_launch_lane_depth##D(a, c);
-        CL_LANE_DEPTHS(CL_LANE_DEPTH_CALL)
-#undef CL_LANE_DEPTH_CALL
-        return -2;
-    }
-    // metadata as LDS rows from DMAX_ALL + 1 columns on (from 9 on it measured slower than the register instances, round 3)
+    if (a.L != NL) return lane_unit_of_depth<CL_LANE_UNIT_DEPTH, LANE_DEPTH_LO, NL - 1>(a, 0, c);
+    // metadata as LDS rows from DMAX_ALL + 1 columns on (from 9 on it measured slower than the register instances)
     const bool rows = a.d > DMAX_ALL;
-    if (a.row_map != nullptr) return rows ? cl_launch_lane_packed_rows(a, c) : cl_launch_lane_packed_reg(a, c);
-    return rows ? cl_launch_lane_plain_rows(a, c) : cl_launch_lane_plain_reg(a, c);
+    if (a.row_map != nullptr) return rows ? cl_lane_unit<CL_LANE_UNIT_PACKED_ROWS, NL>(a, 0, c) : cl_lane_unit<CL_LANE_UNIT_PACKED_REG, NL>(a, 0, c);
+    return rows ? cl_lane_unit<CL_LANE_UNIT_PLAIN_ROWS, NL>(a, 0, c) : cl_lane_unit<CL_LANE_UNIT_DISPATCH, NL>(a, 0, c);
 }
-#elif CL_LANE_PART == 1
-int cl_launch_lane_packed_reg(const cl_mlp_args& a, const cl_launch_ctx& c) {
-#define CL_LANE_CASE(WW) (a.d <= 8 ? launch_lane_one<WW, 8, true>(a, c) : (WW <= CL_LANE_WMAX ? launch_lane_one<(WW <= CL_LANE_WMAX ? WW : 4), DMAX_ALL, true>(a, c) : -2))
-    CL_LANE_WIDTHS_REG(CL_LANE_CASE)
-#undef CL_LANE_CASE
+#elif CL_LANE_UNIT == CL_LANE_UNIT_PACKED_REG
+template <>
+int cl_lane_unit<CL_LANE_UNIT, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) { return launch_lane_reg<LANE_FULL_ONLY, true>(a, c); }
+#elif CL_LANE_UNIT == CL_LANE_UNIT_PLAIN_ROWS
+template <>
+int cl_lane_unit<CL_LANE_UNIT, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) { return launch_lane_rows<LANE_PROD_FULL, false>(a, c); }
+#elif CL_LANE_UNIT == CL_LANE_UNIT_PACKED_ROWS
+template <>
+int cl_lane_unit<CL_LANE_UNIT, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) { return launch_lane_rows<LANE_FULL_ONLY, true>(a, c); }
+#elif CL_LANE_UNIT == CL_LANE_UNIT_IMGL
+template <>
+int cl_lane_unit<CL_LANE_UNIT, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) { return a.n_imgl == 1 ? launch_lane_imgl_of<1>(a, c) : launch_lane_imgl_of<2>(a, c); }
+#elif CL_LANE_UNIT == CL_LANE_UNIT_IMGL3
+// 23 layers of activations; with the four parked layers the LDS has room for (157.5 of 160 KB) and without the compiler option (see the
+// table) 97 .. 145 spilled registers: still ahead of the 16-wide IMGL instance of elbo_mlp.hip
+template <>
+int cl_lane_unit<CL_LANE_UNIT, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) { return launch_lane_imgl_of<LANE_IMGL_MAX_NL>(a, c); }
+#elif CL_LANE_UNIT == CL_LANE_UNIT_IMGL_DEPTH
+template <>
+int cl_lane_unit<CL_LANE_UNIT, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) {
+    if (a.n_imgl == 1) return launch_lane_imgl_of<1>(a, c);
+    if (a.n_imgl == 2) return launch_lane_imgl_of<2>(a, c);
+    if constexpr (NL <= LANE_IMGL3_DEPTH_MAX) return launch_lane_imgl_of<LANE_IMGL_MAX_NL>(a, c);
+    else return -2;
 }
-#elif CL_LANE_PART == 2
-int cl_launch_lane_plain_rows(const cl_mlp_args& a, const cl_launch_ctx& c) {
-#define CL_LANE_CASE(WW) launch_lane_one<WW, 0, false>(a, c)
-    CL_LANE_WIDTHS(CL_LANE_CASE)
-#undef CL_LANE_CASE
+#elif CL_LANE_UNIT == CL_LANE_UNIT_DEPTH
+// the plain layout in its three forms, the packed one in its full form; and this depth's block launches
+template <>
+int cl_lane_unit<CL_LANE_UNIT_DEPTH, NL>(const cl_mlp_args& a, int, const cl_launch_ctx& c) {
+    return a.row_map != nullptr ? launch_lane_reg<LANE_FULL_ONLY, true>(a, c) : launch_lane_reg<LANE_ALL_FORMS, false>(a, c);
 }
-#elif CL_LANE_PART == 7
-// another depth than the default (-DCL_LANE_NL=D): widths 8, 10 and 12, metadata in registers -- plain layout (production / full) and packed
-#define CL_LANE_DEPTH_FN2(D) cl_launch_lane_depth##D
-#define CL_LANE_DEPTH_FN(D) CL_LANE_DEPTH_FN2(D)
-// (one metadata capacity -- 15 columns in registers -- for every depth below the default: the eight-column instances of the default depth buy
-//  back registers the shallower units do not miss, and would double the 19 units' compile time)
-template <int WW>
-static int launch_lane_depth_w(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    if (a.row_map != nullptr) return launch_lane_inst<WW, DMAX_ALL, true, true>(a, c);
-    if (lane_wants_full(a)) return launch_lane_inst<WW, DMAX_ALL, false, true>(a, c);
-    // behind a peeled first layer (more than 15 metadata columns: the engine hands over the layer's w pre-activations): dZ_0 out
-    if (a.dZ0_out != nullptr) return launch_lane_inst<WW, DMAX_ALL, false, false, true>(a, c);
-    return launch_lane_inst<WW, DMAX_ALL, false, false>(a, c);
-}
-int CL_LANE_DEPTH_FN(CL_LANE_NL)(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    return a.w <= 8 ? launch_lane_depth_w<8>(a, c) : (a.w <= 10 ? launch_lane_depth_w<CL_LANE_WMAX>(a, c) : launch_lane_depth_w<CL_LANE_W12>(a, c));
-}
-#endif
-#if CL_LANE_PART == 7 || CL_LANE_PART == 8
-// the two launches of a head-less layer block of this depth (part 8: the default depth)
-template <int WW, int MODE>
-static int launch_lane_block_w(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    if constexpr (NL == CL_MLP_LMAX_W16) return a.d <= 8 ? launch_lane_inst<WW, 8, false, false, false, 0, MODE>(a, c) : launch_lane_inst<WW, DMAX_ALL, false, false, false, 0, MODE>(a, c);
-    else return launch_lane_inst<WW, DMAX_ALL, false, false, false, 0, MODE>(a, c);
-}
-#define CL_LANE_BLOCK_FN2(D) cl_launch_lane_block##D
-#define CL_LANE_BLOCK_FN(D) CL_LANE_BLOCK_FN2(D)
-int CL_LANE_BLOCK_FN(CL_LANE_NL)(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) {
-    // (widths 11, 12: the per-depth units only -- at the default depth twelve activations per layer spill)
-    if constexpr (NL != CL_MLP_LMAX_W16) {
-        if (a.w > CL_LANE_WMAX) return mode == 1 ? launch_lane_block_w<CL_LANE_W12, 1>(a, c) : launch_lane_block_w<CL_LANE_W12, 2>(a, c);
-    } else if (a.w > CL_LANE_WMAX) return -2;
-    if (mode == 1) return a.w <= 8 ? launch_lane_block_w<8, 1>(a, c) : launch_lane_block_w<CL_LANE_WMAX, 1>(a, c);
-    return a.w <= 8 ? launch_lane_block_w<8, 2>(a, c) : launch_lane_block_w<CL_LANE_WMAX, 2>(a, c);
-}
-#endif
-#if CL_LANE_PART == 5
-// THREE per-image layers on the default depth (round 6): 23 layers of activations.  With the four parked layers the LDS has room for
-// (157.5 of 160 KB) hipcc's `AMDGPU Rewrite AGPR-Copy-MFMA` pass -- what -amdgpu-mfma-vgpr-form=1 switches on -- crashes on these
-// instances, so this unit is compiled WITHOUT that option (build.py): 97 .. 145 spilled registers, still ahead of the 16-wide IMGL
-// instance of elbo_mlp.hip these scalers ran on.  One metadata capacity; behind a peeled first layer (dZ_0 out) the FULL instance: without
-// the option the dZ_0-storing production instance comes out with accumulator-register copies one instruction in front of the inline-assembly
-// MFMAs that read them (the build's wait-state scan refuses it: scripts/check_lane_isa.py, rule R1).
-int cl_launch_lane_imgl3(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    if (lane_wants_full(a) || a.dZ0_out != nullptr) return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, CL_LANE_IMGL_MAX_NL>(a, c);
-    return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, CL_LANE_IMGL_MAX_NL>(a, c);
-}
-#endif
-#if CL_LANE_PART == 9
-// per-image layers on another depth than the default (-DCL_LANE_NL=D): the widest instance, one metadata capacity, as the Dense-only units
-#define CL_LANE_IMGLD_FN2(D) cl_launch_lane_imgl_depth##D
-#define CL_LANE_IMGLD_FN(D) CL_LANE_IMGLD_FN2(D)
-int CL_LANE_IMGLD_FN(CL_LANE_NL)(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    const bool full = lane_wants_full(a);
-#define CL_LANE_IMGL_CASE(NI_) (full ? launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, NI_>(a, c) : \
-                                (a.dZ0_out != nullptr ? launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, true, NI_>(a, c) : \
-                                                        launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, NI_>(a, c)))
-    if (a.n_imgl == 1) return CL_LANE_IMGL_CASE(1);
-    if (a.n_imgl == 2) return CL_LANE_IMGL_CASE(2);
-#undef CL_LANE_IMGL_CASE
-    // three per-image layers: production and full instance (behind a peeled first layer the full one, as at the default depth) -- up to
-    // CL_LANE_IMGL3_DEPTH_MAX Dense layers: on 19 the full instance (22 layers) crashes the compiler pass named at CL_LANE_PART 5
-#if CL_LANE_NL <= CL_LANE_IMGL3_DEPTH_MAX
-    if (full || a.dZ0_out != nullptr) return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, true, false, CL_LANE_IMGL_MAX_NL>(a, c);
-    return launch_lane_inst<CL_LANE_WMAX, DMAX_ALL, true, false, false, CL_LANE_IMGL_MAX_NL>(a, c);
-#else
-    return -2;
-#endif
-}
-#endif
-#if CL_LANE_PART == 4
-// per-image layers: the widest instance serves every w <= 10 (a narrower scaler pays the padded MFMA steps: --image-layers on a
-// non-default width is rare); with and without the optional inputs / outputs, as the plain layout
-int cl_launch_lane_imgl_inst(const cl_mlp_args& a, const cl_launch_ctx& c) {
-    // Behind a peeled first layer (more than 15 metadata columns) the launch stores dZ_0: the production instance <.., false, true, NI>.
-    // (Round 5 built it, saw results that moved from run to run and withdrew it for the FULL instance; round 6 found the cause -- the
-    //  inline-assembly LeakyReLU one wait state in front of an MFMA, NOTEBOOK R6.1 -- and it is back: 4.44 -> 4.0 ms per step at 10 M
-    //  observations and 8 samples.)
-    const bool full = lane_wants_full(a);
-#define CL_LANE_IMGL_CASE(DM, NI_) (full ? launch_lane_inst<CL_LANE_WMAX, DM, true, true, false, NI_>(a, c) : \
-                                    (a.dZ0_out != nullptr ? launch_lane_inst<CL_LANE_WMAX, DM, true, false, true, NI_>(a, c) : \
-                                                            launch_lane_inst<CL_LANE_WMAX, DM, true, false, false, NI_>(a, c)))
-    if (a.n_imgl == 1) return a.d <= 8 ? CL_LANE_IMGL_CASE(8, 1) : CL_LANE_IMGL_CASE(DMAX_ALL, 1);
-    return a.d <= 8 ? CL_LANE_IMGL_CASE(8, 2) : CL_LANE_IMGL_CASE(DMAX_ALL, 2);
-#undef CL_LANE_IMGL_CASE
-}
-#elif CL_LANE_PART == 3
-int cl_launch_lane_packed_rows(const cl_mlp_args& a, const cl_launch_ctx& c) {
-#define CL_LANE_CASE(WW) launch_lane_one<WW, 0, true>(a, c)
-    CL_LANE_WIDTHS(CL_LANE_CASE)
-#undef CL_LANE_CASE
-}
+template <>
+int cl_lane_unit<CL_LANE_UNIT_BLOCK, NL>(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) { return mode == 1 ? launch_lane_block<1>(a, c) : launch_lane_block<2>(a, c); }
+#elif CL_LANE_UNIT == CL_LANE_UNIT_BLOCK
+template <>
+int cl_lane_unit<CL_LANE_UNIT_BLOCK, NL>(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) { return mode == 1 ? launch_lane_block<1>(a, c) : launch_lane_block<2>(a, c); }
 #endif

@@ -1525,8 +1525,8 @@ int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n) {
         case CL_ROUTE_NONE: return snprintf(out, n, "(unsupported)");
         case CL_ROUTE_LANE:
         case CL_ROUTE_LANE_IMGL:
+        case CL_ROUTE_LANE_BLOCK:
         case CL_ROUTE_NARROW: return mlp_dispatch(a, mode, r, {0, nullptr, out, n});
-        case CL_ROUTE_LANE_BLOCK:             // (still labelled with the chain instance it replaced in round 6: the lane kernel has no name for its block launches)
         case CL_ROUTE_MLP_CHAIN: unit = ", chain"; break;
         case CL_ROUTE_MLP: break;
         case CL_ROUTE_MLP_PACKED: unit = ", packed"; break;

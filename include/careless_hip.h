@@ -252,9 +252,11 @@ typedef enum cl_epilogue {
     CL_EPI_PLAIN_STUDENTT        /* plain epilogue, Student-T likelihood */
 } cl_epilogue;
 int cl_mlp_epilogue(const cl_mlp_args* args, int mode);
-/* Diagnostics: the name of the kernel instance the launch cl_mlp_route chose runs, e.g. "elbo_lane_kernel<10, 0, false>": what a
- * rocprofv3 kernel trace lists; "(unsupported)" for CL_ROUTE_NONE.  Writes at most n bytes (NUL-terminated), returns the length of
- * the name or < 0 for bad arguments.  No reference counterpart. */
+/* Diagnostics: the name of the kernel instance the launch cl_mlp_route chose runs, e.g. "elbo_lane_kernel<10, 0, false, false>": what a
+ * rocprofv3 kernel trace lists; "(unsupported)" for CL_ROUTE_NONE.  The lane kernel's names leave out trailing template parameters at
+ * their defaults; the launches of a layer block (CL_ROUTE_LANE_BLOCK) print all of them, the mode last:
+ * "elbo_lane_kernel<10, 8, false, false, false, 0, 20, 1>".  Writes at most n bytes (NUL-terminated), returns the length of the name
+ * or < 0 for bad arguments.  No reference counterpart. */
 int cl_mlp_kernel_name(const cl_mlp_args* args, int mode, char* out, size_t n);
 /* Diagnostics: the return code the call of `mode` would give for these arguments and this grid WITHOUT launching -- 0 where it would
  * reach the launch, else its negative code (-1, -2, -4; -3 is found at the launch itself).  The entry checks of that call, the route

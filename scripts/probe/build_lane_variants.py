@@ -3,7 +3,7 @@ other flags, linked against the unchanged rest.  Cross-compiles here (no GPU); t
 
     python scripts/probe/build_lane_variants.py [name ...]       # -> careless_amd/lib/variants/libcareless_hip_<name>.so
 
-A variant = (lane part, extra -D flags, keep the internal -amdgpu-mfma-vgpr-form flag?).
+A variant = (lane unit kind, extra -D flags, keep the internal -amdgpu-mfma-vgpr-form flag?).
 """
 from __future__ import annotations
 
@@ -21,14 +21,14 @@ OUT = os.path.join(B.LIBDIR, "variants")
 
 OLD = ["-DCL_LANE_LRELU_ASM"]        # the inline-assembly LeakyReLU of rounds 2-5
 VARIANTS = {
-    # name: (part, defines, vgpr_form).  The round-6 sources ship the dZ_0-storing production instance with per-image layers
-    # (<10, DM, true, false, true, NI>: lane part 4); what the first GPU call of round 6 ran (gpurun_out/r6_defect_variants.jsonl,
-    # profiles/r6_lane_defect.txt) is these builds with the instance re-enabled by hand:
-    "lrelu_asm": (4, OLD, True),                                          # round 5's LeakyReLU: one wait state short in two instances -> unrepeatable
-    "lrelu_asm_pad": (4, OLD + ['-DCL_LANE_PAD_PRE="s_nop 1\\n\\t"', '-DCL_LANE_PAD_POST="\\n\\ts_nop 7\\n\\ts_nop 7"'], True),   # + wait states around every asm MFMA: still unrepeatable
-    "lrelu_asm_sel_c": (4, OLD + ["-DCL_LANE_SEL_C"], True),              # + LeakyReLU derivative as plain C
-    "shipped_part4": (4, [], True),                                       # the shipped form of the part (control)
-    "novgprform": (4, [], False),                                         # without the internal LLVM flag
+    # name: (unit kind, defines, vgpr_form).  The round-6 sources ship the dZ_0-storing production instance with per-image layers
+    # (<10, DM, true, false, true, NI>: unit kind IMGL); what round 6 first measured (profiles/r6_lane_defect.txt)
+    # is these builds with the instance re-enabled by hand:
+    "lrelu_asm": ("IMGL", OLD, True),                                     # round 5's LeakyReLU: one wait state short in two instances -> unrepeatable
+    "lrelu_asm_pad": ("IMGL", OLD + ['-DCL_LANE_PAD_PRE="s_nop 1\\n\\t"', '-DCL_LANE_PAD_POST="\\n\\ts_nop 7\\n\\ts_nop 7"'], True),   # + wait states around every asm MFMA: still unrepeatable
+    "lrelu_asm_sel_c": ("IMGL", OLD + ["-DCL_LANE_SEL_C"], True),         # + LeakyReLU derivative as plain C
+    "shipped_part4": ("IMGL", [], True),                                  # the shipped form of the unit (control)
+    "novgprform": ("IMGL", [], False),                                    # without the internal LLVM flag
 }
 
 
@@ -63,17 +63,18 @@ def main():
     os.makedirs(d, exist_ok=True)
 
     def one(name):
-        part, defs, vf = VARIANTS[name]
-        o = os.path.join(d, f"elbo_lane{part}_{name}.o")
-        flags = [f"-DCL_LANE_PART={part}"] + (B.LANE_FLAG if vf else []) + B.NNAN + defs
+        kind, defs, vf = VARIANTS[name]
+        stem = next(s for s, k, D, _ in B.LANE_TABLE if k == kind and D is None)       # the object of the production build the variant replaces
+        o = os.path.join(d, f"{stem}_{name}.o")
+        flags = [f"-DCL_LANE_UNIT=CL_LANE_UNIT_{kind}"] + (B.LANE_FLAG if vf else []) + B.NNAN + defs
         if not os.path.exists(o):
             run([hipcc, f"--offload-arch={B.ARCH}", "-O3", "-fPIC", "-std=c++17"] + flags + ["-c", os.path.join(B.CSRC, "elbo_lane.hip"), "-o", o])
         if os.environ.get("CL_VARIANT_ASM"):
-            s = os.path.join(d, f"elbo_lane{part}_{name}.s")
+            s = os.path.join(d, f"{stem}_{name}.s")
             if not os.path.exists(s):
                 run([hipcc, f"--offload-arch={B.ARCH}", "-O3", "-fPIC", "-std=c++17", "--cuda-device-only", "-S"] + flags + [os.path.join(B.CSRC, "elbo_lane.hip"), "-o", s])
         lib = os.path.join(OUT, f"libcareless_hip_{name}.so")
-        link = [objs[st] if st != f"elbo_lane{part}" else o for st in objs]
+        link = [objs[st] if st != stem else o for st in objs]
         run([hipcc, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-pthread", "-o", lib] + link)
         return lib
 

@@ -281,10 +281,9 @@ def test_kernel_name_follows_the_librarys_routing():
     import itertools
     from careless_amd import _lib
     lib = _lib.get_lib()
-    # the family of the name of every route ("elbo_mlp_kernel<" for the others; the lane kernel's layer-block launches keep the label of
-    # the chain instance they replaced)
+    # the family of the name of every route ("elbo_mlp_kernel<" for the others)
     family = {_lib.CL_ROUTE_NONE: "(unsupported)", _lib.CL_ROUTE_LANE: "elbo_lane_kernel<", _lib.CL_ROUTE_LANE_IMGL: "elbo_lane_kernel<",
-              _lib.CL_ROUTE_NARROW: "elbo_narrow_kernel<"}
+              _lib.CL_ROUTE_LANE_BLOCK: "elbo_lane_kernel<", _lib.CL_ROUTE_NARROW: "elbo_narrow_kernel<"}
 
     def name(mode=0, **kw):
         a = _lib.MlpArgs()
@@ -341,7 +340,7 @@ def test_kernel_name_follows_the_librarys_routing():
     assert name(d=5, w=32, L=2, S=2, dzf_obs=1, **imgl) == "(unsupported)"
     assert name(d=21, w=64, L=5, S=8) == "elbo_mlp_kernel<64, 32, 5, 0, KS=4>"
     assert name(d=21, w=64, L=5, S=8, mode=1) == "elbo_mlp_kernel<64, 32, 5, 1, KS=4>"
-    assert name(d=5, w=10, L=20, S=1, act_out=1, mode=1).startswith("elbo_mlp_kernel<16, 8, 20, 1, chain")
+    assert name(d=5, w=10, L=20, S=1, act_out=1, mode=1) == "elbo_lane_kernel<10, 8, false, false, false, 0, 20, 1>"      # (a block launch: every parameter, the mode last)
     assert lib.cl_mlp_kernel_name(None, 0, C.create_string_buffer(8), 8) < 0
     # the route beside the name (cl_mlp_route: the launcher cl_launch_mlp hands the launch to)
     assert route(d=5, w=10, L=20, S=1) == route(d=31, w=4, L=20, S=40, row_map=1) == route(d=6, w=9, L=19, S=1, row_map=1) == _lib.CL_ROUTE_LANE
@@ -371,6 +370,36 @@ def test_kernel_name_follows_the_librarys_routing():
         name(mode, **kw)
         seen.add(route(mode, **kw))
     assert seen == set(range(_lib.CL_ROUTE_MLP_CHAIN_DET + 1)) - {_lib.CL_ROUTE_MLP_PACKED_DET, _lib.CL_ROUTE_MLP_CHAIN_DET}   # (two flags each: above)
+
+
+def test_lane_instance_table_matches_the_record():
+    """Which instance the lane kernel's launch layer selects, as data: `scripts/lane_table.py` walks widths, columns and depths on both sides
+    of every threshold that layer tests, in every layout, with every optional buffer that picks another form, and the two launches of a
+    layer block (31 416 launches), and asks the library for route and name.  tests/golden/lane_instances.json is that record taken on
+    the library BEFORE the launch layer was rewritten: every entry equals it.  The one exception are the names of the block launches
+    (CL_ROUTE_LANE_BLOCK), which until then carried the label of a chain instance that does not run: their route is the record's, their
+    name follows the rule the launch layer implements -- the record holds the names since, so that a later change shows.  Host only."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("lane_table", os.path.join(ROOT, "scripts", "lane_table.py"))
+    lane_table = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lane_table)
+    assert not [k for k in os.environ if k.startswith(lane_table.SWITCHES)]
+    with open(os.path.join(ROOT, "tests", "golden", "lane_instances.json")) as f:
+        want = lane_table.decode(json.load(f))
+    got = lane_table.table(_lib.get_lib())
+    assert len(got) == len(want) == 31416
+    differ = [(mode, kw, g, w_) for (mode, kw), g, w_ in zip(lane_table.walk(), got, want) if g != w_]
+    assert not differ, (len(differ), differ[:5])
+    blocks = 0
+    for (mode, kw), (route, name) in zip(lane_table.walk(), got):
+        if route != _lib.CL_ROUTE_LANE_BLOCK:
+            continue
+        blocks += 1
+        W = 8 if kw["w"] <= 8 else (10 if kw["w"] <= 10 else 12)
+        D = 8 if kw["L"] == 20 and kw["d"] <= 8 else 15
+        assert name == f"elbo_lane_kernel<{W}, {D}, false, false, false, 0, {kw['L']}, {mode}>", (mode, kw, name)
+    assert blocks > 0
 
 
 def test_one_argument_check_answers_for_every_route():
