@@ -492,7 +492,13 @@ size_t cl_frozen_args_size(void);                  /* sizeof(cl_frozen_args) as 
 
 /* --- gradient norm, sanitise, clip, Adam -------------------------------------------------------------------------
  * replaces: tf.linalg.global_norm, tf.where(is_finite), optimizer.apply_gradients (variational.py:202-209)
- *           tfk.optimizers.Adam(lr, b1, b2, clipnorm, clipvalue, global_clipnorm) (careless/io/manager.py:494-501) */
+ *           tfk.optimizers.Adam(lr, b1, b2, clipnorm, clipvalue, global_clipnorm) (careless/io/manager.py:494-501)
+ * Order inside cl_adam_step, per element: non-finite g -> 0 FIRST; then clipnorm (g c / |tensor| only where |tensor| > c, |tensor| =
+ * sqrt(seg_sq[tensor])); then global_clipnorm (g c / max(|g|, c), |g| = sqrt(scalars[CL_SC_GNORM2_SANE])); then clipvalue; then
+ * m += (g - m)(1 - beta1), v += (g^2 - v)(1 - beta2), p -= m alpha / (sqrt v + adam_eps) with the NEW m and v.  The call accepts any
+ * combination of the three modes and applies them in that order (the engine passes one: tf_keras uses the first active mode only).
+ * Nothing but p / m / v of the elements inside the ranges whose tensor is not frozen, and the norm outputs, is written; g is read only.
+ * A raised stop flag: no call of this block except cl_step_finalize writes anything. */
 typedef struct cl_adam_args {
     float* p; const float* g; float* m; float* v;   /* [n] each */
     int n;
@@ -519,7 +525,13 @@ typedef struct cl_adam_args {
 } cl_adam_args;
 
 /* frozen (optional [nseg], as cl_adam_args.frozen): tensors that are not trainable stay out of the norm -- the reference takes
- * tf.linalg.global_norm of tape.gradient(loss, self.trainable_variables) (variational.py:201-205); cl_adam_step's fused norm does the same */
+ * tf.linalg.global_norm of tape.gradient(loss, self.trainable_variables) (variational.py:201-205); cl_adam_step's fused norm does the same.
+ * cl_grad_sqnorm ADDS to what is there (the caller zeroes per step): the raw sum of squares to scalars[CL_SC_GNORM2] (a NaN / inf
+ * gradient gives a NaN / inf norm), the sum over the finite elements to scalars[CL_SC_GNORM2_SANE] and, per tensor, to seg_sq
+ * (optional [nseg]); seg_sq of a frozen tensor is not touched.  scalars[CL_SC_NLL / _KL] are not touched.
+ * cl_adam_step's fused norm: the same two sums over the elements it updates in the ranges >= norm_skip_ranges, plus norm_extra ONCE,
+ * either ADDED to norm_out[CL_SC_GNORM2 / _SANE] (atomics) or, with norm_part, stored per workgroup -- all 2 * cl_adam_grid(args)
+ * slots are written and norm_out is then only the switch: it is not written. */
 int cl_grad_sqnorm(const float* g, int n, const int* seg_off, int nseg, double* seg_sq, double* scalars,
                    const unsigned char* frozen, const int* stop_flag, void* stream);
 int cl_adam_step(const cl_adam_args* args, void* stream);
@@ -527,11 +539,15 @@ int cl_adam_step(const cl_adam_args* args, void* stream);
  * part of the surrogate-posterior gradient -- g[r_begin .. r_end) (d a) and g[R + r_begin .. R + r_end) (d b) -- as four floats the
  * step's all-reduce sums over the ranks next to the replicated tail: out[0] = raw (NaN / inf propagate, variational.py:205),
  * out[1] = sanitised (what the optimizer's clipping sees, :208), out[2] / out[3] = sanitised, per tensor (clipnorm).  Accumulated in
- * double in scratch[0..3] (scratch[4] is the block ticket; the caller zeroes all five per step).                               */
+ * double in scratch[0..3] (scratch[4] is the block ticket; the caller zeroes all five per step): afterwards scratch[0] = raw,
+ * scratch[2] / [3] = sanitised per tensor, scratch[1] = scratch[2] + scratch[3], the ticket's low word = the number of workgroups;
+ * out[k] = (float)scratch[k].                                                                                                  */
 int cl_owner_qnorm(const float* g, int R, int r_begin, int r_end, float* out, double* scratch, const int* stop_flag, void* stream);
 /* history[step_index] = {loss, F KLDiv, NLL, Grad Norm, skipped}; sets *stop_flag when the norm is not finite
  * (careless/models/merging/variational.py:262-274).  norm_part (optional, n_norm_part workgroups' pairs left by cl_adam_step) is added,
- * in index order, to scalars[CL_SC_GNORM2 / _SANE] first. */
+ * in index order, to scalars[CL_SC_GNORM2 / _SANE] first.  Of history only the five doubles of record step_index are written (the three
+ * spare ones are not); a non-finite norm still writes the record.  With *stop_flag already set the record is {0, 0, 0, 0, 1} and
+ * scalars are left alone. */
 int cl_step_finalize(double* scalars, float kl_weight_or_one, double* history, int step_index, int* stop_flag,
                      const double* norm_part, int n_norm_part, void* stream);
 /* workgroups cl_adam_step launches for these arguments (the length / 2 of norm_part) */
