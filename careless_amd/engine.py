@@ -394,8 +394,6 @@ class ElboEngine(WidePath):
         self._frozen_epoch = 0
         self.scaler_frozen = False
         self.obs = self._build_obs(inputs, self.shard.start, self.shard.stop, grid, self.laue_groups, rows=self.shard.rows if self.owner else None)
-        if self.blocks is not None:
-            self.obs.alloc_chain(self.lib, self.blocks, self.w, dev, self.chain_lane)
         RS = self.R * self.S
         o_dz = 0
         # the buffer a step all-reduces starts on a 16-byte boundary: the flat gradient (row split), or -- reflection-owner split -- what
@@ -442,25 +440,22 @@ class ElboEngine(WidePath):
         per = launch_row_limit(self.d, self.S if self.deterministic else 0)
         if rows is not None:
             start, stop = 0, len(rows)
-        if self.laue or self.imgl is not None or self.wide or stop - start <= per:
-            o = ObsData(self.lib, inputs, start, stop, self.S, self.layout.P, self.device, rows=rows, **kw)
-            o.host_inputs = inputs
-            if self.deterministic:
-                self._det_attach(o, [o])
-            return o
+        whole = self.laue or self.imgl is not None or self.wide or stop - start <= per
+        bounds = [(start, stop)] if whole else [(a, min(stop, a + per)) for a in range(start, stop, per)]
         pieces = []
-        for a in range(start, stop, per):
-            b = min(stop, a + per)
-            pieces.append(ObsData(self.lib, inputs, a, b, self.S, self.layout.P, self.device, rows=None if rows is None else rows[a:b], **kw))
-            pieces[-1].host_inputs = inputs
+        for a, b in bounds:
+            pieces.append(ObsData(self.lib, inputs, a, b, self.S, self.layout.P, self.device, rows=None if rows is None else rows[a:b], host_inputs=inputs, **kw))
             kw["n_refl"] = kw["n_images"] = None          # (the id ranges were checked over the whole input by the first piece)
-            if len(pieces) > 1:
-                pieces[-1].partials = pieces[0].partials  # launches are serialised on one stream: one partial buffer
-        o = ObsChunks(pieces)
-        if rows is not None:
-            o.rows = np.asarray(rows, dtype=np.int64)
+            pieces[-1].partials = pieces[0].partials      # launches are serialised on one stream: one partial buffer
+        o = pieces[0]
+        if len(pieces) > 1:
+            o = ObsChunks(pieces)
+            if rows is not None:
+                o.rows = np.asarray(rows, dtype=np.int64)
         if self.deterministic:
             self._det_attach(o, pieces)
+        if self.blocks is not None:
+            o.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         return o
 
     def _det_attach(self, obs, pieces):
@@ -535,8 +530,6 @@ class ElboEngine(WidePath):
             first = self.obs.children[0] if isinstance(self.obs, ObsChunks) else self.obs
             self.obs = self._build_obs(first.host_inputs, self.shard.start, self.shard.stop, self._grid_arg, self.laue_groups,
                                        rows=self.shard.rows if self.owner else None)
-            if self.blocks is not None:
-                self.obs.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         opt = m.optimizer
         self.opt = opt
         S, N, R = self.S, self.N_total, self.R
@@ -1099,8 +1092,6 @@ class ElboEngine(WidePath):
         o = self._build_obs(inputs, 0, None, None, None, rows=rows)
         if o.d != self.d:
             raise ValueError("validation metadata width differs from the training data")
-        if self.blocks is not None:
-            o.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         return o
 
     def _laue_passes(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):

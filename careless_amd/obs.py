@@ -1,6 +1,7 @@
 """Device images of observation sets and the data-parallel splits of the observation axis (host side, numpy + torch tensors):
 `Shard` / `make_shard` / `owner_shard` / `laue_group_shard` (who takes which rows), `pack_by_image` / `pack_laue` (the packed orders
-of the per-image-layer and single-pass Laue kernels), `ObsData` (one launch's arrays in HBM), `ObsChunks` (a shard cut into several
+of the per-image-layer and single-pass Laue kernels), `select_rows` -> `lay_out` (`layout_plain` / `_by_image` / `_laue` / `_wide` fill
+a host `Layout`) -> `ObsData` (one launch's arrays in HBM: selection, layout, upload), `ObsChunks` (a shard cut into several
 launches), `launch_row_limit`.  Split out of careless_amd/engine.py in round 4; the engine re-exports every name.
 
 What the arrays replace in the reference: the `inputs` tuple of `BaseModel.input_index` order (careless/models/base.py:22-121) as
@@ -9,7 +10,7 @@ What the arrays replace in the reference: the `inputs` tuple of `BaseModel.input
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -196,6 +197,201 @@ class _ShardRows:
         return np.asarray(self.a[sl], dtype=np.float32)
 
 
+class Selection(NamedTuple):
+    """What `select_rows` answers: which rows of the caller's arrays a launch holds, and their small columns."""
+    sl: object                          # the rows inside the caller's arrays: a slice or an int64 index array
+    rows: Optional[np.ndarray]          # their global row numbers when they are not a contiguous range (ascending), else None
+    start: int
+    N: int
+    N_total: int
+    refl_id: np.ndarray                 # int32 [N]
+    image_id: np.ndarray                # int32 [N]
+    metadata: _ShardRows                # metadata[sl] -> float32 [N][d], converted on demand
+    iobs: np.ndarray                    # fp32 per slot (mono: a row is its own slot; a group shard: its groups, then its share of the padded slots)
+    sig: np.ndarray
+    harmonic_id: Optional[np.ndarray]   # int64 [N], local to the shard (its first group is 0); None: monochromatic data
+
+
+def select_rows(inputs, start, stop, laue_groups=None, rows=None, n_refl=None, n_images=None) -> Selection:
+    """Row selection: a contiguous range, the explicit row list of a reflection-owner shard, or the harmonic groups
+    `laue_groups = (g0, g1, pad0, pad1)` of `laue_group_shard`.  Every range check of the inputs is made here, before anything indexes
+    with an id.  Views of the caller's arrays (possibly memory-mapped files shared by the ranks of a node): only this shard's rows are
+    ever copied / converted -- a rank of an 8-GPU job does not hold eight copies' worth of the 50 M-observation problem."""
+    refl_all = _np(BaseModel.get_refl_id(inputs)).reshape(-1)
+    image_all = _np(BaseModel.get_image_id(inputs)).reshape(-1)
+    meta_all = _np(BaseModel.get_metadata(inputs))
+    meta_all = meta_all.reshape(len(refl_all), -1)
+    iobs_all = _np(BaseModel.get_intensities(inputs)).reshape(-1)
+    sig_all = _np(BaseModel.get_uncertainties(inputs)).reshape(-1)
+    n_total = int(len(refl_all))
+    laue = BaseModel.is_laue(inputs)
+    hid_all = _np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64) if laue else None
+    g0 = 0
+    if laue and laue_groups is not None:
+        g0, g1, pad0, pad1 = laue_groups
+        rows = np.nonzero((hid_all >= g0) & (hid_all < g1))[0]
+        # per-slot arrays of this shard: its own groups first, then its share of the padded slots (formatter.py:637-640)
+        slots = np.concatenate([np.arange(g0, g1), np.arange(pad0, pad1)])
+        assert len(slots) == len(rows)
+    elif rows is not None:
+        # monochromatic rows that are not a contiguous range (reflection-owner shard): stored in ascending row order; the global
+        # row numbers key the in-kernel noise (noise_row) and pick the columns of injected noise
+        if laue:
+            raise ValueError("explicit rows are for monochromatic data (Laue shards go by harmonic group)")
+        rows = np.asarray(rows, dtype=np.int64)
+        slots = rows
+    else:
+        slots = slice(start, n_total if stop is None else stop)
+    if rows is not None:
+        sl, start, n = rows, 0, len(rows)
+    else:
+        sl, n = slots, slots.stop - start
+    iobs, sig = iobs_all[slots].astype(np.float32), sig_all[slots].astype(np.float32)
+    if n <= 0:
+        raise ValueError("empty observation shard")
+    if n_refl is not None and refl_all.size and (refl_all.min() < 0 or refl_all.max() >= n_refl):
+        raise ValueError("refl_id outside the range of the surrogate posterior")
+    if n_images is not None and image_all.size and image_all.max() >= n_images:
+        raise ValueError("image_id exceeds ImageScaler.max_images")
+    if laue and hid_all.size and (hid_all.min() < 0 or hid_all.max() >= n_total):
+        raise ValueError("harmonic_id outside [0, N)")
+    return Selection(sl, rows, int(start), int(n), n_total, refl_all[sl].astype(np.int32), image_all[sl].astype(np.int32),
+                     _ShardRows(meta_all, sl), iobs, sig, hid_all[sl] - g0 if laue else None)
+
+
+@dataclass
+class Layout:
+    """What the layout step answers: the host image of one launch's arrays in the order the kernels read them (numpy arrays and scalars; `ObsData` uploads
+    it and lets it go).  None: the layout has no such array."""
+    n_pad: int
+    meta_t: np.ndarray                         # fp32 [meta_rows][n_pad], feature-major ((4, 4) of zeros in the wide layout)
+    refl_id: np.ndarray                        # int32; padding -1
+    image_id: np.ndarray                       # int32; padding 0
+    iobs: np.ndarray                           # fp32 per stored row (packed mono / single-pass Laue; padding 0) or per slot
+    sig: np.ndarray                            # ... padding 1
+    rows: Optional[np.ndarray] = None          # int64: global row of every stored row when that is not start + its position
+    row_index: Optional[np.ndarray] = None     # ... the copy the slot kernels and the wide path read on the device
+    harmonic_id: Optional[np.ndarray] = None   # int32 per stored row: the slot kernels' group ids (two-pass Laue, wide Laue)
+    row_map: Optional[np.ndarray] = None       # int32 [n_pad]: the caller's local row of a packed position, -1 on padding
+    tile_img: Optional[np.ndarray] = None      # int32 per tile: its image (by image)
+    gmeta: Optional[np.ndarray] = None         # int32 [n_pad]: member | size << 8 (single-pass Laue)
+    tile_gmax: Optional[np.ndarray] = None     # int32 per tile: its largest group
+    noise_row: Optional[np.ndarray] = None     # int32 [n_pad]: the global row that keys the in-kernel noise
+    pad_iobs: Optional[np.ndarray] = None      # fp32: the padded slots' own arrays (single-pass Laue)
+    pad_sig: Optional[np.ndarray] = None
+    pad_uniform: bool = False
+    fused_laue: bool = False
+    meta_rm: Optional[np.ndarray] = None       # fp32 [N][meta_ld], row-major (wide)
+    meta_ld: int = 0
+    perm: Optional[np.ndarray] = None          # int64: stored position -> the caller's local row (wide, sorted by image)
+    img_seg: Optional[np.ndarray] = None       # int64 [n_images + 1]: first stored row of every image
+
+    ARRAYS = ("meta_t", "refl_id", "image_id", "iobs", "sig", "row_index", "harmonic_id", "row_map", "tile_img", "gmeta", "tile_gmax",
+              "noise_row", "pad_iobs", "pad_sig", "meta_rm")          # what lives on the device; rows / perm / img_seg stay on the host
+
+
+def _tiles(n: int) -> int:
+    return ((n + TILE - 1) // TILE) * TILE
+
+
+def _scatter(v: np.ndarray, pos, n_pad: int, fill) -> np.ndarray:
+    """`v` at the positions `pos` of an array of n_pad entries, `fill` elsewhere"""
+    out = np.full(n_pad, fill, dtype=v.dtype)
+    out[pos] = v
+    return out
+
+
+def _meta_t(s: Selection, meta_rows: int, n_pad: int, pos) -> np.ndarray:
+    """The feature-major metadata image, written once: rows d .. meta_rows - 1 and the padding columns are zero."""
+    d = s.metadata.shape[1]
+    meta_t = np.zeros((meta_rows, n_pad), dtype=np.float32)
+    meta_t[:d, pos] = s.metadata[s.sl].T
+    return meta_t
+
+
+def _slot_ids(s: Selection) -> dict:
+    """What the slot kernels of the two-pass Laue path read per row: the group id and -- a shard of groups -- the global row."""
+    if s.harmonic_id is None:
+        return {}
+    return dict(harmonic_id=s.harmonic_id.astype(np.int32), row_index=s.rows)
+
+
+def layout_plain(s: Selection, meta_rows: int) -> Layout:
+    """Rows in the caller's order, padded to whole tiles at the end."""
+    n_pad = _tiles(s.N)
+    noise_row = None
+    if s.rows is not None and s.harmonic_id is None:      # (every plain-layout kernel reads the per-row noise key when it is given)
+        noise_row = _scatter(s.rows.astype(np.int32), slice(0, s.N), n_pad, 0)
+    return Layout(n_pad, _meta_t(s, meta_rows, n_pad, slice(0, s.N)), s.refl_id, s.image_id, s.iobs, s.sig, rows=s.rows, noise_row=noise_row,
+                  **_slot_ids(s))
+
+
+def layout_by_image(s: Selection, meta_rows: int) -> Layout:
+    """Per-image layers: rows grouped by image, every image padded to whole tiles (`pack_by_image`)."""
+    pos, n_pad, tile_img, row_map = pack_by_image(s.image_id)
+    meta_t = _meta_t(s, meta_rows, n_pad, pos)
+    rid, img, iobs, sig = s.refl_id, s.image_id, s.iobs, s.sig
+    if s.harmonic_id is None:           # the mono likelihood runs inside the fused kernel: its inputs are packed too
+        rid, img = _scatter(rid, pos, n_pad, -1), _scatter(img, pos, n_pad, 0)
+        iobs, sig = _scatter(iobs, pos, n_pad, 0.0), _scatter(sig, pos, n_pad, 1.0)
+    return Layout(n_pad, meta_t, rid, img, iobs, sig, rows=s.rows, row_map=row_map, tile_img=tile_img, **_slot_ids(s))
+
+
+def layout_laue(s: Selection, meta_rows: int, lp) -> Layout:
+    """Single-pass Laue (`lp`: what `pack_laue` answered): everything the fused kernel streams is packed so that a harmonic group sits
+    in one wave; the group's observed intensity is replicated on its member rows; the padded slots keep their own small arrays."""
+    pos, n_pad, gmeta, tile_gmax, row_map, tile_img = lp
+    hid = s.harmonic_id
+    G = int(hid.max()) + 1
+    # the formatter pads every empty slot with the same (1.0, 1.0) (reference io/formatter.py:637-640): their terms are one term times
+    # their number -- the engine then launches the slot kernel on ONE slot with the weight multiplied (round 5: 29 us per step at 5 M rows)
+    pi, ps = s.iobs[G:], s.sig[G:]
+    return Layout(n_pad, _meta_t(s, meta_rows, n_pad, pos), _scatter(s.refl_id, pos, n_pad, -1), _scatter(s.image_id, pos, n_pad, 0),
+                  _scatter(s.iobs[hid], pos, n_pad, 0.0), _scatter(s.sig[hid], pos, n_pad, 1.0), rows=s.rows, row_index=s.rows,
+                  row_map=row_map, tile_img=tile_img, gmeta=gmeta, tile_gmax=tile_gmax,
+                  # a shard of whole harmonic groups: rows are not a contiguous range
+                  noise_row=_scatter(s.rows.astype(np.int32), pos, n_pad, 0) if s.rows is not None else None,
+                  pad_iobs=pi, pad_sig=ps, pad_uniform=bool(len(pi) > 1 and np.all(pi == pi[0]) and np.all(ps == ps[0])), fused_laue=True)
+
+
+def layout_wide(s: Selection, meta_ld: int, sort_images: bool = False, n_images=None) -> Layout:
+    """Scaler wider than the fused kernel holds: layer-by-layer GEMMs on the row-major metadata [rows][ld] (the features, zero padding
+    to a multiple of four; ElboEngine._data_term_wide).  Monochromatic rows are their own "harmonic group" (harmonic_id NULL): the slot
+    kernels then ARE the mono likelihood."""
+    d = s.metadata.shape[1]
+    rm = np.zeros((s.N, meta_ld), dtype=np.float32)
+    rm[:, :d] = s.metadata[s.sl]
+    lay = Layout(_tiles(s.N), np.zeros((4, 4), dtype=np.float32), s.refl_id, s.image_id, s.iobs, s.sig, rows=s.rows, meta_rm=rm, meta_ld=meta_ld,
+                 **_slot_ids(s))
+    if sort_images:
+        # per-image layers on this path: the rows of an image must be consecutive (grouped GEMM kernels); everything per row
+        # is stored in image order, `perm` maps the local order back to the caller's
+        perm = lay.perm = np.argsort(s.image_id, kind="stable")
+        lay.refl_id, lay.image_id, lay.meta_rm = s.refl_id[perm], s.image_id[perm], rm[perm]
+        if s.harmonic_id is None:                   # (mono: a row is its own slot; Laue keeps iobs / sig per slot)
+            lay.iobs, lay.sig = s.iobs[perm], s.sig[perm]
+        else:
+            lay.harmonic_id = lay.harmonic_id[perm]
+        lay.img_seg = np.concatenate([[0], np.cumsum(np.bincount(lay.image_id, minlength=int(n_images or (lay.image_id.max() + 1))))]).astype(np.int64)
+        # global rows in the stored (image) order: the noise key of every row, and which columns of an injected eta are its
+        lay.rows = lay.row_index = (s.rows if s.rows is not None else np.arange(s.start, s.start + s.N))[perm]
+    return lay
+
+
+def lay_out(s: Selection, size, pack_images=False, laue_single_pass=True, wide=False, sort_images=False, n_images=None) -> Layout:
+    """The precedence between the four layouts: single-pass Laue when it is asked for and every harmonic group fits a wave (`pack_laue`
+    answers None when one does not: those data take the two-pass path on one of the other layouts), else by image, else wide, else plain.
+    `size(name)`: the library's `cl_mlp_meta_rows` / `cl_wide_ld` of this metadata width; the layout chosen asks for the one it needs."""
+    lp = pack_laue(s.harmonic_id, s.image_id, by_image=pack_images) if (s.harmonic_id is not None and laue_single_pass) else None
+    if lp is not None:
+        return layout_laue(s, size("cl_mlp_meta_rows"), lp)
+    if pack_images:
+        return layout_by_image(s, size("cl_mlp_meta_rows"))
+    if wide:
+        return layout_wide(s, size("cl_wide_ld"), sort_images, n_images)
+    return layout_plain(s, size("cl_mlp_meta_rows"))
+
+
 class ObsData:
     """refl_id / image_id int32 [N], meta_t fp32 [rows][n_pad], iobs / sig fp32 [N], optional harmonic_id + Laue work
     buffers, and the per-launch workspace of the fused kernel (grid, gradient partials).  With `pack_images` (per-image
@@ -203,22 +399,34 @@ class ObsData:
 
     def __init__(self, lib, inputs, start: int, stop: int, S: int, P: int, device, grid=None, n_refl=None, n_images=None,
                  laue_groups=None, pack_images: bool = False, laue_single_pass: bool = True, wide: bool = False, sort_images: bool = False,
-                 rows: Optional[np.ndarray] = None):
-        # Views of the caller's arrays (possibly memory-mapped files shared by the ranks of a node): only this shard's rows are
-        # ever copied / converted -- a rank of an 8-GPU job does not hold eight copies' worth of the 50 M-observation problem
-        refl_all = _np(BaseModel.get_refl_id(inputs)).reshape(-1)
-        image_all = _np(BaseModel.get_image_id(inputs)).reshape(-1)
-        meta_all = _np(BaseModel.get_metadata(inputs))
-        meta_all = meta_all.reshape(len(refl_all), -1)
-        iobs_all = _np(BaseModel.get_intensities(inputs)).reshape(-1)
-        sig_all = _np(BaseModel.get_uncertainties(inputs)).reshape(-1)
-        self.N_total = int(len(refl_all))
-        stop = self.N_total if stop is None else stop
-        self.laue = BaseModel.is_laue(inputs)
-        self.rows = None                      # explicit row list when the shard is not a contiguous range
+                 rows: Optional[np.ndarray] = None, host_inputs=None):
+        # 1. the library's answers for this metadata width, asked when a step needs one (a launch trace shows the queries too)
+        size = lambda name: int(getattr(lib, name)(self.d))
+        # 2. which rows
+        s = select_rows(inputs, start, stop, laue_groups, rows, n_refl, n_images)
+        self.start, self.N, self.N_total, self.d = s.start, s.N, s.N_total, int(s.metadata.shape[1])
+        self.laue = s.harmonic_id is not None
         self.empty = False
+        # 3. in which order
+        lay = lay_out(s, size, pack_images, laue_single_pass, wide, sort_images, n_images)
+        # 4. onto the device (rows: the explicit row list when the stored rows are not a contiguous range; perm, img_seg: the wide path's image order)
+        self.n_pad, self.pad_uniform, self.fused_laue, self.meta_ld = lay.n_pad, lay.pad_uniform, lay.fused_laue, lay.meta_ld
+        self.rows, self.perm, self.img_seg = lay.rows, lay.perm, lay.img_seg
+        for name in Layout.ARRAYS:
+            v = getattr(lay, name)
+            setattr(self, name, None if v is None else torch.as_tensor(np.ascontiguousarray(v), device=device))
+        # 5. work buffers: the slot kernels' (two-pass Laue, wide), the padded slots', the fused kernel's gradient partials
+        slots = wide or (self.laue and not self.fused_laue)
+        self.laue_loc = torch.empty(self.N, dtype=torch.float32, device=device) if slots else None
+        self.laue_sig = torch.empty(self.N, dtype=torch.float32, device=device) if slots else None
+        self.laue_iconv = torch.empty(self.N * S, dtype=torch.float32, device=device) if slots else None
+        self.laue_dO = torch.empty(self.N * 2, dtype=torch.float32, device=device) if slots else None
+        self.pad_iconv = torch.zeros(max(1, len(lay.pad_iobs) * S), dtype=torch.float32, device=device) if self.fused_laue else None
+        g = int(grid) if grid is not None else max(1, int(lib.cl_mlp_default_grid()))
+        self.grid = min(g, self.n_pad // TILE)
+        self.partials = torch.empty(0 if wide else self.grid * P, dtype=torch.float32, device=device)
         # what the engine attaches later (careless_amd/engine.py, wide.py); None / 0 / False until then
-        self.host_inputs = None               # the caller's inputs (a reference: the frozen-scaler path reads the rows' metadata once per training)
+        self.host_inputs = host_inputs        # the caller's inputs (a reference: the frozen-scaler path reads the rows' metadata once per training)
         self.row0, self.is_piece = 0, False   # piece of a chunked shard (`ObsChunks`): its first row inside the shard's eta / ipred arrays
         self.det = self.det_parent = None     # deterministic mode: the shard's buffers (on the set `cl_det_reduce` runs on), the set a piece stores into
         self.det_index = 0                    # ... and the piece's part of its NLL / Evans-2011 slots
@@ -226,152 +434,6 @@ class ObsData:
         self.frozen_sorted = self.locsig_epoch = None         # frozen scaler: the per-training row arrays, the `train_model` call (loc, sigma) are of
         self.chain_act = self.chain_dact = self.chain_dz0 = None      # chained scaler: activations / their gradients at the block boundaries, dZ_0 of a lane-kernel last block
         self.wide_chunks = self.wide_tiles = self.wide_full = self.wide_dsd = None     # layer-by-layer path: row chunks, tile lists, kept activations, d sigma / d raw
-        self.harmonic_id = self.laue_loc = self.laue_sig = self.laue_iconv = self.laue_dO = None      # slot kernels' inputs and work buffers
-        self.pad_iobs = self.pad_sig = self.pad_iconv = None          # single-pass Laue: the padded slots' own arrays
-        self.pad_uniform = False
-        self.perm = self.img_seg = self.meta_rm = None                # layer-by-layer path: image order of the rows, row-major metadata [rows][meta_ld]
-        self.meta_ld = 0
-        if self.laue and laue_groups is not None:
-            hid_all = _np(BaseModel.get_harmonic_id(inputs)).reshape(-1)
-            g0, g1, pad0, pad1 = laue_groups
-            self.rows = np.nonzero((hid_all >= g0) & (hid_all < g1))[0]
-            sl = self.rows
-            start, stop = 0, len(self.rows)
-            # per-slot arrays of this shard: its own groups first, then its share of the padded slots (formatter.py:637-640)
-            slot_idx = np.concatenate([np.arange(g0, g1), np.arange(pad0, pad1)])
-            assert len(slot_idx) == len(self.rows)
-            iobs_l, sig_l = iobs_all[slot_idx].astype(np.float32), sig_all[slot_idx].astype(np.float32)
-        elif rows is not None:
-            # monochromatic rows that are not a contiguous range (reflection-owner shard): stored in ascending row order; the global
-            # row numbers key the in-kernel noise (noise_row) and pick the columns of injected noise
-            if self.laue:
-                raise ValueError("explicit rows are for monochromatic data (Laue shards go by harmonic group)")
-            self.rows = np.asarray(rows, dtype=np.int64)
-            sl = self.rows
-            start, stop = 0, len(self.rows)
-            iobs_l, sig_l = iobs_all[sl].astype(np.float32), sig_all[sl].astype(np.float32)
-        else:
-            sl = slice(start, stop)
-            iobs_l, sig_l = iobs_all[sl].astype(np.float32), sig_all[sl].astype(np.float32)
-        self.start, self.N = int(start), int(stop - start)
-        if self.N <= 0:
-            raise ValueError("empty observation shard")
-        if n_refl is not None and refl_all.size and (refl_all.min() < 0 or refl_all.max() >= n_refl):
-            raise ValueError("refl_id outside the range of the surrogate posterior")
-        if n_images is not None and image_all.size and image_all.max() >= n_images:
-            raise ValueError("image_id exceeds ImageScaler.max_images")
-        metadata = _ShardRows(meta_all, sl)       # metadata[sl] -> this shard's rows as float32
-        self.d = int(metadata.shape[1])
-        self.tile_img = self.row_map = self.gmeta = self.tile_gmax = self.noise_row = None
-        self.fused_laue = False
-        rid_l, img_l = refl_all[sl].astype(np.int32), image_all[sl].astype(np.int32)
-        lp = None
-        if self.laue:
-            hid_all0 = _np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64)
-            hl0 = hid_all0[sl] - (laue_groups[0] if (laue_groups is not None and self.rows is not None) else 0)
-            if laue_single_pass:
-                lp = pack_laue(hl0, img_l, by_image=pack_images)       # None: a group larger than a wave -> two-pass path
-        if lp is not None:
-            # single-pass Laue: everything the fused kernel streams is packed so that a harmonic group sits in one wave; the
-            # group's observed intensity is replicated on its member rows; the padded slots keep their own small arrays
-            pos, self.n_pad, gmeta, tile_gmax, row_map, tile_img = lp
-            G = int(hl0.max()) + 1
-            meta_t = np.zeros((int(lib.cl_mlp_meta_rows(self.d)), self.n_pad), dtype=np.float32)
-            meta_t[: self.d, pos] = metadata[sl].T
-
-            def packed(v, fill):
-                out = np.full(self.n_pad, fill, dtype=v.dtype)
-                out[pos] = v
-                return out
-            iobs_s, sig_s = np.asarray(iobs_l), np.asarray(sig_l)
-            self.pad_iobs = torch.as_tensor(np.ascontiguousarray(iobs_s[G:]), device=device)
-            self.pad_sig = torch.as_tensor(np.ascontiguousarray(sig_s[G:]), device=device)
-            self.pad_iconv = torch.zeros(max(1, (len(iobs_s) - G) * S), dtype=torch.float32, device=device)
-            # the formatter pads every empty slot with the same (1.0, 1.0) (reference io/formatter.py:637-640): their terms are one term times
-            # their number -- the engine then launches the slot kernel on ONE slot with the weight multiplied (round 5: 29 us per step at 5 M rows)
-            pi, ps = iobs_s[G:], sig_s[G:]
-            self.pad_uniform = bool(len(pi) > 1 and np.all(pi == pi[0]) and np.all(ps == ps[0]))
-            rid_l, img_l = packed(rid_l, -1), packed(img_l, 0)
-            iobs_l, sig_l = packed(iobs_s[hl0], 0.0), packed(sig_s[hl0], 1.0)
-            self.gmeta = torch.as_tensor(gmeta, device=device)
-            self.tile_gmax = torch.as_tensor(tile_gmax, device=device)
-            self.row_map = torch.as_tensor(row_map, device=device)
-            self.tile_img = torch.as_tensor(tile_img, device=device) if tile_img is not None else None
-            self.noise_row = None
-            if self.rows is not None:                 # a shard of whole harmonic groups: rows are not a contiguous range
-                nr = np.full(self.n_pad, 0, dtype=np.int32)
-                nr[pos] = self.rows.astype(np.int32)
-                self.noise_row = torch.as_tensor(nr, device=device)
-            self.fused_laue = True
-        elif pack_images:
-            pos, self.n_pad, tile_img, row_map = pack_by_image(img_l)
-            meta_t = np.zeros((int(lib.cl_mlp_meta_rows(self.d)), self.n_pad), dtype=np.float32)
-            meta_t[: self.d, pos] = metadata[sl].T
-            self.tile_img = torch.as_tensor(tile_img, device=device)
-            self.row_map = torch.as_tensor(row_map, device=device)
-            if not self.laue:           # the mono likelihood runs inside the fused kernel: its inputs are packed too
-                def packed(v, fill):
-                    out = np.full(self.n_pad, fill, dtype=v.dtype)
-                    out[pos] = v
-                    return out
-                rid_l, img_l = packed(rid_l, -1), packed(img_l, 0)
-                iobs_l, sig_l = packed(np.asarray(iobs_l), 0.0), packed(np.asarray(sig_l), 1.0)
-        elif wide:
-            # scaler wider than the fused kernel holds: layer-by-layer GEMMs on the row-major metadata (ElboEngine._data_term_wide)
-            self.n_pad = ((self.N + TILE - 1) // TILE) * TILE
-            meta_t = np.zeros((4, 4), dtype=np.float32)
-            self.meta_ld = int(lib.cl_wide_ld(self.d))                 # [rows][ld]: the features, zero padding to a multiple of four
-            rm = np.zeros((self.N, self.meta_ld), dtype=np.float32)
-            rm[:, : self.d] = metadata[sl]
-            if sort_images:
-                # per-image layers on this path: the rows of an image must be consecutive (grouped GEMM kernels); everything per row
-                # is stored in image order, `perm` maps the local order back to the caller's
-                self.perm = np.argsort(img_l, kind="stable")
-                rid_l, img_l, rm = rid_l[self.perm], img_l[self.perm], rm[self.perm]
-                if not self.laue:                       # (mono: a row is its own slot; Laue keeps iobs / sig per slot)
-                    iobs_l, sig_l = np.asarray(iobs_l)[self.perm], np.asarray(sig_l)[self.perm]
-                self.img_seg = np.concatenate([[0], np.cumsum(np.bincount(img_l, minlength=int(n_images or (img_l.max() + 1))))]).astype(np.int64)
-            self.meta_rm = torch.as_tensor(rm, device=device)
-        else:
-            self.n_pad = ((self.N + TILE - 1) // TILE) * TILE
-            meta_t = np.zeros((int(lib.cl_mlp_meta_rows(self.d)), self.n_pad), dtype=np.float32)
-            meta_t[: self.d, : self.N] = metadata[sl].T
-            if rows is not None:             # (every plain-layout kernel reads the per-row noise key when it is given)
-                nr = np.zeros(self.n_pad, dtype=np.int32)
-                nr[: self.N] = self.rows.astype(np.int32)
-                self.noise_row = torch.as_tensor(nr, device=device)
-        self.refl_id = torch.as_tensor(rid_l, device=device)
-        self.image_id = torch.as_tensor(img_l, device=device)
-        self.meta_t = torch.as_tensor(meta_t, device=device)
-        self.iobs = torch.as_tensor(np.ascontiguousarray(iobs_l), device=device)
-        self.sig = torch.as_tensor(np.ascontiguousarray(sig_l), device=device)
-        self.row_index = None
-        if self.laue:
-            hid = _np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64)
-            if hid.size and (hid.min() < 0 or hid.max() >= self.N_total):
-                raise ValueError("harmonic_id outside [0, N)")
-            hl = hid[sl]
-            if self.rows is not None:
-                hl = hl - laue_groups[0]
-                self.row_index = torch.as_tensor(self.rows.astype(np.int64), device=device)
-        if wide and not self.laue:
-            hl = None                          # every row its own "harmonic group" (harmonic_id NULL): the slot kernels then ARE the mono likelihood
-        elif wide and self.perm is not None:
-            hl = hl[self.perm]
-        if wide and self.perm is not None:
-            # global rows in the stored (image) order: the noise key of every row, and which columns of an injected eta are its
-            base_rows = self.rows if self.rows is not None else np.arange(self.start, self.start + self.N)
-            self.rows = np.asarray(base_rows)[self.perm]
-            self.row_index = torch.as_tensor(self.rows.astype(np.int64), device=device)
-        if (self.laue and not self.fused_laue) or wide:
-            self.harmonic_id = torch.as_tensor(hl.astype(np.int32), device=device) if hl is not None else None
-            self.laue_loc = torch.empty(self.N, dtype=torch.float32, device=device)
-            self.laue_sig = torch.empty(self.N, dtype=torch.float32, device=device)
-            self.laue_iconv = torch.empty(self.N * S, dtype=torch.float32, device=device)
-            self.laue_dO = torch.empty(self.N * 2, dtype=torch.float32, device=device)
-        g = int(grid) if grid is not None else max(1, int(lib.cl_mlp_default_grid()))
-        self.grid = min(g, self.n_pad // TILE)
-        self.partials = torch.empty(0 if wide else self.grid * P, dtype=torch.float32, device=device)
 
     def alloc_chain(self, lib, blocks, w, device, lane: bool = False):
         """Buffers of a chained scaler; `lane`: the last block runs on the lane kernel, which hands back dZ_0 of its first layer."""
