@@ -17,7 +17,9 @@ CL_HIST_STRIDE = 8
 CL_SC_NLL, CL_SC_KL, CL_SC_GNORM2, CL_SC_GNORM2_SANE, CL_SC_COUNT = 0, 1, 2, 3, 4
 CL_LIK_NORMAL, CL_LIK_STUDENTT = 0, 1
 CL_BIJ_EXP, CL_BIJ_SOFTPLUS = 0, 1
-CL_PRIOR_WILSON, CL_PRIOR_DOUBLE_WILSON = 0, 1
+CL_PRIOR_WILSON, CL_PRIOR_DOUBLE_WILSON, CL_PRIOR_REFERENCE = 0, 1, 2
+# cl_ref_prior: the base density of an empirical reference prior (include/careless_hip.h, cl_refprior_args.kind)
+CL_REFPRIOR_NORMAL, CL_REFPRIOR_LAPLACE, CL_REFPRIOR_STUDENTT, CL_REFPRIOR_RICE_WOOLFSON = range(4)
 CL_LAUE_LIK_MAX_BLOCKS = 2048
 CL_EV11_WAVES = 8               # wave slots per workgroup in ev11_part (include/careless_hip.h)
 # cl_mlp_route: the launcher a scaler launch goes to (include/careless_hip.h, enum cl_route)
@@ -131,6 +133,18 @@ class FrozenArgs(C.Structure):
     ]
 
 
+class RefPriorArgs(C.Structure):
+    """mirror of `cl_refprior_args` (include/careless_hip.h)"""
+    _fields_ = [
+        ("z_f", _vp), ("loc", _vp), ("scale", _vp), ("observed", _vp), ("centric", _vp),
+        ("kind", C.c_int), ("dof", C.c_float),
+        ("R", C.c_int), ("S", C.c_int),
+        ("w_kl", C.c_float), ("kl_grad_mult", C.c_float),
+        ("kl_begin", C.c_int), ("kl_end", C.c_int),
+        ("dz_f", _vp), ("kl_part", _vp), ("scalars", _vp), ("stop_flag", _vp),
+    ]
+
+
 class AdamArgs(C.Structure):
     """mirror of `cl_adam_args` (include/careless_hip.h)"""
     _fields_ = [
@@ -200,6 +214,8 @@ EXPORTS = {
     "cl_frozen_edge_floats": (C.c_int, [C.c_longlong, C.c_int]),
     "cl_frozen_grid": (C.c_int, [C.c_longlong]),
     "cl_frozen_args_size": (C.c_size_t, []),
+    "cl_ref_prior": (C.c_int, [C.POINTER(RefPriorArgs), _vp]),
+    "cl_refprior_args_size": (C.c_size_t, []),
     "cl_reduce_partials": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "cl_grad_sqnorm": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cl_adam_step": (C.c_int, [C.POINTER(AdamArgs), _vp]),
@@ -257,6 +273,8 @@ def get_lib() -> C.CDLL:
         raise CarelessHipError(f"ABI mismatch between careless_amd/_lib.py {mine} and the library {tuple(sizes)}")
     if int(lib.cl_frozen_args_size()) != C.sizeof(FrozenArgs):
         raise CarelessHipError(f"ABI mismatch: cl_frozen_args is {int(lib.cl_frozen_args_size())} bytes in the library, {C.sizeof(FrozenArgs)} in careless_amd/_lib.py")
+    if int(lib.cl_refprior_args_size()) != C.sizeof(RefPriorArgs):
+        raise CarelessHipError(f"ABI mismatch: cl_refprior_args is {int(lib.cl_refprior_args_size())} bytes in the library, {C.sizeof(RefPriorArgs)} in careless_amd/_lib.py")
     _lib = lib
     return lib
 

@@ -113,12 +113,12 @@ int cl_reduce_partials(const float* partials, int nparts, int P, float* grad_mlp
 }
 
 static int check_tn(const cl_tn_args* a) {
-    if (a == nullptr || a->q_loc_raw == nullptr || a->q_scale_raw == nullptr || a->low == nullptr ||
-        a->centric == nullptr || a->es == nullptr || a->R < 1 || a->S < 1)
-        return -1;
+    if (a == nullptr || a->q_loc_raw == nullptr || a->q_scale_raw == nullptr || a->low == nullptr || a->R < 1 || a->S < 1) return -1;
+    // (a reference prior's term is cl_ref_prior's: the Wilson arrays are not read)
+    if (a->prior_kind != CL_PRIOR_REFERENCE_ && (a->centric == nullptr || a->es == nullptr)) return -1;
     if (a->prior_kind == CL_PRIOR_DOUBLE_WILSON_ && (a->parent_ids == nullptr || a->root == nullptr)) return -1;
     if (a->prior_kind == CL_PRIOR_DOUBLE_WILSON_ && a->dw_r == nullptr && (a->dw_r_raw == nullptr || a->asu_ids == nullptr)) return -1;
-    if (a->prior_kind != CL_PRIOR_DOUBLE_WILSON_ && a->prior_kind != CL_PRIOR_WILSON_) return -1;
+    if (a->prior_kind != CL_PRIOR_DOUBLE_WILSON_ && a->prior_kind != CL_PRIOR_WILSON_ && a->prior_kind != CL_PRIOR_REFERENCE_) return -1;
     if (a->r_end > a->r_begin && (a->r_begin < 0 || a->r_end > a->R)) return -1;
     // an owned reflection range and the double-Wilson prior do not go together: a child's parent may belong to another rank
     if (a->r_end > a->r_begin && a->prior_kind == CL_PRIOR_DOUBLE_WILSON_) return -2;
@@ -149,6 +149,16 @@ int cl_dw_prior_forward(const cl_tn_args* a, void* stream) {
     if (a->dw_child_seg != nullptr && a->dw_r_raw != nullptr) return -2;          // deterministic mode: fixed r only
     return cl_launch_dw_forward(*a, (hipStream_t)stream);
 }
+
+int cl_ref_prior(const cl_refprior_args* a, void* stream) {
+    if (a == nullptr || a->z_f == nullptr || a->loc == nullptr || a->scale == nullptr || a->dz_f == nullptr || a->R < 1 || a->S < 1) return -1;
+    if (a->kind < CL_REFPRIOR_NORMAL || a->kind > CL_REFPRIOR_RICE_WOOLFSON) return -1;
+    if (a->kind == CL_REFPRIOR_STUDENTT && !(a->dof > 0.0f)) return -1;
+    if (a->kind == CL_REFPRIOR_RICE_WOOLFSON && a->centric == nullptr) return -1;
+    if (a->kl_part == nullptr && a->scalars == nullptr) return -1;
+    return cl_launch_ref_prior(*a, (hipStream_t)stream);
+}
+size_t cl_refprior_args_size(void) { return sizeof(cl_refprior_args); }
 
 int cl_grad_sqnorm(const float* g, int n, const int* seg_off, int nseg, double* seg_sq, double* scalars,
                    const unsigned char* frozen, const int* stop_flag, void* stream) {

@@ -48,6 +48,7 @@ int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* o
 int cl_launch_tn_forward(const cl_tn_args& a, hipStream_t st);
 int cl_launch_tn_backward(const cl_tn_args& a, hipStream_t st);
 int cl_launch_dw_forward(const cl_tn_args& a, hipStream_t st);
+int cl_launch_ref_prior(const cl_refprior_args& a, hipStream_t st);        // elbo_elem.hip: empirical reference priors
 int cl_launch_grad_sqnorm(const float* g, int n, const int* seg_off, int nseg, double* seg_sq, double* scalars,
                           const unsigned char* frozen, const int* stop_flag, hipStream_t st);
 int cl_launch_adam(const cl_adam_args& a, hipStream_t st);

@@ -10,6 +10,7 @@
 //   careless/models/priors/wilson.py:13-57                   Wilson prior
 //   careless/models/likelihoods/mono.py:10-37                Normal / Student-T likelihood
 //   careless/models/scaling/nn.py:10-25                      NormalLayer scale bijector
+//   careless/models/priors/empirical.py:45-131               base densities of the empirical reference priors
 #pragma once
 #include <stdint.h>
 #include <math.h>
@@ -37,7 +38,8 @@
 
 enum { CL_LIK_NORMAL = 0, CL_LIK_STUDENTT = 1 };
 enum { CL_BIJ_EXP = 0, CL_BIJ_SOFTPLUS = 1 };
-enum { CL_PRIOR_WILSON = 0, CL_PRIOR_DOUBLE_WILSON = 1 };
+enum { CL_PRIOR_WILSON = 0, CL_PRIOR_DOUBLE_WILSON = 1, CL_PRIOR_REFERENCE = 2 };
+enum { CL_REF_NORMAL = 0, CL_REF_LAPLACE = 1, CL_REF_STUDENTT = 2, CL_REF_RICE_WOOLFSON = 3 };
 
 // ---------------------------------------------------------------------------------------------------------
 // Philox4x32-10 counter-based generator (Salmon et al. 2011).  counter = (index lo, index hi | stream, sample, step)
@@ -386,6 +388,32 @@ CL_HD float cl_dw_log_prob(float z, float z_parent, bool has_parent, float r, bo
     *dzp = has_parent ? dloc * r : 0.0f;
     *dr = (has_parent ? dloc * z_parent : 0.0f) - dscale * c * r / scale;
     return lp;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Empirical reference priors (careless/models/priors/empirical.py:45-131): log-density of the base distribution at z and d/dz.
+//   Normal   tfd.Normal(Fobs, SigFobs)                  (empirical.py:83-85)    -- the likelihood's Normal, expression for expression
+//   Laplace  tfd.Laplace(Fobs, SigFobs / sqrt 2)        (empirical.py:62-64)    -- -|z - loc| / b - log(2 b); the derivative is
+//            -sign(z - loc) / b, 0 at z == loc (TensorFlow's gradient of abs is sign)
+//   StudentT tfd.StudentT(dof, Fobs, SigFobs)           (empirical.py:106-108)  -- the likelihood's Student-T; t_const as its lik_const
+//   RiceWoolfson(Fobs, SigFobs, centric)                (empirical.py:129-131)  -- tf.where(centric, woolfson, rice)
+//            (careless/models/merging/surrogate_posteriors.py:168-169)
+// A NaN parameter gives a NaN density and a NaN derivative (the non-finite step contract rests on it).
+// ---------------------------------------------------------------------------------------------------------
+CL_HD float cl_laplace_log_prob(float z, float loc, float b, float* dz) {
+    const float inv = 1.0f / b;
+    const float d = z - loc;
+    const float sgn = (d > 0.0f) ? 1.0f : ((d < 0.0f) ? -1.0f : d);      // sign(d): +-0 at the kink, NaN for NaN
+    *dz = -sgn * inv;
+    return -fabsf(d) * inv - logf(2.0f * b);
+}
+CL_HD float cl_ref_prior_log_prob(int kind, float z, float loc, float scale, bool centric, float dof, float t_const, float* dz) {
+    if (kind == CL_REF_NORMAL) return cl_lik_log_prob(z, loc, scale, CL_LIK_NORMAL, 0.0f, 0.0f, dz);
+    CL_KEEP_BRANCH();
+    if (kind == CL_REF_LAPLACE) return cl_laplace_log_prob(z, loc, scale, dz);
+    if (kind == CL_REF_STUDENTT) return cl_lik_log_prob(z, loc, scale, CL_LIK_STUDENTT, dof, t_const, dz);
+    float dloc, dscale;
+    return centric ? cl_folded_normal_log_prob(z, loc, scale, dz, &dloc, &dscale) : cl_rice_log_prob(z, loc, scale, dz, &dloc, &dscale);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -5,6 +5,8 @@
 //                         [surrogate_posteriors.py:50-53,104-131; variational.py:123-139,154,173; wilson.py:50-57]
 //   tn_backward_kernel    chain rule from dL/dz_f (data term, accumulated by the fused MLP kernel) plus the KL
 //                         term's own derivatives back to the raw q parameters (a = log loc, b = log(scale - eps))
+//   ref_prior_kernel      an empirical reference prior's -log p(z_f) into the KL and its z-derivative onto dL/dz_f, between the two
+//                         [priors/empirical.py:9-131; variational.py:123-139]
 //   grad_sqnorm_kernel    global (and per-tensor) squared L2 norm of the flat gradient   [variational.py:205]
 //   adam_kernel           non-finite -> 0, optional clipping, tf_keras Adam update       [variational.py:208-209, manager.py:494-501]
 //   finalize_kernel       per-step history record + the sticky stop flag               [variational.py:262-274]
@@ -81,8 +83,9 @@ __global__ __launch_bounds__(256) void tn_forward_kernel(const cl_tn_args A) {
             if (in_kl) {
                 float dlp;
                 const float lq = cl_tn_log_prob(t);
-                // non-root reflections of a double-Wilson model get their conditional prior in dw_forward_kernel (needs z_parent)
-                const float lp = dw_child ? 0.0f : prior_lp(A, h, t.z, &dlp);
+                // non-root reflections of a double-Wilson model get their conditional prior in dw_forward_kernel (needs z_parent), every
+                // reflection of a reference-prior model in ref_prior_kernel
+                const float lp = (dw_child || A.prior_kind == CL_PRIOR_REFERENCE_) ? 0.0f : prior_lp(A, h, t.z, &dlp);
                 kl += (double)(lq - lp);
             }
         }
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(256) void tn_backward_kernel(const cl_tn_args A) {
         const int nb = nb_tn;
         double t = 0.0;
         for (int i = threadIdx.x; i < nb; i += blockDim.x) t += A.kl_part[i];
-        if (A.kl_part_dw != nullptr && A.prior_kind == CL_PRIOR_DOUBLE_WILSON_)
+        if (A.kl_part_dw != nullptr && (A.prior_kind == CL_PRIOR_DOUBLE_WILSON_ || A.prior_kind == CL_PRIOR_REFERENCE_))
             for (int i = threadIdx.x; i < (A.R + 255) / 256; i += blockDim.x) t += A.kl_part_dw[i];
         __shared__ double sh[4];
         const double w = wave_sum_d(t);
@@ -139,6 +142,8 @@ __global__ __launch_bounds__(256) void tn_backward_kernel(const cl_tn_args A) {
             const float zp = (par >= 0) ? A.z_f[(size_t)par * A.S + s] : 0.0f;
             float dzp, dr;
             (void)cl_dw_log_prob(t.z, zp, par >= 0, dw_r_of(A, h), A.centric[h] != 0, A.es[h], &dp_dz, &dzp, &dr);
+        } else if (A.prior_kind == CL_PRIOR_REFERENCE_) {
+            dp_dz = 0.0f;               // (ref_prior_kernel has added the prior's z-derivative to dz_f)
         } else {
             (void)prior_lp(A, h, t.z, &dp_dz);
         }
@@ -198,6 +203,37 @@ __global__ __launch_bounds__(256) void dw_forward_kernel(const cl_tn_args A) {
         if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
         __syncthreads();
         if (threadIdx.x == 0) A.kl_part_dw[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    } else {
+        block_atomic_add_d(kl * (double)A.w_kl, A.scalars + CL_SC_KL);
+    }
+}
+
+// Empirical reference prior (include/careless_hip.h: cl_ref_prior): thread per reflection, loop over S, like dw_forward_kernel -- but the
+// density depends on the reflection's own sample only: the thread owns dz_f[h][.] (a plain read-modify-write, no atomic; the stream orders it
+// behind the data term).  t_const: the Student-t density's constant, from the launcher.
+__global__ __launch_bounds__(256) void ref_prior_kernel(const cl_refprior_args A, const float t_const) {
+    if (A.stop_flag != nullptr && *A.stop_flag != 0) return;
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    double kl = 0.0;
+    if (h < A.R && h >= A.kl_begin && h < A.kl_end && (A.observed == nullptr || A.observed[h] != 0)) {
+        const float loc = A.loc[h], scale = A.scale[h];
+        const bool c = (A.kind == CL_REFPRIOR_RICE_WOOLFSON) && A.centric[h] != 0;
+        const float wg = A.w_kl * A.kl_grad_mult;
+        for (int s = 0; s < A.S; ++s) {
+            const size_t i = (size_t)h * A.S + s;
+            float dz;
+            const float lp = cl_ref_prior_log_prob(A.kind, A.z_f[i], loc, scale, c, A.dof, t_const, &dz);
+            kl -= (double)lp;
+            A.dz_f[i] += -wg * dz;
+        }
+    }
+    if (A.kl_part != nullptr) {
+        // one store per workgroup, as tn_forward_kernel: the step's cl_tn_backward adds the parts up (no atomics, fixed order)
+        __shared__ double sh[4];
+        const double w = wave_sum_d(kl * (double)A.w_kl);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
+        __syncthreads();
+        if (threadIdx.x == 0) A.kl_part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
     } else {
         block_atomic_add_d(kl * (double)A.w_kl, A.scalars + CL_SC_KL);
     }
@@ -506,6 +542,15 @@ int cl_launch_dw_forward(const cl_tn_args& a, hipStream_t st) {
     hipLaunchKernelGGL(dw_forward_kernel, dim3((a.R + 255) / 256), dim3(256), 0, st, a);
     if (a.dw_child_seg != nullptr) hipLaunchKernelGGL(dw_parent_pull_kernel, dim3((a.R + 255) / 256), dim3(256), 0, st, a);
     return (int)hipGetLastError();
+}
+int cl_launch_ref_prior(const cl_refprior_args& a, hipStream_t st) {
+    if (a.R <= 0 || a.S <= 0) return -1;
+    float t_const = 0.0f;
+    if (a.kind == CL_REFPRIOR_STUDENTT) {       // lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2, as the likelihood's lik_const
+        const double nu = (double)a.dof;
+        t_const = (float)(lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.14159265358979323846));
+    }
+    return cl_launch_lds<ref_prior_kernel>(dim3((a.R + 255) / 256), dim3(256), 0, st, a, t_const);
 }
 int cl_launch_grad_sqnorm(const float* g, int n, const int* seg_off, int nseg, double* seg_sq, double* scalars,
                           const unsigned char* frozen, const int* stop_flag, hipStream_t st) {

@@ -5,7 +5,8 @@ What one step replaces in the reference: `train_step_with_gradient_norm` (carele
 = forward (`call`, :141-183), `tape.gradient`, `tf.linalg.global_norm`, non-finite sanitise, Adam.
 
 Step schedule (all on one HIP stream, no host synchronisation):
-    cl_tn_forward (clears the step's accumulators on its way) -> cl_elbo_mono_fwd_bwd -> cl_tn_backward (carries cl_reduce_partials)
+    cl_tn_forward (clears the step's accumulators on its way) -> cl_elbo_mono_fwd_bwd -> [cl_ref_prior: empirical reference priors]
+    -> cl_tn_backward (carries cl_reduce_partials)
     -> [cl_owner_qnorm + all-reduce, data-parallel only: the flat gradient (row split) or its tail + 4 norm terms (reflection-owner
     split)] -> [cl_grad_sqnorm: clip modes only] -> cl_adam_step -> cl_step_finalize
 
@@ -31,7 +32,7 @@ import numpy as np
 import torch
 
 from careless_amd import _lib
-from careless_amd._lib import AdamArgs, DetArgs, FrozenArgs, LaueArgs, MlpArgs, TnArgs, check, ptr
+from careless_amd._lib import AdamArgs, DetArgs, FrozenArgs, LaueArgs, MlpArgs, RefPriorArgs, TnArgs, check, ptr
 from careless_amd.models.base import BaseModel
 # (re-exported: the tests, bench.py and scripts import the sharding / layout names from here)
 from careless_amd.obs import (GRANULE, ObsChunks, ObsData, Shard, _EmptyObs, _ShardRows, _np, laue_group_shard, launch_row_limit,  # noqa: F401
@@ -39,6 +40,8 @@ from careless_amd.obs import (GRANULE, ObsChunks, ObsData, Shard, _EmptyObs, _Sh
 from careless_amd.wide import WidePath
 
 TILE = _lib.CL_MLP_TILE
+REFPRIOR_KINDS = {"normal": _lib.CL_REFPRIOR_NORMAL, "laplace": _lib.CL_REFPRIOR_LAPLACE, "studentt": _lib.CL_REFPRIOR_STUDENTT,
+                  "rice_woolfson": _lib.CL_REFPRIOR_RICE_WOOLFSON}       # ReferencePrior.engine_kind -> cl_refprior_args.kind
 HISTORY_KEYS = ("loss", "F KLDiv", "NLL", "Grad Norm")
 
 
@@ -209,6 +212,35 @@ def plan_scaler(lib, d: int, w: int, L: int, K: int = 0, laue: bool = False, two
     return ScalerPlan(False, peel, None, False, launches[-1] if two_pass else route(0, **train, **det))
 
 
+def prior_kind(prior, owner: bool = False) -> int:
+    """CL_PRIOR_* under which the engine runs `prior` (`owner`: on a reflection-owner split); NotImplementedError for what it does not
+    run.  Host logic: needs no device."""
+    from careless_amd.models.priors.empirical import ReferencePrior
+    from careless_amd.models.priors.wilson import DoubleWilsonPrior, WilsonPrior
+    if isinstance(prior, ReferencePrior):
+        if prior.base_dist is None or prior.engine_kind not in REFPRIOR_KINDS:
+            raise NotImplementedError(f"prior {type(prior).__name__} has no base distribution the HIP engine evaluates (use one of its subclasses: "
+                                      "Normal-, Laplace-, StudentT- or RiceWoolfsonReferencePrior)")
+        if owner:
+            raise NotImplementedError(f"the reflection-owner split runs the Wilson prior only, not {type(prior).__name__}: use the row split")
+        return _lib.CL_PRIOR_REFERENCE
+    if isinstance(prior, DoubleWilsonPrior):
+        return _lib.CL_PRIOR_DOUBLE_WILSON
+    if isinstance(prior, WilsonPrior):
+        return _lib.CL_PRIOR_WILSON
+    raise NotImplementedError(f"prior {type(prior).__name__} is not supported by the HIP engine yet")
+
+
+def reference_prior_arrays(prior, R: int) -> dict:
+    """What `cl_ref_prior` takes from an empirical reference prior, expanded to all R reflections (host arrays); ValueError where the
+    prior's lengths do not match R or a Student-t prior has no positive dof."""
+    out = dict(kind=REFPRIOR_KINDS[prior.engine_kind], dof=float(prior.dof), loc=prior.loc_full(R), scale=prior.scale_full(R),
+               observed=prior.observed_mask(R), centric=prior.centric_full(R))
+    if out["kind"] == _lib.CL_REFPRIOR_STUDENTT and not out["dof"] > 0.0:
+        raise ValueError(f"{type(prior).__name__} needs dof > 0 (got {prior.dof})")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------------------------
@@ -235,7 +267,7 @@ class ElboEngine(WidePath):
         dev = self.device
 
         from careless_amd.models.merging.surrogate_posteriors import TruncatedNormal
-        from careless_amd.models.priors.wilson import DoubleWilsonPrior, WilsonPrior
+        from careless_amd.models.priors.wilson import DoubleWilsonPrior
         from careless_amd.models.likelihoods.mono import LocationScaleLikelihood
         from careless_amd.models.scaling.image import HybridImageScaler, NeuralImageScaler
         from careless_amd.models.scaling.nn import MetadataScaler
@@ -243,8 +275,7 @@ class ElboEngine(WidePath):
         q, prior, lik, scaler = model.surrogate_posterior, model.prior, model.likelihood, model.scaling_model
         if not isinstance(q, TruncatedNormal):
             raise NotImplementedError(f"surrogate posterior {type(q).__name__} is not supported by the HIP engine")
-        if not isinstance(prior, (WilsonPrior, DoubleWilsonPrior)):
-            raise NotImplementedError(f"prior {type(prior).__name__} is not supported by the HIP engine yet")
+        self.ref_prior = prior_kind(prior) == _lib.CL_PRIOR_REFERENCE
         from careless_amd.models.likelihoods.laue import LaueBase
         self.laue = BaseModel.is_laue(inputs)
         if self.laue != isinstance(lik, LaueBase):
@@ -276,10 +307,17 @@ class ElboEngine(WidePath):
 
         # ---- per-reflection constants ----------------------------------------------------------------
         self.low = q.low.to(dev, torch.float32).contiguous()
-        self.centric = torch.as_tensor(prior.centric.astype(np.uint8), device=dev)
-        self.es = torch.as_tensor(prior.eps_sigma, device=dev)
-        if self.centric.numel() != self.R or self.es.numel() != self.R:
-            raise ValueError("prior and surrogate posterior disagree on the number of reflections")
+        if self.ref_prior:
+            # an empirical reference prior (models/priors/empirical.py): its arrays expanded to all reflections, uploaded once; the Wilson
+            # arrays stay NULL (`_tn_args`) -- cl_ref_prior evaluates the density in front of the step's cl_tn_backward
+            self.centric = self.es = None
+            up = lambda a: None if a is None else torch.as_tensor(a, device=dev)
+            self.ref = {k: (up(v) if isinstance(v, np.ndarray) else v) for k, v in reference_prior_arrays(prior, self.R).items()}
+        else:
+            self.centric = torch.as_tensor(prior.centric.astype(np.uint8), device=dev)
+            self.es = torch.as_tensor(prior.eps_sigma, device=dev)
+            if self.centric.numel() != self.R or self.es.numel() != self.R:
+                raise ValueError("prior and surrogate posterior disagree on the number of reflections")
         self.double_wilson = isinstance(prior, DoubleWilsonPrior)
         if self.double_wilson:
             if prior.reflids.size != self.R or (prior.reflids >= self.R).any():
@@ -377,6 +415,8 @@ class ElboEngine(WidePath):
         if want is None:
             env = os.environ.get("CARELESS_HIP_OWNER_SHARD", "")
             want = env == "1"
+        if self.shard.owner or (want and self.shard.world > 1):
+            prior_kind(prior, owner=True)                # (the reflection-owner split is Wilson-only: raises for a reference prior)
         if (want and self.shard.world > 1 and not self.laue and not self.double_wilson and not self.wide and imgl is None
                 and not self.deterministic and not self.shard.owner):
             osh = owner_shard(_np(BaseModel.get_refl_id(inputs)).reshape(-1), self.R, self.shard.rank, self.shard.world)
@@ -416,7 +456,7 @@ class ElboEngine(WidePath):
         assert (self.msg if self.owner else self.grads).data_ptr() % 16 == 0 and self.ws_step.data_ptr() % 16 == 0
         self.norm_part = torch.zeros(2 * 1024, dtype=torch.float64, device=dev)                  # per-workgroup norm sums of cl_adam_step (<= 1024 workgroups)
         self.kl_part = torch.zeros((self.R + 255) // 256, dtype=torch.float64, device=dev)      # per-workgroup KL sums of cl_tn_forward
-        self.kl_part_dw = torch.zeros_like(self.kl_part) if self.double_wilson else None        # ... and of cl_dw_prior_forward
+        self.kl_part_dw = torch.zeros_like(self.kl_part) if (self.double_wilson or self.ref_prior) else None    # ... and of cl_dw_prior_forward / cl_ref_prior
         self.z_f = torch.empty(RS, dtype=torch.float32, device=dev)
         self.stop_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.frozen = torch.zeros(self.nseg, dtype=torch.uint8, device=dev)
@@ -565,6 +605,8 @@ class ElboEngine(WidePath):
         a.d_scale_raw = self.grads.data_ptr() + 4 * self.R
         a.scalars = ptr(self.scalars)
         a.stop_flag = ptr(self.stop_flag)
+        if self.ref_prior:
+            a.prior_kind = _lib.CL_PRIOR_REFERENCE               # (no Wilson term in cl_tn_forward / _backward: centric and es stay NULL)
         if self.double_wilson:
             a.prior_kind = _lib.CL_PRIOR_DOUBLE_WILSON
             a.parent_ids, a.root, a.dw_r = ptr(self.parent_ids), ptr(self.root), ptr(self.dw_r)
@@ -704,7 +746,7 @@ class ElboEngine(WidePath):
         lib, st = self.lib, _stream()
         tn = self._tn_args(step, u_f)
         tn.kl_part = ptr(self.kl_part)       # the forward launch stores its workgroups' KL sums, the backward launch of this step adds them up
-        if self.double_wilson:
+        if self.double_wilson or self.ref_prior:
             tn.kl_part_dw = ptr(self.kl_part_dw)
         # the step's accumulators are cleared by the forward launch itself (no memset launch in front of it): the flat gradient and
         # the scalars by all its threads, the dz_f rows of the reflections it samples by their threads
@@ -734,6 +776,10 @@ class ElboEngine(WidePath):
             # backward launch (independent work: one launch instead of two)
             tn.red_partials, tn.red_nparts, tn.red_P, tn.red_out = self._pending_reduce
             self._pending_reduce = None
+        if self.ref_prior:
+            # behind EVERY data-term launch, directly in front of cl_tn_backward: the frozen-scaler step stores dz_f (a term added before it
+            # would be lost), every other route adds to it -- added last the prior's term is right on all of them
+            self._ref_prior(tn, st)
         check(lib.cl_tn_backward(C.byref(tn), st), "cl_tn_backward")
         if self.owner:
             # this rank's share of |d a|^2 + |d b|^2 into the message, next to the scaler's gradient
@@ -746,6 +792,21 @@ class ElboEngine(WidePath):
         elif dist_on:
             self._allreduce()        # local_only: a test hook that leaves the per-rank partial gradient in place
         self._keep = (u_f, eta, ipred_out)
+
+    def _ref_prior(self, tn: TnArgs, st):
+        """The empirical reference prior's share of the step (`cl_ref_prior`): -w log p of the step's samples into the KL -- per-workgroup
+        sums in kl_part_dw, which the step's cl_tn_backward adds up -- and -w kl_weight dlog p / dz onto dz_f, for the observed reflections
+        whose KL this rank owns."""
+        ref = self.ref
+        a = RefPriorArgs()
+        a.z_f, a.dz_f = tn.z_f, ptr(self.dz_f)
+        a.loc, a.scale, a.observed, a.centric = ptr(ref["loc"]), ptr(ref["scale"]), ptr(ref["observed"]), ptr(ref["centric"])
+        a.kind, a.dof = ref["kind"], ref["dof"]
+        a.R, a.S = self.R, self.S
+        a.w_kl, a.kl_grad_mult = tn.w_kl, tn.kl_grad_mult
+        a.kl_begin, a.kl_end = tn.kl_begin, tn.kl_end
+        a.kl_part, a.scalars, a.stop_flag = tn.kl_part_dw, tn.scalars, tn.stop_flag
+        check(self.lib.cl_ref_prior(C.byref(a), st), "cl_ref_prior")
 
     def _want_split_message(self) -> bool:
         want = getattr(self.model, "split_message", None)

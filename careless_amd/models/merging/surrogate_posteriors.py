@@ -5,6 +5,9 @@ Mirror of `careless/models/merging/surrogate_posteriors.py:11-131` (reference): 
 `stddev`, `moment_4`.  Sampling, log-prob and their gradients on the training path run in the HIP kernels
 `cl_tn_forward` / `cl_tn_backward`; the moment accessors used by the output step (`mean`, `stddev`, `moment_4(method='tf')`) run
 in `cl_tn_moments`.  `moment_4(method='scipy')` is scipy on the host, as in the reference.
+
+`RiceWoolfson` (reference surrogate_posteriors.py:133-172) is host-side only: the base distribution of `RiceWoolfsonReferencePrior`
+(careless_amd/models/priors/empirical.py).
 """
 from __future__ import annotations
 
@@ -136,3 +139,62 @@ class TruncatedNormal(SurrogatePosterior):
             hi = self.high if high is None else high
             return tn_moments(self, high_m4=hi, want=("m4",))["m4"].cpu().numpy()
         raise ValueError(f"Unknown method {method} for computing moment_4")
+
+
+class RiceWoolfson:
+    """Rice(loc, scale) for acentric and FoldedNormal ("Woolfson") for centric reflections: the hybrid distribution of reference
+    surrogate_posteriors.py:133-172.  Host-side (numpy / scipy, float64 arithmetic, float32 results): the base distribution of
+    `RiceWoolfsonReferencePrior`, whose density on the training path is `cl_ref_prior`'s (csrc/cl_math.h: cl_rice_log_prob,
+    cl_folded_normal_log_prob).  It is not a trainable surrogate posterior of the HIP engine."""
+
+    def __init__(self, loc, scale, centric):
+        self.loc = np.array(loc, dtype=np.float32)
+        self.scale = np.array(scale, dtype=np.float32)
+        self.centric = np.array(centric, dtype=bool)
+        self.eps = np.finfo(np.float32).eps
+
+    def _pick(self, woolfson, rice):
+        return np.where(self.centric, woolfson, rice).astype(np.float32)
+
+    def _moments(self):
+        """(mean, variance) of both families in float64.  Folded normal: scipy.stats.foldnorm.  Rice: mean = scale sqrt(pi / 2) L_1/2(-t),
+        t = loc^2 / (2 scale^2), with the Laguerre function written on exponentially scaled Bessel functions, L_1/2(-t) = (1 + t) i0e(t / 2) +
+        t i1e(t / 2) -- finite at any loc / scale, where the unscaled closed form overflows; variance = 2 scale^2 + loc^2 - mean^2."""
+        from scipy import special, stats
+        loc, scale = self.loc.astype(np.float64), self.scale.astype(np.float64)
+        w = stats.foldnorm(loc / scale, scale=scale)
+        t = 0.5 * (loc / scale) ** 2
+        r_mean = scale * math.sqrt(0.5 * math.pi) * ((1.0 + t) * special.i0e(0.5 * t) + t * special.i1e(0.5 * t))
+        r_var = np.maximum(2.0 * scale ** 2 + loc ** 2 - r_mean ** 2, 0.0)
+        return (w.mean(), r_mean), (w.var(), r_var)
+
+    def mean(self):
+        return self._pick(*self._moments()[0])
+
+    def variance(self):
+        return self._pick(*self._moments()[1])
+
+    def stddev(self):
+        return self._pick(*np.sqrt(self._moments()[1]))
+
+    def sample(self, sample_shape=(), seed=None):
+        """Folded normal draws (+ float32 eps, as the reference: off the boundary of the support) and Rice draws |loc + scale (n1 + i n2)|."""
+        rng = np.random.default_rng(seed)
+        shape = (() if sample_shape in ((), None) else (int(sample_shape),)) + self.loc.shape
+        loc, scale = self.loc.astype(np.float64), self.scale.astype(np.float64)
+        n1, n2 = rng.normal(size=shape), rng.normal(size=shape)
+        return self._pick(np.abs(loc + scale * n1) + self.eps, np.hypot(loc + scale * n1, scale * n2))
+
+    def log_prob(self, x):
+        """where(centric, FoldedNormal.log_prob(x), Rice.log_prob(x)) (reference surrogate_posteriors.py:168-169)."""
+        from scipy import special
+        x = np.asarray(x, dtype=np.float64)
+        loc, scale = self.loc.astype(np.float64), self.scale.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            arg = x * loc / scale ** 2
+            rice = np.log(x) - 2 * np.log(scale) - (x * x + loc * loc) / (2 * scale ** 2) + np.log(special.i0e(arg)) + np.abs(arg)
+            fn = np.logaddexp(-0.5 * ((x - loc) / scale) ** 2, -0.5 * ((-x - loc) / scale) ** 2) - 0.5 * math.log(2 * math.pi) - np.log(scale)
+        return self._pick(fn, rice)
+
+    def prob(self, x):
+        return np.exp(self.log_prob(x))

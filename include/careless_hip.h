@@ -60,8 +60,8 @@ typedef struct cl_tn_args {
     const float* q_loc_raw;     /* [R] a = log(loc)                        */
     const float* q_scale_raw;   /* [R] b = log(scale - eps)                */
     const float* low;           /* [R] lower truncation (io/manager.py:434) */
-    const unsigned char* centric; /* [R] 0/1                               */
-    const float* es;            /* [R] multiplicity * Sigma                */
+    const unsigned char* centric; /* [R] 0/1                                (CL_PRIOR_REFERENCE_: NULL, not read) */
+    const float* es;            /* [R] multiplicity * Sigma                 (CL_PRIOR_REFERENCE_: NULL, not read) */
     int R, S;
     float high, eps;
     float w_kl;                 /* weight of every KL element in the reported KL: 1/S (sum) or 1/(S R) (mean)   */
@@ -81,7 +81,7 @@ typedef struct cl_tn_args {
                                  * adding it to scalars[CL_SC_KL] (a 312 k-reflection launch is resident all at once: its 1 200 same-address
                                  * fp64 atomics queue up at the end, 9 of the kernel's 19 us), and the cl_tn_backward of the same step adds
                                  * them up, in index order, into scalars[CL_SC_KL]                                                       */
-    double* kl_part_dw;         /* optional [ceil(R / 256)]: the same for cl_dw_prior_forward (also summed by cl_tn_backward)               */
+    double* kl_part_dw;         /* optional [ceil(R / 256)]: the same for cl_dw_prior_forward or cl_ref_prior (also summed by cl_tn_backward) */
     /* Fewer launches per step (each small kernel costs ~4.5 us of launch + drain, a quarter of the step of a 250 k-observation data set):
      * cl_tn_forward can clear the step's accumulators on its way, cl_tn_backward can carry the scaler-gradient reduction.            */
     float* zero_ptr;            /* optional: cl_tn_forward zeroes zero_ptr[0 .. zero_n) (the caller's flat gradient + scalar block) ...     */
@@ -92,7 +92,8 @@ typedef struct cl_tn_args {
     float* red_out;
     const int* stop_flag;       /* optional device int: non-zero => skip (numerical failure in an earlier step)  */
     /* double-Wilson prior (careless/models/priors/wilson.py:82-175); all NULL / 0 for the plain Wilson prior        */
-    int prior_kind;             /* CL_PRIOR_WILSON_ | CL_PRIOR_DOUBLE_WILSON_                                       */
+    int prior_kind;             /* CL_PRIOR_WILSON_ | CL_PRIOR_DOUBLE_WILSON_ | CL_PRIOR_REFERENCE_ (no prior term in
+                                 * cl_tn_forward / _backward: the caller runs cl_ref_prior between them)              */
     const int* parent_ids;      /* [R] reflection id of the parent in the parent ASU, -1 = absent (`reflids`)       */
     const unsigned char* root;  /* [R] 1 = reflection of a root ASU (plain Wilson prior)                            */
     const float* dw_r;          /* [R] correlation r of the reflection's ASU with its parent (`r[asu_ids]`)         */
@@ -109,13 +110,47 @@ typedef struct cl_tn_args {
     const int* dw_child_seg;    /* [R + 1] */
     const int* dw_child_ids;    /* [number of reflections with a parent] */
 } cl_tn_args;
-enum { CL_PRIOR_WILSON_ = 0, CL_PRIOR_DOUBLE_WILSON_ = 1 };
+enum { CL_PRIOR_WILSON_ = 0, CL_PRIOR_DOUBLE_WILSON_ = 1, CL_PRIOR_REFERENCE_ = 2 };
 
 int cl_tn_forward(const cl_tn_args* args, void* stream);
 int cl_tn_backward(const cl_tn_args* args, void* stream);
 /* double-Wilson only, after cl_tn_forward: adds -w log p(z_h | z_parent) of every non-root reflection to the KL and scatters
  * its derivative w.r.t. the parent's sample into dz_f_out (replaces DoubleWilsonPrior.log_prob, wilson.py:146-175)          */
 int cl_dw_prior_forward(const cl_tn_args* args, void* stream);
+
+/* --- empirical reference priors -------------------------------------------------------------------------------------
+ * replaces: ReferencePrior.log_prob and the base distributions of Laplace- / Normal- / StudentT- / RiceWoolfsonReferencePrior
+ *           (careless/models/priors/empirical.py:9-131; RiceWoolfson.log_prob, careless/models/merging/surrogate_posteriors.py:133-172;
+ *           Rice / FoldedNormal, careless/utils/distributions.py:228-348) inside add_kl_div (careless/models/merging/variational.py:123-139),
+ *           and tape.gradient through them (variational.py:197-202).
+ * A reference prior depends on a reflection's own sample only.  With prior_kind = CL_PRIOR_REFERENCE_ cl_tn_forward / cl_tn_backward leave
+ * the prior term out; this call, anywhere between the two and BEHIND every launch that stores (rather than adds to) dz_f, adds it: for
+ * every reflection h in [kl_begin, kl_end) with observed[h] != 0 and every sample s
+ *     KL      -= w_kl log p(z_f[h][s]),      dz_f[h][s] += -w_kl kl_grad_mult dlog p / dz      (a plain read-modify-write: no atomic)
+ * with p the base density of `kind` at (loc[h], scale[h]).  Nothing else is written: dz_f of unobserved reflections and of reflections
+ * outside the range stays bit-identical.  The KL leaves as in cl_tn_forward: every workgroup STORES -w_kl sum log p into
+ * kl_part[0 .. ceil(R / 256)) (the kl_part_dw of the step's cl_tn_backward, which adds the parts up in index order), or, kl_part NULL, adds
+ * it to scalars[CL_SC_KL] with one fp64 atomic.  -1: a NULL z_f / loc / scale / dz_f, R or S < 1, an unknown kind, dof <= 0 with
+ * CL_REFPRIOR_STUDENTT, centric NULL with CL_REFPRIOR_RICE_WOOLFSON, kl_part and scalars both NULL.                                    */
+typedef struct cl_refprior_args {
+    const float* z_f;           /* [R][S] the step's samples (cl_tn_forward wrote them)                                */
+    const float* loc;           /* [R] Fobs expanded to all reflections (unobserved: never read)                       */
+    const float* scale;         /* [R] the base distribution's scale: SigFobs, or SigFobs / sqrt(2) (Laplace)          */
+    const unsigned char* observed; /* [R] 0/1, NULL = every reflection                                                 */
+    const unsigned char* centric;  /* [R] 0/1, CL_REFPRIOR_RICE_WOOLFSON only                                          */
+    int kind;                   /* CL_REFPRIOR_NORMAL | _LAPLACE | _STUDENTT | _RICE_WOOLFSON                          */
+    float dof;                  /* Student-t                                                                           */
+    int R, S;
+    float w_kl, kl_grad_mult;   /* as in cl_tn_args                                                                    */
+    int kl_begin, kl_end;       /* as in cl_tn_args: reflections whose KL this rank owns                               */
+    float* dz_f;                /* [R][S] += -w_kl kl_grad_mult dlog p / dz                                            */
+    double* kl_part;            /* [ceil(R / 256)] STORE of every workgroup's -w_kl sum log p, or NULL -> scalars      */
+    double* scalars;            /* [CL_SC_COUNT]: scalars[CL_SC_KL] += (kl_part NULL only)                             */
+    const int* stop_flag;
+} cl_refprior_args;
+enum { CL_REFPRIOR_NORMAL = 0, CL_REFPRIOR_LAPLACE = 1, CL_REFPRIOR_STUDENTT = 2, CL_REFPRIOR_RICE_WOOLFSON = 3 };
+int cl_ref_prior(const cl_refprior_args* args, void* stream);
+size_t cl_refprior_args_size(void);                /* sizeof(cl_refprior_args) as the library was compiled (binding check, like cl_abi_sizes) */
 
 /* --- scaler + likelihood -----------------------------------------------------------------------------------------
  * replaces: MLPScaler.call / MetadataScaler / NormalLayer        (careless/models/scaling/nn.py:10-120)
