@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("CARELESS_HIP_LIB") or os.path.join(_HERE, "lib", "lib
 CL_MLP_TILE = 128
 CL_HIST_STRIDE = 8
 CL_SC_NLL, CL_SC_KL, CL_SC_GNORM2, CL_SC_GNORM2_SANE, CL_SC_COUNT = 0, 1, 2, 3, 4
-CL_LIK_NORMAL, CL_LIK_STUDENTT = 0, 1
+CL_LIK_NORMAL, CL_LIK_STUDENTT, CL_LIK_LAPLACE = 0, 1, 2
 CL_BIJ_EXP, CL_BIJ_SOFTPLUS = 0, 1
 CL_PRIOR_WILSON, CL_PRIOR_DOUBLE_WILSON, CL_PRIOR_REFERENCE = 0, 1, 2
 # cl_ref_prior: the base density of an empirical reference prior (include/careless_hip.h, cl_refprior_args.kind)

@@ -65,7 +65,7 @@ static int check_mlp_entry(const cl_mlp_args* a, int mode) {
                 a->partials == nullptr || a->scalars == nullptr || a->S < 1 || a->R < 1)
                 return -1;
             if (a->use_img && (a->image_id == nullptr || a->img == nullptr || a->d_img == nullptr)) return -1;
-            return 0;
+            return cl_lik_check(a->lik_kind, a->ev11, a->d_ev11, a->ev11_part, true);
         case 1: return (a->act_out == nullptr && (a->loc_out == nullptr || a->sig_out == nullptr)) ? -1 : 0;
         case 2: return ((a->dO_ext == nullptr && a->dH_ext == nullptr) || a->partials == nullptr) ? -1 : 0;
     }

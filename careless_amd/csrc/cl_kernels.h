@@ -68,6 +68,18 @@ int cl_launch_laue_backward(const cl_laue_args& a, hipStream_t st);
 int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st);
 int cl_launch_frozen_rows(const cl_frozen_args& a, hipStream_t st);      // elbo_frozen.hip (round 6)
 
+// The likelihood of a launch, checked by every entry that evaluates one.  -1: a kind nobody compiles (it would run as Student-T), or
+// Laplace beside an Evans-2011 buffer (cl_lik_ev11 has no Laplace form: the reference has no such class).  -2: Laplace at an entry whose
+// kernels have no Laplace instance (`has_laplace` false: cl_wide_dense_forward_head_lik -- its caller then runs cl_slot_rows).  The lane
+// and the narrow kernel have none either: cl_lane_*_supports / cl_narrow_supports answer 0 for the kind and mlp_route takes the launch to
+// elbo_mlp.hip's instances (csrc/cl_math.h says why the kind is an instance and not a branch).
+static inline int cl_lik_check(int lik_kind, const void* ev11, const void* d_ev11, const void* ev11_part, bool has_laplace) {
+    if (lik_kind != CL_LIK_NORMAL_ && lik_kind != CL_LIK_STUDENTT_ && lik_kind != CL_LIK_LAPLACE_) return -1;
+    if (lik_kind == CL_LIK_LAPLACE_ && (ev11 != nullptr || d_ev11 != nullptr || ev11_part != nullptr)) return -1;
+    if (lik_kind == CL_LIK_LAPLACE_ && !has_laplace) return -2;
+    return 0;
+}
+
 // Launch of a kernel instance with `sm` bytes of dynamic LDS: -3 above the 160 KB of a gfx950 workgroup, else 0 or the hipError_t.
 // The kernel is a template ARGUMENT, so the mark below -- the largest dynamic-LDS size the instance has been configured for -- is one
 // per instance: the lane, narrow and 16/32/64-wide kernels share one function-pointer type, and a mark keyed by type would publish

@@ -1,4 +1,4 @@
-// Scalar fp32 math of the ELBO path: truncated-normal surrogate posterior, Wilson prior, Normal / Student-T
+// Scalar fp32 math of the ELBO path: truncated-normal surrogate posterior, Wilson prior, Normal / Student-T / Laplace
 // likelihood, scale bijectors and the counter-based RNG.  Every kernel in this directory gets its per-element
 // arithmetic from here, so the formulas are written (and unit-checked) once.
 //
@@ -8,7 +8,7 @@
 // Reference semantics (paths relative to the reference checkout; [3P] = recalled TFP/Keras behaviour):
 //   careless/models/merging/surrogate_posteriors.py:45-131   truncated normal q(F)
 //   careless/models/priors/wilson.py:13-57                   Wilson prior
-//   careless/models/likelihoods/mono.py:10-37                Normal / Student-T likelihood
+//   careless/models/likelihoods/mono.py:10-37                Normal / Laplace / Student-T likelihood
 //   careless/models/scaling/nn.py:10-25                      NormalLayer scale bijector
 //   careless/models/priors/empirical.py:45-131               base densities of the empirical reference priors
 #pragma once
@@ -36,7 +36,7 @@
 #define CL_TINY_F 1.17549435e-38f          // np.finfo(float32).tiny  [3P: clip in TFP's sample gradient]
 #define CL_EPS_F 1.1920929e-07f            // np.finfo(float32).eps
 
-enum { CL_LIK_NORMAL = 0, CL_LIK_STUDENTT = 1 };
+enum { CL_LIK_NORMAL = 0, CL_LIK_STUDENTT = 1, CL_LIK_LAPLACE = 2 };
 enum { CL_BIJ_EXP = 0, CL_BIJ_SOFTPLUS = 1 };
 enum { CL_PRIOR_WILSON = 0, CL_PRIOR_DOUBLE_WILSON = 1, CL_PRIOR_REFERENCE = 2 };
 enum { CL_REF_NORMAL = 0, CL_REF_LAPLACE = 1, CL_REF_STUDENTT = 2, CL_REF_RICE_WOOLFSON = 3 };
@@ -268,6 +268,41 @@ CL_HD float cl_lik_log_prob(float ipred, float iobs, float sig, int kind, float 
     const float y2 = y * y;
     *dll = -(dof + 1.0f) * y / (dof + y2) * inv;
     return -0.5f * (dof + 1.0f) * log1pf(y2 / dof) - logf(sig) + lik_const;
+}
+
+// Laplace likelihood (mono.py:20-23, laue.py:76-81): tfd.Laplace(Iobs, SigIobs / sqrt 2).  With d = ipred - Iobs
+//   log p = -sqrt2 |d| / sig - log sig - 0.5 log 2,     d log p / d ipred = -sign(d) sqrt2 / sig
+// It is NOT a third arm of the two-way forms above and below ("Normal, else Student-T"): a third wave-uniform branch in them moved hipcc's
+// register allocation in every fused kernel (spilled registers and scratch gained in 427 of 580 kernel copies: NOTEBOOK R17.1), so those
+// stay as they were, instruction for instruction, and the Laplace kind is a COMPILE-TIME instance of the kernels that evaluate a likelihood
+// picked at run time (elbo_mlp.hip: EPI = CL_EPI_GENERIC_LAPLACE; elbo_narrow.hip, elbo_frozen.hip, elbo_laue.hip: the *_laplace_kernel
+// instances of the kernel bodies); the lane kernel has none and refuses the kind (cl_lane_supports).
+#define CL_SQRT2_F 1.41421356237309505f
+#define CL_HALF_LOG_2_F 0.34657359027997264f
+// sign(d) as TensorFlow's gradient of abs has it: +-1, d itself (+-0) at the kink, and a NaN stays the NaN it is.  Taken from the BITS of d,
+// so that it also holds in a unit compiled with -fno-honor-nans (build.py: NNAN), where hipcc may rewrite float compares as if d were never
+// a NaN: |d| - 1 (unsigned, wrapping at zero) is below the bits of infinity exactly for 0 < |d| <= inf.
+CL_HD float cl_sign_bits(float d) {
+    uint32_t u;
+    __builtin_memcpy(&u, &d, 4);
+    const uint32_t one = (u & 0x80000000u) | 0x3F800000u;      // copysign(1, d)
+    float s;
+    __builtin_memcpy(&s, &one, 4);
+    return ((u & 0x7FFFFFFFu) - 1u < 0x7F800000u) ? s : d;
+}
+CL_HD float cl_lik_laplace_log_prob(float ipred, float iobs, float sig, float* dll) {
+    const float c = CL_SQRT2_F / sig;
+    const float d = ipred - iobs;
+    *dll = -cl_sign_bits(d) * c;
+    return -fabsf(d) * c - logf(sig) - CL_HALF_LOG_2_F;
+}
+
+// ... with 1/sig and log(sig) hoisted by the caller, as cl_lik_log_prob2 / 3 below
+CL_HD float cl_lik_laplace_log_prob2(float ipred, float iobs, float inv_sig, float log_sig, float* dll) {
+    const float c = CL_SQRT2_F * inv_sig;
+    const float d = ipred - iobs;
+    *dll = -cl_sign_bits(d) * c;
+    return -fabsf(d) * c - log_sig - CL_HALF_LOG_2_F;
 }
 
 // log(1 + x) for x >= 0 from the hardware log: log(u) + (x - (u - 1)) / u with u = fl(1 + x) (the correction term restores

@@ -1285,6 +1285,7 @@ static inline bool lane_full_step(const cl_mlp_args& a) { return a.S >= 1 && a.a
 // (batches of SPRE).  4 M observations, 20 x 10, Student-T, ms per step here / on elbo_narrow.hip (scripts/narrow_samples.py):
 // S = 1 0.96 / 1.11, 2: 1.01 / 1.12, 4: 1.07 / 1.19, 8: 1.16 / 1.34.
 int cl_lane_supports(const cl_mlp_args& a) {
+    if (a.lik_kind == CL_LIK_LAPLACE) return 0;         // no Laplace instance of the lane kernel (512-register wall): narrow's too -> elbo_mlp.hip's 16-wide instances
     const bool regs = lane_cols_in_regs(a);
     if (!(lane_envelope(a, regs ? LANE_W12 : CL_LANE_WMAX, DMAX_LX) && lane_full_step(a) && a.n_imgl == 0 && (a.row_map != nullptr || a.gmeta == nullptr))) return 0;
     // the other depths: metadata in registers (more columns: behind the engine's peeled first layer, dZ_0 out in the plain layout)
@@ -1300,6 +1301,7 @@ int cl_lane_supports(const cl_mlp_args& a) {
 // packed-by-image layout (Laue data: harmonic groups inside 16-row granules, single pass, as without per-image layers); everything
 // else with per-image layers stays on the IMGL instances of elbo_mlp.hip.
 int cl_lane_imgl_supports(const cl_mlp_args& a) {
+    if (a.lik_kind == CL_LIK_LAPLACE) return 0;
     const int nmax = (a.L == NL || a.L <= LANE_IMGL3_DEPTH_MAX) ? LANE_IMGL_MAX_NL : LANE_IMGL_MAX;
     return lane_envelope(a, CL_LANE_WMAX, DMAX_ALL) && lane_full_step(a) && a.n_imgl >= 1 && a.n_imgl <= nmax && a.row_map != nullptr &&
            (a.gmeta == nullptr || a.tile_gmax != nullptr) && !a.use_img && a.imgl != nullptr && a.d_imgl != nullptr && a.tile_img != nullptr && a.n_images >= 1;

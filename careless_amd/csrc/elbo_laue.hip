@@ -42,7 +42,10 @@ __global__ __launch_bounds__(256) void laue_predict_kernel(const cl_laue_args A)
     else atomicAdd(A.iconv + (size_t)A.harmonic_id[i] * A.S + s, ipred);
 }
 
-__global__ __launch_bounds__(256) void laue_likelihood_kernel(const cl_laue_args A) {
+// (LAP: the Laplace likelihood, compiled as kernels of its own -- the Normal / Student-T instances are what they were, instruction for
+//  instruction; the launch refuses Laplace beside the Evans-2011 buffers)
+template <bool LAP>
+__device__ __forceinline__ void laue_likelihood_body(const cl_laue_args& A) {
     if (A.stop_flag != nullptr && *A.stop_flag != 0) return;
     // grid-stride over the (slot, sample) pairs: the NLL ends in ONE double atomic per workgroup on one address (they
     // serialise at ~12 ns each), so the grid is kept at a few workgroups per CU instead of one per 256 elements
@@ -58,7 +61,9 @@ __global__ __launch_bounds__(256) void laue_likelihood_kernel(const cl_laue_args
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x) {
         const int g = (int)(p / A.S);
         float dll, ll;
-        if (A.ev11 != nullptr) {
+        if (LAP) {
+            ll = cl_lik_laplace_log_prob(A.iconv[p], A.iobs[g], A.sig[g], &dll);
+        } else if (A.ev11 != nullptr) {
             float gf, gb, ga;
             ll = cl_lik_ev11(A.iconv[p], A.iobs[g], A.sig[g], A.lik_kind, A.dof, A.lik_const, ev, &dll, &gf, &gb, &ga);
             g0 -= gf * A.w_ll * sg0; g1 -= ga * A.w_ll * sg1; g2 -= gb * A.w_ll * sg2;
@@ -87,6 +92,9 @@ __global__ __launch_bounds__(256) void laue_likelihood_kernel(const cl_laue_args
         }
     }
 }
+
+__global__ __launch_bounds__(256) void laue_likelihood_kernel(const cl_laue_args A) { laue_likelihood_body<false>(A); }
+__global__ __launch_bounds__(256) void laue_likelihood_laplace_kernel(const cl_laue_args A) { laue_likelihood_body<true>(A); }
 
 // One thread per (row, sample): the S samples of a row are consecutive lanes, so the amplitude-gradient atomics of a row hit S
 // consecutive floats of dz_f (one request) -- with a thread per row and a loop over the samples every instruction sent 64 lanes to 64
@@ -155,7 +163,8 @@ __global__ __launch_bounds__(256) void laue_backward_kernel(const cl_laue_args A
 // atomics); grid-stride with a bounded grid, every thread running the same number of rounds (the reductions are wave-wide), so the NLL
 // ends in one double atomic per workgroup as in laue_likelihood_kernel.  When S divides 64 a row never straddles two waves: its sums
 // over the samples are complete in the first lane of its segment and dO is STORED (no memset, no atomics).
-__global__ __launch_bounds__(256) void slot_rows_kernel(const cl_laue_args A, int dO_store) {
+template <bool LAP>
+__device__ __forceinline__ void slot_rows_body(const cl_laue_args& A, int dO_store) {
     if (A.stop_flag != nullptr && *A.stop_flag != 0) return;
     const long long total = (long long)A.n_obs * A.S, stride = (long long)gridDim.x * blockDim.x;
     const long long rounds = (total + stride - 1) / stride;
@@ -196,7 +205,9 @@ __global__ __launch_bounds__(256) void slot_rows_kernel(const cl_laue_args A, in
             const float ipred = aim * tq * zf * zf;
             if (A.ipred_out) A.ipred_out[p] = ipred;
             float dll, ll;
-            if (A.ev11 != nullptr) {
+            if (LAP) {
+                ll = cl_lik_laplace_log_prob(ipred, P.iobs, P.sig, &dll);
+            } else if (A.ev11 != nullptr) {
                 float gf, gb, ga;
                 ll = cl_lik_ev11(ipred, P.iobs, P.sig, A.lik_kind, A.dof, A.lik_const, ev, &dll, &gf, &gb, &ga);
                 g0 -= gf * A.w_ll * sg0; g1 -= ga * A.w_ll * sg1; g2 -= gb * A.w_ll * sg2;
@@ -277,6 +288,9 @@ __global__ __launch_bounds__(256) void slot_rows_kernel(const cl_laue_args A, in
     }
 }
 
+__global__ __launch_bounds__(256) void slot_rows_kernel(const cl_laue_args A, int dO_store) { slot_rows_body<false>(A, dO_store); }
+__global__ __launch_bounds__(256) void slot_rows_laplace_kernel(const cl_laue_args A, int dO_store) { slot_rows_body<true>(A, dO_store); }
+
 static int laue_check(const cl_laue_args& a) {
     if (a.n_obs <= 0 || a.S <= 0 || a.refl_id == nullptr || a.loc == nullptr || a.sigma == nullptr ||
         a.z_f == nullptr || a.iconv == nullptr)
@@ -295,17 +309,20 @@ int cl_launch_laue_predict(const cl_laue_args& a, hipStream_t st) {
 int cl_launch_laue_likelihood(const cl_laue_args& a, hipStream_t st) {
     // needs the slot arrays only (it is also called on the padded slots alone by the single-pass path)
     if (a.n_obs <= 0 || a.S <= 0 || a.iconv == nullptr || a.iobs == nullptr || a.sig == nullptr || a.scalars == nullptr) return -1;
+    if (int e = cl_lik_check(a.lik_kind, a.ev11, a.d_ev11, a.ev11_part, true)) return e;
     const long long n = (long long)a.n_obs * a.S;
     (void)hipGetLastError();
     long long blocks = (n + 255) / 256;
     if (blocks > CL_LAUE_LIK_MAX_BLOCKS) blocks = CL_LAUE_LIK_MAX_BLOCKS;
-    hipLaunchKernelGGL(laue_likelihood_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    if (a.lik_kind == CL_LIK_LAPLACE_) hipLaunchKernelGGL(laue_likelihood_laplace_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(laue_likelihood_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st) {
     if (int e = laue_check(a)) return e;
     if (a.harmonic_id != nullptr) return -2;           // rows that share slots need the three passes (group sums between them)
     if (a.iobs == nullptr || a.sig == nullptr || a.scalars == nullptr || a.dz_f == nullptr || a.dO == nullptr || (a.use_img && a.d_img == nullptr)) return -1;
+    if (int e = cl_lik_check(a.lik_kind, a.ev11, a.d_ev11, a.ev11_part, true)) return e;
     if (a.dzf_obs != nullptr) {          // deterministic mode: stores per (row, sample) / row / workgroup; a row's samples must sit inside one wave
         if (64 % a.S != 0) return -2;
         if (a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr) || (a.ev11 != nullptr && a.ev11_part == nullptr)) return -1;
@@ -319,7 +336,8 @@ int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st) {
     const long long n = (long long)a.n_obs * a.S;
     long long blocks = (n + 255) / 256;
     if (blocks > CL_LAUE_LIK_MAX_BLOCKS) blocks = CL_LAUE_LIK_MAX_BLOCKS;
-    hipLaunchKernelGGL(slot_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, store);
+    if (a.lik_kind == CL_LIK_LAPLACE_) hipLaunchKernelGGL(slot_rows_laplace_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, store);
+    else hipLaunchKernelGGL(slot_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, store);
     return (int)hipGetLastError();
 }
 int cl_launch_laue_backward(const cl_laue_args& a, hipStream_t st) {

@@ -146,11 +146,16 @@ struct AccPlan {
 //     kind, Evans-2011 model, injected noise or Philox, noise_row, ipred_out, any S); the two plain values compile the common launch --
 //     in-kernel noise keyed by the row, none of the optional buffers, S <= 8 (epi_plain, below), the likelihood kind a constant -- as
 //     straight-line code for the lane's two samples.  64-wide full-step instances of the plain unit only.
+//     CL_EPI_GENERIC_LAPLACE (internal, not a value of the public enum): the generic epilogue with the Laplace likelihood compiled in
+//     (no Evans-2011 terms) -- an instance of its own, so that the instances Normal and Student-T launches run are what they were.
+#define CL_EPI_GENERIC_LAPLACE 100
 template <int WP, int DP, int LMAX, int MODE, bool IMGL, bool CHAIN = false, bool ILAY = IMGL, int KS = 4, bool DET = (CL_DET != 0),
           int EPI = CL_EPI_GENERIC>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void elbo_mlp_kernel(const cl_mlp_args A) {
-    static_assert(EPI == CL_EPI_GENERIC || (WP == 64 && MODE == 0 && !IMGL && !CHAIN && !DET), "plain epilogue: 64-wide full step of the plain unit");
+    constexpr bool EPI_GEN = (EPI == CL_EPI_GENERIC || EPI == CL_EPI_GENERIC_LAPLACE);       // every option decided per MC sample
+    static_assert(EPI != CL_EPI_GENERIC_LAPLACE || MODE == 0, "the Laplace instance is a full step");
+    static_assert(EPI_GEN || (WP == 64 && MODE == 0 && !IMGL && !CHAIN && !DET), "plain epilogue: 64-wide full step of the plain unit");
     using SL = SmemLayout<WP, DP, LMAX>;
     constexpr int FB = WP / 16;          // 16-feature blocks of a hidden layer
     constexpr int KS1 = DP / 4;          // MFMA k-steps of the first layer (4 metadata features per step)
@@ -455,8 +460,8 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
         if (MODE == 0 && rid >= 0 && E0->det_slot != nullptr) dzo = 4u * (unsigned)E0->det_slot[drow] * (unsigned)S;
 #endif
         // (plain epilogue: the launch has neither, and the tile's gathers are the image scale and the two z_f values)
-        const float* __restrict__ eta_t = (EPI == CL_EPI_GENERIC && E0->eta) ? (IMGL ? E0->eta : E0->eta + (size_t)tile_u * CL_TILE * S) : nullptr;
-        float* __restrict__ ipred_t = (EPI == CL_EPI_GENERIC && E0->ipred_out) ? (IMGL ? E0->ipred_out : E0->ipred_out + (size_t)tile_u * CL_TILE * S) : nullptr;
+        const float* __restrict__ eta_t = (EPI_GEN && E0->eta) ? (IMGL ? E0->eta : E0->eta + (size_t)tile_u * CL_TILE * S) : nullptr;
+        float* __restrict__ ipred_t = (EPI_GEN && E0->ipred_out) ? (IMGL ? E0->ipred_out : E0->ipred_out + (size_t)tile_u * CL_TILE * S) : nullptr;
         if (MODE == 0 && rid >= 0) {
             if (E0->use_img && img > 0) aim = ld_uo(E0->img, 4u * (unsigned)(img - 1));
             if (qe < S) zf0 = ld_uo(E0->z_f, zoff + 4u * qe);
@@ -464,7 +469,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
             if (eta_t != nullptr) {
                 if (qe < S) et0 = ld_uo(eta_t, eoff + 4u * qe);
                 if (qe + 4 < S) et1 = ld_uo(eta_t, eoff + 4u * (qe + 4));
-            } else if (EPI == CL_EPI_GENERIC && !IMGL && E0->noise_row != nullptr) {
+            } else if (EPI_GEN && !IMGL && E0->noise_row != nullptr) {
                 // plain layout over rows that are not a contiguous range of the caller's (a rank that owns a reflection range takes
                 // every observation of those reflections): the row's GLOBAL number, the key of the in-kernel noise, rides in the
                 // register the injected noise would use
@@ -641,7 +646,8 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                             ll = cl_lik_ev11(tot, io, sg, E->lik_kind, E->dof, E->lik_const, ev, &dll, &gf, &gb, &ga);
                             if (mem == 0) { ev_g0 -= gf * E->w_ll; ev_g1 -= ga * E->w_ll; ev_g2 -= gb * E->w_ll; }
                         } else {
-                            ll = cl_lik_log_prob2(tot, io, inv_sg, log_sg, E->lik_kind, E->dof, E->lik_const, &dll);
+                            if constexpr (EPI == CL_EPI_GENERIC_LAPLACE) ll = cl_lik_laplace_log_prob2(tot, io, inv_sg, log_sg, &dll);
+                            else ll = cl_lik_log_prob2(tot, io, inv_sg, log_sg, E->lik_kind, E->dof, E->lik_const, &dll);
                         }
                         if (mem == 0) nll_acc -= ll * E->w_ll;
                         const float gi = -dll * E->w_ll;                 // dNLL / d iconv = dNLL / d ipred of every member
@@ -657,7 +663,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                         pda += dzs * tq;
                     }
                 }
-            } else if (EPI != CL_EPI_GENERIC) {
+            } else if (!EPI_GEN) {
                 // ---- plain epilogue: a lane's samples are s = qe and s = qe + 4 (S <= 8), straight-line, the same expressions in the same
                 //      order as the loop below.  Both z_f values came with the tile-start gathers, so the sample code holds no load and no
                 //      vmcnt wait; the scalar arguments are read once, in front of the first sample; both dz_f atomics leave after both
@@ -724,7 +730,8 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                         ll = cl_lik_ev11(ipred, io, sg, E->lik_kind, E->dof, E->lik_const, ev, &dll, &gf, &gb, &ga);
                         ev_g0 -= gf * E->w_ll; ev_g1 -= ga * E->w_ll; ev_g2 -= gb * E->w_ll;     // order: Sdfac, Sdadd, SdB
                     } else {
-                        ll = cl_lik_log_prob2(ipred, io, inv_sg, log_sg, E->lik_kind, E->dof, E->lik_const, &dll);
+                        if constexpr (EPI == CL_EPI_GENERIC_LAPLACE) ll = cl_lik_laplace_log_prob2(ipred, io, inv_sg, log_sg, &dll);
+                        else ll = cl_lik_log_prob2(ipred, io, inv_sg, log_sg, E->lik_kind, E->dof, E->lik_const, &dll);
                     }
                     nll_acc -= ll * E->w_ll;
                     const float gi = -dll * E->w_ll;                 // dNLL / d ipred
@@ -1363,28 +1370,29 @@ cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r) {
 #endif
 
 
-template <int MODE>
+// GEN: the generic epilogue's instance -- CL_EPI_GENERIC, or, for a full step under the Laplace likelihood, CL_EPI_GENERIC_LAPLACE
+template <int MODE, int GEN = CL_EPI_GENERIC>
 static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
     const MlpGeom g = mlp_geom(a, MODE, CL_IMGL == 1);
     constexpr int L16 = (CL_IMGL == 1 ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16);
     if (g.WP == 0) return -2;
     if (g.WP == 16) {
-        if (g.KS == 2) return launch_dp<16, L16, MODE, 2>(a, g.DP, grid, st);
-        if (g.KS == 3) return launch_dp<16, L16, MODE, 3>(a, g.DP, grid, st);
+        if (g.KS == 2) return launch_dp<16, L16, MODE, 2, GEN>(a, g.DP, grid, st);
+        if (g.KS == 3) return launch_dp<16, L16, MODE, 3, GEN>(a, g.DP, grid, st);
 #if CL_IMGL != 1
-        if (g.KS == 5) return launch_dp<16, CL_MLP_LMAX_W16, MODE, 5>(a, g.DP, grid, st);
+        if (g.KS == 5) return launch_dp<16, CL_MLP_LMAX_W16, MODE, 5, GEN>(a, g.DP, grid, st);
 #endif
-        return launch_dp<16, L16, MODE, 4>(a, g.DP, grid, st);
+        return launch_dp<16, L16, MODE, 4, GEN>(a, g.DP, grid, st);
     }
-    if (g.WP == 32) return g.LMAX == 5 ? launch_dp<32, 5, MODE>(a, g.DP, grid, st) : launch_dp<32, CL_MLP_LMAX_W32, MODE>(a, g.DP, grid, st);
+    if (g.WP == 32) return g.LMAX == 5 ? launch_dp<32, 5, MODE, 4, GEN>(a, g.DP, grid, st) : launch_dp<32, CL_MLP_LMAX_W32, MODE, 4, GEN>(a, g.DP, grid, st);
 #if CL_PLAIN_UNIT
-    if constexpr (MODE == 0) {
+    if constexpr (MODE == 0 && GEN == CL_EPI_GENERIC) {
         const cl_epilogue e = mlp_epilogue(a, MODE, CL_ROUTE_MLP);
         if (e == CL_EPI_PLAIN_NORMAL) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_NORMAL>(a, g.DP, grid, st);
         if (e == CL_EPI_PLAIN_STUDENTT) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_STUDENTT>(a, g.DP, grid, st);
     }
 #endif
-    return launch_dp<64, CL_MLP_LMAX_W64, MODE>(a, g.DP, grid, st);
+    return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, GEN>(a, g.DP, grid, st);
 }
 
 // This compilation's launcher (cl_kernels.h lists the eight; cl_launch_mlp has checked the arguments and clamped the grid)
@@ -1405,7 +1413,7 @@ static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
 #endif
 int CL_MLP_UNIT(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
     switch (mode) {
-        case 0: return launch_mode<0>(a, grid, st);
+        case 0: return a.lik_kind == CL_LIK_LAPLACE ? launch_mode<0, CL_EPI_GENERIC_LAPLACE>(a, grid, st) : launch_mode<0>(a, grid, st);
         case 1: return launch_mode<1>(a, grid, st);
         case 2: return launch_mode<2>(a, grid, st);
     }

@@ -654,6 +654,7 @@ static int launch_narrow_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
 
 // 1 = this geometry runs on the narrow kernel (full ELBO step; plain observation layout, or the packed one of single-pass Laue)
 int cl_narrow_supports(const cl_mlp_args& a) {
+    if (a.lik_kind == CL_LIK_LAPLACE) return 0;         // (no Laplace instance of this kernel: the 16-wide instances of elbo_mlp.hip take the shape)
     return a.w >= 1 && a.w <= 15 && a.d >= 1 && a.d <= 15 && a.L >= 1 && a.L <= NL && a.n_imgl == 0 && a.act_out == nullptr &&
            a.dH_ext == nullptr && a.dX_out == nullptr && (a.row_map != nullptr || a.gmeta == nullptr);
 }

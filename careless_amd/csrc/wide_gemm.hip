@@ -1511,6 +1511,7 @@ int cl_wide_dense_forward_head_lik(const float* X, int ldx, const float* Wt, con
     if (any_null(a.refl_id, a.iobs, a.sig, a.z_f, a.dz_f, a.dO, a.scalars) || a.S < 1 || a.n_obs != (int)n ||
         (a.use_img && any_null(a.image_id, a.img, a.d_img)))
         return -1;
+    if (int e = cl_lik_check(a.lik_kind, a.ev11, a.d_ev11, a.ev11_part, false)) return e;
     if (!sq_ok(s)) return -2;
     s.lik.refl_id = a.refl_id; s.lik.image_id = a.image_id; s.lik.iobs = a.iobs; s.lik.sig = a.sig;
     s.lik.row_index = a.row_index; s.lik.obs_offset = a.obs_offset;

@@ -172,12 +172,12 @@ class ScalerPlan:
 
 
 def plan_scaler(lib, d: int, w: int, L: int, K: int = 0, laue: bool = False, two_pass: bool = False, gmax: int = 1, ev11: bool = False,
-                deterministic: bool = False) -> ScalerPlan:
+                deterministic: bool = False, lik_kind: int = 0) -> ScalerPlan:
     """How `ElboEngine` runs L Dense layers of width w on d columns with K per-image layers (`gmax`: the largest harmonic group): the plan
     chooses the launches -- peel the first layer, cut a deep scaler into blocks, go layer by layer --, the library's routes decide."""
     NONE, LANE, NARROW, LANE_IMGL = _lib.CL_ROUTE_NONE, _lib.CL_ROUTE_LANE, _lib.CL_ROUTE_NARROW, _lib.CL_ROUTE_LANE_IMGL
     proto = dict(d=d, w=w, L=L, S=1, refl_id=1, meta_t=1, iobs=1, sig=1, mlp=1, z_f=1, dz_f=1, partials=1, scalars=1, stop_flag=1,
-                 ev11=int(ev11), d_ev11=int(ev11))
+                 ev11=int(ev11), d_ev11=int(ev11), lik_kind=lik_kind)      # (the lane and the narrow kernel refuse CL_LIK_LAPLACE: the routes say so)
     det = dict(dzf_obs=1, dimg_obs=1, nll_part=1, det_slot=1, ev11_part=int(ev11)) if deterministic else {}
     route = lambda mode, **kw: _lib.mlp_route(lib, mode, **{**proto, **kw})
     if w > 64 or d > 64:        # a layer's activations no longer fit a wave's registers next to the weight-gradient blocks
@@ -281,8 +281,10 @@ class ElboEngine(WidePath):
         if self.laue != isinstance(lik, LaueBase):
             raise ValueError("Laue inputs (8-tuple with harmonic_id) need a careless_amd.models.likelihoods.laue likelihood, "
                              "monochromatic inputs a careless_amd.models.likelihoods.mono one")
-        if not isinstance(lik, (LocationScaleLikelihood, LaueBase)) or lik.kind not in ("normal", "studentt"):
+        if not isinstance(lik, (LocationScaleLikelihood, LaueBase)) or lik.kind not in ("normal", "studentt", "laplace"):
             raise NotImplementedError(f"likelihood {type(lik).__name__} is not supported by the HIP engine yet")
+        if lik.kind == "laplace" and getattr(lik, "ev11", False):
+            raise NotImplementedError(f"likelihood {type(lik).__name__}: the Evans-2011 error model has no Laplace form (the reference has no such class)")
         imgl = None
         if isinstance(scaler, HybridImageScaler):
             mlp, img = scaler.mlp_scaler, scaler.image_scaler
@@ -342,7 +344,8 @@ class ElboEngine(WidePath):
         two_pass = self.laue and bool(getattr(model, "laue_two_pass", False))
         gmax = int(np.bincount(_np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64)).max()) if self.laue else 1
         self.plan = plan_scaler(self.lib, self.d, self.w, self.L, imgl.n_image_layers if imgl is not None else 0, laue=self.laue,
-                                two_pass=two_pass, gmax=gmax, ev11=self.ev11, deterministic=self.deterministic)
+                                two_pass=two_pass, gmax=gmax, ev11=self.ev11, deterministic=self.deterministic,
+                                lik_kind=_lib.CL_LIK_LAPLACE if lik.kind == "laplace" else 0)
         self.wide, self.peel, self.blocks, self.chain_lane = self.plan.wide, self.plan.peel, self.plan.blocks, self.plan.chain_lane
         if imgl is not None:
             imgl.build(self.d)
@@ -354,7 +357,7 @@ class ElboEngine(WidePath):
         if self.deterministic and (two_pass or (self.wide and not wide_det_ok) or (imgl is not None and not imgl_det_ok) or
                                    (self.blocks is not None and self.laue) or (self.double_wilson and prior.r_raw is not None)):
             raise NotImplementedError("deterministic mode covers monochromatic and single-pass Laue data, the Wilson and the double-Wilson prior "
-                                      "(fixed r), Normal / Student-T likelihoods with or without the Evans-2011 error model, scalers of any depth up to "
+                                      "(fixed r), Normal / Student-T likelihoods with or without the Evans-2011 error model, the Laplace likelihood, scalers of any depth up to "
                                       "width 64, up to three per-image layers on 2 .. 20 Dense layers of width 5 .. 10 (two on 19; the default scaler's kernels) and, "
                                       "for monochromatic data with a sample count that divides 64, scalers wider than 64; the two-pass "
                                       "Laue path (also under a chained scaler), a trainable double-Wilson r and every other shape with per-image layers "
@@ -581,6 +584,8 @@ class ElboEngine(WidePath):
             nu = float(self.lik.dof)
             self.lik_kind, self.dof = _lib.CL_LIK_STUDENTT, nu
             self.lik_const = math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi)
+        elif self.lik.kind == "laplace":                # (neither dof nor lik_const is read)
+            self.lik_kind, self.dof, self.lik_const = _lib.CL_LIK_LAPLACE, 0.0, 0.0
         else:
             self.lik_kind, self.dof, self.lik_const = _lib.CL_LIK_NORMAL, 0.0, 0.0
         self.bij_kind = _lib.CL_BIJ_EXP if self.mlp.scale_bijector == "exp" else _lib.CL_BIJ_SOFTPLUS

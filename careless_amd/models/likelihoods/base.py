@@ -5,7 +5,7 @@ from careless_amd.models.base import BaseModel
 
 
 class Likelihood(BaseModel):
-    kind = None          # "normal" | "studentt": what the engine dispatches on
+    kind = None          # "normal" | "studentt" | "laplace": what the engine dispatches on
 
     def call(self, inputs):
         raise NotImplementedError("Likelihoods must implement a call method that returns an object with a `log_prob` method.")

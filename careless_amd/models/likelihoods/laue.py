@@ -55,6 +55,15 @@ class NormalLikelihood(LaueBase):
         return _BoundLocationScale("normal", _squeeze(self.get_intensities(inputs)), _squeeze(self.get_uncertainties(inputs)))
 
 
+class LaplaceLikelihood(LaueBase):
+    """Laplace(Iobs, SigIobs / sqrt 2) on the convolved predictions  (reference laue.py:76-81)."""
+    kind = "laplace"
+
+    def dist(self, inputs):
+        return _BoundLocationScale("laplace", _squeeze(self.get_intensities(inputs)),
+                                   _squeeze(self.get_uncertainties(inputs)) / np.sqrt(2.0))
+
+
 class StudentTLikelihood(LaueBase):
     kind = "studentt"
 

@@ -1,6 +1,6 @@
 """Monochromatic likelihoods.
 
-Mirror of `careless/models/likelihoods/mono.py:10-37` (reference).  `likelihood(inputs)` returns a small object
+Mirror of `careless/models/likelihoods/mono.py:10-73` (reference).  `likelihood(inputs)` returns a small object
 bound to (Iobs, SigIobs) with `.log_prob(ipred)`, like the tfd distribution the reference returns.  On the hot path
 the engine reads `kind` / `dof` from the likelihood and evaluates log-prob and its derivative inside the fused HIP
 kernel `cl_elbo_mono_fwd_bwd` (careless_amd/csrc/elbo_mlp.hip).
@@ -28,6 +28,8 @@ class _BoundLocationScale:
         y = (x - self.loc) / self.scale
         if self.kind == "normal":
             return (-0.5 * y * y - 0.5 * math.log(2 * math.pi) - np.log(self.scale)).astype(np.float32)
+        if self.kind == "laplace":          # tfd.Laplace(loc, scale): -|x - loc| / scale - log(2 scale)
+            return (-np.abs(y) - math.log(2.0) - np.log(self.scale)).astype(np.float32)
         nu = float(self.dof)
         return (-0.5 * (nu + 1.0) * np.log1p(y * y / nu) - np.log(np.abs(self.scale)) - 0.5 * math.log(nu)
                 - 0.5 * math.log(math.pi) - math.lgamma(0.5 * nu) + math.lgamma(0.5 * (nu + 1.0))).astype(np.float32)
@@ -36,6 +38,8 @@ class _BoundLocationScale:
         return self.loc
 
     def stddev(self):
+        if self.kind == "laplace":          # (as tfd.Laplace answers: sqrt 2 * scale)
+            return math.sqrt(2.0) * self.scale
         return self.scale
 
 
@@ -53,6 +57,15 @@ class NormalLikelihood(LocationScaleLikelihood):
 
     def call(self, inputs):
         return _BoundLocationScale("normal", *self.get_loc_and_scale(inputs))
+
+
+class LaplaceLikelihood(LocationScaleLikelihood):
+    """Laplace(Iobs, SigIobs / sqrt 2)  (reference mono.py:20-23)."""
+    kind = "laplace"
+
+    def call(self, inputs):
+        loc, scale = self.get_loc_and_scale(inputs)
+        return _BoundLocationScale("laplace", loc, scale / math.sqrt(2.0))
 
 
 class StudentTLikelihood(LocationScaleLikelihood):

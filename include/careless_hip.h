@@ -156,7 +156,7 @@ size_t cl_refprior_args_size(void);                /* sizeof(cl_refprior_args) a
  * replaces: MLPScaler.call / MetadataScaler / NormalLayer        (careless/models/scaling/nn.py:10-120)
  *           ImageScaler.call / HybridImageScaler.call            (careless/models/scaling/image.py:27-63)
  *           VariationalMergingModel.call gather + predict        (careless/models/merging/variational.py:156-167)
- *           NormalLikelihood / StudentTLikelihood log_prob       (careless/models/likelihoods/mono.py:10-37)
+ *           Normal- / Laplace- / StudentTLikelihood log_prob     (careless/models/likelihoods/mono.py:10-37)
  *           tape.gradient of all of the above                    (careless/models/merging/variational.py:197-202) */
 typedef struct cl_mlp_args {
     const int* refl_id;         /* [n_obs]                                    */
@@ -173,7 +173,12 @@ typedef struct cl_mlp_args {
     int use_img;
     const float* z_f;           /* [R][S]                                      */
     int R, S;
-    int lik_kind; float dof, lik_const;   /* CL_LIK_*; lik_const = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2 */
+    int lik_kind; float dof, lik_const;   /* CL_LIK_*_; Student-T: lik_const = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2; Normal and Laplace
+                                           * read neither dof nor lik_const.  Every entry that evaluates a likelihood (here, cl_laue_args,
+                                           * cl_frozen_args) returns -1 for any other kind and for CL_LIK_LAPLACE_ beside an Evans-2011 buffer
+                                           * (ev11 / d_ev11 / ev11_part: the reference has no Laplace Ev11 class).  Laplace runs on instances of its
+                                           * own of the kernels (the others' code does not know the kind); the lane and the narrow kernel have none:
+                                           * cl_mlp_route takes their shapes to elbo_mlp.hip's instances, cl_wide_dense_forward_head_lik returns -2 */
     int bij_kind; float eps, shift;       /* CL_BIJ_*; sigma = f(raw) + eps; shift = tfb.Shift(std(Iobs)) (nn.py:84-87) */
     float w_ll;                 /* weight of every log-likelihood term: 1/S or 1/(S N_total) */
     const float* eta;           /* [n_obs][S] injected normals or NULL         */
@@ -244,7 +249,7 @@ typedef struct cl_mlp_args {
 } cl_mlp_args;
 
 #define CL_EV11_WAVES 8          /* wave slots per workgroup in ev11_part (the kernels run four or eight waves) */
-enum { CL_LIK_NORMAL_ = 0, CL_LIK_STUDENTT_ = 1 };
+enum { CL_LIK_NORMAL_ = 0, CL_LIK_STUDENTT_ = 1, CL_LIK_LAPLACE_ = 2 };      /* Laplace(Iobs, SigIobs / sqrt 2): careless/models/likelihoods/mono.py:20-23, laue.py:76-81 */
 enum { CL_BIJ_EXP_ = 0, CL_BIJ_SOFTPLUS_ = 1 };
 
 int cl_mlp_default_grid(void);                       /* workgroups of a persistent launch = CUs of the current device */

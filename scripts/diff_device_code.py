@@ -1,6 +1,7 @@
 """Are the gfx950 kernels of two builds of libcareless_hip.so the same, instruction for instruction?  (No GPU needed.)
 
     python scripts/diff_device_code.py OLD.so NEW.so
+    python scripts/diff_device_code.py --report OLD.so NEW.so      # every kernel: unchanged, or its registers / spills / scratch before -> after
 
 A change that touches host code only -- or moves a device helper from one file to another -- must leave every kernel as it was: then the
 speed of the kernels is the parent's by construction.  Both libraries are unbundled and disassembled (the tools of
@@ -57,7 +58,53 @@ def kernels_of(lib: str) -> dict:
     return {k: sorted(v, key=repr) for k, v in out.items()}
 
 
+REPORT = (".vgpr_count", ".agpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size")
+
+
+def _family(name: str) -> str:
+    """`elbo_lane_kernel` of a mangled (or demangled) kernel name: the identifier in front of the template or function arguments"""
+    m = re.match(r"_ZN?(?:12_GLOBAL__N_1)?(\d+)", name)
+    if m:
+        return name[m.end():m.end() + int(m.group(1))]
+    return re.split(r"[<(]", name.split("::")[-1])[0].split()[-1]
+
+
+def report(old_lib: str, new_lib: str) -> int:
+    """One line per kernel name: `=` (every copy unchanged instruction for instruction, resources included), `+` a kernel the new library
+    adds, or `*` with the REPORT fields of every changed copy before -> after and its instruction counts; in front of them one `#` line of
+    counts per kernel family.  Exit code 1 when a changed kernel gained spilled registers or scratch, or a kernel of the old library is missing."""
+    from collections import Counter
+    old, new = kernels_of(old_lib), kernels_of(new_lib)
+    idx = [RESOURCES.index(f) for f in REPORT]
+    worse, same, changed, added = [], [], [], []
+    for k in sorted(set(old) | set(new)):
+        if k not in old:
+            for r1, i1 in new[k]:
+                added.append(f"+ {k}: " + ", ".join(f"{n[1:]} {int(r1[i])}" for n, i in zip(REPORT, idx)) + f"; instructions {len(i1)}")
+        elif k not in new or len(old[k]) != len(new[k]):
+            worse.append(f"! {k}: missing from the new library, or another number of copies")
+        elif old[k] == new[k]:
+            same.append(k)
+        else:
+            for (r0, i0), (r1, i1) in zip(old[k], new[k]):
+                if (r0, i0) == (r1, i1):
+                    continue
+                f0, f1 = [int(r0[i]) for i in idx], [int(r1[i]) for i in idx]
+                changed.append(f"* {k}: " + ", ".join(f"{n[1:]} {a} -> {b}" for n, a, b in zip(REPORT, f0, f1)) + f"; instructions {len(i0)} -> {len(i1)}")
+                if any(b > a for a, b in zip(f0[2:], f1[2:])):
+                    worse.append(f"! {k}: gained spilled registers or scratch")
+    print(f"# {len(same)} kernel names unchanged instruction for instruction (=), {len(changed)} changed copies (*), {len(added)} added (+), {len(worse)} findings (!)")
+    for mark, names in (("=", same), ("*", [c[2:].split(":")[0] for c in changed]), ("+", [a[2:].split(":")[0] for a in added])):
+        fam = Counter(_family(n) for n in names)
+        print(f"# {mark} by family: " + (", ".join(f"{k} {v}" for k, v in sorted(fam.items())) or "none"))
+    for ln in worse + changed + added + [f"= {k}" for k in same]:
+        print(ln)
+    return 1 if worse else 0
+
+
 def main() -> int:
+    if len(sys.argv) == 4 and sys.argv[1] == "--report":
+        return report(sys.argv[2], sys.argv[3])
     if len(sys.argv) != 3:
         print(__doc__)
         return 2
