@@ -26,6 +26,16 @@
 //     by all of them: LDS operands are double-buffered by hand one MFMA group ahead (CL_SCHED_FENCE) and the post-barrier
 //     latency windows are filled with independent work (bias-gradient reads, the next layer's dZ, staging writes between the
 //     dgrad MFMAs) -- DESIGN.md section 4.1.
+//   * synchronisation of a tile's backward pass: per layer step barrier B (staging tiles complete for all 128 observations) in front of
+//     the wgrad, and barrier A (every wave done reading them) before the next step's staging writes; the tile-seam barrier is barrier A of
+//     the next tile's top layer.  In the plain-epilogue instances on up to 8 (Student-T: 32) metadata columns (`EARLY`: the common full
+//     step of a 64-wide scaler, the headline) a wave SIGNALS barrier A and the seam barrier as soon as its own last read of the staging tiles has landed: at
+//     the top of the last MFMA group of the wgrad loop in front of them (that group's operands are in registers and no read follows), so
+//     the restart after the barrier runs under 8 MFMAs per wave, and a wave that is ahead walks through the next tile's forward, epilogue,
+//     head and top-layer dgrad -- its own sS row, its own 16 columns of the staging tiles, launch-constant weight images -- up to barrier
+//     B.  Every wave executes the same barriers in the same order; the first tile needs no seam barrier (the __syncthreads() behind the
+//     weight staging), the last is followed by the flush's.  Every other instance keeps barrier A at the top of the layer step and the
+//     seam barrier in front of the backward pass (the 16-wide ones as wave-local ordering): the early form costs them spilled registers.
 // The file is compiled eight times (build.py): plain; packed layout + per-image layers (-DCL_IMGL=1, NeuralImageScaler); packed layout only
 // (-DCL_IMGL=2, single-pass Laue: harmonic group sums as lane reductions in the epilogue); layer-block chains (-DCL_CHAIN=1, scalers deeper
 // than one launch holds); and the plain, packed and chain forms once more with the epilogue's atomics turned into stores (-DCL_DET=1, the
@@ -168,6 +178,13 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
     constexpr bool WLOC = (FB == 1);                 // hidden layers are wave-local
     constexpr bool WLOC0 = WLOC && (IB1 == 1);       // ... and so is the first layer
     static_assert(!WLOC || (WgradPlan<1, 1>::KPARTS == CL_NW && WgradPlan<1, 1>::GROUPS == 1), "wave-local wgrad plan");
+    // Plain-epilogue instances on up to 8 (Student-T: up to 32) metadata columns, the headline's among them: a wave signals barrier A and the
+    // tile-seam barrier as soon as its own last read of the staging tiles has landed -- at the top of the last MFMA group of the wgrad
+    // loop in front of them, not behind that group.  Every other instance keeps the late barriers and is, instruction
+    // for instruction, what it was: there the early form costs spilled registers (profiles/r7_early_barriers_device_code.txt) -- one
+    // VGPR and 8 bytes of scratch already in the Normal instance on 32 metadata columns, which had none.
+    constexpr bool EARLY = !EPI_GEN && (DP <= 8 || (DP <= 32 && EPI == CL_EPI_PLAIN_STUDENTT));
+    static_assert(!EARLY || (!WLOC && !ILAY), "early barriers: Dense-only instances with workgroup barriers");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const sW1 = smem + SL::oW1;
@@ -789,9 +806,12 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
         STAMP(14);
 
         // ================= backward =======================================================================
-        // tile seam: every wave must be done reading the staging tiles of the previous tile's last wgrad
+        // tile seam: every wave must be done reading the staging tiles of the previous tile's last wgrad.  EARLY: each wave signalled
+        // that inside the previous tile's layer-0 wgrad (the first tile follows the __syncthreads() of the weight staging), so a wave
+        // that is ahead goes on through the head and the top layer's dgrad -- its own sS row, its own 16 columns of the staging tiles,
+        // the launch-constant weight images -- and meets the others at barrier B
         STAMP(2);
-        if (WLOC0) wave_lds_sync(); else lds_barrier();
+        if (WLOC0) wave_lds_sync(); else if (!EARLY) lds_barrier();
         STAMP(3);
         // the dO tile for the Dense(2) wgrad (wave-private), interleaved: (dL/dloc, dL/draw) of observation j at [2j, 2j+1]
         if (q == 0) *reinterpret_cast<f32x2*>(sS + 2 * j) = f32x2{dloc, draw};
@@ -807,9 +827,14 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
         constexpr bool WPIPE = WLOC;
         f32x4 pa4 = {0.0f, 0.0f, 0.0f, 0.0f}, pb4 = {0.0f, 0.0f, 0.0f, 0.0f}, pacc = {0.0f, 0.0f, 0.0f, 0.0f};
         float r0w[2][4] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+        // EARLY: "l is the top layer" as a bit test, not as `l == Lt - 1`.  Inside a block guarded by that equality hipcc rewrites hs[l] as
+        // hs[Lt - 1] BEFORE it unrolls the layer loop -- an index known only at run time, which takes the whole activation array out of
+        // registers into scratch memory (20 stores and 12 loads of 16 bytes per lane and tile) once the seam barrier is gone
+        const unsigned top_bit = EARLY ? (unsigned)opaque_uniform(1 << (Lt - 1)) : 0u;
 #pragma unroll
         for (int l = LMAX - 1; l >= 0; --l) {
-            if (l == Lt - 1 && no_head) {
+            const bool is_top = EARLY ? (((top_bit >> l) & 1u) != 0u) : (l == Lt - 1);
+            if (is_top && no_head) {
                 // head-less block of a chain: dL/dH_L comes from the next block (feature-major, like the metadata)
 #pragma unroll
                 for (int mb = 0; mb < FB; ++mb)
@@ -818,7 +843,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                         const int f = sl(16 * mb + 4 * q + t);
                         dH[mb][t] = (valid && f < ((w + 3) & ~3)) ? A.dH_ext[(size_t)f * A.n_pad + gobs] : 0.0f;
                     }
-            } else if (l == Lt - 1) {
+            } else if (is_top) {
                 // dH_L = W_o^T dO ; Dense(2) wgrad from the wave-private columns of the H staging tile
 #pragma unroll
                 for (int mb = 0; mb < FB; ++mb) {
@@ -853,7 +878,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                 if (l == pf_layer && tile + tile_step < tile_end) prefetch(tile + tile_step);
                 // dZ_l = dH_l * lrelu'(H_l)   (sign of the post-activation == sign of the pre-activation).  Only the top layer
                 // does it here: for the others it was done one step earlier, in the shadow of the wgrad operand reads (below)
-                if (l == Lt - 1) {
+                if (is_top) {
 #pragma unroll
                     for (int mb = 0; mb < FB; ++mb)
 #pragma unroll
@@ -912,8 +937,8 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) { pa4[t] = 0.0f; pb4[t] = 0.0f; }
                 }
-                // barrier A: the previous layer's wgrad reads are complete
-                if (l < Lt - 1) { if (WLOC) wave_lds_sync(); else lds_barrier(); }
+                // barrier A: the previous layer's wgrad reads are complete (EARLY: signalled inside that wgrad, below)
+                if (l < Lt - 1) { if (WLOC) wave_lds_sync(); else if (!EARLY) lds_barrier(); }
                 STAMP(6);
                 // staging writes of this wave's 16 columns: dZ_l into sZ and H_{l-1} into sH.  With a dgrad to run (l > 0) they
                 // are issued BETWEEN its MFMAs (both only read registers), so the LDS write phase costs no matrix-pipe time
@@ -1041,6 +1066,13 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                             nb = *reinterpret_cast<const f32x4*>(pb + 16 * (g + 1));
                             if (WG::BPW == 2) nc = *reinterpret_cast<const f32x4*>(pb + 16 * PB + 16 * (g + 1));
                         }
+                        if (EARLY && g + 1 == WG::KLEN / 16 && tile + tile_step < tile_end) {
+                            // early tile-seam barrier of the NEXT tile (workgroup-uniform condition: all waves or none; after the last
+                            // tile the flush's __syncthreads() follows): this wave's last read of the staging tiles has landed
+                            STAMP(9);
+                            lds_barrier();
+                            STAMP(3);
+                        }
                         CL_SCHED_FENCE();
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
@@ -1094,6 +1126,14 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                             na = *reinterpret_cast<const f32x4*>(pa + 16 * (g + 1));
                             nb = *reinterpret_cast<const f32x4*>(pb + 16 * (g + 1));
                             if (WG::BPW == 2) nc = *reinterpret_cast<const f32x4*>(pb + 16 * PB + 16 * (g + 1));
+                        }
+                        if (EARLY && g + 1 == WG::KLEN / 16) {
+                            // early barrier A of layer step l-1.  The wait the last group's MFMAs need anyway is lgkmcnt(0): this wave's
+                            // a4 / b4 / c4 / z4 reads have all landed, no read of the staging tiles follows, and it writes nothing to them
+                            // before the next dgrad -- so it signals now and the barrier's restart hides under 8 MFMAs per wave
+                            STAMP(9);
+                            lds_barrier();
+                            STAMP(6);
                         }
                         CL_SCHED_FENCE();
 #pragma unroll
