@@ -34,14 +34,19 @@ import torch
 from careless_amd import _lib
 from careless_amd._lib import AdamArgs, DetArgs, FrozenArgs, LaueArgs, MlpArgs, RefPriorArgs, TnArgs, check, ptr
 from careless_amd.models.base import BaseModel
+from careless_amd.models.scaling.image import image_layer_layout
+from careless_amd.models.scaling.nn import dense_layout, dense_slices
 # (re-exported: the tests, bench.py and scripts import the sharding / layout names from here)
-from careless_amd.obs import (GRANULE, ObsChunks, ObsData, Shard, _EmptyObs, _ShardRows, _np, laue_group_shard, launch_row_limit,  # noqa: F401
-                              make_shard, owner_bounds, owner_shard, pack_by_image, pack_laue)
-from careless_amd.wide import WidePath
+from careless_amd.obs import (GRANULE, ObsChunks, ObsData, Shard, _EmptyObs, _ShardRows, _np, _tiles, image_order, laue_group_shard,  # noqa: F401
+                              launch_row_limit, make_shard, meta_by_image, meta_feature_major, meta_row_major, owner_bounds, owner_shard,
+                              pack_by_image, pack_laue)
+from careless_amd.wide import WidePath, WideShape, hidden_forward, row_chunks
 
 TILE = _lib.CL_MLP_TILE
 REFPRIOR_KINDS = {"normal": _lib.CL_REFPRIOR_NORMAL, "laplace": _lib.CL_REFPRIOR_LAPLACE, "studentt": _lib.CL_REFPRIOR_STUDENTT,
                   "rice_woolfson": _lib.CL_REFPRIOR_RICE_WOOLFSON}       # ReferencePrior.engine_kind -> cl_refprior_args.kind
+BIJ_KINDS = {"exp": _lib.CL_BIJ_EXP, "softplus": _lib.CL_BIJ_SOFTPLUS}       # MetadataScaler.scale_bijector -> cl_mlp_args.bij_kind
+FORWARD_CHUNK_BYTES = 256 << 20       # `scaler_forward`, layer by layer: bytes of its two alternating hidden buffers; sizes the row chunk
 HISTORY_KEYS = ("loss", "F KLDiv", "NLL", "Grad Norm")
 
 
@@ -63,6 +68,26 @@ def _copy_args(ma: MlpArgs) -> MlpArgs:
     return a
 
 
+def scaler_fields(a: MlpArgs, mlp, d: int, pmlp: int, imgl=None, pimgl=None, tile_img=None, row_map=None) -> MlpArgs:
+    """The scaler's own fields of `cl_mlp_args`, filled in one place for the training step (`ElboEngine._mlp_args`) and the forward-only
+    path (`scaler_forward`): the Dense stack at `pmlp`, the per-image layers `imgl` at `pimgl`, and what a packed layout adds (`a.n_pad` is set)."""
+    a.mlp = pmlp
+    a.d, a.w, a.L, a.leak = d, mlp.width, mlp.n_layers, mlp.leakiness
+    a.bij_kind, a.eps = BIJ_KINDS[mlp.scale_bijector], mlp.epsilon
+    if row_map is not None:
+        a.n_obs, a.row_map = a.n_pad, ptr(row_map)       # packed: validity is per row (row_map / refl_id = -1)
+    if imgl is not None:
+        a.imgl, a.n_imgl, a.n_images, a.tile_img = pimgl, imgl.n_image_layers, imgl.max_images, ptr(tile_img)
+    return a
+
+
+def block_fields(a: MlpArgs, b: "LayerBlock", pmlp: int, x: int) -> MlpArgs:
+    """`a` turned into the launch of block `b` of a chain: its slice of the parameters at `pmlp`, its input `x` (metadata or the previous block's output)."""
+    a.mlp = pmlp + 4 * b.off
+    a.d, a.L, a.meta_t = b.d_in, b.l1 - b.l0, x
+    return a
+
+
 # ------------------------------------------------------------------------------------------------------------
 # layout of the flat parameter vector
 # ------------------------------------------------------------------------------------------------------------
@@ -75,7 +100,7 @@ class FlatLayout:
     seg_owner: List[str]       # "q" | "scaler" | "likelihood" per tensor (for --freeze-*)
     n_ev11: int = 0            # 3 with the Evans-2011 error model
     n_dwr: int = 0             # number of ASUs with --optimize-double-wilson-r
-    n_imgl: int = 0            # floats of the per-image layers (NeuralImageScaler): K * M * (w*w + w)
+    n_imgl: int = 0            # floats of the per-image layers (NeuralImageScaler: `image_layer_layout`)
 
     @property
     def n(self) -> int:
@@ -105,23 +130,19 @@ class FlatLayout:
 def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_dwr: int = 0, imgl=None) -> FlatLayout:
     """`imgl` = (K, M): K per-image layers over M images (NeuralImageScaler)."""
     seg, owner = [0, R, 2 * R], ["q", "q"]
-    off, fan_in = 2 * R, d
-    for _ in range(L):
-        off += w * fan_in; seg.append(off); owner.append("scaler")
-        off += w; seg.append(off); owner.append("scaler")
-        fan_in = w
-    off += 2 * fan_in; seg.append(off); owner.append("scaler")
-    off += 2; seg.append(off); owner.append("scaler")
+    for _, out, _, ob in dense_slices(d, w, L):       # kernel and bias of every Dense layer, then of the head
+        seg += [2 * R + ob, 2 * R + ob + out]; owner += ["scaler", "scaler"]
+    off = seg[-1]
     P = off - 2 * R
     if n_img > 0:
         off += n_img; seg.append(off); owner.append("scaler")
     n_imgl = 0
     if imgl is not None:
         K, M = imgl
-        for _ in range(K):               # ImageLayer kernel (M, w, w) and bias (M, w) (image.py:76-88)
-            off += M * w * w; seg.append(off); owner.append("scaler")
-            off += M * w; seg.append(off); owner.append("scaler")
-        n_imgl = K * M * (w * w + w)
+        blocks, n_imgl = image_layer_layout(K, M, w)
+        for ow, ob in blocks:                # ImageLayer kernel (M, w, w) and bias (M, w) (image.py:76-88)
+            seg += [off + ob, off + ob + M * w]; owner += ["scaler", "scaler"]
+        off += n_imgl
     for _ in range(n_ev11):              # Sdfac, Sdadd, SdB: three scalar variables (mono.py:42-44)
         off += 1; seg.append(off); owner.append("likelihood")
     if n_dwr > 0:                        # the double-Wilson r vector (wilson.py:105-110)
@@ -151,7 +172,8 @@ def chain_plan(d: int, w: int, L: int, max_layers: int, last: int = 0) -> List[L
     else:
         K = -(-L // max_layers)
         sizes = [L // K + (1 if i < L % K else 0) for i in range(K)]
-    off_of = lambda l: 0 if l == 0 else w * d + w + (l - 1) * (w * w + w)
+    layers, head = dense_layout(d, w, L)
+    off_of = lambda l: layers[l][0] if l < L else head
     blocks, l0 = [], 0
     for k, n in enumerate(sizes):
         l1 = l0 + n
@@ -588,7 +610,7 @@ class ElboEngine(WidePath):
             self.lik_kind, self.dof, self.lik_const = _lib.CL_LIK_LAPLACE, 0.0, 0.0
         else:
             self.lik_kind, self.dof, self.lik_const = _lib.CL_LIK_NORMAL, 0.0, 0.0
-        self.bij_kind = _lib.CL_BIJ_EXP if self.mlp.scale_bijector == "exp" else _lib.CL_BIJ_SOFTPLUS
+        self.bij_kind = BIJ_KINDS[self.mlp.scale_bijector]
 
     # ------------------------------------------------------------------------------------------------------
     def _tn_args(self, step: int, u_f) -> TnArgs:
@@ -659,23 +681,15 @@ class ElboEngine(WidePath):
         a.iobs = ptr(obs.iobs); a.sig = ptr(obs.sig)
         a.n_obs, a.n_pad = obs.N, obs.n_pad
         a.obs_offset = obs.start
-        if obs.row_map is not None:
-            a.n_obs = obs.n_pad                         # packed: validity is per row (row_map / refl_id = -1)
-            a.row_map = ptr(obs.row_map)
         if obs.fused_laue:
             a.gmeta, a.tile_gmax = ptr(obs.gmeta), ptr(obs.tile_gmax)
         a.noise_row = ptr(obs.noise_row)
+        scaler_fields(a, self.mlp, self.d, self.params.data_ptr() + 4 * lay.off_mlp, self.imgl, self.params.data_ptr() + 4 * lay.off_imgl,
+                      obs.tile_img, obs.row_map)
         if self.imgl is not None:
-            a.imgl = self.params.data_ptr() + 4 * lay.off_imgl
             a.d_imgl = self.grads.data_ptr() + 4 * lay.off_imgl
-            a.n_imgl, a.n_images = self.imgl.n_image_layers, self.imgl.max_images
-            a.tile_img = ptr(obs.tile_img)
-        a.mlp = self.params.data_ptr() + 4 * lay.off_mlp
-        a.d, a.w, a.L = self.d, self.w, self.L
-        a.leak = self.mlp.leakiness
         a.use_img = 1 if lay.n_img > 0 else 0
         a.img = (self.params.data_ptr() + 4 * lay.off_img) if lay.n_img > 0 else None
-        a.bij_kind, a.eps = self.bij_kind, self.mlp.epsilon
         a.eta, a.ipred_out = self._shard_rows(obs, eta), self._shard_rows(obs, ipred_out)
         a.d_img = (self.grads.data_ptr() + 4 * lay.off_img) if lay.n_img > 0 else None
         a.partials = ptr(obs.partials)
@@ -1089,12 +1103,8 @@ class ElboEngine(WidePath):
 
     def _block_args(self, ma: MlpArgs, obs: ObsData, k: int) -> MlpArgs:
         """Arguments of block k of the chain: its slice of the parameters, its input (metadata or the previous block's output)."""
-        lay, b = self.layout, self.blocks[k]
-        a = _copy_args(ma)
-        a.mlp = self.params.data_ptr() + 4 * (lay.off_mlp + b.off)
-        a.d, a.L = b.d_in, b.l1 - b.l0
-        a.meta_t = ptr(obs.meta_t) if k == 0 else ptr(obs.chain_act[k - 1])
-        return a
+        return block_fields(_copy_args(ma), self.blocks[k], self.params.data_ptr() + 4 * self.layout.off_mlp,
+                            ptr(obs.meta_t) if k == 0 else ptr(obs.chain_act[k - 1]))
 
     def _data_term_chain(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
         """Scaler deeper than one launch: forward through the head-less blocks (activations to HBM), the last block does the
@@ -1346,11 +1356,7 @@ class ElboEngine(WidePath):
         if lay.n_img > 0:
             out.append(g[lay.off_img: lay.off_img + lay.n_img])
         if lay.n_imgl > 0:
-            K, M, w = self.imgl.n_image_layers, self.imgl.max_images, self.w
-            for k in range(K):
-                o = lay.off_imgl + k * M * (w * w + w)
-                out.append(g[o: o + M * w * w].view(M, w, w))
-                out.append(g[o + M * w * w: o + M * (w * w + w)].view(M, w))
+            out += self.imgl.layer_views(g[lay.off_imgl: lay.off_imgl + lay.n_imgl])
         if lay.n_ev11 > 0:
             out.append(g[lay.off_ev11: lay.off_ev11 + lay.n_ev11])
         if lay.n_dwr > 0:
@@ -1433,137 +1439,69 @@ def predict_moments(scale_mean, scale_std, refl_id, mom):
 
 
 def scaler_forward(mlp, metadata, imgl=None, image_id=None):
-    """loc, sigma of the scaler's Normal for every row of `metadata` via `cl_mlp_forward`; `imgl` + `image_id` add the
-    per-image layers of a `NeuralImageScaler`."""
+    """loc, sigma of the scaler's Normal for every row of `metadata`, forward only; `imgl` + `image_id` add the per-image layers of a
+    `NeuralImageScaler`.  One question to `cl_mlp_route`, then one of three routes: the fused `cl_mlp_forward` on the whole scaler, a chain
+    of layer blocks where a Dense-only scaler is deeper than one launch holds (`chain_plan`), or layer by layer (`_forward_layers`)."""
     dev = require_gpu("MLPScaler.call")
-    lib = _lib.get_lib()
+    lib, st = _lib.get_lib(), _stream()
     md = _np(metadata).astype(np.float32)
     md = md.reshape(md.shape[0], -1) if md.ndim > 1 else md.reshape(-1, 1)
-    N, d = md.shape
-    mlp.build(d)
-    if mlp.flat.device != dev:
-        mlp.flat = mlp.flat.to(dev)
-    # no route for the forward-only launch on the whole scaler: a chain of layer blocks (Dense layers only) or layer by layer
-    fwd = _lib.mlp_route(lib, 1, d=d, w=mlp.width, L=mlp.n_layers, S=1, meta_t=1, mlp=1, loc_out=1, sig_out=1, **(
-        dict(row_map=1, tile_img=1, imgl=1, n_imgl=imgl.n_image_layers, n_images=imgl.max_images) if imgl is not None else {}))
-    chain = fwd == _lib.CL_ROUTE_NONE and imgl is None and mlp.width <= 64 and d <= 64
-    if fwd == _lib.CL_ROUTE_NONE and not chain:
-        # wider (or, with per-image layers, deeper) than the fused kernel holds: the layer-by-layer GEMM kernels (see
-        # ElboEngine._data_term_wide), forward only; per-image layers run grouped on the rows sorted by image
-        w, L, st = mlp.width, mlp.n_layers, _stream()
-        order = seg = None
-        keep = []
-        if imgl is not None:
-            imgl.build(d)
-            if imgl.flat.device != dev:
-                imgl.flat = imgl.flat.to(dev)
-            ids = _np(image_id).reshape(-1).astype(np.int64)
-            if ids.size != N or (ids.size and (ids.min() < 0 or ids.max() >= imgl.max_images)):
-                raise ValueError("image_id does not match the metadata / exceeds max_images")
-            order = np.argsort(ids, kind="stable")
-            md = md[order]
-            seg = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=imgl.max_images))]).astype(np.int64)
-        ld0, ldw = int(lib.cl_wide_ld(d)), int(lib.cl_wide_ld(w))
-        chunk = max(128, min(N, ((256 << 20) // (8 * max(ld0, ldw))) // 128 * 128))
-        if seg is None:
-            chunks = [(a, min(N, a + chunk), 0, None) for a in range(0, N, chunk)]
-        else:                                   # whole images per chunk
-            chunks, m0, M = [], 0, imgl.max_images
-            while m0 < M:
-                m1 = m0 + 1
-                while m1 < M and seg[m1 + 1] - seg[m0] <= chunk:
-                    m1 += 1
-                if seg[m1] > seg[m0]:
-                    chunks.append((int(seg[m0]), int(seg[m1]), m0, torch.as_tensor((seg[m0:m1 + 1] - seg[m0]).astype(np.int32), device=dev)))
-                m0 = m1
-            chunk = max(b - a for a, b, _, _ in chunks)
-        loc = torch.empty(N, dtype=torch.float32, device=dev)
-        sig = torch.empty(N, dtype=torch.float32, device=dev)
-        x = torch.zeros(chunk * ld0, dtype=torch.float32, device=dev)
-        hb = [torch.zeros(chunk * ldw, dtype=torch.float32, device=dev) for _ in range(2)]
-        bij = _lib.CL_BIJ_EXP if mlp.scale_bijector == "exp" else _lib.CL_BIJ_SOFTPLUS
-        base = mlp.flat.data_ptr()
-        for a, b, m0, sg in chunks:
-            x.view(chunk, ld0)[: b - a, :d] = torch.as_tensor(md[a:b], device=dev)
-            src, off, fan_in, nl = (x.data_ptr(), ld0), 0, d, 0
-            for l in range(L):
-                dst = hb[nl & 1]
-                check(lib.cl_wide_dense_forward(src[0], src[1], base + 4 * off, base + 4 * (off + w * fan_in), b - a, fan_in, w, mlp.leakiness, 1,
-                                                ptr(dst), ldw, None, st), "cl_wide_dense_forward")
-                src, off, fan_in, nl = (dst.data_ptr(), ldw), off + w * fan_in + w, w, nl + 1
-            for k in range(imgl.n_image_layers if imgl is not None else 0):
-                dst = hb[nl & 1]
-                M = imgl.max_images
-                kb = imgl.flat.data_ptr() + 4 * k * M * (w * w + w)
-                if w > 128:                         # wider than the grouped streaming kernel holds: the tiled kernel over a list of row pieces
-                    from careless_amd.wide import image_tiles
-                    tl = image_tiles(sg.cpu().numpy(), dev)
-                    keep.append(tl)
-                    check(lib.cl_wide_image_forward_tiles(src[0], src[1], kb + 4 * m0 * w * w, kb + 4 * (M * w * w + m0 * w), ptr(sg), ptr(tl), tl.numel() // 2,
-                                                          w, mlp.leakiness, ptr(dst), ldw, None, st), "cl_wide_image_forward_tiles")
-                else:
-                    check(lib.cl_wide_image_forward(src[0], src[1], kb + 4 * m0 * w * w, kb + 4 * (M * w * w + m0 * w), ptr(sg), sg.numel() - 1, b - a, w,
-                                                    mlp.leakiness, ptr(dst), ldw, None, st), "cl_wide_image_forward")
-                src, nl = (dst.data_ptr(), ldw), nl + 1
-            check(lib.cl_wide_head_forward(src[0], src[1], base + 4 * off, b - a, w, bij, mlp.epsilon, loc.data_ptr() + 4 * a,
-                                           sig.data_ptr() + 4 * a, None, st), "cl_wide_head_forward")
-        if order is not None:                   # back to the caller's row order
-            inv = torch.as_tensor(order, device=dev)
-            loc_c, sig_c = torch.empty_like(loc), torch.empty_like(sig)
-            loc_c[inv], sig_c[inv] = loc, sig
-            return loc_c, sig_c
-        return loc, sig
-    keep = []
+    (N, d), w, L = md.shape, mlp.width, mlp.n_layers
+    for net in (mlp,) if imgl is None else (mlp, imgl):
+        net.build(d)
+        if net.flat.device != dev:
+            net.flat = net.flat.to(dev)
+    ids = None if imgl is None else _np(image_id).reshape(-1).astype(np.int64)
+    if imgl is not None and (ids.size != N or (ids.size and (ids.min() < 0 or ids.max() >= imgl.max_images))):
+        raise ValueError("image_id does not match the metadata / exceeds max_images")
+    packed = dict(row_map=1, tile_img=1, imgl=1, n_imgl=imgl.n_image_layers, n_images=imgl.max_images) if imgl is not None else {}
+    fwd = _lib.mlp_route(lib, 1, d=d, w=w, L=L, S=1, meta_t=1, mlp=1, loc_out=1, sig_out=1, **packed)
+    loc, sig = (torch.empty(N, dtype=torch.float32, device=dev) for _ in range(2))
+    if fwd == _lib.CL_ROUTE_NONE and (imgl is not None or w > 64 or d > 64):
+        return _forward_layers(lib, mlp, md, imgl, ids, loc, sig, dev, st)
+    a, tile_img, row_map = MlpArgs(), None, None
     if imgl is not None:
-        imgl.build(d)
-        if imgl.flat.device != dev:
-            imgl.flat = imgl.flat.to(dev)
-        ids = _np(image_id).reshape(-1).astype(np.int64)
-        if ids.size != N or (ids.size and (ids.min() < 0 or ids.max() >= imgl.max_images)):
-            raise ValueError("image_id does not match the metadata / exceeds max_images")
-        pos, n_pad, tile_img, row_map = pack_by_image(ids)
-        meta_t = np.zeros((int(lib.cl_mlp_meta_rows(d)), n_pad), dtype=np.float32)
-        meta_t[:d, pos] = md.T
-        keep = [torch.as_tensor(tile_img, device=dev), torch.as_tensor(row_map, device=dev)]
+        meta_t, _, n_pad, tile_img, row_map = meta_by_image(md, ids, int(lib.cl_mlp_meta_rows(d)))
+        tile_img, row_map = torch.as_tensor(tile_img, device=dev), torch.as_tensor(row_map, device=dev)
     else:
-        n_pad = ((N + TILE - 1) // TILE) * TILE
-        meta_t = np.zeros((int(lib.cl_mlp_meta_rows(d)), n_pad), dtype=np.float32)
-        meta_t[:d, :N] = md.T
-    meta_t = torch.as_tensor(meta_t, device=dev)
-    loc = torch.empty(N, dtype=torch.float32, device=dev)
-    sig = torch.empty(N, dtype=torch.float32, device=dev)
-    a = MlpArgs()
-    a.meta_t, a.n_obs, a.n_pad = ptr(meta_t), N, n_pad
-    a.mlp = ptr(mlp.flat)
-    a.d, a.w, a.L, a.leak = d, mlp.width, mlp.n_layers, mlp.leakiness
-    a.bij_kind = _lib.CL_BIJ_EXP if mlp.scale_bijector == "exp" else _lib.CL_BIJ_SOFTPLUS
-    a.eps = mlp.epsilon
-    a.S, a.R = 1, 1
-    a.loc_out, a.sig_out = ptr(loc), ptr(sig)
-    if imgl is not None:
-        a.n_obs = n_pad
-        a.imgl, a.n_imgl, a.n_images = ptr(imgl.flat), imgl.n_image_layers, imgl.max_images
-        a.tile_img, a.row_map = ptr(keep[0]), ptr(keep[1])
+        n_pad = _tiles(N)
+        meta_t = meta_feature_major(md, int(lib.cl_mlp_meta_rows(d)), n_pad, slice(0, N))
+    a.n_obs, a.n_pad, a.S, a.R, a.loc_out, a.sig_out = N, n_pad, 1, 1, ptr(loc), ptr(sig)
+    scaler_fields(a, mlp, d, ptr(mlp.flat), imgl, ptr(imgl.flat) if imgl is not None else None, tile_img, row_map)
     grid = min(max(1, int(lib.cl_mlp_default_grid())), n_pad // TILE)
-    if chain:
-        # deeper than one launch: chain of layer blocks (see ElboEngine._data_term_chain)
-        blocks = chain_plan(d, mlp.width, mlp.n_layers, int(lib.cl_mlp_max_layers(mlp.width)))
-        rows = int(lib.cl_mlp_meta_rows(mlp.width))
-        x = meta_t
-        for b in blocks:
-            a.mlp = mlp.flat.data_ptr() + 4 * b.off
-            a.d, a.L, a.meta_t = b.d_in, b.l1 - b.l0, ptr(x)
-            if not b.final:
-                y = torch.zeros(rows, n_pad, dtype=torch.float32, device=dev)
-                a.act_out = ptr(y)
-                check(lib.cl_mlp_forward(C.byref(a), grid, _stream()), "cl_mlp_forward")
-                keep.append(x)
-                x = y
-            else:
-                a.act_out = None
-                check(lib.cl_mlp_forward(C.byref(a), grid, _stream()), "cl_mlp_forward")
-        return loc, sig
-    check(lib.cl_mlp_forward(C.byref(a), grid, _stream()), "cl_mlp_forward")
+    # one launch holds the scaler, or a chain of blocks, the activations between them in feature-major buffers (ElboEngine._data_term_chain)
+    blocks = [LayerBlock(0, L, d, 0, 0, True)] if fwd != _lib.CL_ROUTE_NONE else chain_plan(d, w, L, int(lib.cl_mlp_max_layers(w)))
+    act_rows = int(lib.cl_mlp_meta_rows(w)) if len(blocks) > 1 else 0
+    xs = [torch.as_tensor(meta_t, device=dev)]
+    for b in blocks:
+        block_fields(a, b, ptr(mlp.flat), ptr(xs[-1]))
+        if not b.final:
+            xs.append(torch.zeros(act_rows, n_pad, dtype=torch.float32, device=dev))
+        a.act_out = None if b.final else ptr(xs[-1])
+        check(lib.cl_mlp_forward(C.byref(a), grid, st), "cl_mlp_forward")
+    return loc, sig
+
+
+def _forward_layers(lib, mlp, md, imgl, ids, loc, sig, dev, st):
+    """`scaler_forward` on a scaler no fused launch holds: the layer-by-layer GEMM kernels (ElboEngine._data_term_wide), forward only, in
+    row chunks of whole images (rows sorted by image: the per-image layers run grouped), the metadata uploaded chunk by chunk."""
+    (N, d), w, L = md.shape, mlp.width, mlp.n_layers
+    sh = WideShape(d, w, L, imgl.n_image_layers if imgl is not None else 0, imgl.max_images if imgl is not None else 0, mlp.leakiness)
+    perm, seg = image_order(ids, sh.M) if imgl is not None else (None, None)
+    ld0, ldw = int(lib.cl_wide_ld(d)), int(lib.cl_wide_ld(w))
+    rm = meta_row_major(md if perm is None else md[perm], ld0)
+    chunks, tiles, rows = row_chunks(N, seg, max(128, min(N, (FORWARD_CHUNK_BYTES // (8 * max(ld0, ldw))) // 128 * 128)), w, dev)
+    x = torch.zeros(rows * ld0, dtype=torch.float32, device=dev)
+    hb = [torch.zeros(rows * ldw, dtype=torch.float32, device=dev) for _ in range(2)]
+    for ch in chunks:
+        x.view(rows, ld0)[: ch.b - ch.a] = torch.as_tensor(rm[ch.a:ch.b], device=dev)
+        hs = hidden_forward(lib, ptr(mlp.flat), ptr(imgl.flat) if imgl is not None else None, sh, (x.data_ptr(), ld0),
+                            [hb[l & 1].data_ptr() for l in range(L + sh.K)], ldw, ch, tiles and tiles[ch.a], None, st)
+        check(lib.cl_wide_head_forward(*hs[-1], ptr(mlp.flat) + 4 * dense_layout(d, w, L)[1], ch.b - ch.a, w, BIJ_KINDS[mlp.scale_bijector], mlp.epsilon,
+                                       loc.data_ptr() + 4 * ch.a, sig.data_ptr() + 4 * ch.a, None, st), "cl_wide_head_forward")
+    if perm is not None:                    # back to the caller's row order
+        inv = torch.as_tensor(perm, device=dev)
+        loc[inv], sig[inv] = loc.clone(), sig.clone()
     return loc, sig
 
 

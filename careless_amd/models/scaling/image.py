@@ -19,6 +19,13 @@ def _to_index(x, device):
     return x.reshape(-1).to(device=device, dtype=torch.int64)
 
 
+def image_layer_layout(K: int, M: int, w: int):
+    """`NeuralImageScaler.flat` (the `cl_mlp_args.imgl` layout of include/careless_hip.h), the one place that walks it: [(kernel offset,
+    bias offset)] of the K per-image layers -- layer k's block is the kernels [M][w][w], then the biases [M][w] -- and the total."""
+    block = M * (w * w + w)
+    return [(k * block, k * block + M * w * w) for k in range(K)], K * block
+
+
 class ImageScaler(Scaler):
     """Simple linear image scales (reference image.py:9-42)."""
 
@@ -108,22 +115,24 @@ class NeuralImageScaler(Scaler):
         self.metadata_scaler.build(d, device=device)
         if self.flat is not None:
             return
-        K, M, w = self.n_image_layers, self.max_images, self.width
-        flat = torch.zeros(K * M * (w * w + w), dtype=torch.float32)
-        for k in range(K):
-            o = k * M * (w * w + w)
-            flat[o:o + M * w * w] = torch.eye(w).repeat(M, 1, 1).reshape(-1)      # tf.eye(w, w, (M,)) (image.py:73-74)
+        M, w = self.max_images, self.width
+        layers, total = image_layer_layout(self.n_image_layers, M, w)
+        flat = torch.zeros(total, dtype=torch.float32)
+        for ow, ob in layers:
+            flat[ow:ob] = torch.eye(w).repeat(M, 1, 1).reshape(-1)      # tf.eye(w, w, (M,)) (image.py:73-74)
         self.flat = flat.to(device) if device is not None else flat
 
     @property
     def image_weights(self):
         """[kernel_0 (M, w, w), bias_0 (M, w), kernel_1, ...] views into the flat buffer (kernel[m] maps in -> out as W h)."""
-        K, M, w = self.n_image_layers, self.max_images, self.width
+        return self.layer_views(self.flat)
+
+    def layer_views(self, flat: torch.Tensor):
+        """[kernel_0 (M, w, w), bias_0 (M, w), kernel_1, ...] as views into `flat`, a vector laid out like `self.flat`."""
+        M, w = self.max_images, self.width
         out = []
-        for k in range(K):
-            o = k * M * (w * w + w)
-            out.append(self.flat[o:o + M * w * w].view(M, w, w))
-            out.append(self.flat[o + M * w * w:o + M * (w * w + w)].view(M, w))
+        for ow, ob in image_layer_layout(self.n_image_layers, M, w)[0]:
+            out += [flat[ow:ob].view(M, w, w), flat[ob:ob + M * w].view(M, w)]
         return out
 
     @property

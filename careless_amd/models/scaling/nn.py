@@ -27,6 +27,24 @@ def _parse_bijector(scale_bijector) -> str:
     raise ValueError(f"Unsupported scale bijector type, {scale_bijector}")
 
 
+def dense_layout(d: int, w: int, L: int):
+    """The scaler's flat W^T layout (include/careless_hip.h), the one place that walks it: [(kernel offset, bias offset, fan-in)] of the
+    L Dense layers of width w on d columns -- every kernel stored transposed, [w][fan-in], then its bias --, and the offset of the
+    Dense(2) head behind them (kernel [2][fan-in], then 2 biases)."""
+    layers, off, fan_in = [], 0, d
+    for _ in range(L):
+        layers.append((off, off + w * fan_in, fan_in))
+        off, fan_in = off + w * fan_in + w, w
+    return layers, off
+
+
+def dense_slices(d: int, w: int, L: int):
+    """`dense_layout` tensor by tensor: [(kernel offset, out, in, bias offset)] of every Dense layer, the Dense(2) head last."""
+    layers, head = dense_layout(d, w, L)
+    fan_in = w if L else d
+    return [(ow, w, i, ob) for ow, ob, i in layers] + [(head, 2, fan_in, head + 2 * fan_in)]
+
+
 class NormalDistribution:
     """What `scaler(inputs)` returns: Normal(loc, scale) optionally shifted (tfb.Shift, nn.py:84-87) and scaled by the
     per-observation image scale (tfb.Scale, image.py:60-63).  Tensors stay on the device of the scaler."""
@@ -67,20 +85,11 @@ class MetadataScaler(Scaler):
 
     # -- parameters ---------------------------------------------------------------------------------------
     def param_count(self, d: int) -> int:
-        w, L = self.width, self.n_layers
-        return w * d + w + (L - 1) * (w * w + w) + 2 * w + 2
+        return self.layer_slices(d)[-1][3] + 2
 
     def layer_slices(self, d: Optional[int] = None):
-        """[(kernel_offset, out, in, bias_offset)] per Dense layer in the flat W^T layout."""
-        d = self.input_dim if d is None else d
-        w, L = self.width, self.n_layers
-        out, off, fan_in = [], 0, d
-        for _ in range(L):
-            out.append((off, w, fan_in, off + w * fan_in))
-            off += w * fan_in + w
-            fan_in = w
-        out.append((off, 2, fan_in, off + 2 * fan_in))
-        return out
+        """[(kernel_offset, out, in, bias_offset)] per Dense layer in the flat W^T layout, the Dense(2) head last."""
+        return dense_slices(self.input_dim if d is None else d, self.width, self.n_layers)
 
     def build(self, d: int, device=None):
         """Identity-initialised kernels (tf.eye(in, out), also when non-square) and zero biases (nn.py:62-78)."""

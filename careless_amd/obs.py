@@ -1,7 +1,8 @@
 """Device images of observation sets and the data-parallel splits of the observation axis (host side, numpy + torch tensors):
 `Shard` / `make_shard` / `owner_shard` / `laue_group_shard` (who takes which rows), `pack_by_image` / `pack_laue` (the packed orders
-of the per-image-layer and single-pass Laue kernels), `select_rows` -> `lay_out` (`layout_plain` / `_by_image` / `_laue` / `_wide` fill
-a host `Layout`) -> `ObsData` (one launch's arrays in HBM: selection, layout, upload), `ObsChunks` (a shard cut into several
+of the per-image-layer and single-pass Laue kernels), `meta_feature_major` / `meta_by_image` / `meta_row_major` / `image_order` (the
+metadata images and the order by image, from plain arrays: the layouts and the forward-only scaler path share them), `select_rows` ->
+`lay_out` (`layout_plain` / `_by_image` / `_laue` / `_wide` fill a host `Layout`) -> `ObsData` (one launch's arrays in HBM: selection, layout, upload), `ObsChunks` (a shard cut into several
 launches), `launch_row_limit`.  Split out of careless_amd/engine.py in round 4; the engine re-exports every name.
 
 What the arrays replace in the reference: the `inputs` tuple of `BaseModel.input_index` order (careless/models/base.py:22-121) as
@@ -301,12 +302,32 @@ def _scatter(v: np.ndarray, pos, n_pad: int, fill) -> np.ndarray:
     return out
 
 
-def _meta_t(s: Selection, meta_rows: int, n_pad: int, pos) -> np.ndarray:
-    """The feature-major metadata image, written once: rows d .. meta_rows - 1 and the padding columns are zero."""
-    d = s.metadata.shape[1]
+def meta_feature_major(md: np.ndarray, meta_rows: int, n_pad: int, pos) -> np.ndarray:
+    """The feature-major metadata image [meta_rows][n_pad] of the rows `md` [N][d], row i at column pos[i], written once: rows
+    d .. meta_rows - 1 and the padding columns are zero."""
     meta_t = np.zeros((meta_rows, n_pad), dtype=np.float32)
-    meta_t[:d, pos] = s.metadata[s.sl].T
+    meta_t[:md.shape[1], pos] = md.T
     return meta_t
+
+
+def meta_by_image(md: np.ndarray, image_id: np.ndarray, meta_rows: int):
+    """The feature-major image of `md` in the packed order of `pack_by_image`: (meta_t, pos, n_pad, tile_img, row_map)."""
+    pos, n_pad, tile_img, row_map = pack_by_image(image_id)
+    return meta_feature_major(md, meta_rows, n_pad, pos), pos, n_pad, tile_img, row_map
+
+
+def meta_row_major(md: np.ndarray, meta_ld: int) -> np.ndarray:
+    """The row-major metadata image [N][meta_ld] of the layer-by-layer path: the features, zero padding behind them."""
+    rm = np.zeros((md.shape[0], meta_ld), dtype=np.float32)
+    rm[:, :md.shape[1]] = md
+    return rm
+
+
+def image_order(image_id: np.ndarray, n_images: int):
+    """Rows grouped by image for the grouped GEMM kernels: (perm, img_seg) -- the stable order by image (stored position -> row) and the
+    first stored row of every image, int64 [n_images + 1]."""
+    seg = np.concatenate([[0], np.cumsum(np.bincount(image_id, minlength=n_images))]).astype(np.int64)
+    return np.argsort(image_id, kind="stable"), seg
 
 
 def _slot_ids(s: Selection) -> dict:
@@ -322,14 +343,13 @@ def layout_plain(s: Selection, meta_rows: int) -> Layout:
     noise_row = None
     if s.rows is not None and s.harmonic_id is None:      # (every plain-layout kernel reads the per-row noise key when it is given)
         noise_row = _scatter(s.rows.astype(np.int32), slice(0, s.N), n_pad, 0)
-    return Layout(n_pad, _meta_t(s, meta_rows, n_pad, slice(0, s.N)), s.refl_id, s.image_id, s.iobs, s.sig, rows=s.rows, noise_row=noise_row,
+    return Layout(n_pad, meta_feature_major(s.metadata[s.sl], meta_rows, n_pad, slice(0, s.N)), s.refl_id, s.image_id, s.iobs, s.sig, rows=s.rows, noise_row=noise_row,
                   **_slot_ids(s))
 
 
 def layout_by_image(s: Selection, meta_rows: int) -> Layout:
     """Per-image layers: rows grouped by image, every image padded to whole tiles (`pack_by_image`)."""
-    pos, n_pad, tile_img, row_map = pack_by_image(s.image_id)
-    meta_t = _meta_t(s, meta_rows, n_pad, pos)
+    meta_t, pos, n_pad, tile_img, row_map = meta_by_image(s.metadata[s.sl], s.image_id, meta_rows)
     rid, img, iobs, sig = s.refl_id, s.image_id, s.iobs, s.sig
     if s.harmonic_id is None:           # the mono likelihood runs inside the fused kernel: its inputs are packed too
         rid, img = _scatter(rid, pos, n_pad, -1), _scatter(img, pos, n_pad, 0)
@@ -346,7 +366,7 @@ def layout_laue(s: Selection, meta_rows: int, lp) -> Layout:
     # the formatter pads every empty slot with the same (1.0, 1.0) (reference io/formatter.py:637-640): their terms are one term times
     # their number -- the engine then launches the slot kernel on ONE slot with the weight multiplied (round 5: 29 us per step at 5 M rows)
     pi, ps = s.iobs[G:], s.sig[G:]
-    return Layout(n_pad, _meta_t(s, meta_rows, n_pad, pos), _scatter(s.refl_id, pos, n_pad, -1), _scatter(s.image_id, pos, n_pad, 0),
+    return Layout(n_pad, meta_feature_major(s.metadata[s.sl], meta_rows, n_pad, pos), _scatter(s.refl_id, pos, n_pad, -1), _scatter(s.image_id, pos, n_pad, 0),
                   _scatter(s.iobs[hid], pos, n_pad, 0.0), _scatter(s.sig[hid], pos, n_pad, 1.0), rows=s.rows, row_index=s.rows,
                   row_map=row_map, tile_img=tile_img, gmeta=gmeta, tile_gmax=tile_gmax,
                   # a shard of whole harmonic groups: rows are not a contiguous range
@@ -358,21 +378,19 @@ def layout_wide(s: Selection, meta_ld: int, sort_images: bool = False, n_images=
     """Scaler wider than the fused kernel holds: layer-by-layer GEMMs on the row-major metadata [rows][ld] (the features, zero padding
     to a multiple of four; ElboEngine._data_term_wide).  Monochromatic rows are their own "harmonic group" (harmonic_id NULL): the slot
     kernels then ARE the mono likelihood."""
-    d = s.metadata.shape[1]
-    rm = np.zeros((s.N, meta_ld), dtype=np.float32)
-    rm[:, :d] = s.metadata[s.sl]
+    rm = meta_row_major(s.metadata[s.sl], meta_ld)
     lay = Layout(_tiles(s.N), np.zeros((4, 4), dtype=np.float32), s.refl_id, s.image_id, s.iobs, s.sig, rows=s.rows, meta_rm=rm, meta_ld=meta_ld,
                  **_slot_ids(s))
     if sort_images:
         # per-image layers on this path: the rows of an image must be consecutive (grouped GEMM kernels); everything per row
         # is stored in image order, `perm` maps the local order back to the caller's
-        perm = lay.perm = np.argsort(s.image_id, kind="stable")
+        perm, lay.img_seg = image_order(s.image_id, int(n_images or (s.image_id.max() + 1)))
+        lay.perm = perm
         lay.refl_id, lay.image_id, lay.meta_rm = s.refl_id[perm], s.image_id[perm], rm[perm]
         if s.harmonic_id is None:                   # (mono: a row is its own slot; Laue keeps iobs / sig per slot)
             lay.iobs, lay.sig = s.iobs[perm], s.sig[perm]
         else:
             lay.harmonic_id = lay.harmonic_id[perm]
-        lay.img_seg = np.concatenate([[0], np.cumsum(np.bincount(lay.image_id, minlength=int(n_images or (lay.image_id.max() + 1))))]).astype(np.int64)
         # global rows in the stored (image) order: the noise key of every row, and which columns of an injected eta are its
         lay.rows = lay.row_index = (s.rows if s.rows is not None else np.arange(s.start, s.start + s.N))[perm]
     return lay

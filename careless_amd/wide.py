@@ -12,6 +12,8 @@ import numpy as np
 import torch
 
 from careless_amd._lib import check, ptr
+from careless_amd.models.scaling.image import image_layer_layout
+from careless_amd.models.scaling.nn import dense_layout
 from careless_amd.obs import ObsData
 
 
@@ -29,6 +31,65 @@ def image_tiles(rel_seg: np.ndarray, device) -> torch.Tensor:
 # The Dense(2) head of one row chunk, for the top layer's epilogue: the head's offset in the scaler's flat layout, the device pointers of the
 # chunk's loc / sigma rows and of its d sigma / d raw rows (None unless the head's backward pass is fused into the top layer's backward)
 WideHead = namedtuple("WideHead", "off loc sig dsd")
+# A scaler as the layer-by-layer launches see it: d columns, L Dense layers of width w, K per-image layers over M images, LeakyReLU slope
+WideShape = namedtuple("WideShape", "d w L K M leak")
+# One row chunk [a, b): its first image and the device array of its images' row starts relative to a (0, None without per-image layers)
+RowChunk = namedtuple("RowChunk", "a b m0 seg")
+
+
+def image_chunks(img_seg, chunk: int):
+    """Whole images per row chunk: [(a, b, first image, row starts of the chunk's images relative to a)] from `img_seg`, the first row of
+    every image of rows sorted by image.  Images are taken while they fit `chunk` rows; an image longer than that gets a chunk of its
+    own; empty images in front of a chunk are skipped (those inside or behind one ride along as empty groups)."""
+    seg, M = np.asarray(img_seg, dtype=np.int64), len(img_seg) - 1
+    out, m0 = [], 0
+    while m0 < M:
+        m1 = m0 + 1
+        while m1 < M and seg[m1 + 1] - seg[m0] <= chunk:
+            m1 += 1
+        if seg[m1] > seg[m0]:
+            out.append((int(seg[m0]), int(seg[m1]), m0, (seg[m0:m1 + 1] - seg[m0]).astype(np.int32)))
+        m0 = m1
+    return out
+
+
+def row_chunks(N: int, img_seg, chunk: int, w: int, device):
+    """The `RowChunk`s of N rows for the layer-by-layer launches -- `chunk` rows each, or whole images (`image_chunks`) when `img_seg` is
+    given --, the tile list of every chunk by its first row (`image_tiles`, made here, once: per-image layers wider than 128; else None),
+    and the rows the work buffers need: `chunk`, or the longest chunk of whole images."""
+    if img_seg is None:
+        return [RowChunk(a, min(N, a + chunk), 0, None) for a in range(0, N, chunk)], None, chunk
+    walk = image_chunks(img_seg, chunk)
+    tiles = {a: image_tiles(rel, device) for a, _, _, rel in walk} if w > 128 else None
+    return [RowChunk(a, b, m0, torch.as_tensor(rel, device=device)) for a, b, m0, rel in walk], tiles, max(b - a for a, b, _, _ in walk)
+
+
+def imgl_ptrs(base: int, sh: WideShape, k: int, m0: int):
+    """Device pointers of (kernel, bias) of image m0 in per-image layer k of the per-image block at `base` (parameters or gradients)."""
+    ow, ob = image_layer_layout(sh.K, sh.M, sh.w)[0][k]
+    return base + 4 * (ow + m0 * sh.w * sh.w), base + 4 * (ob + m0 * sh.w)
+
+
+def hidden_forward(lib, pmlp: int, pimgl, sh: WideShape, src, dsts, ldw: int, ch: RowChunk, tiles, sf, st, layers=None):
+    """The unfused hidden-layer launches of one row chunk, the one place that issues them: of the L + K hidden layers those in `layers` (a
+    range; default all) -- a Dense layer through cl_wide_dense_forward, a per-image layer (image.py:116-125) through cl_wide_image_forward,
+    or _tiles above width 128.  `pmlp` / `pimgl`: device pointers of the scaler's flat parameters and of its per-image block; `src`: the
+    (pointer, ld) of the first of these layers' input; `dsts[l]`: where layer l's output goes (row pitch `ldw`); `tiles`: the chunk's tile
+    list; `sf`: the stop flag.
+    Returns the (pointer, ld) of every output."""
+    dense, n, hs = dense_layout(sh.d, sh.w, sh.L)[0], ch.b - ch.a, [src]
+    for l in (range(sh.L + sh.K) if layers is None else layers):
+        if l < sh.L:
+            ow, ob, fan_in = dense[l]
+            check(lib.cl_wide_dense_forward(*hs[-1], pmlp + 4 * ow, pmlp + 4 * ob, n, fan_in, sh.w, sh.leak, 1, dsts[l], ldw, sf, st), "cl_wide_dense_forward")
+        elif sh.w > 128:                # wider than the grouped streaming kernel holds: the tiled kernel over the chunk's list of row pieces
+            check(lib.cl_wide_image_forward_tiles(*hs[-1], *imgl_ptrs(pimgl, sh, l - sh.L, ch.m0), ptr(ch.seg), ptr(tiles), tiles.numel() // 2,
+                                                  sh.w, sh.leak, dsts[l], ldw, sf, st), "cl_wide_image_forward_tiles")
+        else:
+            check(lib.cl_wide_image_forward(*hs[-1], *imgl_ptrs(pimgl, sh, l - sh.L, ch.m0), ptr(ch.seg), ch.seg.numel() - 1, n, sh.w, sh.leak,
+                                            dsts[l], ldw, sf, st), "cl_wide_image_forward")
+        hs.append((dsts[l], ldw))
+    return hs[1:]
 
 
 class WidePath:
@@ -75,43 +136,17 @@ class WidePath:
         if obs.wide_chunks is not None:
             return obs.wide_chunks
         W = self._wide_setup()
-        chunks = []
-        if self.imgl is None:
-            chunks = [(a, min(obs.N, a + W["chunk"]), 0, None) for a in range(0, obs.N, W["chunk"])]
-        else:
-            seg, M = obs.img_seg, len(obs.img_seg) - 1
-            m0 = 0
-            while m0 < M:
-                m1 = m0 + 1
-                while m1 < M and seg[m1 + 1] - seg[m0] <= W["chunk"]:
-                    m1 += 1
-                if seg[m1] > seg[m0]:
-                    rel = torch.as_tensor((seg[m0:m1 + 1] - seg[m0]).astype(np.int32), device=self.device)
-                    chunks.append((int(seg[m0]), int(seg[m1]), m0, rel))
-                    if self.w > 128:            # wider than the grouped streaming kernel holds: the tiled kernel's list of row pieces
-                        if obs.wide_tiles is None:
-                            obs.wide_tiles = {}
-                        obs.wide_tiles[int(seg[m0])] = image_tiles(seg[m0:m1 + 1] - seg[m0], self.device)
-                m0 = m1
-            self._wide_buffers(max(b - a for a, b, _, _ in chunks))
-        obs.wide_chunks = chunks
-        return chunks
+        obs.wide_chunks, obs.wide_tiles, rows = row_chunks(obs.N, obs.img_seg if self.imgl is not None else None, W["chunk"], self.w, self.device)
+        self._wide_buffers(rows)
+        return obs.wide_chunks
 
-    def _wide_layers(self):
-        """(offset of Wt, offset of b, fan-in) of every Dense layer inside the scaler's flat W^T layout, then the head's offset."""
-        out, off, fan_in = [], 0, self.d
-        for _ in range(self.L):
-            out.append((off, off + self.w * fan_in, fan_in))
-            off += self.w * fan_in + self.w
-            fan_in = self.w
-        return out, off
+    def _wide_shape(self) -> WideShape:
+        K, M = (self.imgl.n_image_layers, self.imgl.max_images) if self.imgl is not None else (0, 0)
+        return WideShape(self.d, self.w, self.L, K, M, self.mlp.leakiness)
 
     def _imgl_ptrs(self, flat: torch.Tensor, k: int, m0: int):
-        """Device pointers of (kernel, bias) of image m0 in per-image layer k inside `flat` (params or grads): the layer's block is
-        [W: n_images x (w x w) | b: n_images x w] (include/careless_hip.h)."""
-        M, w = self.imgl.max_images, self.w
-        base = flat.data_ptr() + 4 * (self.layout.off_imgl + k * M * (w * w + w))
-        return base + 4 * m0 * w * w, base + 4 * (M * w * w + m0 * w)
+        """Device pointers of (kernel, bias) of image m0 in per-image layer k inside `flat` (params or grads)."""
+        return imgl_ptrs(flat.data_ptr() + 4 * self.layout.off_imgl, self._wide_shape(), k, m0)
 
     WIDE_KEEP_BUDGET = 64 << 30     # bytes of activations of a whole observation set the forward pass may keep for the backward pass
     # The fusions of round 4, each with the separate launches it replaced still behind it (the fallback of shapes outside the fused
@@ -153,56 +188,44 @@ class WidePath:
         """Hidden layers on one row chunk of `obs`: layer l's output lands in acts[l] when `keep` (else two buffers alternate), or
         in the chunk's rows of the whole-set buffers `full`.  Returns the (buffer, ld) pairs of h_0 .. h_(L + K), whether `head` (a WideHead)
         rode in the top layer's epilogue and whether the slot likelihood `lik` did too."""
-        a, b, m0, seg = chunk
-        lib, W = self.lib, self._wide_setup()
-        n, ldw, base = b - a, W["ldw"], self.params.data_ptr() + 4 * self.layout.off_mlp
-        layers, _ = self._wide_layers()
+        a, n = chunk.a, chunk.b - chunk.a
+        lib, W, sh = self.lib, self._wide_setup(), self._wide_shape()
+        ldw, base = W["ldw"], self.params.data_ptr() + 4 * self.layout.off_mlp
+        layers, _ = dense_layout(self.d, self.w, self.L)
         sf, leak = ptr(self.stop_flag), self.mlp.leakiness
-        dst_of = (lambda l: full[l].data_ptr() + 4 * a * ldw) if full is not None else (lambda l: W["acts"][l if keep else l & 1].data_ptr())
+        dsts = [None if t is None else t.data_ptr() + 4 * a * ldw for t in full] if full is not None else \
+            [W["acts"][l if keep else l & 1].data_ptr() for l in range(self.L + sh.K)]
+        unfused = lambda src, l0, l1: hidden_forward(lib, base, self.params.data_ptr() + 4 * self.layout.off_imgl, sh, src, dsts, ldw, chunk,
+                                                     obs.wide_tiles and obs.wide_tiles[a], sf, st, range(l0, l1))
         hs = [(obs.meta_rm.data_ptr() + 4 * a * obs.meta_ld, obs.meta_ld)]
         head_fused = lik_fused = False
-        pre = self._wide_pre()
-        for l, (ow, ob, fan_in) in enumerate(layers):
-            if pre and l == 0:
-                hs.append((None, ldw))          # h_0 is never stored: layer 1's launch makes it from the metadata
-                continue
-            dst = dst_of(l)
-            if pre and l == 1:
-                (ow0, ob0, d0) = layers[0]
-                head_fused = head is not None and self.L == 2 and self.imgl is None
-                hd = head if head_fused else WideHead(0, None, None, None)
-                check(lib.cl_wide_dense2_forward(*hs[0], d0, base + 4 * ow0, base + 4 * ob0, base + 4 * ow, base + 4 * ob, n, self.w, self.w,
-                                                 leak, dst, ldw, (base + 4 * hd.off) if head_fused else None, self.bij_kind, self.mlp.epsilon,
-                                                 hd.loc, hd.sig, sf, st), "cl_wide_dense2_forward")
-            elif head is not None and l == self.L - 1 and self.imgl is None and fan_in <= 128 and self.w <= 128:
-                # the top layer carries the Dense(2) head in its epilogue: (loc, sigma) come out of the same pass
-                top = (*hs[-1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, dst, ldw,
-                       base + 4 * head.off, self.bij_kind, self.mlp.epsilon, head.loc, head.sig, head.dsd)
-                rc = -2
-                if lik is not None:
-                    # ... and the slot likelihood of the chunk's rows too: (loc, sigma) never wait in memory for a launch of their own
-                    rc = lib.cl_wide_dense_forward_head_lik(*top, C.byref(lik), sf, st)
-                    if rc != -2:
-                        check(rc, "cl_wide_dense_forward_head_lik")
-                        lik_fused = True
-                if rc == -2:
-                    check(lib.cl_wide_dense_forward_head(*top, sf, st), "cl_wide_dense_forward_head")
-                head_fused = True
-            else:
-                check(lib.cl_wide_dense_forward(*hs[-1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, 1, dst, ldw, sf, st), "cl_wide_dense_forward")
-            hs.append((dst, ldw))
-        for k in range(self.imgl.n_image_layers if self.imgl is not None else 0):       # image.py:116-125
-            l = self.L + k
-            dst = dst_of(l)
-            wk, bk = self._imgl_ptrs(self.params, k, m0)
-            if self.w > 128:
-                tl = obs.wide_tiles[a]
-                check(lib.cl_wide_image_forward_tiles(*hs[-1], wk, bk, ptr(seg), ptr(tl), tl.numel() // 2, self.w, leak, dst, ldw, sf, st),
-                      "cl_wide_image_forward_tiles")
-            else:
-                check(lib.cl_wide_image_forward(*hs[-1], wk, bk, ptr(seg), seg.numel() - 1, n, self.w, leak, dst, ldw, sf, st), "cl_wide_image_forward")
-            hs.append((dst, ldw))
-        return hs, head_fused, lik_fused
+        first = 0
+        if self._wide_pre():
+            # h_0 is never stored: layer 1's launch makes it from the metadata
+            (ow0, ob0, d0), (ow, ob, _), first = layers[0], layers[1], 2
+            head_fused = head is not None and self.L == 2 and self.imgl is None
+            hd = head if head_fused else WideHead(0, None, None, None)
+            check(lib.cl_wide_dense2_forward(*hs[0], d0, base + 4 * ow0, base + 4 * ob0, base + 4 * ow, base + 4 * ob, n, self.w, self.w,
+                                             leak, dsts[1], ldw, (base + 4 * hd.off) if head_fused else None, self.bij_kind, self.mlp.epsilon,
+                                             hd.loc, hd.sig, sf, st), "cl_wide_dense2_forward")
+            hs += [(None, ldw), (dsts[1], ldw)]
+        ow, ob, fan_in = layers[-1]
+        if not (head is not None and self.L > first and self.imgl is None and fan_in <= 128 and self.w <= 128):
+            return hs + unfused(hs[-1], first, self.L + sh.K), head_fused, lik_fused
+        # the top layer carries the Dense(2) head in its epilogue: (loc, sigma) come out of the same pass
+        hs += unfused(hs[-1], first, self.L - 1)
+        top = (*hs[-1], base + 4 * ow, base + 4 * ob, n, fan_in, self.w, leak, dsts[self.L - 1], ldw,
+               base + 4 * head.off, self.bij_kind, self.mlp.epsilon, head.loc, head.sig, head.dsd)
+        rc = -2
+        if lik is not None:
+            # ... and the slot likelihood of the chunk's rows too: (loc, sigma) never wait in memory for a launch of their own
+            rc = lib.cl_wide_dense_forward_head_lik(*top, C.byref(lik), sf, st)
+            if rc != -2:
+                check(rc, "cl_wide_dense_forward_head_lik")
+                lik_fused = True
+        if rc == -2:
+            check(lib.cl_wide_dense_forward_head(*top, sf, st), "cl_wide_dense_forward_head")
+        return hs + [(dsts[self.L - 1], ldw)], True, lik_fused
 
     def _data_term_wide(self, obs: ObsData, step: int, eta, ipred_out, st):
         """Hidden / metadata width > 64 (or more hidden layers with per-image layers than one fused launch holds): unfused scaler on
@@ -213,7 +236,7 @@ class WidePath:
         lib = self.lib
         chunks = self._wide_chunks(obs)
         ma = self._mlp_args(step, eta, ipred_out, obs)
-        _, off_head = self._wide_layers()
+        _, off_head = dense_layout(self.d, self.w, self.L)
         pbase = self.params.data_ptr() + 4 * self.layout.off_mlp
         # The activations of ALL rows are kept by the forward pass when they fit (WIDE_KEEP_BUDGET, a quarter of the free memory at
         # most: 15 GB for 10 M rows of a 3 x 128 scaler on a 288-GB device) and the backward pass starts from them -- 6 P_mm flops per
@@ -229,7 +252,7 @@ class WidePath:
         # shape (-2), the same for every chunk
         want_lik = (self.FUSE_LIK and obs.harmonic_id is None and eta is None and ipred_out is None and not self.ev11 and not self.deterministic)
         for ch in chunks:
-            a, b = ch[0], ch[1]
+            a, b = ch.a, ch.b
             loc, sig = obs.laue_loc.data_ptr() + 4 * a, obs.laue_sig.data_ptr() + 4 * a
             head = WideHead(off_head, loc, sig, obs.wide_dsd.data_ptr() + 4 * a if headb else None)
             lik = self._slot_args(ma, obs, step, None, None, a, b - a) if want_lik else None
@@ -253,7 +276,7 @@ class WidePath:
         a, b, m0, seg = chunk
         n = b - a
         lib, W = self.lib, self._wide_setup()
-        layers, off_head = self._wide_layers()
+        layers, off_head = dense_layout(self.d, self.w, self.L)
         pbase, gbase = (t.data_ptr() + 4 * self.layout.off_mlp for t in (self.params, self.grads))
         sf, leak, w, ldw = ptr(self.stop_flag), self.mlp.leakiness, self.w, W["ldw"]
         dz, dzn = W["dz"]

@@ -7,7 +7,9 @@ Every callable export of the loaded library object is wrapped (tests/test_epilog
 engine per entry of tests/test_nonfinite.py's MATRIX -- every route of the library at the smallest shapes that still have a ragged last
 tile, padded slots or several blocks -- plus chunked shards (plain, deterministic, a chain with a lane block, a frozen scaler), the three class flags flipped, an explicit
 reflection-owner shard and shards of harmonic groups.  Each engine runs two `train_step` calls and one `evaluate_nll` on a `make_obs`
-set with in-kernel noise, then the same with injected `u_f` / `eta` and a `forward_backward` with `ipred_out`.
+set with in-kernel noise, then the same with injected `u_f` / `eta` and a `forward_backward` with `ipred_out`.  Behind them the
+forward-only scaler path (`engine.scaler_forward`) on each of its routes: the cases of tests/test_scaler_forward.py, one
+`model.scaling_model(inputs)` and one `model.scale_mean_stddev(inputs)` each, the unbalanced-image case a second time in row chunks of 128.
 
 One line per call: the entry point, its return value, every scalar argument, every non-pointer struct field, and for every pointer null,
 "outside" (a flag of a query, a host buffer) or [byte size of the live device storage that holds it, offset into it] -- the storages are
@@ -200,6 +202,21 @@ def shard_case(tr, name, kw, shard_of, det=False, frozen=False, injected=True, e
             del os.environ[k]
 
 
+def forward_case(tr, name, budget=None):
+    """The forward-only scaler path on a case of tests/test_scaler_forward.py (`budget`: `engine.FORWARD_CHUNK_BYTES` for the run)."""
+    from careless_amd import engine
+    from tests import test_scaler_forward as SF
+    model, inputs = SF.build(name[len("forward_"):].replace("_chunk128", ""))[:2]
+    old = engine.FORWARD_CHUNK_BYTES
+    try:
+        if budget is not None:
+            engine.FORWARD_CHUNK_BYTES = budget
+        _phase(tr, f"{name}: scaling_model(inputs)", lambda: model.scaling_model(inputs))
+        _phase(tr, f"{name}: scale_mean_stddev(inputs)", lambda: model.scale_mean_stddev(inputs))
+    finally:
+        engine.FORWARD_CHUNK_BYTES = old
+
+
 def extra_cases():
     from careless_amd.engine import make_shard, owner_shard
     from tests import test_frozen_scaler as F
@@ -219,6 +236,10 @@ def extra_cases():
     out["laue_group_shard_2x32"] = lambda tr, n: shard_case(tr, n, laue, lambda d, kw: make_shard(kw["N"], kw["R"], 1, 2))
     out["laue_group_shard_2x32_frozen"] = lambda tr, n: shard_case(tr, n, laue, lambda d, kw: make_shard(kw["N"], kw["R"], 1, 2), frozen=True,
                                                                     injected=False)
+    from tests import test_scaler_forward as SF
+    for name in SF.CASES:
+        out["forward_" + name] = forward_case
+    out[f"forward_{SF.UNBALANCED}_chunk128"] = lambda tr, n: forward_case(tr, n, SF.CHUNK_128)
     return out
 
 

@@ -788,3 +788,74 @@ def test_round6_entry_points_host_side():
     assert lib.cl_chain_dx(None, None, 10, 128, 10, 10, None, None, None) == -1
     assert lib.cl_chain_dx(1, 1, 10, 128, 16, 10, 1, None, None) == -2    # widths beyond 15
     assert lib.cl_chain_dx(1, 1, 200, 128, 10, 10, 1, None, None) == -1   # n_pad < n_obs
+
+
+# --- the scaler's flat layouts and the row-chunk walk, each written once (nn.dense_layout, image.image_layer_layout, wide.image_chunks) ------
+def test_dense_layout_is_what_the_library_the_scaler_the_flat_layout_and_the_chain_plan_count():
+    from careless_amd.engine import chain_plan
+    from careless_amd.models.scaling.nn import dense_layout
+    lib = _lib.get_lib()
+    for d in (1, 5, 37, 70):
+        for w in (3, 10, 16, 64, 96):
+            for L in (1, 2, 13, 24):
+                layers, head = dense_layout(d, w, L)
+                P = head + 2 * w + 2
+                assert P == int(lib.cl_mlp_param_count(d, w, L)) == MLPScaler(L, w).param_count(d)
+                assert [f for _, _, f in layers] == [d] + [w] * (L - 1) and layers[0][0] == 0
+                for (ow, ob, f), nxt in zip(layers, [l[0] for l in layers[1:]] + [head]):       # kernel, bias, next kernel: no gap
+                    assert ob == ow + w * f and nxt == ob + w
+                slices = MLPScaler(L, w).layer_slices(d)
+                assert slices == [(ow, w, f, ob) for ow, ob, f in layers] + [(head, 2, w, head + 2 * w)]
+                lay = make_layout(R=11, d=d, w=w, L=L, n_img=0)
+                bounds = [x for _, o, _, ob in slices for x in (ob, ob + o)]              # the end of every kernel and of every bias
+                assert lay.P == P and lay.seg_off == [0, 11, 22] + [22 + x for x in bounds]
+                for m in (3, 10):
+                    for last in (0, 20):
+                        blocks, at = chain_plan(d, w, L, m, last=last), 0
+                        for b in blocks:                                                   # the blocks tile [0, P)
+                            assert b.off == at and b.P > 0 and b.d_in == (d if b.l0 == 0 else w)
+                            assert b.off == (layers[b.l0][0]) and b.final == (b is blocks[-1])
+                            at += b.P
+                        assert at == P and blocks[0].l0 == 0 and blocks[-1].l1 == L
+                        assert all(a.l1 == b.l0 for a, b in zip(blocks[:-1], blocks[1:]))
+
+
+def test_image_layer_layout_tiles_the_per_image_block():
+    from careless_amd.models.scaling.image import NeuralImageScaler, image_layer_layout
+    for K in (1, 3):
+        for M in (1, 7):
+            for w in (5, 72):
+                layers, total = image_layer_layout(K, M, w)
+                at = 0
+                for ow, ob in layers:                       # kernels [M][w][w], then biases [M][w], layer after layer
+                    assert ow == at and ob == ow + M * w * w
+                    at = ob + M * w
+                assert at == total == K * M * (w * w + w) and len(layers) == K
+                s = NeuralImageScaler(K, M, 2, w)
+                s.build(4)
+                assert s.flat.numel() == total and [tuple(t.shape) for t in s.image_weights] == [(M, w, w), (M, w)] * K
+                assert all(torch.equal(t, torch.eye(w).expand(M, w, w)) for t in s.image_weights[0::2])
+                lay = make_layout(R=3, d=4, w=w, L=2, n_img=0, imgl=(K, M))
+                assert lay.n_imgl == total and lay.seg_off[-2 * K - 1:] == [lay.off_imgl] + [lay.off_imgl + x for ow, ob in layers for x in (ob, ob + M * w)]
+
+
+def test_image_chunks_keep_whole_images_and_cover_every_row_once():
+    from careless_amd.wide import image_chunks
+    rng = np.random.default_rng(5)
+    counts = [np.array([20, 0, 280, 0])] + [rng.integers(0, 200, size=rng.integers(1, 12)) * (rng.random(1) < 2) for _ in range(10)]
+    for k, c in enumerate(counts):
+        if k:
+            c = np.where(rng.random(len(c)) < 0.3, 0, c)                    # empty images, also in front and at the end
+            c[rng.integers(len(c))] = 150                                  # (at least one row; an image longer than 128)
+        seg = np.concatenate([[0], np.cumsum(c)]).astype(np.int64)
+        for chunk in (128, 384):
+            out = image_chunks(seg, chunk)
+            assert [a for a, _, _, _ in out] == [0] + [b for _, b, _, _ in out[:-1]] and out[-1][1] == seg[-1]      # every row in exactly one chunk
+            for a, b, m0, rel in out:
+                m1 = m0 + len(rel) - 1
+                assert b > a and rel.dtype == np.int32                                                   # no chunk is empty
+                assert seg[m0] == a and seg[m1] == b and np.array_equal(rel, seg[m0:m1 + 1] - a)       # whole images: no image is split
+                assert b - a <= max(chunk, int(np.max(np.diff(rel))))                                  # at most the chunk, or its single long image
+                assert b - a <= chunk or np.count_nonzero(np.diff(rel)) == 1
+    assert [(a, b, m0, rel.tolist()) for a, b, m0, rel in image_chunks(np.array([0, 20, 20, 300, 300]), 128)] == \
+        [(0, 20, 0, [0, 20, 20]), (20, 300, 2, [0, 280])]
