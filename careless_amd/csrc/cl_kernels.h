@@ -80,6 +80,10 @@ static inline int cl_lik_check(int lik_kind, const void* ev11, const void* d_ev1
     return 0;
 }
 
+// What the entry checks of wide_gemm.hip and elbo_frozen.hip ask of their required pointers.
+template <class... P>
+static inline bool any_null(const P*... p) { return ((p == nullptr) || ...); }
+
 // Launch of a kernel instance with `sm` bytes of dynamic LDS: -3 above the 160 KB of a gfx950 workgroup, else 0 or the hipError_t.
 // The kernel is a template ARGUMENT, so the mark below -- the largest dynamic-LDS size the instance has been configured for -- is one
 // per instance: the lane, narrow and 16/32/64-wide kernels share one function-pointer type, and a mark keyed by type would publish

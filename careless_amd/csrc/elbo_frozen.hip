@@ -187,23 +187,6 @@ __global__ __launch_bounds__(256) void frozen_edges_kernel(const cl_frozen_args 
     else A.dz_f[(size_t)r * S + s] = sum;
 }
 
-// workgroups of a launch: as many as the device holds at once (a grid-stride loop over equal shares: a second, partial round of
-// workgroups would leave most of the device waiting for it), never more than cl_frozen_grid(n) (the size of nll_part / ev11_part)
-template <int TAG, class K>
-static int frozen_blocks(K kern, long long n) {
-    const int cap = cl_frozen_grid(n);
-    static std::atomic<int> resident{0};                 // (asked once per kernel: TAG tells the instances apart)
-    int g = resident.load(std::memory_order_relaxed);
-    if (g == 0) {
-        int dev = 0, cus = 0, per = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return cap;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, FB, 0) != hipSuccess || per < 1 || cus < 1) return cap;
-        g = per * cus;
-        resident.store(g, std::memory_order_relaxed);
-    }
-    return g < cap ? g : cap;
-}
-
 int cl_frozen_edge_floats(long long n, int S) { return (n <= 0 || S <= 0) ? 0 : (int)(2 * ((n + 63) / 64) * S); }
 int cl_frozen_grid(long long n) {
     long long b = (n + FB - 1) / FB;
@@ -211,40 +194,63 @@ int cl_frozen_grid(long long n) {
     return (int)(b < 1 ? 1 : b);
 }
 
-int cl_launch_frozen_rows(const cl_frozen_args& a, hipStream_t st) {
-    // (the second call of the harmonic-group form sums stored gradients: it evaluates no likelihood)
-    if (a.gmeta != nullptr || a.gbuf == nullptr)
+namespace {
+
+// The three launches cl_frozen_rows serves (include/careless_hip.h: cl_frozen_args), told apart by gmeta / gbuf.
+enum class frozen_form {
+    ROWS,       // monochromatic rows sorted by reflection: likelihood, per-reflection sums, edges
+    GROUPS,     // gmeta: harmonic groups in packed order, first call -- likelihood, per-row gradients into gbuf (no sums, no edges)
+    SUMS,       // gbuf without gmeta: second call -- the stored gradients summed per reflection, edges (evaluates no likelihood)
+};
+frozen_form frozen_form_of(const cl_frozen_args& a) {
+    return a.gmeta != nullptr ? frozen_form::GROUPS : a.gbuf != nullptr ? frozen_form::SUMS : frozen_form::ROWS;
+}
+
+// 0, or the negative code of the call -- every clause once, in the order that decides which code answers when several apply
+int frozen_check(const cl_frozen_args& a, frozen_form f) {
+    const bool lik = f != frozen_form::SUMS, edges = f != frozen_form::GROUPS;
+    if (lik)
         if (int e = cl_lik_check(a.lik_kind, a.ev11, a.d_ev11, a.ev11_part, true)) return e;
-    if (a.gmeta != nullptr) {
-        // harmonic groups, first pass: per-row amplitude gradients into gbuf (no sums, no edges)
-        if (a.n <= 0 || a.S <= 0 || a.refl_id == nullptr || a.loc == nullptr || a.sigma == nullptr || a.iobs == nullptr || a.sig == nullptr ||
-            a.z_f == nullptr || a.gbuf == nullptr || a.scalars == nullptr)
-            return -1;
-        if (a.n >= (1ll << 31) - 64) return -4;
-        if (a.ev11 != nullptr && a.d_ev11 == nullptr && a.ev11_part == nullptr) return -1;
-        (void)hipGetLastError();
-        if (a.lik_kind == CL_LIK_LAPLACE_) {
-            if (a.S == 1) hipLaunchKernelGGL(frozen_laue_laplace_kernel<1>, dim3((unsigned)frozen_blocks<4>(frozen_laue_laplace_kernel<1>, a.n)), dim3(FB), 0, st, a);
-            else hipLaunchKernelGGL(frozen_laue_laplace_kernel<8>, dim3((unsigned)frozen_blocks<5>(frozen_laue_laplace_kernel<8>, a.n)), dim3(FB), 0, st, a);
-        } else if (a.S == 1) hipLaunchKernelGGL(frozen_laue_kernel<1>, dim3((unsigned)frozen_blocks<0>(frozen_laue_kernel<1>, a.n)), dim3(FB), 0, st, a);
-        else hipLaunchKernelGGL(frozen_laue_kernel<8>, dim3((unsigned)frozen_blocks<1>(frozen_laue_kernel<8>, a.n)), dim3(FB), 0, st, a);
+    if (a.n <= 0 || a.S <= 0 || a.refl_id == nullptr) return -1;
+    if (lik && any_null(a.loc, a.sigma, a.iobs, a.sig, a.z_f, a.scalars)) return -1;
+    if (edges ? any_null(a.dz_f, a.edge_rid, a.edge_val) : a.gbuf == nullptr) return -1;        // (SUMS has its gbuf by definition)
+    // the kernels' 32-bit row indices; a reflection id beside the THROUGH flag of edge_rid
+    if (a.n >= (1ll << 31) - 64 || (edges && a.R >= THROUGH)) return -4;
+    if (a.ev11 != nullptr && a.d_ev11 == nullptr && a.ev11_part == nullptr) return -1;
+    return 0;
+}
+
+// Launch of the row-per-thread instance `Kern` over n rows on as many workgroups as the device holds at once (a grid-stride loop over
+// equal shares: a second, partial round of workgroups would leave most of the device waiting for it), never more than cl_frozen_grid(n)
+// (the size of nll_part / ev11_part).  The kernel is a template ARGUMENT, so the cache of its resident grid is one per instance (as
+// cl_launch_lds' mark: cl_kernels.h).  One process drives one device: the cache is filled for the device current at the first call.
+template <auto Kern>
+void frozen_launch(const cl_frozen_args& a, hipStream_t st) {
+    static std::atomic<int> resident{0};
+    int g = resident.load(std::memory_order_relaxed), dev = 0, cus = 0, per = 0;
+    if (g == 0 && hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, Kern, FB, 0) == hipSuccess && per >= 1 && cus >= 1)
+        resident.store(g = per * cus, std::memory_order_relaxed);
+    const int cap = cl_frozen_grid(a.n);
+    hipLaunchKernelGGL(Kern, dim3((unsigned)(g > 0 && g < cap ? g : cap)), dim3(FB), 0, st, a);
+}
+
+}  // namespace
+
+int cl_launch_frozen_rows(const cl_frozen_args& a, hipStream_t st) {
+    const frozen_form f = frozen_form_of(a);
+    if (int e = frozen_check(a, f)) return e;
+    (void)hipGetLastError();
+    // S = 1 (--mc-samples 1, the default) has its own instances; Laplace is an instance, Normal / Student-T a run-time kind (cl_math.h);
+    // SUMS evaluates no likelihood and runs the run-time-kind instance whatever lik_kind says
+    const bool one = a.S == 1, lap = a.lik_kind == CL_LIK_LAPLACE_ && f != frozen_form::SUMS;
+    if (f == frozen_form::GROUPS) {
+        if (lap) one ? frozen_launch<frozen_laue_laplace_kernel<1>>(a, st) : frozen_launch<frozen_laue_laplace_kernel<8>>(a, st);
+        else one ? frozen_launch<frozen_laue_kernel<1>>(a, st) : frozen_launch<frozen_laue_kernel<8>>(a, st);
         return (int)hipGetLastError();
     }
-    if (a.gbuf != nullptr) {
-        // ... second pass: the gradients in reflection order summed per reflection (refl_id ascending; gbuf row i, or src[i] when given)
-        if (a.n <= 0 || a.S <= 0 || a.refl_id == nullptr || a.gbuf == nullptr || a.dz_f == nullptr || a.edge_rid == nullptr || a.edge_val == nullptr) return -1;
-    } else if (a.n <= 0 || a.S <= 0 || a.refl_id == nullptr || a.loc == nullptr || a.sigma == nullptr || a.iobs == nullptr || a.sig == nullptr ||
-               a.z_f == nullptr || a.dz_f == nullptr || a.scalars == nullptr || a.edge_rid == nullptr || a.edge_val == nullptr)
-        return -1;
-    if (a.n >= (1ll << 31) - 64 || a.R >= THROUGH) return -4;
-    if (a.ev11 != nullptr && a.d_ev11 == nullptr && a.ev11_part == nullptr) return -1;
-    (void)hipGetLastError();
-    // (the second call of the harmonic-group form -- gbuf without gmeta -- evaluates no likelihood: the run-time-kind instance)
-    if (a.lik_kind == CL_LIK_LAPLACE_ && a.gbuf == nullptr) {
-        if (a.S == 1) hipLaunchKernelGGL(frozen_rows_laplace_kernel<1>, dim3((unsigned)frozen_blocks<6>(frozen_rows_laplace_kernel<1>, a.n)), dim3(FB), 0, st, a);
-        else hipLaunchKernelGGL(frozen_rows_laplace_kernel<8>, dim3((unsigned)frozen_blocks<7>(frozen_rows_laplace_kernel<8>, a.n)), dim3(FB), 0, st, a);
-    } else if (a.S == 1) hipLaunchKernelGGL(frozen_rows_kernel<1>, dim3((unsigned)frozen_blocks<2>(frozen_rows_kernel<1>, a.n)), dim3(FB), 0, st, a);
-    else hipLaunchKernelGGL(frozen_rows_kernel<8>, dim3((unsigned)frozen_blocks<3>(frozen_rows_kernel<8>, a.n)), dim3(FB), 0, st, a);
+    if (lap) one ? frozen_launch<frozen_rows_laplace_kernel<1>>(a, st) : frozen_launch<frozen_rows_laplace_kernel<8>>(a, st);
+    else one ? frozen_launch<frozen_rows_kernel<1>>(a, st) : frozen_launch<frozen_rows_kernel<8>>(a, st);
     const long long t = ((a.n + 63) / 64) * a.S;
     hipLaunchKernelGGL(frozen_edges_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, st, a);
     return (int)hipGetLastError();

@@ -1326,8 +1326,6 @@ constexpr size_t stream_lds(int NA, bool pre) { return (size_t)(16 * NA * SKP + 
 // what the entry checks repeat
 bool rows_ok(long long n) { return n >= 1 && n <= 0x7fffffffLL; }        // (a row count the kernels' 32-bit row indices hold)
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-template <class... P>
-bool any_null(const P*... p) { return ((p == nullptr) || ...); }
 
 // f(std::integral_constant<int, NA>) for the run-time block count na = LO .. 7; every other count takes the 8-block instance
 template <int LO, class F>

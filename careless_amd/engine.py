@@ -17,7 +17,7 @@ HBM layout owned by the engine (see include/careless_hip.h):
 PyTorch is used for device memory, streams and torch.distributed only.
 
 Round 4: the observation layouts and the data-parallel splits live in careless_amd/obs.py, the layer-by-layer path of scalers wider
-than 64 in careless_amd/wide.py (a mixin of `ElboEngine`); this file keeps the flat parameter layout, the step schedule and the helpers
+than 64 in careless_amd/wide.py, the data term of a step behind a frozen scaler in careless_amd/frozen.py (mixins of `ElboEngine`); this file keeps the flat parameter layout, the step schedule and the helpers
 behind the plugin protocol methods.
 """
 from __future__ import annotations
@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from careless_amd import _lib
-from careless_amd._lib import AdamArgs, DetArgs, FrozenArgs, LaueArgs, MlpArgs, RefPriorArgs, TnArgs, check, ptr
+from careless_amd._lib import AdamArgs, DetArgs, LaueArgs, MlpArgs, RefPriorArgs, TnArgs, check, ptr
+from careless_amd.frozen import FrozenPath
 from careless_amd.models.base import BaseModel
 from careless_amd.models.scaling.image import image_layer_layout
 from careless_amd.models.scaling.nn import dense_layout, dense_slices
@@ -266,9 +267,7 @@ def reference_prior_arrays(prior, R: int) -> dict:
 # ------------------------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------------------------
-class ElboEngine(WidePath):
-    FROZEN_LAUE_PACKED = True        # ... harmonic groups: packed order + the two-call form of `cl_frozen_rows` (tests flip it to compare with the three slot launches)
-    FROZEN_SORTED_ROWS = True        # a frozen scaler's monochromatic rows: sorted by reflection, `cl_frozen_rows` (round 6; tests flip it to compare with `cl_slot_rows`)
+class ElboEngine(WidePath, FrozenPath):
     SLOT_ROWS_ONE_LAUNCH = True      # rows that are their own slot: predict + log-prob + gradient in one `cl_slot_rows` launch (tests flip it)
     local_only = False               # test hook: a rank shard on one device, the per-rank partial gradient stays in place (no collective call)
     force_allreduce = False          # CARELESS_FORCE_DIST=1: a one-rank run makes every collective call of the multi-GPU step
@@ -450,12 +449,12 @@ class ElboEngine(WidePath):
         self.owner = bool(self.shard.owner)
         # A frozen scaling model (`--freeze-scales`; the half-dataset trainings of `--merge-half-datasets`, reference careless.py:102-128):
         # its output (loc, sigma) per observation does not change from step to step, so a step needs neither its forward nor its backward
-        # pass -- only the sampling / likelihood part (`_data_term_frozen`).  An engine built around a frozen scaler lays its observations out
-        # for that (plain rows in the caller's order: no packing by image or harmonic group).
+        # pass -- only the sampling / likelihood part (careless_amd/frozen.py).  An engine built around a frozen scaler lays its observations
+        # out for that (`_frozen_layout_kw`).
         want_ff = getattr(model, "frozen_scaler_fast_path", None)
         self.frozen_fast = (os.environ.get("CARELESS_HIP_FROZEN_FAST", "1") != "0") if want_ff is None else bool(want_ff)
         self._grid_arg = grid
-        self._frozen_layout = self.frozen_fast and not model.scaling_model.trainable and not (self.deterministic and self.laue)
+        self._frozen_layout = self._frozen_layout_kw() is not None
         self._frozen_epoch = 0
         self.scaler_frozen = False
         self.obs = self._build_obs(inputs, self.shard.start, self.shard.stop, grid, self.laue_groups, rows=self.shard.rows if self.owner else None)
@@ -495,11 +494,7 @@ class ElboEngine(WidePath):
         kw = dict(grid=grid, n_refl=self.R, n_images=self._max_images(), laue_groups=laue_groups, pack_images=self.imgl is not None and not self.wide,
                   sort_images=self.imgl is not None and self.wide,
                   laue_single_pass=not getattr(self.model, "laue_two_pass", False) and self.blocks is None and not self.wide, wide=self.wide)
-        if self._frozen_layout:
-            # plain rows for a frozen scaler (its output is a constant: no tile / image constraint) -- except Laue data, which keeps the packed
-            # order of the single-pass kernels (a group inside a 16-row granule) for `cl_frozen_rows`' group sums (round 6)
-            kw.update(pack_images=False, sort_images=False,
-                      laue_single_pass=bool(self.laue and self.FROZEN_LAUE_PACKED and not self.deterministic and not getattr(self.model, "laue_two_pass", False)))
+        kw.update((self._frozen_layout and self._frozen_layout_kw()) or {})
         n_total = int(_np(BaseModel.get_refl_id(inputs)).reshape(-1).shape[0])
         stop = n_total if stop is None else stop
         per = launch_row_limit(self.d, self.S if self.deterministic else 0)
@@ -589,7 +584,7 @@ class ElboEngine(WidePath):
         self.frozen.copy_(torch.as_tensor(fr))
         self.scaler_frozen = not m.scaling_model.trainable
         self._frozen_epoch += 1                          # (loc, sigma) of a frozen scaler are taken again at every train_model call
-        if self._frozen_layout and not self.scaler_frozen:
+        if self._frozen_layout and self._frozen_layout_kw() is None:
             # the scaler was frozen when the engine laid its observations out and is trainable now: the fused kernels' layouts again
             self._frozen_layout = False
             first = self.obs.children[0] if isinstance(self.obs, ObsChunks) else self.obs
@@ -874,8 +869,9 @@ class ElboEngine(WidePath):
     def _data_term_launch(self, obs: ObsData, step: int, eta, ipred_out, st, defer_reduce: bool):
         """The data term of one `ObsData`: exactly one path, then the reduction of the weight-gradient partials that goes with it."""
         lib, lay = self.lib, self.layout
-        if self.scaler_frozen and self.frozen_fast and self._frozen_ok(obs):
-            self._data_term_frozen(obs, step, eta, ipred_out, st)             # (no scaler gradient: nothing to reduce)
+        form = self._frozen_form(obs, injected=eta is not None or ipred_out is not None)
+        if form is not None:
+            self._data_term_frozen(form, obs, step, eta, ipred_out, st)       # (no scaler gradient: nothing to reduce)
             return
         if self.wide:
             self._data_term_wide(obs, step, eta, ipred_out, st)               # (reduces layer by layer)
@@ -924,143 +920,6 @@ class ElboEngine(WidePath):
         if self.deterministic:      # the padded slots' workgroups store their NLL behind the fused launch's parts
             la.nll_part, la.ev11_part = self._det_parts(obs, obs.det_parent.det["pieces"])
         check(lib.cl_laue_likelihood(C.byref(la), st), "cl_laue_likelihood")
-
-    def _frozen_ok(self, obs: ObsData) -> bool:
-        """The sampling / likelihood kernels take this observation image as it is: rows in the caller's order (not packed by image or
-        harmonic group, not sorted by image), and -- deterministic mode -- rows that are their own slot."""
-        if obs.host_inputs is None:
-            return False
-        if obs.fused_laue:
-            # harmonic groups in the packed order of the single-pass kernels (round 6): `cl_frozen_rows` in its two-call form -- an engine
-            # built around a frozen scaler keeps that layout for Laue data (_build_obs)
-            return self._frozen_layout and self.FROZEN_LAUE_PACKED and not self.deterministic and obs.tile_img is None
-        if obs.row_map is not None or obs.perm is not None:
-            return False
-        if self.imgl is not None and not self._frozen_layout:
-            return False
-        return not (self.deterministic and obs.laue)
-
-    def _data_term_frozen(self, obs: ObsData, step: int, eta, ipred_out, st):
-        """The data term of a step whose scaling model is frozen (round 5): (loc, sigma) of every row once per `train_model` call -- any
-        scaler the package runs, through `scaler_forward` -- then per step only what depends on the sampled amplitudes: sample the scale,
-        predict, log-prob and its gradient to dz_f (and the Evans-2011 terms) on the slot kernels of the two-pass path
-        (`cl_slot_rows`, or `cl_laue_predict / _likelihood / _backward` for harmonic groups).  The scaler's own gradient is not computed at
-        all: the reference takes gradients of `trainable_variables` only (variational.py:201), so its "Grad Norm" does not see it either."""
-        if obs.locsig_epoch != self._frozen_epoch:
-            sl = obs.rows if obs.rows is not None else slice(obs.start, obs.start + obs.N)
-            md = _np(BaseModel.get_metadata(obs.host_inputs))
-            md = md.reshape(md.shape[0], -1)[sl]
-            ids = _np(BaseModel.get_image_id(obs.host_inputs)).reshape(-1)[sl] if self.imgl is not None else None
-            obs.laue_loc, obs.laue_sig = scaler_forward(self.mlp, md, self.imgl, ids)
-            if obs.laue_dO is None:
-                obs.laue_dO = torch.empty(obs.N * 2, dtype=torch.float32, device=self.device)
-            if obs.laue_iconv is None and not obs.fused_laue:      # (rows that are their own slot never touch it; the entry point wants a pointer)
-                obs.laue_iconv = torch.empty(obs.N * self.S if obs.harmonic_id is not None else 4, dtype=torch.float32, device=self.device)
-            if obs.rows is not None and obs.row_index is None:
-                obs.row_index = torch.as_tensor(np.asarray(obs.rows, dtype=np.int64), device=self.device)     # the noise key of every row
-            obs.locsig_epoch = self._frozen_epoch
-        if obs.fused_laue:
-            self._frozen_laue(obs, step, eta, ipred_out, st)
-            return
-        keyed = obs.row_index is not None and (eta is not None or ipred_out is not None)      # (injected noise on rows that are not a contiguous range: the slot kernels index it by local row)
-        if obs.harmonic_id is None and not self.deterministic and self.FROZEN_SORTED_ROWS and not keyed:
-            self._frozen_rows(obs, step, eta, ipred_out, st)
-            return
-        self._slot_likelihood(self._mlp_args(step, eta, ipred_out, obs), obs, step, eta, ipred_out, st, frozen=True)
-
-    def _row_image_scales(self, image_id: torch.Tensor) -> Optional[torch.Tensor]:
-        """The image scale of every row of `image_id` (image 0 is pinned to 1: image.py:23-25); None without image scales."""
-        lay = self.layout
-        if lay.n_img <= 0:
-            return None
-        scales = torch.cat([torch.ones(1, dtype=torch.float32, device=self.device), self.params[lay.off_img: lay.off_img + lay.n_img].detach()])
-        return scales.index_select(0, image_id)
-
-    def _frozen_args(self, obs: ObsData, step: int, eta, ipred_out) -> FrozenArgs:
-        """What the row-per-thread launches of `cl_frozen_rows` share: (loc, sigma), image scale and noise key of every row from
-        `obs.frozen_sorted`, the step's constants, the set's rows of eta / ipred_out.  The caller adds the row arrays, `n` and the fields of
-        its form (`edge_*` and `accumulate`, or `gmeta` / `gbuf` / `src`)."""
-        fz = obs.frozen_sorted
-        fa = self._step_fields(FrozenArgs(), obs, step)
-        fa.loc, fa.sigma, fa.aim, fa.key = ptr(fz["loc"]), ptr(fz["sigma"]), ptr(fz["aim"]), ptr(fz["key"])
-        fa.obs_offset = int(obs.start)
-        fa.eta, fa.ipred_out = self._shard_rows(obs, eta), self._shard_rows(obs, ipred_out)
-        return fa
-
-    def _frozen_rows(self, obs: ObsData, step: int, eta, ipred_out, st):
-        """Monochromatic rows behind a frozen scaler (round 6, `cl_frozen_rows`): the rows sorted by reflection ONCE per training -- the
-        scaler's output is a constant, so no layout constraint binds their order -- with (loc, sigma), the image scale and the global row
-        number (the noise key) of every row beside them; per step one row-per-thread launch that sums the amplitude gradients of a
-        reflection's rows inside the wave and stores them (no float atomics into dz_f), plus the small launch for the runs that cross a
-        wave border.  The image scales are part of the frozen scaling model: their gradient is not computed either."""
-        fz = obs.frozen_sorted
-        if fz is None or fz["epoch"] != self._frozen_epoch:
-            dev = self.device
-            rid = obs.refl_id[: obs.N]
-            order = torch.argsort(rid, stable=True)
-            take = lambda t: t[: obs.N].index_select(0, order).contiguous()
-            aim = self._row_image_scales(obs.image_id[: obs.N].long())
-            if obs.row_index is not None:
-                key = obs.row_index[: obs.N].index_select(0, order).to(torch.int32).contiguous()
-            else:
-                key = (order + int(obs.start)).to(torch.int32).contiguous()
-            n_waves = (obs.N + 63) // 64
-            fz = obs.frozen_sorted = dict(
-                epoch=self._frozen_epoch, refl=take(rid).to(torch.int32), loc=take(obs.laue_loc), sigma=take(obs.laue_sig),
-                aim=None if aim is None else take(aim), iobs=take(obs.iobs), sig=take(obs.sig), key=key,
-                edge_rid=torch.empty(2 * n_waves, dtype=torch.int32, device=dev),
-                edge_val=torch.empty(max(int(self.lib.cl_frozen_edge_floats(obs.N, self.S)), 1), dtype=torch.float32, device=dev))
-        fa = self._frozen_args(obs, step, eta, ipred_out)
-        fa.refl_id, fa.iobs, fa.sig, fa.n = ptr(fz["refl"]), ptr(fz["iobs"]), ptr(fz["sig"]), int(obs.N)
-        # (several launches into one dz_f -- the pieces of a chunked shard -- and the double-Wilson prior, whose dlog p / dz is in dz_f
-        #  before the data term: add with atomics instead of storing)
-        fa.accumulate = 1 if (obs.is_piece or self.double_wilson) else 0
-        fa.edge_rid, fa.edge_val = ptr(fz["edge_rid"]), ptr(fz["edge_val"])
-        check(self.lib.cl_frozen_rows(C.byref(fa), st), "cl_frozen_rows")
-
-    def _frozen_laue(self, obs: ObsData, step: int, eta, ipred_out, st):
-        """Harmonic groups behind a frozen scaler (round 6): `cl_frozen_rows` twice -- in the packed order of the single-pass kernels the group
-        sums, the likelihood and every row's amplitude gradient (stored per row: the rows of a group belong to different reflections), then
-        the same rows in reflection order, gathered and summed per reflection like monochromatic rows -- and the padded slots' constant."""
-        fz = obs.frozen_sorted
-        dev = self.device
-        if obs.noise_row is not None and (eta is not None or ipred_out is not None):
-            raise NotImplementedError("injected noise / ipred_out on a shard of harmonic groups behind a frozen scaler (a parity-test input: "
-                                      "set model.frozen_scaler_fast_path = False)")
-        if fz is None or fz["epoch"] != self._frozen_epoch:
-            rm = obs.row_map.long()
-            valid = rm >= 0
-            rmc = rm.clamp(min=0)
-            loc_p = obs.laue_loc.index_select(0, rmc).contiguous()
-            sig_p = obs.laue_sig.index_select(0, rmc).contiguous()
-            aim = self._row_image_scales(obs.image_id.long().clamp(min=0))
-            key = obs.noise_row if obs.noise_row is not None else (rmc + int(obs.start)).to(torch.int32).contiguous()
-            active = torch.nonzero(valid & (obs.refl_id >= 0)).flatten()
-            order = torch.argsort(obs.refl_id.index_select(0, active), stable=True)
-            src = active.index_select(0, order)
-            refl_sorted = obs.refl_id.index_select(0, src).to(torch.int32).contiguous()
-            n2 = int(src.numel())
-            # the first pass writes a row's gradients at its position in reflection order (a 4 S-byte store per row), the second reads them front to back
-            dst = torch.full((obs.n_pad,), -1, dtype=torch.int32, device=dev)
-            dst[src] = torch.arange(n2, dtype=torch.int32, device=dev)
-            fz = obs.frozen_sorted = dict(
-                epoch=self._frozen_epoch, loc=loc_p, sigma=sig_p, aim=aim, key=key, dst=dst, refl_sorted=refl_sorted, n2=n2,
-                gbuf=torch.zeros(max(n2, 1) * self.S, dtype=torch.float32, device=dev),
-                edge_rid=torch.empty(2 * ((n2 + 63) // 64) + 2, dtype=torch.int32, device=dev),
-                edge_val=torch.empty(max(int(self.lib.cl_frozen_edge_floats(n2, self.S)), 1), dtype=torch.float32, device=dev))
-        fa = self._frozen_args(obs, step, eta, ipred_out)
-        fa.refl_id, fa.iobs, fa.sig, fa.n = ptr(obs.refl_id), ptr(obs.iobs), ptr(obs.sig), int(obs.n_pad)
-        fa.gmeta, fa.gbuf, fa.src = ptr(obs.gmeta), ptr(fz["gbuf"]), ptr(fz["dst"])
-        check(self.lib.cl_frozen_rows(C.byref(fa), st), "cl_frozen_rows (harmonic groups)")
-        if fz["n2"] > 0:            # (the second call reads the first one's gradients and nothing else of the step: a handful of fields)
-            fb = FrozenArgs()
-            fb.refl_id, fb.gbuf = ptr(fz["refl_sorted"]), ptr(fz["gbuf"])
-            fb.n, fb.R, fb.S = fz["n2"], self.R, self.S
-            fb.dz_f, fb.stop_flag = ptr(self.dz_f), ptr(self.stop_flag)
-            fb.accumulate = 1 if (obs.is_piece or self.double_wilson) else 0
-            fb.edge_rid, fb.edge_val = ptr(fz["edge_rid"]), ptr(fz["edge_val"])
-            check(self.lib.cl_frozen_rows(C.byref(fb), st), "cl_frozen_rows (per-reflection sums)")
-        self._laue_pad_slots(fa, obs, st)
 
     def _peel_bufs(self, obs: ObsData):
         """Buffers of the peeled first layer for one observation set: its pre-activations and dZ_0 (feature-major, like meta_t), the

@@ -14,7 +14,8 @@
  *     > 0 = hipError_t from the launch;  nothing throws, nothing allocates persistent device memory;
  *   - no global mutable state besides the loaded code object, with two exceptions, both monotonic and safe to race on: the
  *     per-kernel-instance mark of the largest dynamic-LDS size configured so far (csrc/cl_kernels.h: cl_launch_lds) and the
- *     occupancy cache of cl_frozen_rows (csrc/elbo_frozen.hip: frozen_blocks); calls are re-entrant across streams;
+ *     per-kernel-instance occupancy cache of cl_frozen_rows (csrc/elbo_frozen.hip: frozen_launch), filled for the device that is
+ *     current at the first call -- one process drives one device; calls are re-entrant across streams;
  *   - a NULL noise pointer (u_f / eta) selects the in-kernel counter-based generator keyed by
  *     (seed, step, sample, global element index), so results are independent of the number of GPUs.
  *
@@ -485,10 +486,27 @@ int cl_slot_rows(const cl_laue_args* args, void* stream);
  * scalars[NLL], amplitude gradient into dz_f -- equal-reflection runs are summed inside the wave and leave as ONE plain store per
  * (reflection, sample); runs that cross a wave border go through `edge_val / edge_rid` and a second small launch of the same call.  No
  * float atomic touches dz_f: the result does not depend on the run (accumulate = 1 -- several calls share dz_f, e.g. the pieces of a
- * shard -- adds with atomics instead of storing).  Rows with refl_id < 0 are skipped; monochromatic rows only (every row its own slot). */
+ * shard -- adds with atomics instead of storing).  Rows with refl_id < 0 are skipped.
+ *
+ * One entry point, THREE FORMS, told apart by gmeta and gbuf.  Monochromatic rows (every row its own slot) take the first.  Harmonic groups
+ * (Laue data, careless/models/likelihoods/laue.py:9-47: the predictions of a group's rows sum before the likelihood) take the second and
+ * then the third, because the rows of a group belong to different reflections.  Every form reads n, S, refl_id, stop_flag.
+ *   ROWS    gmeta == NULL, gbuf == NULL.  refl_id ascending.  Reads loc, sigma, aim, iobs, sig, key, obs_offset, z_f, R, the likelihood
+ *           (lik_kind, dof, lik_const, shift, w_ll, ev11), the noise (eta, or seed and step); writes scalars[NLL] or nll_part, dz_f
+ *           (accumulate), d_ev11 or ev11_part, ipred_out; workspace edge_rid, edge_val.
+ *   GROUPS  gmeta != NULL.  Rows in the packed order of the single-pass kernels (a group inside a 16-row granule; gmeta[i] = member index |
+ *           group size << 8; padding rows refl_id < 0; iobs / sig of the group replicated on its rows); refl_id need not be sorted.  Reads
+ *           what ROWS reads; group sums over shuffles, likelihood, NLL (member 0); instead of dz_f the row's amplitude gradients are STORED
+ *           at gbuf[src ? src[i] : i][s] (src[i] < 0: nowhere) -- with src[i] = the row's position in reflection order the SUMS call reads
+ *           gbuf front to back.  dz_f, accumulate, R, edge_* unused.
+ *   SUMS    gmeta == NULL, gbuf != NULL.  refl_id ascending over the rows that have a reflection; row i's gradients at gbuf[src ? src[i] : i]:
+ *           summed per reflection into dz_f (accumulate) as for ROWS; reads R; workspace edge_rid, edge_val.  Evaluates no likelihood:
+ *           loc / sigma / iobs / sig / z_f / scalars and lik_kind unused.
+ * Returns -1 for a missing buffer of the form, n or S < 1, a lik_kind nobody compiles or Laplace beside an Evans-2011 buffer (ROWS, GROUPS),
+ * ev11 without d_ev11 and ev11_part; -4 for n >= 2^31 - 64 and, where edges are written (ROWS, SUMS), R >= 2^30. */
 typedef struct cl_frozen_args {
-    const int* refl_id;         /* [n] ascending                                                                   */
-    const float* loc;           /* [n] scaler mean per row (cl_mlp_forward / the wide path), in the sorted order   */
+    const int* refl_id;         /* [n] ascending (ROWS, SUMS)                                                      */
+    const float* loc;           /* [n] scaler mean per row (cl_mlp_forward / the wide path), in the order of refl_id */
     const float* sigma;         /* [n] scaler sigma per row                                                        */
     const float* aim;           /* [n] image scale per row, or NULL (= 1): image.py:53-63 with the scale frozen    */
     const float* iobs;          /* [n]                                                                             */
@@ -511,19 +529,13 @@ typedef struct cl_frozen_args {
     float* d_ev11;              /* [3] +=                                                                          */
     int* edge_rid;              /* [2 * ceil(n / 64)] workspace                                                    */
     float* edge_val;            /* [cl_frozen_edge_floats(n, S)] workspace                                         */
-    double* nll_part;           /* optional [cl_frozen_grid(n)]: every workgroup STORES its NLL (no fp64 atomic)   */
+    double* nll_part;           /* optional [cl_frozen_grid(n)]: every workgroup STORES its NLL (no fp64 atomic).  The launch runs on as many
+                                   workgroups as the device holds at once -- sized for the device current at the process' first call -- and never
+                                   more than cl_frozen_grid(n); slots behind the launch's grid are not written     */
     float* ev11_part;           /* optional [3 * 4 * cl_frozen_grid(n)]: every wave stores its Evans-2011 terms    */
-    /* Harmonic groups (Laue data, careless/models/likelihoods/laue.py:9-47: the predictions of a group's rows sum before the likelihood) take
-     * TWO calls, because the rows of a group belong to different reflections:
-     *   1. gmeta != NULL: rows in the packed order of the single-pass kernels (a group inside a 16-row granule; gmeta[i] = member index |
-     *      group size << 8; padding rows refl_id < 0; iobs / sig of the group replicated on its rows): group sums over shuffles, likelihood,
-     *      NLL (member 0), the row's amplitude gradients STORED at gbuf[src ? src[i] : i][s] (src[i] < 0: nowhere) -- with src[i] = the row's
-     *      position in reflection order the second call reads gbuf front to back.  refl_id need not be sorted; dz_f / edge_* unused.
-     *   2. gmeta == NULL, gbuf != NULL: refl_id ascending over the rows that have a reflection; row i's gradients at gbuf[src ? src[i] : i]: summed
-     *      per reflection and stored into dz_f as for monochromatic rows (loc / sigma / iobs / sig / z_f / scalars unused).             */
-    const int* gmeta;
-    float* gbuf;                /* [rows][S]                                                                        */
-    const int* src;
+    const int* gmeta;           /* [n] GROUPS: member index | group size << 8                                      */
+    float* gbuf;                /* [rows][S] GROUPS writes, SUMS reads                                             */
+    const int* src;             /* optional [n] GROUPS, SUMS: row i's row of gbuf                                  */
 } cl_frozen_args;
 int cl_frozen_rows(const cl_frozen_args* args, void* stream);
 int cl_frozen_edge_floats(long long n, int S);     /* floats of edge_val */

@@ -790,6 +790,48 @@ def test_round6_entry_points_host_side():
     assert lib.cl_chain_dx(1, 1, 200, 128, 10, 10, 1, None, None) == -1   # n_pad < n_obs
 
 
+# --- `cl_frozen_rows`: three forms behind one entry point (csrc/elbo_frozen.hip: frozen_check) -------------------------------------------------
+_FP = 0x10000          # a made-up device address: every call below returns before anything is launched or dereferenced
+_F_ROWS = dict(refl_id=_FP, loc=_FP, sigma=_FP, iobs=_FP, sig=_FP, z_f=_FP, dz_f=_FP, scalars=_FP, edge_rid=_FP, edge_val=_FP)      # monochromatic rows
+_F_GROUPS = dict(refl_id=_FP, loc=_FP, sigma=_FP, iobs=_FP, sig=_FP, z_f=_FP, scalars=_FP, gmeta=_FP, gbuf=_FP)                     # harmonic groups, first call
+_F_SUMS = dict(refl_id=_FP, gbuf=_FP, dz_f=_FP, edge_rid=_FP, edge_val=_FP)                                                         # ... second call: per-reflection sums
+_BIG_N, _BIG_R = (1 << 31) - 64, 1 << 30
+
+
+def test_cl_frozen_rows_rejections():
+    """Per form: a call the library would ACCEPT (never made: it would launch), and one rejecting call per clause its checks distinguish --
+    a missing pointer, n / S not positive, the likelihood (the two forms that evaluate one), Evans-2011 raw parameters without a place
+    for their gradient, the 32-bit bounds (-4), and which of -1 and -4 answers when both apply."""
+    import ctypes as C
+    lib = _lib.get_lib()
+
+    def call(base, **over):
+        a = _lib.FrozenArgs()
+        for k, v in dict(dict(base, n=100, S=2, R=50, lik_kind=_lib.CL_LIK_NORMAL), **over).items():
+            setattr(a, k, v)
+        return lib.cl_frozen_rows(C.byref(a), None)
+
+    for name, base in (("rows", _F_ROWS), ("groups", _F_GROUPS), ("sums", _F_SUMS)):
+        lik, edges = base is not _F_SUMS, base is not _F_GROUPS
+        cases = [(-1, {k: None}) for k in base]                          # (a NULL gmeta / gbuf names another form, which misses its own buffers)
+        cases += [(-1, dict(n=0)), (-1, dict(n=-3)), (-1, dict(S=0)), (-1, dict(ev11=_FP)), (-1, dict(ev11=_FP, nll_part=_FP)),
+                  (-4, dict(n=_BIG_N)), (-4, dict(n=_BIG_N, ev11=_FP)), (-1, dict(n=_BIG_N, refl_id=None)), (-1, dict(n=_BIG_N, S=0))]
+        if edges:
+            cases += [(-4, dict(R=_BIG_R)), (-1, dict(R=_BIG_R, dz_f=None)), (-4, dict(R=_BIG_R, ev11=_FP))]
+        else:           # no edges, no bound on R: the clause behind it answers
+            cases += [(-1, dict(R=_BIG_R, ev11=_FP))]
+        if lik:
+            cases += [(-1, dict(lik_kind=3)), (-1, dict(lik_kind=-1)), (-1, dict(lik_kind=3, n=_BIG_N))]
+            for k in ("ev11", "d_ev11", "ev11_part"):                    # Laplace beside an Evans-2011 buffer; the check comes before the bounds
+                cases += [(-1, {"lik_kind": _lib.CL_LIK_LAPLACE, k: _FP}), (-1, {"lik_kind": _lib.CL_LIK_LAPLACE, k: _FP, "n": _BIG_N})]
+        else:           # no likelihood check: neither an unknown kind nor Laplace beside Evans-2011 buffers is answered -1 by it
+            cases += [(-4, dict(lik_kind=3, n=_BIG_N)), (-4, dict(lik_kind=_lib.CL_LIK_LAPLACE, ev11=_FP, d_ev11=_FP, n=_BIG_N))]
+        for want, over in cases:
+            assert set(over) <= set(f for f, _ in _lib.FrozenArgs._fields_), over
+            got = call(base, **over)
+            assert got == want, (name, over, got, want)
+
+
 # --- the scaler's flat layouts and the row-chunk walk, each written once (nn.dense_layout, image.image_layer_layout, wide.image_chunks) ------
 def test_dense_layout_is_what_the_library_the_scaler_the_flat_layout_and_the_chain_plan_count():
     from careless_amd.engine import chain_plan
