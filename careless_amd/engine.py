@@ -26,7 +26,9 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from functools import cached_property
+from itertools import accumulate
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -92,6 +94,9 @@ def block_fields(a: MlpArgs, b: "LayerBlock", pmlp: int, x: int) -> MlpArgs:
 # ------------------------------------------------------------------------------------------------------------
 # layout of the flat parameter vector
 # ------------------------------------------------------------------------------------------------------------
+FLAT_GROUPS = ("q_loc", "q_scale", "mlp", "img", "imgl", "ev11", "dwr")      # the groups of the flat vector, in storage order
+
+
 @dataclass
 class FlatLayout:
     R: int
@@ -103,29 +108,30 @@ class FlatLayout:
     n_dwr: int = 0             # number of ASUs with --optimize-double-wilson-r
     n_imgl: int = 0            # floats of the per-image layers (NeuralImageScaler: `image_layer_layout`)
 
-    @property
-    def n(self) -> int:
-        return 2 * self.R + self.P + self.n_img + self.n_imgl + self.n_ev11 + self.n_dwr
+    @cached_property
+    def groups(self) -> Tuple[Tuple[str, int, int], ...]:
+        """THE table of the flat vector: (name, offset, count) of its groups in storage order; an absent group has count 0.  Every
+        offset below, `n`, the binding of the plugin objects (`bind_flat`) and the per-tensor split (`split_flat`) come from it."""
+        counts = (self.R, self.R, self.P, self.n_img, self.n_imgl, self.n_ev11, self.n_dwr)
+        return tuple(zip(FLAT_GROUPS, accumulate(counts, initial=0), counts))
 
-    @property
-    def off_dwr(self) -> int:
-        return 2 * self.R + self.P + self.n_img + self.n_imgl + self.n_ev11
+    @cached_property
+    def _span(self) -> Dict[str, Tuple[int, int]]:
+        return {name: (off, cnt) for name, off, cnt in self.groups}
 
-    @property
-    def off_ev11(self) -> int:
-        return 2 * self.R + self.P + self.n_img + self.n_imgl
+    def off(self, group: str) -> int:
+        return self._span[group][0]
 
-    @property
-    def off_imgl(self) -> int:
-        return 2 * self.R + self.P + self.n_img
+    def view(self, flat: torch.Tensor, group: str) -> torch.Tensor:
+        off, cnt = self._span[group]
+        return flat[off:off + cnt]
 
-    @property
-    def off_mlp(self) -> int:
-        return 2 * self.R
-
-    @property
-    def off_img(self) -> int:
-        return 2 * self.R + self.P
+    n = property(lambda self: sum(self.groups[-1][1:]))
+    off_mlp = property(lambda self: self.off("mlp"))
+    off_img = property(lambda self: self.off("img"))
+    off_imgl = property(lambda self: self.off("imgl"))
+    off_ev11 = property(lambda self: self.off("ev11"))
+    off_dwr = property(lambda self: self.off("dwr"))
 
 
 def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_dwr: int = 0, imgl=None) -> FlatLayout:
@@ -149,6 +155,74 @@ def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_d
     if n_dwr > 0:                        # the double-Wilson r vector (wilson.py:105-110)
         off += n_dwr; seg.append(off); owner.append("prior")
     return FlatLayout(R, P, n_img, seg, owner, n_ev11, n_dwr, n_imgl)
+
+
+def bind_flat(flat: torch.Tensor, lay: FlatLayout, q, mlp, img=None, imgl=None, lik=None, prior=None) -> None:
+    """The plugin objects become views into `flat`: the tensor that holds each group of `lay` is copied into it and the plugin attribute
+    rebound to that slice, in one loop over (group, holder, attribute).  (A group whose count is 0 is passed over: its holder may be
+    None.)  Any device: needs no engine."""
+    for group, holder, attr in (("q_loc", q, "loc_raw"), ("q_scale", q, "scale_raw"), ("mlp", mlp, "flat"), ("img", img, "_scales"),
+                                ("imgl", imgl, "flat"), ("ev11", lik, "raw"), ("dwr", prior, "r_raw")):
+        view = lay.view(flat, group)
+        if view.numel() > 0:
+            view[:] = getattr(holder, attr).to(flat.device)
+            setattr(holder, attr, view)
+
+
+def split_flat(g: torch.Tensor, lay: FlatLayout, dense, imgl_views=None) -> List[torch.Tensor]:
+    """`g`, a vector laid out like the parameters, per trainable tensor in the oracle's order and Keras shapes: the groups of `lay` in
+    order, the Dense stack by `dense` (`MetadataScaler.layer_slices`) as kernel (in, out) and bias per layer, the per-image block by
+    `imgl_views` (`NeuralImageScaler.layer_views`)."""
+    out = []
+    for name, off, cnt in lay.groups:
+        v = g[off:off + cnt]
+        if name == "mlp":
+            for ow, o, i, ob in dense:
+                out += [v[ow:ow + o * i].view(o, i).t(), v[ob:ob + o]]
+        elif name == "imgl" and cnt > 0:
+            out += imgl_views(v)
+        elif cnt > 0:
+            out.append(v)
+    return out
+
+
+@dataclass(frozen=True)
+class Workspace:
+    """The step workspace in floats, as (offset, count) per region (`carve_workspace`).  `dz_f`, `grads`, the four floats of slack behind
+    them, `msg_norm`, `scalars` (4 doubles), `seg_sq` (nseg doubles) and `own_scratch` (5 doubles) follow each other without overlap;
+    `msg` (what an owner-mode step all-reduces: the gradient behind a and b, the slack, the norm terms) and `ws_step` (what such a step
+    clears: everything from the gradient's padding on) are spans over them."""
+    owner: bool
+    dz_f: Tuple[int, int]
+    grads: Tuple[int, int]
+    msg: Tuple[int, int]
+    msg_norm: Tuple[int, int]
+    scalars: Tuple[int, int]
+    seg_sq: Tuple[int, int]
+    own_scratch: Tuple[int, int]
+    ws_step: Tuple[int, int]
+    total: int
+
+    @property
+    def aligned(self) -> bool:
+        """In a 16-byte aligned allocation the buffer a data-parallel step all-reduces -- the flat gradient (row split) or the message
+        (reflection-owner split) -- and `ws_step` start on 16-byte boundaries, the doubles on 8-byte ones."""
+        reduced = self.msg if self.owner else self.grads
+        return reduced[0] % 4 == 0 and self.ws_step[0] % 4 == 0 and all(r[0] % 2 == 0 for r in (self.scalars, self.seg_sq, self.own_scratch))
+
+
+def carve_workspace(R: int, S: int, n: int, nseg: int, owner: bool) -> Workspace:
+    """Offsets of the step workspace for R reflections, S samples, n parameters in nseg tensors.  The buffer a step all-reduces starts on
+    a 16-byte boundary: the flat gradient (row split), or -- reflection-owner split -- what lies behind a and b in it (two floats of
+    padding in front of the gradient when 2 R is not a multiple of four)."""
+    pad = (-2 * R) % 4 if owner else 0
+    g = (R * S + 3) // 4 * 4 + pad
+    sc = (g + n + 8 + 3) // 4 * 4           # 4 floats of slack, then the 4 norm terms of the owner-mode message; 16-byte aligned
+    seg = sc + 8                            # 4 doubles = 8 floats
+    own = seg + 2 * nseg                    # owner mode: 4 double accumulators + the block ticket of cl_owner_qnorm
+    total = own + 10
+    return Workspace(owner, dz_f=(0, R * S), grads=(g, n), msg=(g + 2 * R, n + 8 - 2 * R), msg_norm=(g + n + 4, 4), scalars=(sc, 8),
+                     seg_sq=(seg, 2 * nseg), own_scratch=(own, 10), ws_step=(g - pad, total - (g - pad)), total=total)
 
 
 @dataclass
@@ -254,6 +328,44 @@ def prior_kind(prior, owner: bool = False) -> int:
     raise NotImplementedError(f"prior {type(prior).__name__} is not supported by the HIP engine yet")
 
 
+def switch(model, attr: Optional[str], env: str, default: bool = False, env_adds: bool = False) -> bool:
+    """One on / off switch of the engine: `model.<attr>` where it is set (not None), else the environment variable `env` ("1" on, "0"
+    off), else `default`.  `env_adds`: the variable also switches on what the attribute leaves off (`deterministic`)."""
+    want = getattr(model, attr, None) if attr is not None else None
+    if want is None or (env_adds and not want):
+        env = os.environ.get(env, "")
+        want = (env != "0") if default else (env == "1")
+    return bool(want)
+
+
+def check_deterministic(plan: ScalerPlan, laue: bool, two_pass: bool, imgl: bool, S: int, dw_trainable: bool) -> None:
+    """NotImplementedError for what the deterministic mode does not cover, of a scaler run by `plan` on `laue` data (`two_pass`: asked for
+    by the model) with per-image layers (`imgl`), S samples and a trainable double-Wilson r (`dw_trainable`).  Host logic: needs no device."""
+    # (wide scalers: monochromatic rows only -- they are their own slots and one kernel holds every float atomic of the path --, with a
+    #  sample count that divides 64, so that a row's samples sit inside one wave)
+    wide_det_ok = plan.wide and not laue and 64 % S == 0
+    # (per-image layers: where the training launch has a route with the deterministic stores -- the lane kernel's instances, one wave per image)
+    imgl_det_ok = plan.route != _lib.CL_ROUTE_NONE
+    if two_pass or (plan.wide and not wide_det_ok) or (imgl and not imgl_det_ok) or (plan.blocks is not None and laue) or dw_trainable:
+        raise NotImplementedError("deterministic mode covers monochromatic and single-pass Laue data, the Wilson and the double-Wilson prior "
+                                  "(fixed r), Normal / Student-T likelihoods with or without the Evans-2011 error model, the Laplace likelihood, scalers of any depth up to "
+                                  "width 64, up to three per-image layers on 2 .. 20 Dense layers of width 5 .. 10 (two on 19; the default scaler's kernels) and, "
+                                  "for monochromatic data with a sample count that divides 64, scalers wider than 64; the two-pass "
+                                  "Laue path (also under a chained scaler), a trainable double-Wilson r and every other shape with per-image layers "
+                                  "keep their float atomics")
+
+
+def wants_owner_shard(want: bool, prior, world: int, owner_given: bool, laue: bool, double_wilson: bool, wide: bool, imgl: bool,
+                      deterministic: bool) -> bool:
+    """Does an engine asked for the reflection-owner split (`want`) on `world` ranks cut its rows by reflection (`owner_shard`)?  Not on one
+    rank, not when its shard already is an owner's (`owner_given`), not for Laue data (a harmonic group mixes reflections), the
+    double-Wilson prior (a child's parent may live on another rank), wide scalers, per-image layers or the deterministic mode: they keep
+    the row split.  NotImplementedError where the split is asked for or given and the prior is not one it runs.  Host logic: needs no device."""
+    if owner_given or (want and world > 1):
+        prior_kind(prior, owner=True)                # (the reflection-owner split is Wilson-only: raises for a reference prior)
+    return bool(want and world > 1 and not laue and not double_wilson and not wide and not imgl and not deterministic and not owner_given)
+
+
 def reference_prior_arrays(prior, R: int) -> dict:
     """What `cl_ref_prior` takes from an empirical reference prior, expanded to all R reflections (host arrays); ValueError where the
     prior's lengths do not match R or a Student-t prior has no positive dof."""
@@ -262,6 +374,31 @@ def reference_prior_arrays(prior, R: int) -> dict:
     if out["kind"] == _lib.CL_REFPRIOR_STUDENTT and not out["dof"] > 0.0:
         raise ValueError(f"{type(prior).__name__} needs dof > 0 (got {prior.dof})")
     return out
+
+
+@dataclass
+class DetBuffers:
+    """Deterministic mode, per observation set (`ObsData.det`, `ElboEngine._det_attach`): the per-observation stores of the kernels and the
+    sort orders `cl_det_reduce` walks."""
+    slot: Optional[torch.Tensor]        # position of every observation in reflection order (cl_mlp_args.det_slot); None past the 32-bit byte offset
+    dzf: torch.Tensor                   # amplitude gradient per (observation, sample)
+    dimg: torch.Tensor                  # image-scale term per observation
+    nll: torch.Tensor                   # NLL per workgroup: `grid` slots per piece, then the slot / padded-slot likelihood launch's
+    refl: Tuple[torch.Tensor, torch.Tensor]     # (permutation, segment starts) by reflection
+    img: Tuple[torch.Tensor, torch.Tensor]      # ... by image
+    M: int                              # number of images
+    pieces: int                         # launches the set is cut into
+    grid: int                           # workgroups of one of them
+    ev11: Optional[torch.Tensor] = None         # Evans-2011 gradients: three floats per wave of every launch
+
+
+@dataclass
+class PeelBuffers:
+    """A peeled first layer, per observation set (`ObsData.peel`, `ElboEngine._peel_bufs`), feature-major like meta_t."""
+    u: torch.Tensor                     # the layer's pre-activations
+    dz0: torch.Tensor                   # their gradient
+    parts: torch.Tensor                 # weight-gradient partials of cl_peel_backward
+    nparts: int
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -282,14 +419,35 @@ class ElboEngine(WidePath, FrozenPath):
         self.peel_params = self.peel_grad = None    # the peeled scaler's parameters and reduced gradient (`_peel_bufs`)
         self._wide = None                           # work buffers of the layer-by-layer path (`_wide_setup`)
         self._pending_reduce = None                 # a partial reduction left to the step's cl_tn_backward launch (`_data_term`)
-        if os.environ.get("CARELESS_FORCE_DIST", "0") == "1":
+        self._grid_arg = grid
+        if switch(model, None, "CARELESS_FORCE_DIST"):         # (no model attribute: `force_allreduce` is set on the engine)
             import torch.distributed as dist
             self.force_allreduce = dist.is_available() and dist.is_initialized()
-        dev = self.device
+        self._read_plugins(model, inputs)
+        self._reflection_constants()
+        two_pass = self._plan(inputs)
+        if self.deterministic:
+            check_deterministic(self.plan, self.laue, two_pass, self.imgl is not None, self.S, self.dw_trainable)
+        self._bind_parameters()
+        self._decide_shard(inputs, shard)
+        # A frozen scaling model (`--freeze-scales`; the half-dataset trainings of `--merge-half-datasets`, reference careless.py:102-128):
+        # its output (loc, sigma) per observation does not change from step to step, so a step needs neither its forward nor its backward
+        # pass -- only the sampling / likelihood part (careless_amd/frozen.py).  An engine built around a frozen scaler lays its observations
+        # out for that (`_frozen_layout_kw`).
+        self.frozen_fast = switch(model, "frozen_scaler_fast_path", "CARELESS_HIP_FROZEN_FAST", default=True)
+        self._frozen_layout = self._frozen_layout_kw() is not None
+        self._frozen_epoch = 0
+        self.scaler_frozen = False
+        self.obs = self._build_obs(inputs, self.shard.start, self.shard.stop, grid, self.laue_groups, rows=self.shard.rows if self.owner else None)
+        self._build_workspace()
+        self.refresh_config()
 
+    def _read_plugins(self, model, inputs):
+        """The plugin objects the engine runs -- `q, prior, lik, mlp, img, imgl` -- or NotImplementedError / ValueError for those it does
+        not; the sizes `R, N_total, d, S` and what the objects alone decide (`laue`, `ev11`, `double_wilson`, `dw_trainable`, `deterministic`)."""
         from careless_amd.models.merging.surrogate_posteriors import TruncatedNormal
-        from careless_amd.models.priors.wilson import DoubleWilsonPrior
         from careless_amd.models.likelihoods.mono import LocationScaleLikelihood
+        from careless_amd.models.priors.wilson import DoubleWilsonPrior
         from careless_amd.models.scaling.image import HybridImageScaler, NeuralImageScaler
         from careless_amd.models.scaling.nn import MetadataScaler
 
@@ -318,17 +476,22 @@ class ElboEngine(WidePath, FrozenPath):
         if model.scale_prior is not None:
             raise NotImplementedError("scale_prior is never enabled by the reference CLI and is not supported")
         self.q, self.prior, self.lik, self.mlp, self.img, self.imgl = q, prior, lik, mlp, img, imgl
-
-        # ---- observations -> device layout (built after the layout is known, below) ---------------------------
         self.R = int(q.loc_raw.numel())
         self.N_total = int(_np(BaseModel.get_refl_id(inputs)).reshape(-1).shape[0])
         self.d = int(_np(BaseModel.get_metadata(inputs)).reshape(self.N_total, -1).shape[1])
-        self.shard = shard if shard is not None else make_shard(self.N_total, self.R)
-        self.laue_groups = None
-        if self.laue and self.shard.world > 1:
-            self.laue_groups = laue_group_shard(_np(BaseModel.get_harmonic_id(inputs)).reshape(-1), self.shard.rank, self.shard.world)
+        self.S = int(model.mc_sample_size)
+        if self.S < 1:
+            raise ValueError("mc_sample_size must be >= 1")
+        self.ev11 = bool(getattr(lik, "ev11", False))
+        self.double_wilson = isinstance(prior, DoubleWilsonPrior)
+        self.dw_trainable = self.double_wilson and prior.r_raw is not None
+        # Deterministic mode (`model.deterministic = True` or CARELESS_HIP_DETERMINISTIC=1): no float atomics anywhere in the step --
+        # per-observation stores + fixed-order sums (cl_det_reduce) -- so two runs give bit-identical gradients and parameters
+        self.deterministic = switch(model, "deterministic", "CARELESS_HIP_DETERMINISTIC", env_adds=True)
 
-        # ---- per-reflection constants ----------------------------------------------------------------
+    def _reflection_constants(self):
+        """Per-reflection constants of the posterior and the prior, uploaded once."""
+        q, prior, dev = self.q, self.prior, self.device
         self.low = q.low.to(dev, torch.float32).contiguous()
         if self.ref_prior:
             # an empirical reference prior (models/priors/empirical.py): its arrays expanded to all reflections, uploaded once; the Wilson
@@ -341,90 +504,60 @@ class ElboEngine(WidePath, FrozenPath):
             self.es = torch.as_tensor(prior.eps_sigma, device=dev)
             if self.centric.numel() != self.R or self.es.numel() != self.R:
                 raise ValueError("prior and surrogate posterior disagree on the number of reflections")
-        self.double_wilson = isinstance(prior, DoubleWilsonPrior)
         if self.double_wilson:
             if prior.reflids.size != self.R or (prior.reflids >= self.R).any():
                 raise ValueError("DoubleWilsonPrior.reflids does not match the surrogate posterior")
             self.parent_ids = torch.as_tensor(prior.reflids.astype(np.int32), device=dev)
             self.root = torch.as_tensor(prior.root.astype(np.uint8), device=dev)
             self.dw_r = torch.as_tensor(prior.r_per_reflection, device=dev)
-            self.dw_children = None         # deterministic mode: the children of every reflection as a CSR list (built below)
+            self.dw_children = None         # deterministic mode: the children of every reflection as a CSR list
+            if self.deterministic:
+                # parents pull their children's terms in list order instead of children scattering with atomics (cl_dw_prior_forward)
+                par = np.asarray(prior.reflids).astype(np.int64)
+                kids = np.nonzero(par >= 0)[0]
+                kids = kids[np.argsort(par[kids], kind="stable")]
+                seg = np.concatenate([[0], np.cumsum(np.bincount(par[kids], minlength=self.R))]).astype(np.int32)
+                self.dw_children = (torch.as_tensor(seg, device=dev), torch.as_tensor(kids.astype(np.int32) if len(kids) else np.zeros(1, np.int32), device=dev))
+            if self.dw_trainable:
+                self.asu_ids = torch.as_tensor(prior.asu_ids.astype(np.int32), device=dev)
 
-        # ---- flat parameters; the plugin objects become views into them ----------------------------------
+    def _plan(self, inputs) -> bool:
+        """`self.plan`: how the scaler runs (`plan_scaler`), under its old names too; the answer: the model asks for the two-pass Laue path."""
+        mlp, imgl = self.mlp, self.imgl
         mlp.build(self.d)
         self.w, self.L = mlp.width, mlp.n_layers
-        n_img = 0
-        if img is not None:
-            n_img = img.max_images - 1
-        self.ev11 = bool(getattr(lik, "ev11", False))
-        self.dw_trainable = self.double_wilson and prior.r_raw is not None
-        n_dwr = int(prior.r_raw.numel()) if self.dw_trainable else 0
-        # Deterministic mode (`model.deterministic = True` or CARELESS_HIP_DETERMINISTIC=1): no float atomics anywhere in the step --
-        # per-observation stores + fixed-order sums (cl_det_reduce) -- so two runs give bit-identical gradients and parameters
-        self.deterministic = bool(getattr(model, "deterministic", False)) or os.environ.get("CARELESS_HIP_DETERMINISTIC", "0") == "1"
-        two_pass = self.laue and bool(getattr(model, "laue_two_pass", False))
+        two_pass = self.laue and bool(getattr(self.model, "laue_two_pass", False))
         gmax = int(np.bincount(_np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64)).max()) if self.laue else 1
         self.plan = plan_scaler(self.lib, self.d, self.w, self.L, imgl.n_image_layers if imgl is not None else 0, laue=self.laue,
                                 two_pass=two_pass, gmax=gmax, ev11=self.ev11, deterministic=self.deterministic,
-                                lik_kind=_lib.CL_LIK_LAPLACE if lik.kind == "laplace" else 0)
+                                lik_kind=_lib.CL_LIK_LAPLACE if self.lik.kind == "laplace" else 0)
         self.wide, self.peel, self.blocks, self.chain_lane = self.plan.wide, self.plan.peel, self.plan.blocks, self.plan.chain_lane
         if imgl is not None:
             imgl.build(self.d)
-        # (wide scalers: monochromatic rows only -- they are their own slots and one kernel holds every float atomic of the path --, with a
-        #  sample count that divides 64, so that a row's samples sit inside one wave)
-        wide_det_ok = self.wide and not self.laue and 64 % int(model.mc_sample_size) == 0
-        # (per-image layers: where the training launch has a route with the deterministic stores -- the lane kernel's instances, one wave per image)
-        imgl_det_ok = self.plan.route != _lib.CL_ROUTE_NONE
-        if self.deterministic and (two_pass or (self.wide and not wide_det_ok) or (imgl is not None and not imgl_det_ok) or
-                                   (self.blocks is not None and self.laue) or (self.double_wilson and prior.r_raw is not None)):
-            raise NotImplementedError("deterministic mode covers monochromatic and single-pass Laue data, the Wilson and the double-Wilson prior "
-                                      "(fixed r), Normal / Student-T likelihoods with or without the Evans-2011 error model, the Laplace likelihood, scalers of any depth up to "
-                                      "width 64, up to three per-image layers on 2 .. 20 Dense layers of width 5 .. 10 (two on 19; the default scaler's kernels) and, "
-                                      "for monochromatic data with a sample count that divides 64, scalers wider than 64; the two-pass "
-                                      "Laue path (also under a chained scaler), a trainable double-Wilson r and every other shape with per-image layers "
-                                      "keep their float atomics")
-        if self.deterministic and self.double_wilson:
-            # parents pull their children's terms in list order instead of children scattering with atomics (cl_dw_prior_forward)
-            par = np.asarray(prior.reflids).astype(np.int64)
-            kids = np.nonzero(par >= 0)[0]
-            kids = kids[np.argsort(par[kids], kind="stable")]
-            seg = np.concatenate([[0], np.cumsum(np.bincount(par[kids], minlength=self.R))]).astype(np.int32)
-            self.dw_children = (torch.as_tensor(seg, device=dev), torch.as_tensor(kids.astype(np.int32) if len(kids) else np.zeros(1, np.int32), device=dev))
-        self.layout = make_layout(self.R, self.d, self.w, self.L, n_img, 3 if self.ev11 else 0, n_dwr,
-                                  imgl=(imgl.n_image_layers, imgl.max_images) if imgl is not None else None)
-        lay = self.layout
+        return two_pass
+
+    def _bind_parameters(self):
+        """The flat parameter vector and Adam's moments; the plugin objects become views into the parameters (`bind_flat`)."""
+        mlp, img, imgl, dev = self.mlp, self.img, self.imgl, self.device
+        self.layout = lay = make_layout(self.R, self.d, self.w, self.L, img.max_images - 1 if img is not None else 0, 3 if self.ev11 else 0,
+                                        int(self.prior.r_raw.numel()) if self.dw_trainable else 0,
+                                        imgl=(imgl.n_image_layers, imgl.max_images) if imgl is not None else None)
         assert lay.P == mlp.param_count(self.d) == int(self.lib.cl_mlp_param_count(self.d, self.w, self.L))
         self.params = torch.empty(lay.n, dtype=torch.float32, device=dev)
-        self.params[0:self.R] = q.loc_raw.to(dev)
-        self.params[self.R:2 * self.R] = q.scale_raw.to(dev)
-        self.params[lay.off_mlp:lay.off_mlp + lay.P] = mlp.flat.to(dev)
-        q.loc_raw = self.params[0:self.R]
-        q.scale_raw = self.params[self.R:2 * self.R]
-        q.low = self.low
-        mlp.flat = self.params[lay.off_mlp:lay.off_mlp + lay.P]
-        if n_img > 0:
-            self.params[lay.off_img:lay.off_img + n_img] = img._scales.to(dev)
-            img._scales = self.params[lay.off_img:lay.off_img + n_img]
-        if imgl is not None:
-            self.params[lay.off_imgl:lay.off_imgl + lay.n_imgl] = imgl.flat.to(dev)
-            imgl.flat = self.params[lay.off_imgl:lay.off_imgl + lay.n_imgl]
-        if self.ev11:
-            self.params[lay.off_ev11:lay.off_ev11 + 3] = lik.raw.to(dev)
-            lik.raw = self.params[lay.off_ev11:lay.off_ev11 + 3]
-        if self.dw_trainable:
-            self.params[lay.off_dwr:lay.off_dwr + n_dwr] = prior.r_raw.to(dev)
-            prior.r_raw = self.params[lay.off_dwr:lay.off_dwr + n_dwr]
-            self.asu_ids = torch.as_tensor(prior.asu_ids.astype(np.int32), device=dev)
+        bind_flat(self.params, lay, self.q, mlp, img, imgl, self.lik, self.prior)
+        self.q.low = self.low
         self.adam_m = torch.zeros_like(self.params)
         self.adam_v = torch.zeros_like(self.params)
         self.t = 0                                  # optimizer iterations
         self.seg_off = torch.as_tensor(np.asarray(lay.seg_off, dtype=np.int32), device=dev)
         self.nseg = len(lay.seg_off) - 1
 
-        # ---- workspace -----------------------------------------------------------------------------------
-        self.S = int(model.mc_sample_size)
-        if self.S < 1:
-            raise ValueError("mc_sample_size must be >= 1")
+    def _decide_shard(self, inputs, shard: Optional[Shard]):
+        """`self.shard`: the one given, else all rows -- or, asked for, this rank's reflections and their rows; `self.laue_groups`."""
+        self.shard = shard if shard is not None else make_shard(self.N_total, self.R)
+        self.laue_groups = None
+        if self.laue and self.shard.world > 1:
+            self.laue_groups = laue_group_shard(_np(BaseModel.get_harmonic_id(inputs)).reshape(-1), self.shard.rank, self.shard.world)
         # Reflection-owner sharding (DESIGN 5.2): with more than one rank, monochromatic data and the Wilson prior, a rank takes a
         # RANGE OF REFLECTIONS and every observation of theirs instead of a range of rows.  Sampling q(F), its KL, its gradient and
         # its Adam update are then local to the owner (1 / world of the replicated work of the row split), and the step's all-reduce
@@ -434,50 +567,25 @@ class ElboEngine(WidePath, FrozenPath):
         # verified on one device and over gloo (parity suite, shard-sum tests) but has never met RCCL on a multi-GPU node, and on one
         # device its compute side is worth <= 1 % at eight ranks; the row split stays the default until
         # `scripts/scale_curve.sh` has measured both on a node.
-        self.owner = False
-        want = getattr(model, "owner_shard", None)
-        if want is None:
-            env = os.environ.get("CARELESS_HIP_OWNER_SHARD", "")
-            want = env == "1"
-        if self.shard.owner or (want and self.shard.world > 1):
-            prior_kind(prior, owner=True)                # (the reflection-owner split is Wilson-only: raises for a reference prior)
-        if (want and self.shard.world > 1 and not self.laue and not self.double_wilson and not self.wide and imgl is None
-                and not self.deterministic and not self.shard.owner):
+        if wants_owner_shard(switch(self.model, "owner_shard", "CARELESS_HIP_OWNER_SHARD"), self.prior, self.shard.world, bool(self.shard.owner),
+                             self.laue, self.double_wilson, self.wide, self.imgl is not None, self.deterministic):
             osh = owner_shard(_np(BaseModel.get_refl_id(inputs)).reshape(-1), self.R, self.shard.rank, self.shard.world)
             if osh is not None:
                 self.shard = osh
         self.owner = bool(self.shard.owner)
-        # A frozen scaling model (`--freeze-scales`; the half-dataset trainings of `--merge-half-datasets`, reference careless.py:102-128):
-        # its output (loc, sigma) per observation does not change from step to step, so a step needs neither its forward nor its backward
-        # pass -- only the sampling / likelihood part (careless_amd/frozen.py).  An engine built around a frozen scaler lays its observations
-        # out for that (`_frozen_layout_kw`).
-        want_ff = getattr(model, "frozen_scaler_fast_path", None)
-        self.frozen_fast = (os.environ.get("CARELESS_HIP_FROZEN_FAST", "1") != "0") if want_ff is None else bool(want_ff)
-        self._grid_arg = grid
-        self._frozen_layout = self._frozen_layout_kw() is not None
-        self._frozen_epoch = 0
-        self.scaler_frozen = False
-        self.obs = self._build_obs(inputs, self.shard.start, self.shard.stop, grid, self.laue_groups, rows=self.shard.rows if self.owner else None)
-        RS = self.R * self.S
-        o_dz = 0
-        # the buffer a step all-reduces starts on a 16-byte boundary: the flat gradient (row split), or -- reflection-owner split -- what
-        # lies behind a and b in it (two floats of padding in front of the gradient when 2 R is not a multiple of four)
-        pad = (-2 * self.R) % 4 if self.owner else 0
-        o_g = (RS + 3) // 4 * 4 + pad
-        o_sc = (o_g + lay.n + 8 + 3) // 4 * 4           # 4 floats of slack, then the 4 norm terms of the owner-mode message; 16-byte aligned
-        o_seg = o_sc + 8                                # 4 doubles = 8 floats
-        o_own = o_seg + 2 * self.nseg                   # owner mode: 4 double accumulators + the block ticket of cl_owner_qnorm
-        tot = o_own + 10
-        self.ws = torch.zeros(tot, dtype=torch.float32, device=dev)
-        self.dz_f = self.ws[o_dz:o_dz + RS]
-        self.grads = self.ws[o_g:o_g + lay.n]
-        self.scalars = self.ws[o_sc:o_sc + 8].view(torch.float64)
-        self.seg_sq = self.ws[o_seg:o_seg + 2 * self.nseg].view(torch.float64)
-        self.own_scratch = self.ws[o_own:o_own + 10].view(torch.float64)
-        self.msg_norm = self.ws[o_g + lay.n + 4:o_g + lay.n + 8]                # [raw, sanitised, sanitised a, sanitised b]
-        self.msg = self.ws[o_g + 2 * self.R:o_g + lay.n + 8]                    # what an owner-mode step all-reduces
-        self.ws_step = self.ws[o_g - pad:]                                      # owner mode zeroes this (16-byte aligned) and its own slice of dz_f per step
-        assert (self.msg if self.owner else self.grads).data_ptr() % 16 == 0 and self.ws_step.data_ptr() % 16 == 0
+
+    def _build_workspace(self):
+        """The step workspace (`carve_workspace`) and the small per-step buffers beside it."""
+        dev, RS = self.device, self.R * self.S
+        carve = carve_workspace(self.R, self.S, self.layout.n, self.nseg, self.owner)
+        self.ws = torch.zeros(carve.total, dtype=torch.float32, device=dev)
+        assert carve.aligned and self.ws.data_ptr() % 16 == 0
+        part = lambda region: self.ws[region[0]:region[0] + region[1]]
+        self.dz_f, self.grads = part(carve.dz_f), part(carve.grads)
+        self.scalars, self.seg_sq, self.own_scratch = (part(r).view(torch.float64) for r in (carve.scalars, carve.seg_sq, carve.own_scratch))
+        self.msg_norm = part(carve.msg_norm)         # [raw, sanitised, sanitised a, sanitised b]
+        self.msg = part(carve.msg)                   # what an owner-mode step all-reduces
+        self.ws_step = part(carve.ws_step)           # owner mode zeroes this (16-byte aligned) and its own slice of dz_f per step
         self.norm_part = torch.zeros(2 * 1024, dtype=torch.float64, device=dev)                  # per-workgroup norm sums of cl_adam_step (<= 1024 workgroups)
         self.kl_part = torch.zeros((self.R + 255) // 256, dtype=torch.float64, device=dev)      # per-workgroup KL sums of cl_tn_forward
         self.kl_part_dw = torch.zeros_like(self.kl_part) if (self.double_wilson or self.ref_prior) else None    # ... and of cl_dw_prior_forward / cl_ref_prior
@@ -486,7 +594,6 @@ class ElboEngine(WidePath, FrozenPath):
         self.frozen = torch.zeros(self.nseg, dtype=torch.uint8, device=dev)
         self.history_buf: Optional[torch.Tensor] = None
         self._keep = None
-        self.refresh_config()
 
     def _build_obs(self, inputs, start, stop, grid, laue_groups, rows=None):
         """Device image of rows [start, stop) of `inputs`: one `ObsData`, or -- plain layout only -- as many pieces as the 4-GiB
@@ -549,14 +656,14 @@ class ElboEngine(WidePath, FrozenPath):
         if 4 * n * self.S < (1 << 32):          # (the kernels address a record with a 32-bit byte offset from the buffer's start)
             slot = torch.empty(n, dtype=torch.int32, device=dev)
             slot[perm_r.long()] = torch.arange(n, dtype=torch.int32, device=dev)
-        obs.det = dict(slot=slot, dzf=torch.zeros(n * self.S, dtype=torch.float32, device=dev), dimg=torch.zeros(n, dtype=torch.float32, device=dev),
-                       nll=torch.zeros(len(pieces) * pieces[0].grid + (_lib.CL_LAUE_LIK_MAX_BLOCKS if (self.laue or self.wide) else 0), dtype=torch.float64,
-                                       device=dev),
-                       refl=(perm_r, seg_r), img=order(img, M), M=M, pieces=len(pieces), grid=pieces[0].grid)
+        obs.det = DetBuffers(slot=slot, dzf=torch.zeros(n * self.S, dtype=torch.float32, device=dev), dimg=torch.zeros(n, dtype=torch.float32, device=dev),
+                             nll=torch.zeros(len(pieces) * pieces[0].grid + (_lib.CL_LAUE_LIK_MAX_BLOCKS if (self.laue or self.wide) else 0),
+                                             dtype=torch.float64, device=dev),
+                             refl=(perm_r, seg_r), img=order(img, M), M=M, pieces=len(pieces), grid=pieces[0].grid)
         if self.ev11:
             # Evans-2011 gradients: one slot of three floats per wave of every launch (the fused launches' CL_EV11_WAVES per workgroup, then
             # four per workgroup of the slot / padded-slot likelihood launch), summed in slot order by cl_det_reduce
-            obs.det["ev11"] = torch.zeros(3 * (_lib.CL_EV11_WAVES * len(pieces) * pieces[0].grid + 4 * _lib.CL_LAUE_LIK_MAX_BLOCKS), dtype=torch.float32, device=dev)
+            obs.det.ev11 = torch.zeros(3 * (_lib.CL_EV11_WAVES * len(pieces) * pieces[0].grid + 4 * _lib.CL_LAUE_LIK_MAX_BLOCKS), dtype=torch.float32, device=dev)
         for k, p in enumerate(pieces):
             p.det_parent, p.det_index = obs, k
 
@@ -564,6 +671,12 @@ class ElboEngine(WidePath, FrozenPath):
         if self.img is not None:
             return self.img.max_images
         return self.imgl.max_images if self.imgl is not None else None
+
+    def _param_ptr(self, group: str, el: int = 0) -> int:       # device address of element `el` of a group (`FlatLayout.groups`) of the parameters
+        return self.params.data_ptr() + 4 * (self.layout.off(group) + el)
+
+    def _grad_ptr(self, group: str, el: int = 0) -> int:        # ... of the flat gradient
+        return self.grads.data_ptr() + 4 * (self.layout.off(group) + el)
 
     # the training shard's sizes under their old names (bench.py, tests, scripts/stamps*.py)
     N = property(lambda self: self.obs.N)
@@ -609,10 +722,8 @@ class ElboEngine(WidePath, FrozenPath):
 
     # ------------------------------------------------------------------------------------------------------
     def _tn_args(self, step: int, u_f) -> TnArgs:
-        lay = self.layout
         a = TnArgs()
-        a.q_loc_raw = self.params.data_ptr()
-        a.q_scale_raw = self.params.data_ptr() + 4 * self.R
+        a.q_loc_raw, a.q_scale_raw = self._param_ptr("q_loc"), self._param_ptr("q_scale")
         a.low = ptr(self.low); a.centric = ptr(self.centric); a.es = ptr(self.es)
         a.R, a.S = self.R, self.S
         a.high, a.eps = self.q.high, self.q.scale_shift
@@ -623,8 +734,7 @@ class ElboEngine(WidePath, FrozenPath):
         a.u_f = ptr(u_f)
         a.seed, a.step = self.seed, step & 0xFFFFFFFF
         a.z_f = ptr(self.z_f); a.dz_f = ptr(self.dz_f)
-        a.d_loc_raw = self.grads.data_ptr()
-        a.d_scale_raw = self.grads.data_ptr() + 4 * self.R
+        a.d_loc_raw, a.d_scale_raw = self._grad_ptr("q_loc"), self._grad_ptr("q_scale")
         a.scalars = ptr(self.scalars)
         a.stop_flag = ptr(self.stop_flag)
         if self.ref_prior:
@@ -636,14 +746,12 @@ class ElboEngine(WidePath, FrozenPath):
             if self.dw_children is not None:
                 a.dw_child_seg, a.dw_child_ids = ptr(self.dw_children[0]), ptr(self.dw_children[1])
             if self.dw_trainable:
-                a.dw_r_raw = self.params.data_ptr() + 4 * lay.off_dwr
-                a.d_dw_r_raw = self.grads.data_ptr() + 4 * lay.off_dwr
-                a.asu_ids, a.n_asu = ptr(self.asu_ids), lay.n_dwr
+                a.dw_r_raw, a.d_dw_r_raw = self._param_ptr("dwr"), self._grad_ptr("dwr")
+                a.asu_ids, a.n_asu = ptr(self.asu_ids), self.layout.n_dwr
         return a
 
     def _step_fields(self, a, obs: ObsData, step: int):
         """The per-step constants `cl_mlp_args`, `cl_laue_args` and `cl_frozen_args` name alike, on whichever of the three `a` is."""
-        lay = self.layout
         a.R, a.S = self.R, self.S
         a.z_f, a.dz_f = ptr(self.z_f), ptr(self.dz_f)
         a.lik_kind, a.dof, a.lik_const = self.lik_kind, self.dof, self.lik_const
@@ -652,8 +760,7 @@ class ElboEngine(WidePath, FrozenPath):
         a.seed, a.step = self.seed, step & 0xFFFFFFFF
         a.scalars, a.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
         if self.ev11:
-            a.ev11 = self.params.data_ptr() + 4 * lay.off_ev11
-            a.d_ev11 = self.grads.data_ptr() + 4 * lay.off_ev11
+            a.ev11, a.d_ev11 = self._param_ptr("ev11"), self._grad_ptr("ev11")
         return a
 
     def _shard_rows(self, obs: ObsData, t) -> Optional[int]:
@@ -662,11 +769,11 @@ class ElboEngine(WidePath, FrozenPath):
 
     def _det_parts(self, obs: ObsData, k: int):
         """(nll_part, ev11_part) of part k of the shard `obs` belongs to (deterministic mode): the fused launches of its pieces store into parts
-        0 .. pieces - 1 -- det["grid"] NLL slots, CL_EV11_WAVES Evans-2011 slots of three floats per workgroup --, the slot / padded-slot
-        likelihood launch behind them (k = det["pieces"])."""
+        0 .. pieces - 1 -- det.grid NLL slots, CL_EV11_WAVES Evans-2011 slots of three floats per workgroup --, the slot / padded-slot
+        likelihood launch behind them (k = det.pieces)."""
         det = obs.det_parent.det
-        return (det["nll"].data_ptr() + 8 * det["grid"] * k,
-                det["ev11"].data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det["grid"] * k if self.ev11 else None)
+        return (det.nll.data_ptr() + 8 * det.grid * k,
+                det.ev11.data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det.grid * k if self.ev11 else None)
 
     def _mlp_args(self, step: int, eta, ipred_out=None, obs: Optional[ObsData] = None) -> MlpArgs:
         lay = self.layout
@@ -679,23 +786,22 @@ class ElboEngine(WidePath, FrozenPath):
         if obs.fused_laue:
             a.gmeta, a.tile_gmax = ptr(obs.gmeta), ptr(obs.tile_gmax)
         a.noise_row = ptr(obs.noise_row)
-        scaler_fields(a, self.mlp, self.d, self.params.data_ptr() + 4 * lay.off_mlp, self.imgl, self.params.data_ptr() + 4 * lay.off_imgl,
-                      obs.tile_img, obs.row_map)
+        scaler_fields(a, self.mlp, self.d, self._param_ptr("mlp"), self.imgl, self._param_ptr("imgl"), obs.tile_img, obs.row_map)
         if self.imgl is not None:
-            a.d_imgl = self.grads.data_ptr() + 4 * lay.off_imgl
+            a.d_imgl = self._grad_ptr("imgl")
         a.use_img = 1 if lay.n_img > 0 else 0
-        a.img = (self.params.data_ptr() + 4 * lay.off_img) if lay.n_img > 0 else None
+        a.img = self._param_ptr("img") if lay.n_img > 0 else None
         a.eta, a.ipred_out = self._shard_rows(obs, eta), self._shard_rows(obs, ipred_out)
-        a.d_img = (self.grads.data_ptr() + 4 * lay.off_img) if lay.n_img > 0 else None
+        a.d_img = self._grad_ptr("img") if lay.n_img > 0 else None
         a.partials = ptr(obs.partials)
         if self.deterministic:
             det = obs.det_parent.det
-            if det["slot"] is not None:
-                a.dzf_obs = det["dzf"].data_ptr()                  # (records by slot: positions inside the whole shard, not the piece)
-                a.det_slot = det["slot"].data_ptr() + 4 * obs.row0
+            if det.slot is not None:
+                a.dzf_obs = det.dzf.data_ptr()                  # (records by slot: positions inside the whole shard, not the piece)
+                a.det_slot = det.slot.data_ptr() + 4 * obs.row0
             else:
-                a.dzf_obs = det["dzf"].data_ptr() + 4 * self.S * obs.row0
-            a.dimg_obs = det["dimg"].data_ptr() + 4 * obs.row0
+                a.dzf_obs = det.dzf.data_ptr() + 4 * self.S * obs.row0
+            a.dimg_obs = det.dimg.data_ptr() + 4 * obs.row0
             a.nll_part, a.ev11_part = self._det_parts(obs, obs.det_index)
         return a
 
@@ -779,7 +885,7 @@ class ElboEngine(WidePath, FrozenPath):
         # partial reduction are through, so its all-reduce starts then (asynchronously, on the communicator's stream) and runs beside
         # cl_tn_backward; a's and b's gradient follows when that kernel is done.  (Not with a trainable double-Wilson r: its gradient
         # sits in the tail and comes out of cl_tn_backward.)
-        split = dist_on and not self.owner and not self.dw_trainable and self._want_split_message()
+        split = dist_on and not self.owner and not self.dw_trainable and switch(self.model, "split_message", "CARELESS_HIP_SPLIT_MESSAGE")
         self._data_term(self.obs, step, eta, ipred_out, st, defer_reduce=not split)
         tail_work = None
         if split:
@@ -822,12 +928,6 @@ class ElboEngine(WidePath, FrozenPath):
         a.kl_part, a.scalars, a.stop_flag = tn.kl_part_dw, tn.scalars, tn.stop_flag
         check(self.lib.cl_ref_prior(C.byref(a), st), "cl_ref_prior")
 
-    def _want_split_message(self) -> bool:
-        want = getattr(self.model, "split_message", None)
-        if want is None:
-            want = os.environ.get("CARELESS_HIP_SPLIT_MESSAGE", "0") == "1"
-        return bool(want)
-
     def _zero_step(self):
         """Clear the step's accumulators: dz_f, the flat gradient, the scalars.  An owner-mode rank only ever touches the dz_f rows and
         the q gradients of its own reflections (those gradients are rewritten, not accumulated, by nobody else): it clears its slice
@@ -843,15 +943,15 @@ class ElboEngine(WidePath, FrozenPath):
         det, lay = obs.det, self.layout
         a = DetArgs()
         # (records stored in reflection order -- det_slot -- need no gather list)
-        a.dzf_obs, a.perm_refl, a.seg_refl = ptr(det["dzf"]), (None if det["slot"] is not None else ptr(det["refl"][0])), ptr(det["refl"][1])
+        a.dzf_obs, a.perm_refl, a.seg_refl = ptr(det.dzf), (None if det.slot is not None else ptr(det.refl[0])), ptr(det.refl[1])
         a.R, a.S, a.dz_f = self.R, self.S, ptr(self.dz_f)
         if lay.n_img > 0:
-            a.dimg_obs, a.perm_img, a.seg_img = ptr(det["dimg"]), ptr(det["img"][0]), ptr(det["img"][1])
-            a.n_images, a.d_img = det["M"], self.grads.data_ptr() + 4 * lay.off_img
-        a.nll_part, a.nparts, a.scalars = ptr(det["nll"]), int(det["nll"].numel()), ptr(self.scalars)
+            a.dimg_obs, a.perm_img, a.seg_img = ptr(det.dimg), ptr(det.img[0]), ptr(det.img[1])
+            a.n_images, a.d_img = det.M, self._grad_ptr("img")
+        a.nll_part, a.nparts, a.scalars = ptr(det.nll), int(det.nll.numel()), ptr(self.scalars)
         a.stop_flag = ptr(self.stop_flag)
         if self.ev11:
-            a.ev11_part, a.n_ev11, a.d_ev11 = ptr(det["ev11"]), int(det["ev11"].numel()) // 3, self.grads.data_ptr() + 4 * lay.off_ev11
+            a.ev11_part, a.n_ev11, a.d_ev11 = ptr(det.ev11), int(det.ev11.numel()) // 3, self._grad_ptr("ev11")
         check(self.lib.cl_det_reduce(C.byref(a), st), "cl_det_reduce")
 
     def _data_term(self, obs, step: int, eta, ipred_out, st, defer_reduce: bool = False):
@@ -884,7 +984,7 @@ class ElboEngine(WidePath, FrozenPath):
         if mode == 2:
             self._laue_passes(a, obs, step, eta, ipred_out, st)
         else:
-            # (deterministic mode: every workgroup of the launch STORES its NLL slot, det["grid"] slots per piece -- nothing to clear;
+            # (deterministic mode: every workgroup of the launch STORES its NLL slot, det.grid slots per piece -- nothing to clear;
             #  the slots a short last piece leaves unwritten were zero-initialised and are never touched)
             self._fused_step_launch(a, obs, st)
             if obs.fused_laue:
@@ -894,10 +994,9 @@ class ElboEngine(WidePath, FrozenPath):
         if self.peel and mode == 0:
             self._peel_reduce(obs, st, a.n_obs)
         elif defer_reduce and not self.deterministic:
-            self._pending_reduce = (ptr(obs.partials), obs.grid, lay.P, self.grads.data_ptr() + 4 * lay.off_mlp)
+            self._pending_reduce = (ptr(obs.partials), obs.grid, lay.P, self._grad_ptr("mlp"))
         else:
-            check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, lay.P, self.grads.data_ptr() + 4 * lay.off_mlp,
-                                         ptr(self.stop_flag), st), "cl_reduce_partials")
+            check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, lay.P, self._grad_ptr("mlp"), ptr(self.stop_flag), st), "cl_reduce_partials")
 
     def _laue_pad_slots(self, ma, obs: ObsData, st):
         """The padded slots of a packed Laue observation set (no rows, iconv = 0: reference formatter.py:637-640 / laue.py:24) add their
@@ -918,7 +1017,7 @@ class ElboEngine(WidePath, FrozenPath):
         la.scalars, la.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
         la.ev11, la.d_ev11 = ma.ev11, ma.d_ev11
         if self.deterministic:      # the padded slots' workgroups store their NLL behind the fused launch's parts
-            la.nll_part, la.ev11_part = self._det_parts(obs, obs.det_parent.det["pieces"])
+            la.nll_part, la.ev11_part = self._det_parts(obs, obs.det_parent.det.pieces)
         check(lib.cl_laue_likelihood(C.byref(la), st), "cl_laue_likelihood")
 
     def _peel_bufs(self, obs: ObsData):
@@ -927,9 +1026,9 @@ class ElboEngine(WidePath, FrozenPath):
         if obs.peel is None:
             rows = int(self.lib.cl_mlp_meta_rows(self.w))
             nparts = int(self.lib.cl_peel_parts(obs.n_pad))     # (packed layouts: every row of the padded axis may be a real one)
-            obs.peel = dict(u=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
-                            dz0=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
-                            parts=torch.empty(nparts * (self.w * self.d + self.w), dtype=torch.float32, device=self.device), nparts=nparts)
+            obs.peel = PeelBuffers(u=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
+                                   dz0=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
+                                   parts=torch.empty(nparts * (self.w * self.d + self.w), dtype=torch.float32, device=self.device), nparts=nparts)
         if self.peel_params is None:
             Pp = int(self.lib.cl_mlp_param_count(self.w, self.w, self.L))
             self.peel_params = torch.zeros(Pp, dtype=torch.float32, device=self.device)
@@ -940,37 +1039,35 @@ class ElboEngine(WidePath, FrozenPath):
         """The fused launch behind the peeled first layer: the layer's pre-activations as metadata, identity first layer, dZ_0 out."""
         pb = self._peel_bufs(obs)
         a = _copy_args(ma)
-        a.meta_t, a.d, a.mlp, a.dZ0_out = ptr(pb["u"]), self.w, ptr(self.peel_params), ptr(pb["dz0"])
+        a.meta_t, a.d, a.mlp, a.dZ0_out = ptr(pb.u), self.w, ptr(self.peel_params), ptr(pb.dz0)
         return a
 
     def _fused_step_launch(self, a: MlpArgs, obs: ObsData, st):
         """cl_elbo_mono_fwd_bwd on `_likelihood_args`' arguments, behind cl_peel_forward when the first layer is peeled (self.peel)."""
         if self.peel:
-            pb, lay = obs.peel, self.layout
-            check(self.lib.cl_peel_forward(ptr(obs.meta_t), a.n_obs, obs.n_pad, self.d, self.w, self.L, self.params.data_ptr() + 4 * lay.off_mlp, ptr(pb["u"]),
+            check(self.lib.cl_peel_forward(ptr(obs.meta_t), a.n_obs, obs.n_pad, self.d, self.w, self.L, self._param_ptr("mlp"), ptr(obs.peel.u),
                                            ptr(self.peel_params), ptr(self.peel_grad), int(self.peel_grad.numel()), ptr(self.stop_flag), st), "cl_peel_forward")
         check(self.lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
 
     def _peel_reduce(self, obs: ObsData, st, n_obs: int):
         """Gradient of a step with a peeled first layer: the launch's partials -> the peeled scaler's gradient; layer 0's own gradient
         from dZ_0 and the metadata, everything behind it copied over (cl_peel_backward)."""
-        pb, lay = obs.peel, self.layout
+        pb = obs.peel
         check(self.lib.cl_reduce_partials(ptr(obs.partials), obs.grid, int(self.peel_grad.numel()), ptr(self.peel_grad), ptr(self.stop_flag), st),
               "cl_reduce_partials")
-        check(self.lib.cl_peel_backward(ptr(obs.meta_t), n_obs, obs.n_pad, self.d, self.w, self.L, ptr(pb["dz0"]), ptr(self.peel_grad),
-                                        self.grads.data_ptr() + 4 * lay.off_mlp, ptr(pb["parts"]), pb["nparts"], ptr(self.stop_flag), st), "cl_peel_backward")
+        check(self.lib.cl_peel_backward(ptr(obs.meta_t), n_obs, obs.n_pad, self.d, self.w, self.L, ptr(pb.dz0), ptr(self.peel_grad),
+                                        self._grad_ptr("mlp"), ptr(pb.parts), pb.nparts, ptr(self.stop_flag), st), "cl_peel_backward")
 
     def _block_args(self, ma: MlpArgs, obs: ObsData, k: int) -> MlpArgs:
         """Arguments of block k of the chain: its slice of the parameters, its input (metadata or the previous block's output)."""
-        return block_fields(_copy_args(ma), self.blocks[k], self.params.data_ptr() + 4 * self.layout.off_mlp,
-                            ptr(obs.meta_t) if k == 0 else ptr(obs.chain_act[k - 1]))
+        return block_fields(_copy_args(ma), self.blocks[k], self._param_ptr("mlp"), ptr(obs.meta_t) if k == 0 else ptr(obs.chain_act[k - 1]))
 
     def _data_term_chain(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
         """Scaler deeper than one launch: forward through the head-less blocks (activations to HBM), the last block does the
         likelihood and its own backward (recomputing its forward), then the blocks are walked back, each recomputing its
         forward from its stored input.  8 P_mm flops per observation instead of 6, plus 2 x 8 w bytes per block boundary."""
-        lib, lay, K = self.lib, self.layout, len(self.blocks)
-        gptr = lambda k: self.grads.data_ptr() + 4 * (lay.off_mlp + self.blocks[k].off)
+        lib, K = self.lib, len(self.blocks)
+        gptr = lambda k: self._grad_ptr("mlp", self.blocks[k].off)
         for k in range(K - 1):
             a = self._block_args(ma, obs, k)
             a.act_out = ptr(obs.chain_act[k])
@@ -1066,8 +1163,8 @@ class ElboEngine(WidePath, FrozenPath):
             # no float atomics: the amplitude gradient of every (row, sample) and the image-scale term of every row are stored (records in
             # reflection order: det_slot), every workgroup stores its NLL; cl_det_reduce sums them in a fixed order after the backward pass
             det = obs.det_parent.det
-            la.dzf_obs, la.dimg_obs, la.det_slot = ptr(det["dzf"]), ptr(det["dimg"]), ptr(det["slot"])
-            la.nll_part, la.ev11_part = self._det_parts(obs, det["pieces"])
+            la.dzf_obs, la.dimg_obs, la.det_slot = ptr(det.dzf), ptr(det.dimg), ptr(det.slot)
+            la.nll_part, la.ev11_part = self._det_parts(obs, det.pieces)
             check(lib.cl_slot_rows(C.byref(la), st), "cl_slot_rows")
             return
         if obs.harmonic_id is None and self.SLOT_ROWS_ONE_LAUNCH:
@@ -1164,8 +1261,7 @@ class ElboEngine(WidePath, FrozenPath):
     def train_step(self, step_index: int, u_f=None, eta=None):
         """One full ELBO step; `step_index` indexes the history buffer, the noise key is the optimizer iteration."""
         if self.dw_trainable:           # the "rDW_i" metrics are the values used in this step's forward pass (wilson.py:173-174)
-            lay = self.layout
-            self.rdw_hist[step_index] = torch.sigmoid(self.params[lay.off_dwr:lay.off_dwr + lay.n_dwr])
+            self.rdw_hist[step_index] = torch.sigmoid(self.layout.view(self.params, "dwr"))
         self.forward_backward(self.t, u_f, eta)
         self.optimizer_step(step_index)
 
@@ -1206,21 +1302,7 @@ class ElboEngine(WidePath, FrozenPath):
         return self._split(self.params)
 
     def _split(self, g: torch.Tensor) -> List[torch.Tensor]:
-        lay = self.layout
-        out = [g[0:self.R], g[self.R:2 * self.R]]
-        base = lay.off_mlp
-        for off, o, i, boff in self.mlp.layer_slices(self.d):
-            out.append(g[base + off: base + off + o * i].view(o, i).t())
-            out.append(g[base + boff: base + boff + o])
-        if lay.n_img > 0:
-            out.append(g[lay.off_img: lay.off_img + lay.n_img])
-        if lay.n_imgl > 0:
-            out += self.imgl.layer_views(g[lay.off_imgl: lay.off_imgl + lay.n_imgl])
-        if lay.n_ev11 > 0:
-            out.append(g[lay.off_ev11: lay.off_ev11 + lay.n_ev11])
-        if lay.n_dwr > 0:
-            out.append(g[lay.off_dwr: lay.off_dwr + lay.n_dwr])
-        return out
+        return split_flat(g, self.layout, self.mlp.layer_slices(self.d), self.imgl.layer_views if self.imgl is not None else None)
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,8 @@ from __future__ import annotations
 
 import ctypes as C
 from collections import namedtuple
+from dataclasses import dataclass, field
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -92,6 +94,21 @@ def hidden_forward(lib, pmlp: int, pimgl, sh: WideShape, src, dsts, ldw: int, ch
     return hs[1:]
 
 
+@dataclass
+class WideBuffers:
+    """Work buffers of the layer-by-layer path, per engine (`WidePath._wide_setup`; the row buffers by `_wide_buffers`)."""
+    ldw: int                                        # row pitch of a hidden layer's activations
+    chunk: int                                      # rows of a chunk
+    nh: int                                         # hidden layers, Dense + per-image
+    rows: int = 0                                   # rows the buffers below hold
+    acts: List[torch.Tensor] = field(default_factory=list)      # one activation buffer per hidden layer (two at least)
+    dz: List[torch.Tensor] = field(default_factory=list)        # two alternating gradient buffers
+    nsplit: int = 0                                 # weight-gradient partials of `rows` rows
+    nblk: int = 0                                   # ... of the head's backward pass
+    wpart: Optional[torch.Tensor] = None
+    hpart: Optional[torch.Tensor] = None
+
+
 class WidePath:
     # -- scalers wider than 64 ---------------------------------------------------------------------------------------------
     WIDE_BUDGET = 4 << 30     # bytes of activation storage a row chunk may take ((L + 2) buffers of chunk x ld floats), and never more
@@ -110,25 +127,25 @@ class WidePath:
         free = torch.cuda.mem_get_info(dev)[0]
         budget = min(self.WIDE_BUDGET, max(free // 4, 64 << 20))
         chunk = max(128, min(budget // per_row, 1 << 21) // 128 * 128)
-        self._wide = dict(ldw=ldw, chunk=chunk, nh=nh, rows=0, acts=[], dz=[])
+        self._wide = WideBuffers(ldw=ldw, chunk=chunk, nh=nh)
         self._wide_buffers(chunk)
         return self._wide
 
     def _wide_buffers(self, rows: int):
         """(Re)allocate the row buffers for chunks of up to `rows` rows (an image larger than the default chunk needs its own size)."""
         W, lib, dev = self._wide, self.lib, self.device
-        if rows <= W["rows"]:
+        if rows <= W.rows:
             return
-        ldw = W["ldw"]
-        W["acts"] = [torch.zeros(rows * ldw, dtype=torch.float32, device=dev) for _ in range(max(2, W["nh"]))]
-        W["dz"] = [torch.zeros(rows * ldw, dtype=torch.float32, device=dev) for _ in range(2)]
-        W["nsplit"], W["nblk"] = int(lib.cl_wide_wgrad_splits(rows)), int(lib.cl_wide_head_blocks(rows))
+        ldw = W.ldw
+        W.acts = [torch.zeros(rows * ldw, dtype=torch.float32, device=dev) for _ in range(max(2, W.nh))]
+        W.dz = [torch.zeros(rows * ldw, dtype=torch.float32, device=dev) for _ in range(2)]
+        W.nsplit, W.nblk = int(lib.cl_wide_wgrad_splits(rows)), int(lib.cl_wide_head_blocks(rows))
         pmax = max(self.w * self.d + self.w, self.w * self.w + self.w)
         # (the fused dgrad + first-layer weight gradient writes one partial per workgroup: more of them, each smaller)
-        W["wpart"] = torch.empty(max(W["nsplit"] * pmax, int(lib.cl_wide_dgrad_wgrad0_parts(rows)) * (self.w * self.d + self.w)),
+        W.wpart = torch.empty(max(W.nsplit * pmax, int(lib.cl_wide_dgrad_wgrad0_parts(rows)) * (self.w * self.d + self.w)),
                                  dtype=torch.float32, device=dev)
-        W["hpart"] = torch.empty(W["nblk"] * (2 * self.w + 2), dtype=torch.float32, device=dev)
-        W["rows"] = rows
+        W.hpart = torch.empty(W.nblk * (2 * self.w + 2), dtype=torch.float32, device=dev)
+        W.rows = rows
 
     def _wide_chunks(self, obs: ObsData):
         """Row chunks [a, b) of `obs` for the layer-by-layer path.  With per-image layers a chunk holds whole images (their rows are
@@ -136,7 +153,7 @@ class WidePath:
         if obs.wide_chunks is not None:
             return obs.wide_chunks
         W = self._wide_setup()
-        obs.wide_chunks, obs.wide_tiles, rows = row_chunks(obs.N, obs.img_seg if self.imgl is not None else None, W["chunk"], self.w, self.device)
+        obs.wide_chunks, obs.wide_tiles, rows = row_chunks(obs.N, obs.img_seg if self.imgl is not None else None, W.chunk, self.w, self.device)
         self._wide_buffers(rows)
         return obs.wide_chunks
 
@@ -144,9 +161,9 @@ class WidePath:
         K, M = (self.imgl.n_image_layers, self.imgl.max_images) if self.imgl is not None else (0, 0)
         return WideShape(self.d, self.w, self.L, K, M, self.mlp.leakiness)
 
-    def _imgl_ptrs(self, flat: torch.Tensor, k: int, m0: int):
-        """Device pointers of (kernel, bias) of image m0 in per-image layer k inside `flat` (params or grads)."""
-        return imgl_ptrs(flat.data_ptr() + 4 * self.layout.off_imgl, self._wide_shape(), k, m0)
+    def _imgl_ptrs(self, at, k: int, m0: int):
+        """Device pointers of (kernel, bias) of image m0 in per-image layer k of the parameters or the gradient (`at`: `_param_ptr` / `_grad_ptr`)."""
+        return imgl_ptrs(at("imgl"), self._wide_shape(), k, m0)
 
     WIDE_KEEP_BUDGET = 64 << 30     # bytes of activations of a whole observation set the forward pass may keep for the backward pass
     # The fusions of round 4, each with the separate launches it replaced still behind it (the fallback of shapes outside the fused
@@ -173,15 +190,15 @@ class WidePath:
         """Per-layer activation buffers over ALL rows of `obs` (list of tensors), or None when they do not fit: then the backward pass
         recomputes each chunk's forward into the chunk-sized buffers."""
         W = self._wide_setup()
-        need = 4 * (W["nh"] - (1 if self._wide_pre() else 0)) * W["ldw"] * obs.N
+        need = 4 * (W.nh - (1 if self._wide_pre() else 0)) * W.ldw * obs.N
         if obs.wide_full is not None:
             return obs.wide_full
         free = torch.cuda.mem_get_info(self.device)[0]
         if need > min(self.WIDE_KEEP_BUDGET, free // 4):
             return None
         # (with the first layer recomputed its output has no buffer)
-        obs.wide_full = [None if (l == 0 and self._wide_pre()) else torch.zeros(obs.N * W["ldw"], dtype=torch.float32, device=self.device)
-                         for l in range(W["nh"])]
+        obs.wide_full = [None if (l == 0 and self._wide_pre()) else torch.zeros(obs.N * W.ldw, dtype=torch.float32, device=self.device)
+                         for l in range(W.nh)]
         return obs.wide_full
 
     def _wide_forward(self, obs: ObsData, chunk, keep: bool, st, full=None, head=None, lik=None):
@@ -190,13 +207,13 @@ class WidePath:
         rode in the top layer's epilogue and whether the slot likelihood `lik` did too."""
         a, n = chunk.a, chunk.b - chunk.a
         lib, W, sh = self.lib, self._wide_setup(), self._wide_shape()
-        ldw, base = W["ldw"], self.params.data_ptr() + 4 * self.layout.off_mlp
+        ldw, base = W.ldw, self._param_ptr("mlp")
         layers, _ = dense_layout(self.d, self.w, self.L)
         sf, leak = ptr(self.stop_flag), self.mlp.leakiness
         dsts = [None if t is None else t.data_ptr() + 4 * a * ldw for t in full] if full is not None else \
-            [W["acts"][l if keep else l & 1].data_ptr() for l in range(self.L + sh.K)]
-        unfused = lambda src, l0, l1: hidden_forward(lib, base, self.params.data_ptr() + 4 * self.layout.off_imgl, sh, src, dsts, ldw, chunk,
-                                                     obs.wide_tiles and obs.wide_tiles[a], sf, st, range(l0, l1))
+            [W.acts[l if keep else l & 1].data_ptr() for l in range(self.L + sh.K)]
+        unfused = lambda src, l0, l1: hidden_forward(lib, base, self._param_ptr("imgl"), sh, src, dsts, ldw, chunk, obs.wide_tiles and obs.wide_tiles[a],
+                                                     sf, st, range(l0, l1))
         hs = [(obs.meta_rm.data_ptr() + 4 * a * obs.meta_ld, obs.meta_ld)]
         head_fused = lik_fused = False
         first = 0
@@ -237,7 +254,7 @@ class WidePath:
         chunks = self._wide_chunks(obs)
         ma = self._mlp_args(step, eta, ipred_out, obs)
         _, off_head = dense_layout(self.d, self.w, self.L)
-        pbase = self.params.data_ptr() + 4 * self.layout.off_mlp
+        pbase = self._param_ptr("mlp")
         # The activations of ALL rows are kept by the forward pass when they fit (WIDE_KEEP_BUDGET, a quarter of the free memory at
         # most: 15 GB for 10 M rows of a 3 x 128 scaler on a 288-GB device) and the backward pass starts from them -- 6 P_mm flops per
         # observation.  Otherwise the buffers hold one chunk at a time and each chunk's forward is recomputed when its turn in the
@@ -277,10 +294,10 @@ class WidePath:
         n = b - a
         lib, W = self.lib, self._wide_setup()
         layers, off_head = dense_layout(self.d, self.w, self.L)
-        pbase, gbase = (t.data_ptr() + 4 * self.layout.off_mlp for t in (self.params, self.grads))
-        sf, leak, w, ldw = ptr(self.stop_flag), self.mlp.leakiness, self.w, W["ldw"]
-        dz, dzn = W["dz"]
-        nsplit = min(W["nsplit"], int(lib.cl_wide_wgrad_splits(n)))
+        pbase, gbase = self._param_ptr("mlp"), self._grad_ptr("mlp")
+        sf, leak, w, ldw = ptr(self.stop_flag), self.mlp.leakiness, self.w, W.ldw
+        dz, dzn = W.dz
+        nsplit = min(W.nsplit, int(lib.cl_wide_wgrad_splits(n)))
 
         def reduce(parts, nparts, size, off):
             check(lib.cl_reduce_partials(ptr(parts), nparts, size, gbase + 4 * off, sf, st), "cl_reduce_partials")
@@ -290,20 +307,20 @@ class WidePath:
             l = self.L - 1
             ow, ob, fan_in = layers[l]
             hd = (*hs[-1], pbase + 4 * off_head, obs.laue_dO.data_ptr() + 8 * a, obs.wide_dsd.data_ptr() + 4 * a)
-            check(lib.cl_wide_dense_wgrad_head(*hd, leak, *hs[l], n, w, fan_in, ptr(W["wpart"]), ptr(W["hpart"]), nsplit, sf, st), "cl_wide_dense_wgrad_head")
-            reduce(W["wpart"], nsplit, w * fan_in + w, ow)
-            reduce(W["hpart"], nsplit, 2 * w + 2, off_head)
+            check(lib.cl_wide_dense_wgrad_head(*hd, leak, *hs[l], n, w, fan_in, ptr(W.wpart), ptr(W.hpart), nsplit, sf, st), "cl_wide_dense_wgrad_head")
+            reduce(W.wpart, nsplit, w * fan_in + w, ow)
+            reduce(W.hpart, nsplit, 2 * w + 2, off_head)
             check(lib.cl_wide_dense_dgrad_head(*hd, pbase + 4 * ow, n, w, fan_in, *hs[l], leak, ptr(dz), ldw, sf, st), "cl_wide_dense_dgrad_head")
         else:
-            nblk = min(W["nblk"], int(lib.cl_wide_head_blocks(n)))
+            nblk = min(W.nblk, int(lib.cl_wide_head_blocks(n)))
             check(lib.cl_wide_head_backward(*hs[-1], pbase + 4 * off_head, obs.laue_dO.data_ptr() + 8 * a, n, w, self.bij_kind,
-                                            self.mlp.epsilon, leak, ptr(dz), ldw, ptr(W["hpart"]), nblk, sf, st), "cl_wide_head_backward")
-            reduce(W["hpart"], nblk, 2 * w + 2, off_head)
+                                            self.mlp.epsilon, leak, ptr(dz), ldw, ptr(W.hpart), nblk, sf, st), "cl_wide_head_backward")
+            reduce(W.hpart, nblk, 2 * w + 2, off_head)
         K = self.imgl.n_image_layers if self.imgl is not None else 0
         for k in range(K - 1, -1, -1):          # per-image layers: each image's gradient is written once (its rows sit in one chunk)
             l = self.L + k
-            gw, gb = self._imgl_ptrs(self.grads, k, m0)
-            wk, _ = self._imgl_ptrs(self.params, k, m0)
+            gw, gb = self._imgl_ptrs(self._grad_ptr, k, m0)
+            wk, _ = self._imgl_ptrs(self._param_ptr, k, m0)
             check(lib.cl_wide_image_wgrad(ptr(dz), ldw, *hs[l], ptr(seg), seg.numel() - 1, n, w, gw, gb, sf, st), "cl_wide_image_wgrad")
             if w > 128:
                 tl = obs.wide_tiles[a]
@@ -319,21 +336,21 @@ class WidePath:
                 # the layer's input h_0 is recomputed from the metadata: as the weight gradient's operand and as the dgrad's mask
                 ow0, ob0, d0 = layers[0]
                 x0 = (*hs[0], d0, pbase + 4 * ow0, pbase + 4 * ob0)
-                check(lib.cl_wide_dense_wgrad_pre(ptr(dz), ldw, *x0, leak, n, w, fan_in, ptr(W["wpart"]), nsplit, sf, st), "cl_wide_dense_wgrad_pre")
-                reduce(W["wpart"], nsplit, w * fan_in + w, ow)
+                check(lib.cl_wide_dense_wgrad_pre(ptr(dz), ldw, *x0, leak, n, w, fan_in, ptr(W.wpart), nsplit, sf, st), "cl_wide_dense_wgrad_pre")
+                reduce(W.wpart, nsplit, w * fan_in + w, ow)
                 # layer 1's dgrad with layer 0's weight gradient taken where dZ_0 is produced (it is never stored) ...
                 rc = -2 if not self.FUSE_WG0 else \
-                    lib.cl_wide_dense_dgrad_pre_wgrad0(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *x0, leak, ptr(W["wpart"]), sf, st)
+                    lib.cl_wide_dense_dgrad_pre_wgrad0(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *x0, leak, ptr(W.wpart), sf, st)
                 if rc != -2:
                     check(rc, "cl_wide_dense_dgrad_pre_wgrad0")
-                    reduce(W["wpart"], int(lib.cl_wide_dgrad_wgrad0_parts(n)), w * d0 + w, ow0)
+                    reduce(W.wpart, int(lib.cl_wide_dgrad_wgrad0_parts(n)), w * d0 + w, ow0)
                     break
                 # ... or, outside that kernel's envelope, the two launches
                 check(lib.cl_wide_dense_dgrad_pre(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *x0, leak, ptr(dzn), ldw, sf, st), "cl_wide_dense_dgrad_pre")
                 dz, dzn = dzn, dz
                 continue
-            check(lib.cl_wide_dense_wgrad(ptr(dz), ldw, *hs[l], n, w, fan_in, ptr(W["wpart"]), nsplit, sf, st), "cl_wide_dense_wgrad")
-            reduce(W["wpart"], nsplit, w * fan_in + w, ow)
+            check(lib.cl_wide_dense_wgrad(ptr(dz), ldw, *hs[l], n, w, fan_in, ptr(W.wpart), nsplit, sf, st), "cl_wide_dense_wgrad")
+            reduce(W.wpart, nsplit, w * fan_in + w, ow)
             if l > 0:
                 check(lib.cl_wide_dense_dgrad(ptr(dz), ldw, pbase + 4 * ow, n, w, fan_in, *hs[l], leak, ptr(dzn), ldw, sf, st), "cl_wide_dense_dgrad")
                 dz, dzn = dzn, dz

@@ -65,8 +65,8 @@ def main():
         out = dict(nll=float(eng.loss_terms()["nll"]), grads=eng.grads.clone(), dz_f=eng.dz_f.clone(), partials=obs.partials.clone())
         pb = getattr(obs, "peel", None)
         if pb is not None:
-            out["dz0"] = pb["dz0"].clone().view(-1, obs.n_pad)
-            out["u"] = pb["u"].clone().view(-1, obs.n_pad)
+            out["dz0"] = pb.dz0.clone().view(-1, obs.n_pad)
+            out["u"] = pb.u.clone().view(-1, obs.n_pad)
         rec["nll"].append(out["nll"])
         if ref is None:
             ref = out

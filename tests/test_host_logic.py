@@ -901,3 +901,197 @@ def test_image_chunks_keep_whole_images_and_cover_every_row_once():
                 assert b - a <= chunk or np.count_nonzero(np.diff(rel)) == 1
     assert [(a, b, m0, rel.tolist()) for a, b, m0, rel in image_chunks(np.array([0, 20, 20, 300, 300]), 128)] == \
         [(0, 20, 0, [0, 20, 20]), (20, 300, 2, [0, 280])]
+
+
+# --- the engine's state: the table of the flat vector, binding, the workspace carve, the two refusals (host logic of ElboEngine.__init__) ------
+def test_flat_layout_table_gives_every_offset():
+    from careless_amd.engine import FLAT_GROUPS
+    from careless_amd.models.scaling.image import image_layer_layout
+    from careless_amd.models.scaling.nn import dense_slices
+    assert FLAT_GROUPS == ("q_loc", "q_scale", "mlp", "img", "imgl", "ev11", "dwr")
+    for L, w, d in ((2, 32, 5), (20, 10, 5)):
+        slices = dense_slices(d, w, L)
+        P = slices[-1][3] + 2
+        for R in (1, 3, 100):
+            for n_img in (0, 9):
+                for imgl in (None, (2, 7)):
+                    for n_ev11 in (0, 3):
+                        for n_dwr in (0, 4):
+                            lay = make_layout(R=R, d=d, w=w, L=L, n_img=n_img, n_ev11=n_ev11, n_dwr=n_dwr, imgl=imgl)
+                            n_imgl = 0 if imgl is None else imgl[0] * imgl[1] * (w * w + w)
+                            assert [g[0] for g in lay.groups] == list(FLAT_GROUPS)
+                            assert [g[2] for g in lay.groups] == [R, R, P, n_img, n_imgl, n_ev11, n_dwr]
+                            at = 0
+                            for name, off, cnt in lay.groups:            # contiguous, in the stated order
+                                assert off == at == lay.off(name) and cnt >= 0
+                                at += cnt
+                            assert at == lay.n == 2 * R + P + n_img + n_imgl + n_ev11 + n_dwr
+                            # the closed forms the properties restated before the table
+                            assert (lay.P, lay.n_img, lay.n_imgl, lay.n_ev11, lay.n_dwr) == (P, n_img, n_imgl, n_ev11, n_dwr)
+                            assert lay.off_mlp == 2 * R
+                            assert lay.off_img == 2 * R + P
+                            assert lay.off_imgl == 2 * R + P + n_img
+                            assert lay.off_ev11 == 2 * R + P + n_img + n_imgl
+                            assert lay.off_dwr == 2 * R + P + n_img + n_imgl + n_ev11
+                            flat = torch.arange(lay.n)
+                            for name, off, cnt in lay.groups:
+                                assert lay.view(flat, name).tolist() == list(range(off, off + cnt))
+                            # seg_off: the tensors of every group, as before
+                            seg = [0, R, 2 * R] + [2 * R + x for _, o, _, ob in slices for x in (ob, ob + o)]
+                            seg += [lay.off_img + n_img] if n_img else []
+                            if imgl is not None:
+                                seg += [lay.off_imgl + x for ow, ob in image_layer_layout(imgl[0], imgl[1], w)[0] for x in (ob, ob + imgl[1] * w)]
+                            seg += [lay.off_ev11 + k + 1 for k in range(n_ev11)] + ([lay.off_dwr + n_dwr] if n_dwr else [])
+                            assert lay.seg_off == seg and seg[-1] == lay.n
+                            assert lay.seg_owner == ["q", "q"] + ["scaler"] * (len(seg) - 3 - n_ev11 - (1 if n_dwr else 0)) + ["likelihood"] * n_ev11 + \
+                                ["prior"] * (1 if n_dwr else 0)
+    from careless_amd.engine import FlatLayout
+    lay = FlatLayout(R=4, P=10, n_img=2, seg_off=[], seg_owner=[])          # (the keywords bench.py's tests construct one with)
+    assert (lay.n, lay.off_mlp, lay.off_img, lay.off_imgl, lay.off_ev11, lay.off_dwr) == (20, 8, 18, 20, 20, 20)
+
+
+def test_bind_flat_turns_plugin_tensors_into_views_of_the_flat_vector():
+    from types import SimpleNamespace as NS
+    from careless_amd.engine import bind_flat, split_flat
+    from careless_amd.models.scaling.image import NeuralImageScaler
+    from careless_amd.models.scaling.nn import dense_slices
+    R, d, w, L, K, M = 5, 4, 6, 2, 2, 3
+    rng = torch.Generator().manual_seed(3)
+    rand = lambda n: torch.rand(n, generator=rng)
+    for with_img, with_imgl, ev11, n_dwr in ((True, False, True, 2), (False, True, False, 0), (False, False, False, 0), (True, True, True, 3)):
+        slices = dense_slices(d, w, L)
+        lay = make_layout(R=R, d=d, w=w, L=L, n_img=7 if with_img else 0, n_ev11=3 if ev11 else 0, n_dwr=n_dwr, imgl=(K, M) if with_imgl else None)
+        q = NS(loc_raw=rand(R), scale_raw=rand(R))
+        mlp = NS(flat=rand(lay.P))
+        img = NS(_scales=rand(7)) if with_img else None
+        imgl = NS(flat=rand(lay.n_imgl)) if with_imgl else None
+        lik = NS(raw=rand(3)) if ev11 else NS(raw=None)
+        prior = NS(r_raw=rand(n_dwr)) if n_dwr else NS(r_raw=None)
+        bindings = [("q_loc", q, "loc_raw"), ("q_scale", q, "scale_raw"), ("mlp", mlp, "flat"), ("img", img, "_scales"), ("imgl", imgl, "flat"),
+                    ("ev11", lik, "raw"), ("dwr", prior, "r_raw")]
+        assert [b[0] for b in bindings] == [g[0] for g in lay.groups]
+        before = {g: getattr(h, a).clone() for g, h, a in bindings if h is not None and getattr(h, a) is not None}
+        flat = torch.full((lay.n,), float("nan"))
+        bind_flat(flat, lay, q, mlp, img, imgl, lik, prior)
+        assert not torch.isnan(flat).any()                                 # every element was written
+        for (group, holder, attr), (name, off, cnt) in zip(bindings, lay.groups):
+            if cnt == 0:
+                assert group not in before or before[group].numel() == 0   # nothing to bind: the holder is left alone
+                continue
+            t = getattr(holder, attr)
+            assert t.data_ptr() == flat.data_ptr() + 4 * off and t.numel() == cnt and t.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr()
+            assert torch.equal(t, before[group])                           # its original values
+            flat[off:off + cnt] += 1.0                                     # a write through the flat vector is seen by the plugin
+            assert torch.equal(getattr(holder, attr), before[group] + 1.0)
+        # the per-tensor views cover [0, n) exactly once, in order
+        views = split_flat(flat, lay, slices, NeuralImageScaler(K, M, L, w).layer_views if with_imgl else None)
+        marks = torch.zeros(lay.n, dtype=torch.int64)
+        for v in views:
+            assert v.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr()
+            off = (v.data_ptr() - flat.data_ptr()) // 4
+            marks[off:off + v.numel()] += 1
+        assert torch.equal(marks, torch.ones(lay.n, dtype=torch.int64))
+        # ... tensor by tensor as `seg_off` cuts the vector (the three Evans-2011 scalars come as one view)
+        inner = [lay.off_ev11 + k for k in (1, 2)] if ev11 else []
+        assert [v.numel() for v in views] == np.diff([x for x in lay.seg_off if x not in inner]).tolist()
+        assert [tuple(v.shape) for v in views[2:2 + 2 * len(slices)]] == [s for _, o, i, _ in slices for s in ((i, o), (o,))]
+
+
+# (R, S, n, nseg, owner) -> (dz_f, grads, msg, msg_norm, scalars, seg_sq, own_scratch, ws_step, total): offsets and counts in floats, taken from the
+# arithmetic ElboEngine.__init__ held inline before `carve_workspace`
+WORKSPACE_TABLE = {
+    (1, 1, 9, 5, False): ((0, 1), (4, 9), (6, 15), (17, 4), (24, 8), (32, 10), (42, 10), (4, 48), 52),
+    (1, 1, 9, 5, True): ((0, 1), (6, 9), (8, 15), (19, 4), (24, 8), (32, 10), (42, 10), (4, 48), 52),
+    (3, 3, 1100, 9, True): ((0, 9), (14, 1100), (20, 1102), (1118, 4), (1124, 8), (1132, 18), (1150, 10), (12, 1148), 1160),
+    (5, 8, 2251, 8, False): ((0, 40), (40, 2251), (50, 2249), (2295, 4), (2300, 8), (2308, 16), (2324, 10), (40, 2294), 2334),
+    (41, 3, 500, 12, True): ((0, 123), (126, 500), (208, 426), (630, 4), (636, 8), (644, 24), (668, 10), (124, 554), 678),
+    (41, 1, 500, 12, False): ((0, 41), (44, 500), (126, 426), (548, 4), (552, 8), (560, 24), (584, 10), (44, 550), 594),
+    (2, 3, 71, 6, True): ((0, 6), (8, 71), (12, 75), (83, 4), (88, 8), (96, 12), (108, 10), (8, 110), 118),
+    (100, 8, 4567, 15, False): ((0, 800), (800, 4567), (1000, 4375), (5371, 4), (5376, 8), (5384, 30), (5414, 10), (800, 4624), 5424),
+}
+
+
+def test_workspace_carve():
+    from careless_amd.engine import carve_workspace
+    names = ("dz_f", "grads", "msg", "msg_norm", "scalars", "seg_sq", "own_scratch", "ws_step")
+    for key, want in WORKSPACE_TABLE.items():
+        c = carve_workspace(*key)
+        assert tuple(getattr(c, k) for k in names) + (c.total,) == want, key
+    for R in (1, 2, 3, 5, 41):
+        for S in (1, 3, 8):
+            for owner in (False, True):
+                for P, nseg in ((7, 4), (3472, 44)):
+                    n = 2 * R + P
+                    c = carve_workspace(R, S, n, nseg, owner)
+                    assert c.aligned and c.owner == owner
+                    assert (c.msg if owner else c.grads)[0] % 4 == 0 and c.ws_step[0] % 4 == 0        # the all-reduced buffer, ws_step: 16-byte boundaries
+                    assert all(getattr(c, k)[0] % 2 == 0 for k in ("scalars", "seg_sq", "own_scratch"))                 # doubles on 8-byte boundaries
+                    assert (c.dz_f, c.grads[1], c.scalars[1], c.seg_sq[1], c.own_scratch[1], c.msg_norm[1]) == ((0, R * S), n, 8, 2 * nseg, 10, 4)
+                    # the regions follow each other without overlap (four floats of slack in front of the norm terms) and end at the total
+                    slack = (c.grads[0] + n, 4)
+                    regions = [c.dz_f, c.grads, slack, c.msg_norm, c.scalars, c.seg_sq, c.own_scratch]
+                    for (a, na), (b, _) in zip(regions[:-1], regions[1:]):
+                        assert a + na <= b
+                    assert slack[0] + 4 == c.msg_norm[0]
+                    assert c.own_scratch[0] + c.own_scratch[1] == c.total
+                    # the two spans: the message is the gradient behind a and b, the slack and the norm terms; a step clears everything from the
+                    # gradient's padding on
+                    assert c.msg == (c.grads[0] + 2 * R, n + 8 - 2 * R) and c.msg[0] + c.msg[1] == c.msg_norm[0] + 4
+                    assert c.dz_f[1] <= c.ws_step[0] <= c.grads[0] and c.ws_step[0] + c.ws_step[1] == c.total
+
+
+def test_deterministic_refusal_clause_by_clause():
+    from careless_amd.engine import ScalerPlan, chain_plan, check_deterministic
+    LANE, IMGL, NONE = _lib.CL_ROUTE_LANE, _lib.CL_ROUTE_LANE_IMGL, _lib.CL_ROUTE_NONE
+    plain = ScalerPlan(False, False, None, False, LANE)
+    wide = ScalerPlan(True, False, None, False, NONE)
+    chain = ScalerPlan(False, False, chain_plan(5, 10, 24, 20), False, LANE)
+    ok = dict(plan=plain, laue=False, two_pass=False, imgl=False, S=1, dw_trainable=False)
+    accepted = [{}, dict(laue=True), dict(S=3), dict(plan=wide, S=4), dict(plan=wide, S=64), dict(plan=chain), dict(plan=ScalerPlan(False, True, None, False, LANE)),
+                dict(plan=ScalerPlan(False, False, None, False, IMGL), imgl=True), dict(plan=ScalerPlan(False, False, None, False, NONE))]
+    for over in accepted:
+        assert check_deterministic(**dict(ok, **over)) is None, over
+    refused = [dict(two_pass=True), dict(laue=True, two_pass=True),                  # the two-pass Laue path
+               dict(plan=wide, laue=True), dict(plan=wide, S=3), dict(plan=wide, S=128),      # wide: monochromatic, a sample count that divides 64
+               dict(plan=ScalerPlan(False, False, None, False, NONE), imgl=True), dict(plan=wide, S=4, imgl=True),      # per-image layers without a route
+               dict(plan=chain, laue=True),                                          # a chain on Laue data
+               dict(dw_trainable=True)]                                              # a trainable double-Wilson r
+    for over in refused:
+        with pytest.raises(NotImplementedError, match="deterministic mode covers monochromatic and single-pass Laue data.*keep their float atomics"):
+            check_deterministic(**dict(ok, **over))
+
+
+def test_owner_shard_decision_clause_by_clause():
+    from careless_amd.engine import wants_owner_shard
+    from careless_amd.models.priors.empirical import NormalReferencePrior
+    wilson = WilsonPrior(np.zeros(6, dtype=bool), np.ones(6), 1.0)
+    ref = NormalReferencePrior(np.ones(6), np.ones(6), np.ones(6, dtype=bool))
+    ok = dict(want=True, prior=wilson, world=2, owner_given=False, laue=False, double_wilson=False, wide=False, imgl=False, deterministic=False)
+    assert wants_owner_shard(**ok) is True and wants_owner_shard(**dict(ok, world=8)) is True
+    for over in (dict(want=False), dict(world=1), dict(owner_given=True), dict(laue=True), dict(double_wilson=True), dict(wide=True), dict(imgl=True),
+                 dict(deterministic=True)):
+        assert wants_owner_shard(**dict(ok, **over)) is False, over
+    # the split is Wilson-only: asked for on several ranks, or given, it refuses another prior -- also where it would keep the row split
+    for over in ({}, dict(laue=True), dict(owner_given=True), dict(want=False, owner_given=True), dict(world=1, owner_given=True)):
+        with pytest.raises(NotImplementedError, match="reflection-owner split runs the Wilson prior only, not NormalReferencePrior"):
+            wants_owner_shard(**dict(ok, prior=ref, **over))
+    for over in (dict(want=False), dict(world=1)):                        # not asked for, nobody to split with: the prior is not looked at
+        assert wants_owner_shard(**dict(ok, prior=ref, **over)) is False
+
+
+def test_switch_model_attribute_then_environment_then_default(monkeypatch):
+    from types import SimpleNamespace as NS
+    from careless_amd.engine import switch
+    env = "CARELESS_HIP_TEST_SWITCH"
+    monkeypatch.delenv(env, raising=False)
+    assert switch(NS(), "x", env) is False and switch(NS(), "x", env, default=True) is True and switch(NS(x=None), "x", env) is False
+    assert switch(NS(x=True), "x", env) is True and switch(NS(x=False), "x", env, default=True) is False and switch(NS(), None, env) is False
+    monkeypatch.setenv(env, "1")
+    assert switch(NS(), "x", env) is True and switch(NS(x=None), "x", env) is True and switch(NS(), None, env) is True
+    assert switch(NS(x=False), "x", env) is False                          # the attribute wins ...
+    assert switch(NS(x=False), "x", env, env_adds=True) is True             # ... unless the variable may add (`deterministic`)
+    monkeypatch.setenv(env, "0")
+    assert switch(NS(), "x", env, default=True) is False and switch(NS(x=True), "x", env, default=True) is True
+    assert switch(NS(x=True), "x", env, env_adds=True) is True and switch(NS(), "x", env) is False
+    monkeypatch.setenv(env, "yes")                                          # only "1" switches on, only "0" off
+    assert switch(NS(), "x", env) is False and switch(NS(), "x", env, default=True) is True
