@@ -145,6 +145,11 @@ class RefPriorArgs(C.Structure):
     ]
 
 
+class RwArgs(C.Structure):
+    """mirror of `cl_rw_args` (include/careless_hip.h)"""
+    _fields_ = [("tn", TnArgs), ("q_centric", _vp), ("n_f", _vp)]
+
+
 class AdamArgs(C.Structure):
     """mirror of `cl_adam_args` (include/careless_hip.h)"""
     _fields_ = [
@@ -216,6 +221,10 @@ EXPORTS = {
     "cl_frozen_args_size": (C.c_size_t, []),
     "cl_ref_prior": (C.c_int, [C.POINTER(RefPriorArgs), _vp]),
     "cl_refprior_args_size": (C.c_size_t, []),
+    "cl_rw_forward": (C.c_int, [C.POINTER(RwArgs), _vp]),
+    "cl_rw_backward": (C.c_int, [C.POINTER(RwArgs), _vp]),
+    "cl_rw_args_size": (C.c_size_t, []),
+    "cl_rw_moments": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp]),
     "cl_reduce_partials": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "cl_grad_sqnorm": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cl_adam_step": (C.c_int, [C.POINTER(AdamArgs), _vp]),
@@ -275,6 +284,8 @@ def get_lib() -> C.CDLL:
         raise CarelessHipError(f"ABI mismatch: cl_frozen_args is {int(lib.cl_frozen_args_size())} bytes in the library, {C.sizeof(FrozenArgs)} in careless_amd/_lib.py")
     if int(lib.cl_refprior_args_size()) != C.sizeof(RefPriorArgs):
         raise CarelessHipError(f"ABI mismatch: cl_refprior_args is {int(lib.cl_refprior_args_size())} bytes in the library, {C.sizeof(RefPriorArgs)} in careless_amd/_lib.py")
+    if int(lib.cl_rw_args_size()) != C.sizeof(RwArgs):
+        raise CarelessHipError(f"ABI mismatch: cl_rw_args is {int(lib.cl_rw_args_size())} bytes in the library, {C.sizeof(RwArgs)} in careless_amd/_lib.py")
     _lib = lib
     return lib
 

@@ -46,7 +46,7 @@ UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=
          # host threads, no device code: the formatter's symmetry bookkeeping (exact products kept apart from their sums)
          ("host_format.cpp", "host_format", ["-ffp-contract=off", "-pthread"])]
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["cl_math.h", "cl_kernels.h", "elbo_frozen_rows.h", os.path.join("..", "..", "include", "careless_hip.h")]
+HEADERS = ["cl_math.h", "cl_kernels.h", "elbo_frozen_rows.h", "elbo_q_kernels.h", os.path.join("..", "..", "include", "careless_hip.h")]
 ARCH = "gfx950"
 
 

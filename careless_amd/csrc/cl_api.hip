@@ -112,8 +112,9 @@ int cl_reduce_partials(const float* partials, int nparts, int P, float* grad_mlp
     return cl_launch_reduce_partials(partials, nparts, P, grad_mlp, stop_flag, (hipStream_t)stream);
 }
 
-static int check_tn(const cl_tn_args* a) {
-    if (a == nullptr || a->q_loc_raw == nullptr || a->q_scale_raw == nullptr || a->low == nullptr || a->R < 1 || a->S < 1) return -1;
+// `need_low`: the truncated normal reads its lower bound; the Rice-Woolfson posterior (cl_rw_*) has none
+static int check_tn(const cl_tn_args* a, bool need_low = true) {
+    if (a == nullptr || a->q_loc_raw == nullptr || a->q_scale_raw == nullptr || (need_low && a->low == nullptr) || a->R < 1 || a->S < 1) return -1;
     // (a reference prior's term is cl_ref_prior's: the Wilson arrays are not read)
     if (a->prior_kind != CL_PRIOR_REFERENCE_ && (a->centric == nullptr || a->es == nullptr)) return -1;
     if (a->prior_kind == CL_PRIOR_DOUBLE_WILSON_ && (a->parent_ids == nullptr || a->root == nullptr)) return -1;
@@ -125,21 +126,47 @@ static int check_tn(const cl_tn_args* a) {
     return 0;
 }
 
-int cl_tn_forward(const cl_tn_args* a, void* stream) {
-    if (int e = check_tn(a)) return e;
+// what the forward / backward launch of either posterior asks of the shared argument block, beyond check_tn
+static int check_q_forward(const cl_tn_args* a) {
     if (a->z_f == nullptr || a->scalars == nullptr) return -1;
     if (a->zero_ptr != nullptr && (a->zero_n < 1 || (reinterpret_cast<uintptr_t>(a->zero_ptr) & 15) != 0)) return -1;
     // the KL must not be added into a block this launch is clearing: the parts go to kl_part then
     if (a->zero_ptr != nullptr && a->kl_part == nullptr) return -1;
+    return 0;
+}
+static int check_q_backward(const cl_tn_args* a) {
+    if (a->dz_f == nullptr || a->d_loc_raw == nullptr || a->d_scale_raw == nullptr) return -1;
+    if (a->red_partials != nullptr && (a->red_out == nullptr || a->red_nparts < 1 || a->red_P < 1)) return -1;
+    return 0;
+}
+
+int cl_tn_forward(const cl_tn_args* a, void* stream) {
+    if (int e = check_tn(a)) return e;
+    if (int e = check_q_forward(a)) return e;
     return cl_launch_tn_forward(*a, (hipStream_t)stream);
 }
 
 int cl_tn_backward(const cl_tn_args* a, void* stream) {
     if (int e = check_tn(a)) return e;
-    if (a->dz_f == nullptr || a->d_loc_raw == nullptr || a->d_scale_raw == nullptr) return -1;
-    if (a->red_partials != nullptr && (a->red_out == nullptr || a->red_nparts < 1 || a->red_P < 1)) return -1;
+    if (int e = check_q_backward(a)) return e;
     return cl_launch_tn_backward(*a, (hipStream_t)stream);
 }
+
+// Rice-Woolfson posterior (replaces reference surrogate_posteriors.py:133-172 on distributions.py:228-348; include/careless_hip.h: cl_rw_args)
+int cl_rw_forward(const cl_rw_args* a, void* stream) {
+    if (a == nullptr || a->q_centric == nullptr) return -1;
+    if (int e = check_tn(&a->tn, false)) return e;
+    if (int e = check_q_forward(&a->tn)) return e;
+    return cl_launch_rw_forward(*a, (hipStream_t)stream);
+}
+
+int cl_rw_backward(const cl_rw_args* a, void* stream) {
+    if (a == nullptr || a->q_centric == nullptr) return -1;
+    if (int e = check_tn(&a->tn, false)) return e;
+    if (int e = check_q_backward(&a->tn)) return e;
+    return cl_launch_rw_backward(*a, (hipStream_t)stream);
+}
+size_t cl_rw_args_size(void) { return sizeof(cl_rw_args); }
 
 int cl_dw_prior_forward(const cl_tn_args* a, void* stream) {
     if (int e = check_tn(a)) return e;
@@ -197,6 +224,14 @@ int cl_tn_moments(const float* q_loc_raw, const float* q_scale_raw, const float*
     if (q_loc_raw == nullptr || q_scale_raw == nullptr || low == nullptr || R < 1) return -1;
     if (mean == nullptr && std == nullptr && m4 == nullptr) return -1;
     return cl_launch_tn_moments(q_loc_raw, q_scale_raw, low, R, high_moments, high_m4, eps, mean, std, m4, (hipStream_t)stream);
+}
+
+// (replaces RiceWoolfson.mean / .stddev, reference surrogate_posteriors.py:156-163; the fourth moment is this project's)
+int cl_rw_moments(const float* q_loc_raw, const float* q_scale_raw, const unsigned char* q_centric, int R, float eps, float* mean, float* std,
+                  double* m4, void* stream) {
+    if (q_loc_raw == nullptr || q_scale_raw == nullptr || q_centric == nullptr || R < 1) return -1;
+    if (mean == nullptr && std == nullptr && m4 == nullptr) return -1;
+    return cl_launch_rw_moments(q_loc_raw, q_scale_raw, q_centric, R, eps, mean, std, m4, (hipStream_t)stream);
 }
 
 int cl_predict_moments(const float* scale_mean, const float* scale_std, const int* refl_id, long long n, const float* f_mean, const float* f_std,

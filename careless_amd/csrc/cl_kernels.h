@@ -47,6 +47,10 @@ int cl_launch_lane(const cl_mlp_args& a, const cl_launch_ctx& c);               
 int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st);
 int cl_launch_tn_forward(const cl_tn_args& a, hipStream_t st);
 int cl_launch_tn_backward(const cl_tn_args& a, hipStream_t st);
+int cl_launch_rw_forward(const cl_rw_args& a, hipStream_t st);             // elbo_elem.hip: the Rice-Woolfson posterior's instances of the two
+int cl_launch_rw_backward(const cl_rw_args& a, hipStream_t st);
+int cl_launch_rw_moments(const float* a, const float* b, const unsigned char* centric, int R, float eps, float* mean, float* sd, double* m4,
+                         hipStream_t st);
 int cl_launch_dw_forward(const cl_tn_args& a, hipStream_t st);
 int cl_launch_ref_prior(const cl_refprior_args& a, hipStream_t st);        // elbo_elem.hip: empirical reference priors
 int cl_launch_grad_sqnorm(const float* g, int n, const int* seg_off, int nseg, double* seg_sq, double* scalars,

@@ -452,6 +452,110 @@ CL_HD float cl_ref_prior_log_prob(int kind, float z, float loc, float scale, boo
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Rice-Woolfson surrogate posterior, one (reflection, sample) element (careless/models/merging/surrogate_posteriors.py:133-172;
+// careless/utils/distributions.py:252-258, 300-319).  Parameters as the truncated normal's: loc = exp(a), scale = exp(b) + eps.
+//   centric   z = |loc + scale n1| + eps32            (FoldedNormal draw; surrogate_posteriors.py:166 adds eps32; n2 unused)
+//   acentric  z = sqrt((scale n1)^2 + (loc + scale n2)^2)      (Rice draw: s1 alone, s2 + nu)
+// with the plain derivatives of these expressions as pathwise gradients (d|x|/dx = sign x, 0 at 0).
+// The densities are cl_folded_normal_log_prob's and cl_rice_log_prob's, expression for expression, with ONE change: the standardised
+// residual y = (z - loc) / scale is taken from the noise the sample was made of instead of from z - loc, which at loc >> scale has lost
+// log2(loc / scale) bits in fp32 before it is squared (the truncated normal keeps its `y` for the same reason), and the Rice terms in
+// 1 - I1/I0 are taken from an expression that does not cancel.  The reference's -(z^2 + nu^2) / 2 sigma^2 + |z nu / sigma^2| is
+// -y^2 / 2 exactly.
+// ---------------------------------------------------------------------------------------------------------
+struct cl_rw_elem {
+    float loc, scale;        // exp(a), exp(b) + eps
+    float z;                 // the sample
+    float y;                 // (z - loc) / scale, from the noise (no cancellation)
+    float dz_dloc, dz_dscale;
+    bool centric;
+};
+
+CL_HD cl_rw_elem cl_rw_sample(float a_raw, float b_raw, float eps, bool centric, float n1, float n2) {
+    cl_rw_elem r;
+    r.loc = expf(a_raw);
+    r.scale = expf(b_raw) + eps;
+    r.centric = centric;
+    // loc + scale n cancels where n ~ -loc / scale: the roundings of expf alone (1e-7 loc) are then any fraction of the sum, in the sample and
+    // in which side of the kink it is on.  That one sum is taken in fp64 from the raw parameters (loop-invariant exps, one fma per element).
+    const double dloc = exp((double)a_raw), dscale = exp((double)b_raw) + (double)eps;
+    if (centric) {
+        const float x = (float)(dloc + dscale * (double)n1);
+        const float sgn = (x > 0.0f) ? 1.0f : ((x < 0.0f) ? -1.0f : x);      // sign(x): +-0 at the kink, NaN for NaN
+        r.z = fabsf(x) + CL_EPS_F;
+        // z - loc = scale n1 + eps32 on the positive side, -2 loc - scale n1 + eps32 on the negative one
+        r.y = ((x < 0.0f) ? (-n1 - 2.0f * r.loc / r.scale) : n1) + CL_EPS_F / r.scale;
+        r.dz_dloc = sgn;
+        r.dz_dscale = sgn * n1;
+    } else {
+        const float u = r.scale * n1, v = (float)(dloc + dscale * (double)n2);
+        r.z = sqrtf(u * u + v * v);
+        // z^2 - loc^2 = scale^2 (n1^2 + n2^2) + 2 loc scale n2, divided by scale (z + loc)
+        r.y = (r.scale * (n1 * n1 + n2 * n2) + 2.0f * r.loc * n2) / (r.z + r.loc);
+        const float iz = 1.0f / r.z;
+        r.dz_dloc = v * iz;
+        r.dz_dscale = (u * n1 + v * n2) * iz;
+    }
+    return r;
+}
+
+// 1 - I1(x)/I0(x) for x >= 0 without the cancellation of 1 - i1e / i0e: the difference of the two series below 32 (relative error
+// < 4e-7 x), beyond it the asymptotic expansion 1/(2x) + 1/(8x^2) + 1/(8x^3) + 25/(128x^4) (next term 13/(32x^5): < 8e-7 relative)
+CL_HD float cl_one_minus_i1_over_i0(float x, float i0e, float i1e) {
+    if (x > 32.0f) {
+        const float t = 1.0f / x;
+        return t * (0.5f + t * (0.125f + t * (0.125f + t * 0.1953125f)));
+    }
+    return (i0e - i1e) / i0e;
+}
+
+// log q(z) and, non-NULL `dz`, its partial derivatives at fixed z w.r.t. z, loc and scale
+CL_HD float cl_rw_density(const cl_rw_elem& t, float* dz, float* dloc, float* dscale) {
+    const float inv = 1.0f / t.scale;
+    if (t.centric) {                                        // cl_folded_normal_log_prob with ya = t.y
+        const float ya = t.y, yb = -(t.z + t.loc) * inv;
+        const float la = -0.5f * ya * ya, lb = -0.5f * yb * yb;
+        const float m = fmaxf(la, lb);
+        const float ea = expf(la - m), eb = expf(lb - m);
+        const float den = ea + eb;
+        if (dz != nullptr) {
+            const float wa = ea / den, wb = eb / den;
+            *dz = (-wa * ya + wb * yb) * inv;
+            *dloc = (wa * ya + wb * yb) * inv;
+            *dscale = (wa * ya * ya + wb * yb * yb - 1.0f) * inv;
+        }
+        return m + logf(den) - 0.5f * CL_LOG_2PI_F - logf(t.scale);
+    }
+    // cl_rice_log_prob with -(z^2 + nu^2) / 2 sigma^2 + |arg| = -y^2 / 2 and r = I1/I0 = 1 - q
+    const float is2 = inv * inv;
+    const float arg = t.z * t.loc * is2;
+    float i0e, i1e;
+    cl_i0e_i1e(arg, &i0e, &i1e);
+    if (dz != nullptr) {
+        const float q = cl_one_minus_i1_over_i0(arg, i0e, i1e);
+        *dz = 1.0f / t.z - t.y * inv - t.loc * is2 * q;
+        *dloc = t.y * inv - t.z * is2 * q;
+        *dscale = (-2.0f + t.y * t.y + 2.0f * arg * q) * inv;
+    }
+    return logf(t.z) - 2.0f * logf(t.scale) - 0.5f * t.y * t.y + logf(i0e);
+}
+CL_HD float cl_rw_log_prob(const cl_rw_elem& t) { return cl_rw_density(t, nullptr, nullptr, nullptr); }
+CL_HD void cl_rw_log_prob_grads(const cl_rw_elem& t, float* dz, float* dloc, float* dscale) { (void)cl_rw_density(t, dz, dloc, dscale); }
+
+// The standard normals n1, n2 of (reflection idx, sample s): ONE Box-Muller pair from two uniforms of the posterior's own Philox domain
+// (CL_STREAM_QF, the one cl_noise_uniform_block draws from): the block keyed by s >> 1 serves the samples 2k and 2k + 1
+CL_HD cl_u32x4 cl_noise_rw_block(uint64_t seed, uint32_t step, uint32_t s, uint64_t idx) { return cl_noise_uniform_block(seed, step, s >> 1, idx); }
+CL_HD void cl_noise_rw_pick(const cl_u32x4& r, uint32_t s, float* n1, float* n2) {
+    const bool hi = (s & 1u) != 0;
+    const float u1 = cl_u01(hi ? r.z : r.x), u2 = cl_u01(hi ? r.w : r.y);
+    const float rad = cl_fast_sqrt(-2.0f * cl_fast_log(u1));
+    float sn, cs;
+    cl_fast_sincos_rev(u2, &sn, &cs);
+    *n1 = rad * cs;
+    *n2 = rad * sn;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Evans-2011 error model (`Ev11Likelihood`, careless/models/likelihoods/mono.py:39-73): the scale of the likelihood is
 //   sig_c = Sdfac * sqrt(SigIobs^2 + SdB * softplus(ipred) + Sdadd * softplus(ipred)^2),   Sd* = softplus(raw) trainable
 // Returns log p(ipred) and d/d ipred (through the location AND the scale) plus d/d(Sdfac, SdB, Sdadd).

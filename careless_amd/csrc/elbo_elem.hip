@@ -5,6 +5,8 @@
 //                         [surrogate_posteriors.py:50-53,104-131; variational.py:123-139,154,173; wilson.py:50-57]
 //   tn_backward_kernel    chain rule from dL/dz_f (data term, accumulated by the fused MLP kernel) plus the KL
 //                         term's own derivatives back to the raw q parameters (a = log loc, b = log(scale - eps))
+//   rw_forward_kernel /   the same two for the Rice-Woolfson posterior (Rice per acentric, folded normal per centric reflection): one text
+//   rw_backward_kernel    (elbo_q_kernels.h, expanded twice), two posteriors   [surrogate_posteriors.py:133-172; distributions.py:228-348]
 //   ref_prior_kernel      an empirical reference prior's -log p(z_f) into the KL and its z-derivative onto dL/dz_f, between the two
 //                         [priors/empirical.py:9-131; variational.py:123-139]
 //   grad_sqnorm_kernel    global (and per-tensor) squared L2 norm of the flat gradient   [variational.py:205]
@@ -55,106 +57,70 @@ __device__ __forceinline__ float prior_lp(const cl_tn_args& A, int h, float z, f
     return cl_wilson_log_prob(z, c, es);
 }
 
+// What the kernel text of elbo_q_kernels.h asks of a posterior: `load` the reflection's constants, `sample` element (h, s) from injected or
+// in-kernel noise (the backward pass redraws the forward pass' numbers), the element's log-density and its partial derivatives.
+struct tn_post {
+    typedef cl_tn_elem elem;
+    float low;
+    __device__ __forceinline__ void load(const cl_tn_args& A, int h) { low = A.low[h]; }
+    __device__ __forceinline__ elem sample(const cl_tn_args& A, float a, float b, int h, int s, cl_u32x4& blk) const {
+        return cl_tn_sample(a, b, low, A.high, A.eps, tn_uniform(A, h, s, blk));
+    }
+    static __device__ __forceinline__ float log_prob(const elem& t) { return cl_tn_log_prob(t); }
+    static __device__ __forceinline__ void grads(const elem& t, float* dz, float* dloc, float* dscale) { cl_tn_log_prob_grads(t, dz, dloc, dscale); }
+};
+
+struct rw_post {
+    typedef cl_rw_elem elem;
+    const unsigned char* q_centric;
+    const float* n_f;                    // [2][R][S] or NULL
+    bool centric;
+    __device__ __forceinline__ void load(const cl_tn_args&, int h) { centric = q_centric[h] != 0; }
+    // `blk` caches the Philox block shared by samples 2k and 2k + 1 across loop iterations
+    __device__ __forceinline__ elem sample(const cl_tn_args& A, float a, float b, int h, int s, cl_u32x4& blk) const {
+        float n1, n2;
+        if (n_f) {
+            const size_t i = (size_t)h * A.S + s;
+            n1 = n_f[i];
+            n2 = n_f[(size_t)A.R * A.S + i];
+        } else {
+            if ((s & 1) == 0) blk = cl_noise_rw_block(A.seed, A.step, (uint32_t)s, (uint64_t)h);
+            cl_noise_rw_pick(blk, (uint32_t)s, &n1, &n2);
+        }
+        return cl_rw_sample(a, b, A.eps, centric, n1, n2);
+    }
+    static __device__ __forceinline__ float log_prob(const elem& t) { return cl_rw_log_prob(t); }
+    static __device__ __forceinline__ void grads(const elem& t, float* dz, float* dloc, float* dscale) { cl_rw_log_prob_grads(t, dz, dloc, dscale); }
+};
+
 }  // namespace
 
-__global__ __launch_bounds__(256) void tn_forward_kernel(const cl_tn_args A) {
-    if (A.stop_flag != nullptr && *A.stop_flag != 0) return;
-    const bool part = A.r_end > A.r_begin;               // an owned reflection range (reflection-owner data parallelism)
-    const int h = (part ? A.r_begin : 0) + blockIdx.x * blockDim.x + threadIdx.x;
-    // the step's accumulators, cleared on the way (instead of a memset launch in front of this one): the flat gradient + scalar block
-    // by all threads, the dz_f rows of this launch's reflections by their threads
-    if (A.zero_ptr != nullptr) {
-        const long long n4 = A.zero_n >> 2;              // (16-byte aligned, a multiple of four floats: the caller's workspace layout)
-        f32x4_t* z4 = reinterpret_cast<f32x4_t*>(A.zero_ptr);
-        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) z4[i] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
-        for (long long i = 4 * n4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < A.zero_n; i += (long long)gridDim.x * blockDim.x) A.zero_ptr[i] = 0.0f;
-    }
-    double kl = 0.0;
-    if (h < (part ? A.r_end : A.R)) {
-        if (A.zero_dzf != nullptr)
-            for (int s = 0; s < A.S; ++s) A.zero_dzf[(size_t)h * A.S + s] = 0.0f;
-        const float a = A.q_loc_raw[h], b = A.q_scale_raw[h], low = A.low[h];
-        const bool in_kl = (h >= A.kl_begin && h < A.kl_end);
-        const bool dw_child = (A.prior_kind == CL_PRIOR_DOUBLE_WILSON_) && (A.root[h] == 0);
-        cl_u32x4 blk = {};
-        for (int s = 0; s < A.S; ++s) {
-            const cl_tn_elem t = cl_tn_sample(a, b, low, A.high, A.eps, tn_uniform(A, h, s, blk));
-            A.z_f[(size_t)h * A.S + s] = t.z;
-            if (in_kl) {
-                float dlp;
-                const float lq = cl_tn_log_prob(t);
-                // non-root reflections of a double-Wilson model get their conditional prior in dw_forward_kernel (needs z_parent), every
-                // reflection of a reference-prior model in ref_prior_kernel
-                const float lp = (dw_child || A.prior_kind == CL_PRIOR_REFERENCE_) ? 0.0f : prior_lp(A, h, t.z, &dlp);
-                kl += (double)(lq - lp);
-            }
-        }
-    }
-    if (A.kl_part != nullptr) {
-        // one store per workgroup; the step's cl_tn_backward adds the parts up (no atomics, fixed order)
-        __shared__ double sh[4];
-        const double w = wave_sum_d(kl * (double)A.w_kl);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-        __syncthreads();
-        if (threadIdx.x == 0) A.kl_part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    } else {
-        block_atomic_add_d(kl * (double)A.w_kl, A.scalars + CL_SC_KL);
-    }
-}
-
-__global__ __launch_bounds__(256) void tn_backward_kernel(const cl_tn_args A) {
-    if (A.stop_flag != nullptr && *A.stop_flag != 0) return;
-    const bool part = A.r_end > A.r_begin;
-    const int nb_tn = ((part ? A.r_end - A.r_begin : A.R) + 255) / 256;      // workgroups of the reflections; the rest carry the reduction
-    if ((int)blockIdx.x >= nb_tn) {
-        cl_reduce_partials_block(A.red_partials, A.red_nparts, A.red_P, A.red_out, (int)blockIdx.x - nb_tn);
-        return;
-    }
-    if (A.kl_part != nullptr && blockIdx.x == 0) {
-        // the KL sums the forward launch(es) left per workgroup (same grid; the double-Wilson pass always covers all R): added up
-        // here, in index order
-        const int nb = nb_tn;
-        double t = 0.0;
-        for (int i = threadIdx.x; i < nb; i += blockDim.x) t += A.kl_part[i];
-        if (A.kl_part_dw != nullptr && (A.prior_kind == CL_PRIOR_DOUBLE_WILSON_ || A.prior_kind == CL_PRIOR_REFERENCE_))
-            for (int i = threadIdx.x; i < (A.R + 255) / 256; i += blockDim.x) t += A.kl_part_dw[i];
-        __shared__ double sh[4];
-        const double w = wave_sum_d(t);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-        __syncthreads();
-        if (threadIdx.x == 0) A.scalars[CL_SC_KL] += (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    }
-    const int h = (part ? A.r_begin : 0) + blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= (part ? A.r_end : A.R)) return;
-    const float a = A.q_loc_raw[h], b = A.q_scale_raw[h], low = A.low[h];
-    const bool in_kl = (h >= A.kl_begin && h < A.kl_end);
-    const float wkl = in_kl ? A.w_kl * A.kl_grad_mult : 0.0f;
-    const bool dw_child = (A.prior_kind == CL_PRIOR_DOUBLE_WILSON_) && (A.root[h] == 0);
-    float gloc = 0.0f, gscale = 0.0f, loc = 0.0f, scale = 0.0f;
-    cl_u32x4 blk = {};
-    for (int s = 0; s < A.S; ++s) {
-        const cl_tn_elem t = cl_tn_sample(a, b, low, A.high, A.eps, tn_uniform(A, h, s, blk));
-        loc = t.loc; scale = t.scale;
-        float dq_dz, dq_dloc, dq_dscale, dp_dz;
-        cl_tn_log_prob_grads(t, &dq_dz, &dq_dloc, &dq_dscale);
-        if (dw_child) {
-            const int par = A.parent_ids[h];
-            const float zp = (par >= 0) ? A.z_f[(size_t)par * A.S + s] : 0.0f;
-            float dzp, dr;
-            (void)cl_dw_log_prob(t.z, zp, par >= 0, dw_r_of(A, h), A.centric[h] != 0, A.es[h], &dp_dz, &dzp, &dr);
-        } else if (A.prior_kind == CL_PRIOR_REFERENCE_) {
-            dp_dz = 0.0f;               // (ref_prior_kernel has added the prior's z-derivative to dz_f)
-        } else {
-            (void)prior_lp(A, h, t.z, &dp_dz);
-        }
-        const float gz = A.dz_f[(size_t)h * A.S + s] + wkl * (dq_dz - dp_dz);
-        gloc += gz * t.dz_dloc + wkl * dq_dloc;
-        gscale += gz * t.dz_dscale + wkl * dq_dscale;
-    }
-    // raw parameters: loc = exp(a), scale = exp(b) + eps
-    A.d_loc_raw[h] += gloc * loc;
-    A.d_scale_raw[h] += gscale * (scale - A.eps);
-}
+#define CL_Q_FORWARD_KERNEL tn_forward_kernel
+#define CL_Q_BACKWARD_KERNEL tn_backward_kernel
+#define CL_Q_ARGS cl_tn_args
+#define CL_Q_TN(KA) KA
+#define CL_Q_POST tn_post
+#define CL_Q_POST_OF(KA) tn_post{}
+#include "elbo_q_kernels.h"
+#undef CL_Q_FORWARD_KERNEL
+#undef CL_Q_BACKWARD_KERNEL
+#undef CL_Q_ARGS
+#undef CL_Q_TN
+#undef CL_Q_POST
+#undef CL_Q_POST_OF
+#define CL_Q_FORWARD_KERNEL rw_forward_kernel
+#define CL_Q_BACKWARD_KERNEL rw_backward_kernel
+#define CL_Q_ARGS cl_rw_args
+#define CL_Q_TN(KA) KA.tn
+#define CL_Q_POST rw_post
+#define CL_Q_POST_OF(KA) rw_post{KA.q_centric, KA.n_f, false}
+#include "elbo_q_kernels.h"
+#undef CL_Q_FORWARD_KERNEL
+#undef CL_Q_BACKWARD_KERNEL
+#undef CL_Q_ARGS
+#undef CL_Q_TN
+#undef CL_Q_POST
+#undef CL_Q_POST_OF
 
 // Double-Wilson conditional prior of the non-root reflections: -log p(z_h | z_parent) into the KL, and its derivative
 // w.r.t. the parent's sample scattered into dz_f (the child's own derivative is taken in tn_backward_kernel).
@@ -467,6 +433,64 @@ __global__ __launch_bounds__(256) void tn_moments_kernel(const float* __restrict
     }
 }
 
+// Exponentially scaled modified Bessel functions I0(x) e^-x, I1(x) e^-x in fp64 for x >= 0: the ascending series (all terms positive) up to
+// 30, Hankel's asymptotic expansion beyond (smallest term < e^-60 there); both summed until a term no longer counts.
+__device__ void i0e_i1e_d(double x, double* i0e, double* i1e) {
+    if (x <= 30.0) {
+        const double q = 0.25 * x * x;
+        double t0 = 1.0, s0 = 1.0, t1 = 0.5 * x, s1 = t1;
+        for (int k = 1; k < 200; ++k) {
+            t0 *= q / ((double)k * k);
+            t1 *= q / ((double)k * (k + 1));
+            s0 += t0; s1 += t1;
+            if (t0 < 1e-17 * s0 && t1 < 1e-17 * s1) break;
+        }
+        const double e = exp(-x);
+        *i0e = s0 * e; *i1e = s1 * e;
+        return;
+    }
+    const double r = 1.0 / (8.0 * x);
+    double t0 = 1.0, s0 = 1.0, t1 = 1.0, s1 = 1.0;
+    for (int k = 1; k < 60; ++k) {
+        const double m = (2.0 * k - 1.0) * (2.0 * k - 1.0);
+        t0 *= -(0.0 - m) * r / k;
+        t1 *= -(4.0 - m) * r / k;
+        s0 += t0; s1 += t1;
+        if (fabs(t0) < 1e-17 * s0 && fabs(t1) < 1e-17 * s1) break;
+    }
+    const double f = 1.0 / sqrt(6.283185307179586477 * x);
+    *i0e = s0 * f; *i1e = s1 * f;
+}
+
+// Output step (include/careless_hip.h: cl_rw_moments): mean, standard deviation and fourth raw moment of the Rice-Woolfson posterior from
+// the raw vectors, fp64 (the variance nu^2 + 2 sigma^2 - mean^2 cancels by (nu / sigma)^2).  The formulas of RiceWoolfson._moments
+// (careless_amd/models/merging/surrogate_posteriors.py): no normal-limit crossover at nu / sigma > 40.
+__global__ __launch_bounds__(256) void rw_moments_kernel(const float* __restrict__ qa, const float* __restrict__ qb, const unsigned char* __restrict__ centric,
+                                                         int R, float eps, float* __restrict__ mean, float* __restrict__ sd, double* __restrict__ m4) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const double mu = (double)expf(qa[r]), sg = (double)(expf(qb[r]) + eps);
+    const bool c = centric[r] != 0;
+    const double mu2 = mu * mu, sg2 = sg * sg;
+    if (mean != nullptr || sd != nullptr) {
+        double m, var;
+        if (c) {
+            const double y = mu / sg;
+            m = sg * 0.79788456080286535588 * exp(-0.5 * y * y) + mu * erf(y * 0.70710678118654752440);
+            var = mu2 + sg2 - m * m;
+        } else {
+            const double t = 0.5 * mu2 / sg2;
+            double i0e, i1e;
+            i0e_i1e_d(0.5 * t, &i0e, &i1e);
+            m = sg * 1.25331413731550025121 * ((1.0 + t) * i0e + t * i1e);
+            var = 2.0 * sg2 + mu2 - m * m;
+        }
+        if (mean != nullptr) mean[r] = (float)m;
+        if (sd != nullptr) sd[r] = (float)sqrt(fmax(var, 0.0));
+    }
+    if (m4 != nullptr) m4[r] = c ? mu2 * mu2 + 6.0 * mu2 * sg2 + 3.0 * sg2 * sg2 : mu2 * mu2 + 8.0 * sg2 * mu2 + 8.0 * sg2 * sg2;
+}
+
 // Output step, per observation (reference VariationalMergingModel.prediction_mean_stddev, careless/models/merging/variational.py:80-121): with
 // the scale's moments (smean, sstd) of the row and <F^2> = mean^2 + std^2, <F^4> of its reflection, E[I] = smean <F^2> and
 // var[I] = <F^4> (smean^2 + sstd^2) - E[I]^2, in fp64 (the subtraction cancels).  HBM-bound: 12 bytes in, 16 out per row + two gathers.
@@ -489,6 +513,12 @@ __global__ void noise_kernel(unsigned long long seed, unsigned step, int S, long
                              float* out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (kind == 2) {                     // the Rice-Woolfson posterior's pairs: out[n][S][2]
+        for (int s = 0; s < S; ++s)
+            cl_noise_rw_pick(cl_noise_rw_block(seed, step, (uint32_t)s, (uint64_t)(offset + i)), (uint32_t)s, out + 2 * ((size_t)i * S + s),
+                             out + 2 * ((size_t)i * S + s) + 1);
+        return;
+    }
     for (int s = 0; s < S; ++s)
         out[(size_t)i * S + s] = (kind == 0) ? cl_noise_uniform(seed, step, (uint32_t)s, (uint64_t)(offset + i))
                                              : cl_noise_normal(seed, step, (uint32_t)s, (uint64_t)(offset + i));
@@ -510,6 +540,21 @@ int cl_launch_tn_backward(const cl_tn_args& a, hipStream_t st) {
     const int nr = a.r_end > a.r_begin ? a.r_end - a.r_begin : a.R;
     const int nred = (a.red_partials != nullptr) ? (a.red_P + 31) / 32 : 0;
     hipLaunchKernelGGL(tn_backward_kernel, dim3((nr + 255) / 256 + nred), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+int cl_launch_rw_forward(const cl_rw_args& a, hipStream_t st) {
+    if (a.tn.R <= 0 || a.tn.S <= 0) return -1;
+    (void)hipGetLastError();
+    const int nr = a.tn.r_end > a.tn.r_begin ? a.tn.r_end - a.tn.r_begin : a.tn.R;
+    hipLaunchKernelGGL(rw_forward_kernel, dim3((nr + 255) / 256), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+int cl_launch_rw_backward(const cl_rw_args& a, hipStream_t st) {
+    if (a.tn.R <= 0 || a.tn.S <= 0) return -1;
+    (void)hipGetLastError();
+    const int nr = a.tn.r_end > a.tn.r_begin ? a.tn.r_end - a.tn.r_begin : a.tn.R;
+    const int nred = (a.tn.red_partials != nullptr) ? (a.tn.red_P + 31) / 32 : 0;
+    hipLaunchKernelGGL(rw_backward_kernel, dim3((nr + 255) / 256 + nred), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 // Deterministic mode of the double-Wilson prior: what dw_forward_kernel's children scatter into their parents with float atomics, pulled
@@ -602,6 +647,12 @@ int cl_launch_tn_moments(const float* a, const float* b, const float* low, int R
                          double* m4, hipStream_t st) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(tn_moments_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, a, b, low, R, high, high4, eps, mean, sd, m4);
+    return (int)hipGetLastError();
+}
+int cl_launch_rw_moments(const float* a, const float* b, const unsigned char* centric, int R, float eps, float* mean, float* sd, double* m4,
+                         hipStream_t st) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(rw_moments_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, a, b, centric, R, eps, mean, sd, m4);
     return (int)hipGetLastError();
 }
 int cl_launch_predict_moments(const float* smean, const float* sstd, const int* refl_id, long long n, const float* fmean, const float* fstd,

@@ -6,7 +6,7 @@ What one step replaces in the reference: `train_step_with_gradient_norm` (carele
 
 Step schedule (all on one HIP stream, no host synchronisation):
     cl_tn_forward (clears the step's accumulators on its way) -> cl_elbo_mono_fwd_bwd -> [cl_ref_prior: empirical reference priors]
-    -> cl_tn_backward (carries cl_reduce_partials)
+    -> cl_tn_backward (carries cl_reduce_partials)        (a Rice-Woolfson posterior: cl_rw_forward / cl_rw_backward in their place)
     -> [cl_owner_qnorm + all-reduce, data-parallel only: the flat gradient (row split) or its tail + 4 norm terms (reflection-owner
     split)] -> [cl_grad_sqnorm: clip modes only] -> cl_adam_step -> cl_step_finalize
 
@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from careless_amd import _lib
-from careless_amd._lib import AdamArgs, DetArgs, LaueArgs, MlpArgs, RefPriorArgs, TnArgs, check, ptr
+from careless_amd._lib import AdamArgs, DetArgs, LaueArgs, MlpArgs, RefPriorArgs, RwArgs, TnArgs, check, ptr
 from careless_amd.frozen import FrozenPath
 from careless_amd.models.base import BaseModel
 from careless_amd.models.scaling.image import image_layer_layout
@@ -328,6 +328,18 @@ def prior_kind(prior, owner: bool = False) -> int:
     raise NotImplementedError(f"prior {type(prior).__name__} is not supported by the HIP engine yet")
 
 
+def posterior_kind(q) -> str:
+    """The surrogate posteriors the engine samples: "truncated_normal" (cl_tn_forward / _backward) or "rice_woolfson" (cl_rw_forward /
+    _backward: the trainable class of `RiceWoolfson.from_loc_and_scale`); NotImplementedError for anything else -- the host-side
+    `RiceWoolfson(loc, scale, centric)` of the reference priors included."""
+    from careless_amd.models.merging.surrogate_posteriors import TrainableRiceWoolfson, TruncatedNormal
+    if isinstance(q, TruncatedNormal):
+        return "truncated_normal"
+    if isinstance(q, TrainableRiceWoolfson):
+        return "rice_woolfson"
+    raise NotImplementedError(f"surrogate posterior {type(q).__name__} is not supported by the HIP engine")
+
+
 def switch(model, attr: Optional[str], env: str, default: bool = False, env_adds: bool = False) -> bool:
     """One on / off switch of the engine: `model.<attr>` where it is set (not None), else the environment variable `env` ("1" on, "0"
     off), else `default`.  `env_adds`: the variable also switches on what the attribute leaves off (`deterministic`)."""
@@ -445,15 +457,14 @@ class ElboEngine(WidePath, FrozenPath):
     def _read_plugins(self, model, inputs):
         """The plugin objects the engine runs -- `q, prior, lik, mlp, img, imgl` -- or NotImplementedError / ValueError for those it does
         not; the sizes `R, N_total, d, S` and what the objects alone decide (`laue`, `ev11`, `double_wilson`, `dw_trainable`, `deterministic`)."""
-        from careless_amd.models.merging.surrogate_posteriors import TruncatedNormal
         from careless_amd.models.likelihoods.mono import LocationScaleLikelihood
         from careless_amd.models.priors.wilson import DoubleWilsonPrior
         from careless_amd.models.scaling.image import HybridImageScaler, NeuralImageScaler
         from careless_amd.models.scaling.nn import MetadataScaler
 
         q, prior, lik, scaler = model.surrogate_posterior, model.prior, model.likelihood, model.scaling_model
-        if not isinstance(q, TruncatedNormal):
-            raise NotImplementedError(f"surrogate posterior {type(q).__name__} is not supported by the HIP engine")
+        # the Rice-Woolfson posterior (cl_rw_forward / cl_rw_backward in place of cl_tn_*): nothing behind z_f / dz_f knows which one sampled
+        self.rw = posterior_kind(q) == "rice_woolfson"
         self.ref_prior = prior_kind(prior) == _lib.CL_PRIOR_REFERENCE
         from careless_amd.models.likelihoods.laue import LaueBase
         self.laue = BaseModel.is_laue(inputs)
@@ -493,6 +504,11 @@ class ElboEngine(WidePath, FrozenPath):
         """Per-reflection constants of the posterior and the prior, uploaded once."""
         q, prior, dev = self.q, self.prior, self.device
         self.low = q.low.to(dev, torch.float32).contiguous()
+        self.q_centric = None
+        if self.rw:                      # the posterior's own family flag (the prior's `centric` is NULL under a reference prior)
+            if q.centric.size != self.R:
+                raise ValueError("RiceWoolfson.centric does not match the number of reflections")
+            self.q_centric = torch.as_tensor(q.centric.astype(np.uint8), device=dev)
         if self.ref_prior:
             # an empirical reference prior (models/priors/empirical.py): its arrays expanded to all reflections, uploaded once; the Wilson
             # arrays stay NULL (`_tn_args`) -- cl_ref_prior evaluates the density in front of the step's cl_tn_backward
@@ -750,6 +766,17 @@ class ElboEngine(WidePath, FrozenPath):
                 a.asu_ids, a.n_asu = ptr(self.asu_ids), self.layout.n_dwr
         return a
 
+    def _q_launch(self, which: str, tn: TnArgs, st):
+        """`cl_tn_<which>` -- or, under the Rice-Woolfson posterior, `cl_rw_<which>` on the same argument fill (u_f: the injected normals)."""
+        if not self.rw:
+            check(getattr(self.lib, "cl_tn_" + which)(C.byref(tn), st), "cl_tn_" + which)
+            return
+        a = RwArgs()
+        a.tn = tn
+        a.q_centric, a.n_f = ptr(self.q_centric), tn.u_f
+        a.tn.u_f = None
+        check(getattr(self.lib, "cl_rw_" + which)(C.byref(a), st), "cl_rw_" + which)
+
     def _step_fields(self, a, obs: ObsData, step: int):
         """The per-step constants `cl_mlp_args`, `cl_laue_args` and `cl_frozen_args` name alike, on whichever of the three `a` is."""
         a.R, a.S = self.R, self.S
@@ -846,10 +873,14 @@ class ElboEngine(WidePath, FrozenPath):
         return 1.0 / self.S if self.model.kl_weight is None else 1.0 / (self.S * obs.N_total)
 
     def _noise_to_device(self, u_f, eta, obs: Optional[ObsData] = None):
-        """Injected noise arrives in the reference's (S, R) / (S, N_total) orientation; device layout is [R][S] / [N][S]."""
+        """Injected noise arrives in the reference's (S, R) / (S, N_total) orientation; device layout is [R][S] / [N][S].  Under the
+        Rice-Woolfson posterior `u_f` carries the standard normals n1, n2 as (2, S, R); device layout [2][R][S]."""
         obs = self.obs if obs is None else obs
         du = de = None
-        if u_f is not None:
+        if u_f is not None and self.rw:
+            u = torch.as_tensor(_np(u_f), dtype=torch.float32).reshape(2, self.S, self.R)
+            du = u.permute(0, 2, 1).contiguous().to(self.device)
+        elif u_f is not None:
             u = torch.as_tensor(_np(u_f), dtype=torch.float32).reshape(self.S, self.R)
             du = u.t().contiguous().to(self.device)
         if eta is not None:
@@ -875,7 +906,7 @@ class ElboEngine(WidePath, FrozenPath):
             tn.zero_ptr, tn.zero_n, tn.zero_dzf = self.ws_step.data_ptr(), int(self.ws_step.numel()), ptr(self.dz_f)
         else:                                # (per-image layers over many images: a gradient vector far longer than the launch: memset)
             self._zero_step()
-        check(lib.cl_tn_forward(C.byref(tn), st), "cl_tn_forward")
+        self._q_launch("forward", tn, st)
         if self.double_wilson:
             check(lib.cl_dw_prior_forward(C.byref(tn), st), "cl_dw_prior_forward")
         self._pending_reduce = None
@@ -900,7 +931,7 @@ class ElboEngine(WidePath, FrozenPath):
             # behind EVERY data-term launch, directly in front of cl_tn_backward: the frozen-scaler step stores dz_f (a term added before it
             # would be lost), every other route adds to it -- added last the prior's term is right on all of them
             self._ref_prior(tn, st)
-        check(lib.cl_tn_backward(C.byref(tn), st), "cl_tn_backward")
+        self._q_launch("backward", tn, st)
         if self.owner:
             # this rank's share of |d a|^2 + |d b|^2 into the message, next to the scaler's gradient
             check(lib.cl_owner_qnorm(ptr(self.grads), self.R, self.shard.kl_begin, self.shard.kl_end, ptr(self.msg_norm),
@@ -1098,7 +1129,7 @@ class ElboEngine(WidePath, FrozenPath):
         u_f, eta = self._noise_to_device(u_f, eta, obs)
         self._zero_step()
         tn = self._tn_args(key, u_f)
-        check(lib.cl_tn_forward(C.byref(tn), st), "cl_tn_forward")
+        self._q_launch("forward", tn, st)
         self._data_term(obs, key, eta, None, st)
         if self.owner and self.shard.world > 1 and not self.local_only:
             # an owner-mode rank holds the validation rows of ITS reflections (make_obs): the set's NLL is the sum over the ranks
@@ -1309,8 +1340,10 @@ class ElboEngine(WidePath, FrozenPath):
 # stand-alone helpers behind the plugin protocol methods
 # ------------------------------------------------------------------------------------------------------------
 def tn_sample(q, n: int, seed=None, u_f=None) -> torch.Tensor:
-    """`TruncatedNormal.sample(n)` -> (n, R) via `cl_tn_forward` (Philox noise unless `u_f` (n,R) is injected)."""
-    dev = require_gpu("TruncatedNormal.sample")
+    """`TruncatedNormal.sample(n)` -> (n, R) via `cl_tn_forward` (Philox noise unless `u_f` (n,R) is injected); a trainable Rice-Woolfson
+    posterior: via `cl_rw_forward`, `u_f` then (2, n, R) standard normals."""
+    rw = getattr(q, "posterior_kind", None) == "rice_woolfson"
+    dev = require_gpu("RiceWoolfson.sample" if rw else "TruncatedNormal.sample")
     lib = _lib.get_lib()
     R = q.loc_raw.numel()
     loc_raw = q.loc_raw.to(dev, torch.float32).contiguous()
@@ -1321,7 +1354,9 @@ def tn_sample(q, n: int, seed=None, u_f=None) -> torch.Tensor:
     z = torch.empty(R * n, dtype=torch.float32, device=dev)
     sc = torch.zeros(_lib.CL_SC_COUNT, dtype=torch.float64, device=dev)
     du = None
-    if u_f is not None:
+    if u_f is not None and rw:
+        du = torch.as_tensor(_np(u_f), dtype=torch.float32).reshape(2, n, R).permute(0, 2, 1).contiguous().to(dev)
+    elif u_f is not None:
         du = torch.as_tensor(_np(u_f), dtype=torch.float32).reshape(n, R).t().contiguous().to(dev)
     a = TnArgs()
     a.q_loc_raw, a.q_scale_raw, a.low, a.centric, a.es = ptr(loc_raw), ptr(scale_raw), ptr(low), ptr(centric), ptr(es)
@@ -1334,15 +1369,25 @@ def tn_sample(q, n: int, seed=None, u_f=None) -> torch.Tensor:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     a.seed, a.step = int(seed) & 0xFFFFFFFFFFFFFFFF, 0
     a.z_f, a.scalars = ptr(z), ptr(sc)
-    check(lib.cl_tn_forward(C.byref(a), _stream()), "cl_tn_forward")
+    if rw:
+        qc = torch.as_tensor(q.centric.astype(np.uint8), device=dev)
+        ra = RwArgs()
+        ra.tn = a
+        ra.q_centric, ra.n_f = ptr(qc), ptr(du)
+        ra.tn.u_f = None
+        check(lib.cl_rw_forward(C.byref(ra), _stream()), "cl_rw_forward")
+    else:
+        check(lib.cl_tn_forward(C.byref(a), _stream()), "cl_tn_forward")
     return z.view(R, n).t()
 
 
 def tn_moments(q, high_m4=np.inf, want=("mean", "std", "m4")):
     """Moments of the truncated-normal posterior for the output step via `cl_tn_moments` (reference surrogate_posteriors.py:23-27,
     55-102; consumed at io/manager.py:188-197): dict with `mean`, `std` (fp32 torch tensors on the device) and `m4` (fp64).
-    `high_m4` is the upper bound of the fourth moment (the reference's `moment_4(high=np.inf)` default); mean / std use q.high."""
-    dev = require_gpu("TruncatedNormal moments")
+    `high_m4` is the upper bound of the fourth moment (the reference's `moment_4(high=np.inf)` default); mean / std use q.high.
+    A trainable Rice-Woolfson posterior: the same dict via `cl_rw_moments` (no bounds)."""
+    rw = getattr(q, "posterior_kind", None) == "rice_woolfson"
+    dev = require_gpu("RiceWoolfson moments" if rw else "TruncatedNormal moments")
     lib = _lib.get_lib()
     R = q.loc_raw.numel()
     loc_raw = q.loc_raw.to(dev, torch.float32).contiguous()
@@ -1355,6 +1400,11 @@ def tn_moments(q, high_m4=np.inf, want=("mean", "std", "m4")):
         out["std"] = torch.empty(R, dtype=torch.float32, device=dev)
     if "m4" in want:
         out["m4"] = torch.empty(R, dtype=torch.float64, device=dev)
+    if rw:
+        qc = torch.as_tensor(q.centric.astype(np.uint8), device=dev)
+        check(lib.cl_rw_moments(ptr(loc_raw), ptr(scale_raw), ptr(qc), R, float(q.scale_shift), ptr(out.get("mean")), ptr(out.get("std")),
+                                ptr(out.get("m4")), _stream()), "cl_rw_moments")
+        return out
     hi4 = float("inf") if high_m4 is None else float(high_m4)
     check(lib.cl_tn_moments(ptr(loc_raw), ptr(scale_raw), ptr(low), R, float(q.high), hi4, float(q.scale_shift),
                             ptr(out.get("mean")), ptr(out.get("std")), ptr(out.get("m4")), _stream()), "cl_tn_moments")
@@ -1447,10 +1497,11 @@ def _forward_layers(lib, mlp, md, imgl, ids, loc, sig, dev, st):
 
 
 def debug_noise(seed: int, step: int, S: int, n: int, offset: int = 0, kind: int = 1) -> torch.Tensor:
-    """The noise the kernels draw for (seed, step): kind 0 = q(F) uniforms [n][S], kind 1 = scale normals [n][S]."""
+    """The noise the kernels draw for (seed, step): kind 0 = q(F) uniforms [n][S], kind 1 = scale normals [n][S], kind 2 = the normal
+    pairs (n1, n2) of the Rice-Woolfson posterior [n][S][2]."""
     dev = require_gpu("debug_noise")
-    out = torch.empty(n * S, dtype=torch.float32, device=dev)
+    out = torch.empty(n * S * (2 if kind == 2 else 1), dtype=torch.float32, device=dev)
     check(_lib.get_lib().cl_debug_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, step, S, n, offset, kind, ptr(out), _stream()),
           "cl_debug_noise")
-    return out.view(n, S)
+    return out.view(n, S, 2) if kind == 2 else out.view(n, S)
 

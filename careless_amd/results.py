@@ -23,7 +23,7 @@ def get_results(surrogate_posterior, inputs, output_parameters: bool = True, max
     """Reference manager.py:188-236 as a dict of per-reflection arrays:
     F, SigF, I, SigI, N, observed (N > 0) and, with `output_parameters`, the q parameters high / loc / low / scale."""
     q = surrogate_posterior
-    if hasattr(q, "loc_raw"):                                # the truncated normal: one `cl_tn_moments` launch for all three
+    if hasattr(q, "loc_raw"):                                # an engine posterior: one `cl_tn_moments` / `cl_rw_moments` launch for all three
         from careless_amd.engine import tn_moments
         mom = tn_moments(q)                                  # (the reference takes <F^4> from scipy on the host, manager.py:192)
         F, SigF, f4 = _np(mom["mean"]), _np(mom["std"]), _np(mom["m4"])

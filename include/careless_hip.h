@@ -153,6 +153,27 @@ enum { CL_REFPRIOR_NORMAL = 0, CL_REFPRIOR_LAPLACE = 1, CL_REFPRIOR_STUDENTT = 2
 int cl_ref_prior(const cl_refprior_args* args, void* stream);
 size_t cl_refprior_args_size(void);                /* sizeof(cl_refprior_args) as the library was compiled (binding check, like cl_abi_sizes) */
 
+/* --- Rice-Woolfson surrogate posterior ---------------------------------------------------------------------------------
+ * replaces: RiceWoolfson.sample / .log_prob (careless/models/merging/surrogate_posteriors.py:133-172), Rice._sample_n / .log_prob and
+ *           FoldedNormal (careless/utils/distributions.py:252-258, 278-283, 300-335) on two TransformedVariables (the bijectors of
+ *           TruncatedNormal.from_loc_and_scale, surrogate_posteriors.py:120-130), inside VariationalMergingModel.call / add_kl_div
+ *           (careless/models/merging/variational.py:123-139, 154) and tape.gradient through them (variational.py:197-202).
+ * cl_rw_forward / cl_rw_backward do for q(F_h) = Rice(loc_h, scale_h) (q_centric[h] == 0) or FoldedNormal(loc_h, scale_h) (!= 0) what
+ * cl_tn_forward / cl_tn_backward do for the truncated normal, on the same `tn` fill -- workspace clearing, KL parts, owned range, prior
+ * kinds, ride-along reduction, stop_flag -- except that tn.low, tn.high and tn.u_f are not read.  With standard normals n1, n2 per (h, s):
+ *     centric   z = |loc + scale n1| + eps32 (np.finfo(float32).eps; n2 unused)      acentric   z = sqrt((scale n1)^2 + (loc + scale n2)^2)
+ * and pathwise gradients dz/dloc, dz/dscale (d|x|/dx = sign x, 0 at 0).  n_f NULL: n1, n2 are ONE Box-Muller pair per (h, s) from two
+ * uniforms of the Philox domain cl_tn_forward's uniforms come from, keyed by (seed, step, sample, GLOBAL reflection index);
+ * cl_debug_noise(kind = 2) returns them.  -1: what cl_tn_forward / cl_tn_backward answer -1 to (tn.low excepted), and a NULL q_centric.  */
+typedef struct cl_rw_args {
+    cl_tn_args tn;
+    const unsigned char* q_centric; /* [R] 0/1: the posterior's own family flag (tn.centric is the PRIOR's: NULL under a reference prior) */
+    const float* n_f;               /* [2][R][S] injected standard normals (n1 then n2) or NULL                                          */
+} cl_rw_args;
+int cl_rw_forward(const cl_rw_args* args, void* stream);
+int cl_rw_backward(const cl_rw_args* args, void* stream);
+size_t cl_rw_args_size(void);                      /* sizeof(cl_rw_args) as the library was compiled */
+
 /* --- scaler + likelihood -----------------------------------------------------------------------------------------
  * replaces: MLPScaler.call / MetadataScaler / NormalLayer        (careless/models/scaling/nn.py:10-120)
  *           ImageScaler.call / HybridImageScaler.call            (careless/models/scaling/image.py:27-63)
@@ -643,6 +664,15 @@ int cl_chain_dx(const float* dz0_t, const float* Wt, int n_obs, int n_pad, int w
  * reference's fp32 TFP moments, m4 as fp64 like scipy.stats.truncnorm.moment.  Any output pointer may be NULL.                     */
 int cl_tn_moments(const float* q_loc_raw, const float* q_scale_raw, const float* low, int R, double high_moments, double high_m4, float eps,
                   float* mean, float* std, double* m4, void* stream);
+/* The same for the Rice-Woolfson posterior (replaces: RiceWoolfson.mean / .stddev, careless/models/merging/surrogate_posteriors.py:156-163 over
+ * Rice.mean / .variance and FoldedNormal.mean / .variance, careless/utils/distributions.py:285-298, 337-348).  Rice: the exact mean
+ * scale sqrt(pi / 2) L_1/2(-t), t = loc^2 / 2 scale^2, on exponentially scaled Bessel functions at ANY loc / scale (the reference's Rice
+ * switches to the normal limit beyond loc / scale = 40); m4 = loc^4 + 8 scale^2 loc^2 + 8 scale^4.  Folded normal: mean
+ * scale sqrt(2 / pi) exp(-loc^2 / 2 scale^2) + loc erf(loc / sqrt 2 scale), variance loc^2 + scale^2 - mean^2,
+ * m4 = loc^4 + 6 loc^2 scale^2 + 3 scale^4.  The reference defines no fourth moment for this class.  fp64 on the device; any output pointer may
+ * be NULL, not all three.  -1: a NULL q_loc_raw / q_scale_raw / q_centric, R < 1, no output.                                              */
+int cl_rw_moments(const float* q_loc_raw, const float* q_scale_raw, const unsigned char* q_centric, int R, float eps, float* mean, float* std,
+                  double* m4, void* stream);
 
 /* --- output step: posterior predictive moments per observation -------------------------------------------------------------------
  * replaces: VariationalMergingModel.prediction_mean_stddev (careless/models/merging/variational.py:80-121), consumed by
@@ -689,7 +719,8 @@ int cl_host_crystfel_parse(const char* buf, long long nbytes, long long n_rows, 
 const char* cl_version(void);
 /* sizeof(cl_tn_args), sizeof(cl_mlp_args), sizeof(cl_adam_args), sizeof(cl_laue_args), sizeof(cl_det_args): lets a binding verify its mirrors */
 void cl_abi_sizes(size_t out[5]);
-/* out[n][S]: kind 0 = the uniforms of cl_tn_*, kind 1 = the normals of cl_elbo_mono_fwd_bwd, for (seed, step) */
+/* out[n][S]: kind 0 = the uniforms of cl_tn_*, kind 1 = the normals of cl_elbo_mono_fwd_bwd, for (seed, step);
+ * kind 2 = the normal pairs (n1, n2) of cl_rw_*: out[n][S][2] */
 int cl_debug_noise(unsigned long long seed, unsigned step, int S, long long n, long long offset, int kind, float* out,
                    void* stream);
 

@@ -1,0 +1,257 @@
+"""The Rice-Woolfson surrogate posterior without a GPU: the fp64 reference of tests/ref_rw.py against scipy and finite differences, the
+host build of the element math of csrc/cl_math.h against that reference, the trainable plugin class' host side, the C-ABI (symbols, struct
+sizes, one rejecting call per clause of every entry check) and the engine's acceptance rule."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from careless_amd import _lib
+from tests import ref_rw as RR
+from tests.test_ref_prior import PARENT_ABI_SIZES
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+NEW_SYMBOLS = ("cl_rw_forward", "cl_rw_backward", "cl_rw_args_size", "cl_rw_moments")
+
+
+def _params(n, seed, lo=-3.0, hi=3.0):
+    """loc / scale from 1e-3 to 1e3 (log-uniform) at scales from 0.03 to 30, half the reflections centric."""
+    rng = np.random.default_rng(seed)
+    ratio = 10 ** rng.uniform(lo, hi, n)
+    scale = 10 ** rng.uniform(-1.5, 1.5, n)
+    return ratio * scale, scale, rng.random(n) < 0.5, rng
+
+
+# ---- the reference itself ------------------------------------------------------------------------------------------------------------------
+def test_reference_log_prob_is_scipy_rice_and_foldnorm():
+    from scipy import stats
+    loc, scale, c, rng = _params(400, 1, -1.0, 1.0)          # (scipy's own rice.logpdf is the cancelling form: moderate loc / scale)
+    n = rng.normal(size=(2, 3, 400))
+    z = RR.rw_sample(RR.f64(loc), RR.f64(scale), torch.as_tensor(c), RR.f64(n))
+    lq = RR.rw_log_prob(z, RR.f64(loc), RR.f64(scale), torch.as_tensor(c)).numpy()
+    z = z.numpy()
+    ref = np.where(c, stats.foldnorm.logpdf(z, loc / scale, scale=scale), stats.rice.logpdf(z, loc / scale, scale=scale))
+    assert np.max(np.abs(lq - ref) / np.maximum(np.abs(ref), 1.0)) < 1e-12
+    # the draws: centric |loc + scale n1| + eps32, acentric |loc + scale (n2 + i n1)|
+    assert np.array_equal(z[:, c], np.abs(loc + scale * n[0])[:, c] + RR.EPS32)
+    assert np.max(np.abs(z[:, ~c] - np.abs((loc + scale * n[1]) + 1j * scale * n[0])[:, ~c]) / z[:, ~c]) < 1e-14
+
+
+def test_reference_pathwise_gradient_matches_central_differences():
+    loc, scale, c, rng = _params(300, 2)
+    n = RR.f64(RR.noise_for(loc, scale, c, 2, 5))
+    ct = torch.as_tensor(c)
+    L, S = RR.f64(loc).requires_grad_(True), RR.f64(scale).requires_grad_(True)
+    z = RR.rw_sample(L, S, ct, n)
+    gl, gs = torch.autograd.grad(z.sum(), [L, S])
+    h = 1e-6
+    with torch.no_grad():
+        fl = (RR.rw_sample(RR.f64(loc * (1 + h)), S, ct, n) - RR.rw_sample(RR.f64(loc * (1 - h)), S, ct, n)).sum(0) / RR.f64(2 * h * loc)
+        fs = (RR.rw_sample(L, RR.f64(scale * (1 + h)), ct, n) - RR.rw_sample(L, RR.f64(scale * (1 - h)), ct, n)).sum(0) / RR.f64(2 * h * scale)
+    for g, f in ((gl, fl), (gs, fs)):
+        assert float((g - f).abs().max() / f.abs().max()) < 1e-7
+
+
+def test_patched_oracle_is_restored_and_runs_whole_steps():
+    from oracle import elbo_oracle as O
+    from tests import util
+    saved = (O.tn_sample, O.tn_log_prob, O.tn_mean, O.tn_variance)
+    data, cfg, params, x, u_f, eta = util.make_problem(N=120, R=20, S=2)
+    loc, scale = (t.numpy() for t in O.tn_loc_scale(params.q_loc_raw, params.q_scale_raw, cfg.epsilon))
+    n_f = RR.noise_for(loc, scale, data["centric"], 2, 3)
+    out, grads = RR.elbo_value_and_grads(params, x, cfg, n_f, eta, data["centric"])
+    assert (O.tn_sample, O.tn_log_prob, O.tn_mean, O.tn_variance) == saved
+    z = RR.rw_sample(RR.f64(loc), RR.f64(scale), torch.as_tensor(np.asarray(data["centric"], bool)), RR.f64(n_f))
+    assert torch.equal(out["z_f"], z) and np.isfinite(float(out["loss"])) and all(torch.isfinite(g).all() for g in grads)
+    tn_out, _ = O.elbo_value_and_grads(params, x, cfg, RR.f64(u_f), RR.f64(eta))
+    assert abs(float(tn_out["kl"]) - float(out["kl"])) > 1e-3          # another posterior: another KL
+    import scipy.stats
+    with RR.patched(data["centric"], moments=True):
+        res = O.merged_results(params, x, cfg)
+    assert "moment" not in vars(scipy.stats.truncnorm)
+    mean, var, m4 = RR.rw_moments(loc, scale, data["centric"])
+    assert np.allclose(res["F"].numpy(), mean, rtol=1e-14) and np.allclose(res["SigF"].numpy() ** 2, var, rtol=1e-10)
+
+
+# ---- the element math of csrc/cl_math.h, host build ------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def rwm():
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    d = tempfile.mkdtemp(prefix="cl_rw_")
+    so = os.path.join(d, "librw.so")
+    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(HERE, "rw_math_check.cpp")])
+    lib = C.CDLL(so)
+    lib.rw_eval.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rw_noise.argtypes = [C.c_ulonglong, C.c_uint, C.c_uint, C.c_ulonglong, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    yield lib
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def test_host_element_math_matches_fp64(rwm):
+    """cl_rw_sample / cl_rw_log_prob / cl_rw_log_prob_grads in fp32 against the fp64 reference over loc / scale from 1e-3 to 1e3 -- both
+    branches of cl_i0e_i1e (arg 8), of cl_one_minus_i1_over_i0 (arg 32), both signs of a centric draw.  Bounds: a sample is a handful of fp32
+    operations (1e-5 relative to loc + scale: fifty roundings); the log-density is a sum of O(1) .. O(10) terms, each within a few fp32 roundings
+    (1e-5 of max(1, |log q|)); the derivatives feed gradient tensors that the GPU tests hold to RTOL_GRAD = 2e-4 of the tensor's max-norm, so
+    each family's derivative, in the units of the raw parameters (times loc, times scale), is held to a tenth of that."""
+    n, eps = 20000, 1e-7
+    loc, scale, c, rng = _params(n, 0)
+    a, b = np.log(loc).astype(np.float32), np.log(scale - eps).astype(np.float32)
+    n1, n2 = rng.normal(size=n).astype(np.float32), rng.normal(size=n).astype(np.float32)
+    cu, out = c.astype(np.uint8), np.zeros((n, 8), np.float32)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    rwm.rw_eval(n, p(a), p(b), eps, p(cu), p(n1), p(n2), p(out))
+    L = torch.exp(RR.f64(a)).requires_grad_(True)
+    S = (torch.exp(RR.f64(b)) + float(np.float32(eps))).requires_grad_(True)
+    ct, N = torch.as_tensor(c), RR.f64(np.stack([n1, n2]))
+    assert RR.kink_margin(L.detach().numpy(), S.detach().numpy(), c, N.numpy()) >= RR.KINK_GUARD
+    z = RR.rw_sample(L, S, ct, N)
+    dzl, dzs = torch.autograd.grad(z.sum(), [L, S])
+    zd = z.detach().clone().requires_grad_(True)
+    lq = RR.rw_log_prob(zd, L, S, ct)
+    gz, gl, gs = torch.autograd.grad(lq.sum(), [zd, L, S])
+    Ln, Sn = L.detach().numpy(), S.detach().numpy()
+    assert (c & (Ln + Sn * n1 < 0)).sum() > 100 and ((Ln / Sn) > 40).sum() > 1000
+    assert np.max(np.abs(out[:, 0] - z.detach().numpy()) / (Ln + Sn)) < 1e-5
+    assert np.max(np.abs(out[:, 1] - dzl.numpy())) < 1e-5 and np.max(np.abs(out[:, 2] - dzs.numpy()) / np.maximum(1.0, np.abs(dzs.numpy()))) < 1e-5
+    lq = lq.detach().numpy()
+    assert np.max(np.abs(out[:, 3] - lq) / np.maximum(1.0, np.abs(lq))) < 1e-5
+    for k, g, unit in ((4, gz, Sn), (5, gl, Ln), (6, gs, Sn)):
+        for fam in (c, ~c):
+            ref = g.numpy()[fam] * unit[fam]
+            assert np.max(np.abs(out[fam, k] * unit[fam] - ref)) < 2e-5 * np.max(np.abs(ref)), (k, fam[0])
+
+
+def test_host_noise_pairs_are_box_muller_of_the_posteriors_own_uniforms(rwm):
+    """One Philox block of the q(F) domain per two samples: (s, s + 1) for even s share a block, the pair is sqrt(-2 log u1) (cos, sin)(2 pi u2)."""
+    n1, n2 = C.c_float(), C.c_float()
+    got = []
+    for idx in (0, 5, 2 ** 33 + 7):
+        for s in range(4):
+            rwm.rw_noise(1234, 9, s, idx, C.byref(n1), C.byref(n2))
+            got.append((n1.value, n2.value))
+    got = np.array(got)
+    assert np.isfinite(got).all() and len({tuple(g) for g in got}) == len(got) and len(set(got.reshape(-1))) == got.size
+
+
+# ---- the plugin class ---------------------------------------------------------------------------------------------------------------------
+def test_trainable_class_host_side(tmp_path):
+    from careless_amd.models.merging.surrogate_posteriors import RiceWoolfson, SurrogatePosterior, TrainableRiceWoolfson
+    loc, scale, c, rng = _params(50, 3, -1.0, 2.0)
+    q = RiceWoolfson.from_loc_and_scale(loc, scale, c, scale_shift=1e-7)
+    assert isinstance(q, TrainableRiceWoolfson) and isinstance(q, SurrogatePosterior) and not isinstance(q, RiceWoolfson)
+    # bijectors and round trip
+    assert np.allclose(q.loc.numpy(), loc, rtol=1e-6) and np.allclose(q.scale.numpy(), scale, rtol=1e-6)
+    assert torch.equal(q.loc, torch.exp(q.loc_raw)) and torch.equal(q.scale, torch.exp(q.scale_raw) + 1e-7)
+    assert np.array_equal(q.centric, c) and q.centric.dtype == bool
+    assert set(q.parameters) == {"loc", "scale", "centric"} and q.trainable_variables == [q.loc_raw, q.scale_raw]
+    q.trainable = False
+    assert q.trainable_variables == []
+    # save / load
+    path = str(tmp_path / "q.pt")
+    q.save_weights(path)
+    q2 = RiceWoolfson.from_loc_and_scale(np.ones(50), np.ones(50), c)
+    q2.load_weights(path)
+    assert torch.equal(q2.loc_raw, q.loc_raw) and torch.equal(q2.scale_raw, q.scale_raw)
+    # log_prob: host arithmetic, the host class' densities on the same parameters
+    z = np.abs(loc + scale * rng.normal(size=(3, 50))) + 0.01
+    host = RiceWoolfson(q.loc.numpy(), q.scale.numpy(), c)
+    assert np.allclose(q.log_prob(z).numpy(), host.log_prob(z), rtol=2e-5, atol=2e-5)
+    with pytest.raises(ValueError):
+        RiceWoolfson.from_loc_and_scale(loc, scale, c[:-1])
+    if not torch.cuda.is_available():
+        for call in (q.mean, q.stddev, q.variance, q.moment_4, q.sample):
+            with pytest.raises(_lib.CarelessHipError):
+                call()
+
+
+def test_old_constructor_is_unchanged():
+    from careless_amd.models.merging.surrogate_posteriors import RiceWoolfson
+    loc, scale, c, _ = _params(30, 4, -1.0, 1.0)
+    q = RiceWoolfson(loc, scale, c)
+    assert type(q) is RiceWoolfson and isinstance(q.loc, np.ndarray) and q.loc.dtype == np.float32 and not hasattr(q, "loc_raw")
+    assert q.mean().dtype == np.float32 and q.sample(4, seed=1).shape == (4, 30) and np.isfinite(q.log_prob(q.sample(seed=2))).all()
+
+
+# ---- the C-ABI ------------------------------------------------------------------------------------------------------------------------------
+def test_header_declares_and_library_exports_the_new_symbols():
+    with open(os.path.join(os.path.dirname(HERE), "include", "careless_hip.h")) as f:
+        header = f.read()
+    lib = _lib.get_lib()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b" + name + r"\(", header), name
+        assert name in _lib.EXPORTS and getattr(lib, name) is not None
+    assert "typedef struct cl_rw_args" in header and "cl_tn_args tn;" in header
+
+
+def test_abi_sizes():
+    lib = _lib.get_lib()
+    assert int(lib.cl_rw_args_size()) == C.sizeof(_lib.RwArgs) == C.sizeof(_lib.TnArgs) + 16
+    sizes = (C.c_size_t * 5)()
+    lib.cl_abi_sizes(sizes)
+    assert tuple(sizes) == PARENT_ABI_SIZES             # the feature added a struct of its own: none of the pinned ones grew
+
+
+def _accepted(**over):
+    """Arguments cl_rw_forward AND cl_rw_backward would launch with (made-up addresses: the call is never made with them)."""
+    p = 0x10000
+    tn = dict(q_loc_raw=p, q_scale_raw=p, low=None, centric=p, es=p, R=300, S=3, high=1e10, eps=1e-7, w_kl=1.0 / 3, kl_grad_mult=1.0, kl_begin=0, kl_end=300,
+              z_f=p, dz_f=p, d_loc_raw=p, d_scale_raw=p, scalars=p, kl_part=p, prior_kind=_lib.CL_PRIOR_WILSON)
+    rw = dict(q_centric=p, n_f=None)
+    for k, v in over.items():
+        (rw if k in rw else tn)[k] = v
+    a = _lib.RwArgs(**rw)
+    a.tn = _lib.TnArgs(**tn)
+    return a
+
+
+DW, REF = _lib.CL_PRIOR_DOUBLE_WILSON, _lib.CL_PRIOR_REFERENCE
+SHARED_CLAUSES = [dict(q_centric=None), dict(q_loc_raw=None), dict(q_scale_raw=None), dict(R=0), dict(S=0), dict(centric=None), dict(es=None),
+                  dict(prior_kind=DW, root=0x10000), dict(prior_kind=DW, parent_ids=0x10000), dict(prior_kind=DW, parent_ids=0x10000, root=0x10000),
+                  dict(prior_kind=DW, parent_ids=0x10000, root=0x10000, dw_r_raw=0x10000), dict(prior_kind=3), dict(prior_kind=-1),
+                  dict(r_begin=-1, r_end=10), dict(r_begin=5, r_end=301)]
+
+
+def test_entry_checks_answer_without_a_launch():
+    """One rejecting call per clause of the entry checks of cl_rw_forward, cl_rw_backward and cl_rw_moments (csrc/cl_api.hip); every one
+    returns before the launch, so the made-up pointers are never dereferenced."""
+    lib = _lib.get_lib()
+    p = 0x10000
+    for fn in (lib.cl_rw_forward, lib.cl_rw_backward):
+        assert fn(None, None) == -1
+        for over in SHARED_CLAUSES:
+            assert fn(C.byref(_accepted(**over)), None) == -1, over
+        # an owned reflection range and the double-Wilson prior do not go together
+        assert fn(C.byref(_accepted(prior_kind=DW, parent_ids=p, root=p, dw_r=p, r_begin=0, r_end=10)), None) == -2
+    for over in (dict(z_f=None), dict(scalars=None), dict(zero_ptr=p, zero_n=0), dict(zero_ptr=p + 4, zero_n=64), dict(zero_ptr=p, zero_n=64, kl_part=None)):
+        assert lib.cl_rw_forward(C.byref(_accepted(**over)), None) == -1, over
+    for over in (dict(dz_f=None), dict(d_loc_raw=None), dict(d_scale_raw=None), dict(red_partials=p, red_nparts=4, red_P=8),
+                 dict(red_partials=p, red_out=p, red_nparts=0, red_P=8), dict(red_partials=p, red_out=p, red_nparts=4, red_P=0)):
+        assert lib.cl_rw_backward(C.byref(_accepted(**over)), None) == -1, over
+    ok = [p, p, p, 10, 1e-7, p, p, p, None]
+    for i, v in ((0, None), (1, None), (2, None), (3, 0), (3, -4)):
+        args = list(ok)
+        args[i] = v
+        assert lib.cl_rw_moments(*args) == -1, (i, v)
+    assert lib.cl_rw_moments(p, p, p, 10, 1e-7, None, None, None, None) == -1
+
+
+# ---- the engine's acceptance rule (host logic) ---------------------------------------------------------------------------------------------
+def test_engine_accepts_the_trainable_class_and_refuses_the_rest():
+    from careless_amd import engine
+    from careless_amd.models.merging.surrogate_posteriors import RiceWoolfson, SurrogatePosterior, TruncatedNormal
+    loc, scale, c, _ = _params(10, 5, -1.0, 1.0)
+    assert engine.posterior_kind(RiceWoolfson.from_loc_and_scale(loc, scale, c)) == "rice_woolfson"
+    assert engine.posterior_kind(TruncatedNormal.from_loc_and_scale(loc, scale)) == "truncated_normal"
+    for bad in (SurrogatePosterior(), RiceWoolfson(loc, scale, c), object()):
+        with pytest.raises(NotImplementedError, match="is not supported by the HIP engine"):
+            engine.posterior_kind(bad)
+    # the prior's kind does not depend on the posterior: a reference prior built on the host class goes with either
+    from careless_amd.models.priors.empirical import RiceWoolfsonReferencePrior
+    assert engine.prior_kind(RiceWoolfsonReferencePrior(loc, scale, c)) == _lib.CL_PRIOR_REFERENCE
