@@ -150,6 +150,20 @@ class RwArgs(C.Structure):
     _fields_ = [("tn", TnArgs), ("q_centric", _vp), ("n_f", _vp)]
 
 
+class NlikArgs(C.Structure):
+    """mirror of `cl_nlik_args` (include/careless_hip.h)"""
+    _fields_ = [
+        ("iobs", _vp), ("sigiobs", _vp), ("net", _vp),
+        ("L", C.c_int), ("w", C.c_int),
+        ("leak", C.c_float),
+        ("n", C.c_longlong),
+        ("sigpred", _vp), ("pos", _vp), ("sig_image", _vp), ("workspace", _vp),
+        ("ipred", _vp),
+        ("S", C.c_int), ("w_ll", C.c_float),
+        ("d_net", _vp), ("stop_flag", _vp),
+    ]
+
+
 class AdamArgs(C.Structure):
     """mirror of `cl_adam_args` (include/careless_hip.h)"""
     _fields_ = [
@@ -225,6 +239,13 @@ EXPORTS = {
     "cl_rw_backward": (C.c_int, [C.POINTER(RwArgs), _vp]),
     "cl_rw_args_size": (C.c_size_t, []),
     "cl_rw_moments": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp]),
+    "cl_nlik_forward": (C.c_int, [C.POINTER(NlikArgs), _vp]),
+    "cl_nlik_backward": (C.c_int, [C.POINTER(NlikArgs), _vp]),
+    "cl_nlik_supports": (C.c_int, [C.c_int, C.c_int]),
+    "cl_nlik_param_count": (C.c_size_t, [C.c_int, C.c_int]),
+    "cl_nlik_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "cl_nlik_grid": (C.c_int, [C.c_longlong]),
+    "cl_nlik_args_size": (C.c_size_t, []),
     "cl_reduce_partials": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "cl_grad_sqnorm": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cl_adam_step": (C.c_int, [C.POINTER(AdamArgs), _vp]),
@@ -286,6 +307,8 @@ def get_lib() -> C.CDLL:
         raise CarelessHipError(f"ABI mismatch: cl_refprior_args is {int(lib.cl_refprior_args_size())} bytes in the library, {C.sizeof(RefPriorArgs)} in careless_amd/_lib.py")
     if int(lib.cl_rw_args_size()) != C.sizeof(RwArgs):
         raise CarelessHipError(f"ABI mismatch: cl_rw_args is {int(lib.cl_rw_args_size())} bytes in the library, {C.sizeof(RwArgs)} in careless_amd/_lib.py")
+    if int(lib.cl_nlik_args_size()) != C.sizeof(NlikArgs):
+        raise CarelessHipError(f"ABI mismatch: cl_nlik_args is {int(lib.cl_nlik_args_size())} bytes in the library, {C.sizeof(NlikArgs)} in careless_amd/_lib.py")
     _lib = lib
     return lib
 
@@ -297,6 +320,8 @@ def check(code: int, what: str) -> None:
     if code == -2 and what.startswith("cl_wide"):
         raise NotImplementedError(f"{what}: this layer shape / buffer layout is outside the kernel's envelope (row pitch = cl_wide_ld(width), "
                                   "16-byte aligned buffers; the fused forms take hidden widths 65 .. 128)")
+    if code == -2 and what.startswith("cl_nlik"):
+        raise NotImplementedError(f"{what}: the neural likelihood's kernels hold 1 .. 4 hidden layers of width 1 .. 32 (cl_nlik_supports)")
     if code == -2:
         raise NotImplementedError(
             f"{what}: scaler geometry not supported by the fused gfx950 kernel "

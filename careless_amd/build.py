@@ -43,6 +43,8 @@ UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=
          *LANE_UNITS,
          ("elbo_elem.hip", "elbo_elem", []), ("elbo_laue.hip", "elbo_laue", []), ("wide_gemm.hip", "wide_gemm", []),
          ("elbo_peel.hip", "elbo_peel", []), ("elbo_frozen.hip", "elbo_frozen", []),
+         ("elbo_nlik.hip", "elbo_nlik", []),        # the neural likelihood's network: NaNs honoured, so that a poisoned row reaches every sigpred
+
          # host threads, no device code: the formatter's symmetry bookkeeping (exact products kept apart from their sums)
          ("host_format.cpp", "host_format", ["-ffp-contract=off", "-pthread"])]
 SOURCES = sorted({u[0] for u in UNITS})

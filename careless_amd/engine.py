@@ -5,7 +5,8 @@ What one step replaces in the reference: `train_step_with_gradient_norm` (carele
 = forward (`call`, :141-183), `tape.gradient`, `tf.linalg.global_norm`, non-finite sanitise, Adam.
 
 Step schedule (all on one HIP stream, no host synchronisation):
-    cl_tn_forward (clears the step's accumulators on its way) -> cl_elbo_mono_fwd_bwd -> [cl_ref_prior: empirical reference priors]
+    cl_tn_forward (clears the step's accumulators on its way) -> [cl_nlik_forward: neural likelihood] -> cl_elbo_mono_fwd_bwd
+    -> [cl_nlik_backward: neural likelihood] -> [cl_ref_prior: empirical reference priors]
     -> cl_tn_backward (carries cl_reduce_partials)        (a Rice-Woolfson posterior: cl_rw_forward / cl_rw_backward in their place)
     -> [cl_owner_qnorm + all-reduce, data-parallel only: the flat gradient (row split) or its tail + 4 norm terms (reflection-owner
     split)] -> [cl_grad_sqnorm: clip modes only] -> cl_adam_step -> cl_step_finalize
@@ -34,7 +35,7 @@ import numpy as np
 import torch
 
 from careless_amd import _lib
-from careless_amd._lib import AdamArgs, DetArgs, LaueArgs, MlpArgs, RefPriorArgs, RwArgs, TnArgs, check, ptr
+from careless_amd._lib import AdamArgs, DetArgs, LaueArgs, MlpArgs, NlikArgs, RefPriorArgs, RwArgs, TnArgs, check, ptr
 from careless_amd.frozen import FrozenPath
 from careless_amd.models.base import BaseModel
 from careless_amd.models.scaling.image import image_layer_layout
@@ -99,14 +100,17 @@ FLAT_GROUPS = ("q_loc", "q_scale", "mlp", "img", "imgl", "ev11", "dwr")      # t
 
 @dataclass
 class FlatLayout:
+    """The flat parameter vector (`groups`).  The group "ev11" holds the likelihood's trainable floats: the three scalars of the Evans-2011
+    error model, or the network of a neural likelihood (`lik_dense`, its Dense slices) -- never both."""
     R: int
     P: int
     n_img: int                 # M - 1 trainable image scales (0 when image scales are off)
     seg_off: List[int]         # tensor boundaries (Keras trainable-variable granularity) for per-tensor clipnorm
     seg_owner: List[str]       # "q" | "scaler" | "likelihood" per tensor (for --freeze-*)
-    n_ev11: int = 0            # 3 with the Evans-2011 error model
+    n_ev11: int = 0            # the likelihood's trainable floats: 3 with the Evans-2011 error model, P_lik with a neural likelihood
     n_dwr: int = 0             # number of ASUs with --optimize-double-wilson-r
     n_imgl: int = 0            # floats of the per-image layers (NeuralImageScaler: `image_layer_layout`)
+    lik_dense: Optional[list] = None      # a neural likelihood's Dense slices [(kernel offset, out, in, bias offset)] inside its group
 
     @cached_property
     def groups(self) -> Tuple[Tuple[str, int, int], ...]:
@@ -134,8 +138,11 @@ class FlatLayout:
     off_dwr = property(lambda self: self.off("dwr"))
 
 
-def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_dwr: int = 0, imgl=None) -> FlatLayout:
-    """`imgl` = (K, M): K per-image layers over M images (NeuralImageScaler)."""
+def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_dwr: int = 0, imgl=None, lik_dense=None) -> FlatLayout:
+    """`imgl` = (K, M): K per-image layers over M images (NeuralImageScaler).  `lik_dense`: the Dense slices of a neural likelihood's
+    network (`NeuralLikelihood.layer_slices`) -- the likelihood's group then holds the network, one segment per kernel and per bias."""
+    if lik_dense is not None and n_ev11:
+        raise NotImplementedError("a neural likelihood and the Evans-2011 error model are mutually exclusive (the reference has no such class)")
     seg, owner = [0, R, 2 * R], ["q", "q"]
     for _, out, _, ob in dense_slices(d, w, L):       # kernel and bias of every Dense layer, then of the head
         seg += [2 * R + ob, 2 * R + ob + out]; owner += ["scaler", "scaler"]
@@ -152,9 +159,14 @@ def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_d
         off += n_imgl
     for _ in range(n_ev11):              # Sdfac, Sdadd, SdB: three scalar variables (mono.py:42-44)
         off += 1; seg.append(off); owner.append("likelihood")
+    if lik_dense is not None:            # kernel and bias of every Dense layer of the likelihood's network, then of its head (mono.py:79-92)
+        for _, out, _, ob in lik_dense:
+            seg += [off + ob, off + ob + out]; owner += ["likelihood", "likelihood"]
+        n_ev11 = seg[-1] - off
+        off = seg[-1]
     if n_dwr > 0:                        # the double-Wilson r vector (wilson.py:105-110)
         off += n_dwr; seg.append(off); owner.append("prior")
-    return FlatLayout(R, P, n_img, seg, owner, n_ev11, n_dwr, n_imgl)
+    return FlatLayout(R, P, n_img, seg, owner, n_ev11, n_dwr, n_imgl, None if lik_dense is None else list(lik_dense))
 
 
 def bind_flat(flat: torch.Tensor, lay: FlatLayout, q, mlp, img=None, imgl=None, lik=None, prior=None) -> None:
@@ -172,7 +184,7 @@ def bind_flat(flat: torch.Tensor, lay: FlatLayout, q, mlp, img=None, imgl=None, 
 def split_flat(g: torch.Tensor, lay: FlatLayout, dense, imgl_views=None) -> List[torch.Tensor]:
     """`g`, a vector laid out like the parameters, per trainable tensor in the oracle's order and Keras shapes: the groups of `lay` in
     order, the Dense stack by `dense` (`MetadataScaler.layer_slices`) as kernel (in, out) and bias per layer, the per-image block by
-    `imgl_views` (`NeuralImageScaler.layer_views`)."""
+    `imgl_views` (`NeuralImageScaler.layer_views`), a neural likelihood's network by `lay.lik_dense` like the Dense stack."""
     out = []
     for name, off, cnt in lay.groups:
         v = g[off:off + cnt]
@@ -181,6 +193,9 @@ def split_flat(g: torch.Tensor, lay: FlatLayout, dense, imgl_views=None) -> List
                 out += [v[ow:ow + o * i].view(o, i).t(), v[ob:ob + o]]
         elif name == "imgl" and cnt > 0:
             out += imgl_views(v)
+        elif name == "ev11" and cnt > 0 and lay.lik_dense is not None:
+            for ow, o, i, ob in lay.lik_dense:
+                out += [v[ow:ow + o * i].view(o, i).t(), v[ob:ob + o]]
         elif cnt > 0:
             out.append(v)
     return out
@@ -340,6 +355,27 @@ def posterior_kind(q) -> str:
     raise NotImplementedError(f"surrogate posterior {type(q).__name__} is not supported by the HIP engine")
 
 
+def check_neural_likelihood(lik, laue: bool, world: int = 1, lib=None) -> bool:
+    """Is `lik` a neural likelihood (`NeuralNormalLikelihood`: an error model learned from the data, csrc/elbo_nlik.hip)?  NotImplementedError
+    for what the engine does not run it on: Laue data (the reference has no Laue form), the Evans-2011 error model beside it (the
+    reference has no such class), more than one rank (the mean of delta over all rows would take two more collectives per step: DESIGN 7),
+    a network the kernels do not hold.  Host logic: needs no device (`lib`: the loaded library, for `cl_nlik_supports`)."""
+    if not getattr(lik, "neural", False):
+        return False
+    name = type(lik).__name__
+    if laue:
+        raise NotImplementedError(f"likelihood {name}: the neural likelihood is monochromatic only (the reference has no Laue form)")
+    if getattr(lik, "ev11", False):
+        raise NotImplementedError(f"likelihood {name}: a neural likelihood and the Evans-2011 error model are mutually exclusive (the reference has no such class)")
+    if world > 1:
+        raise NotImplementedError(f"likelihood {name}: the neural likelihood runs on one rank (its mean over all rows would need two more "
+                                  f"collectives per step); got a shard of {world} ranks")
+    lib = _lib.get_lib() if lib is None else lib
+    if not lib.cl_nlik_supports(int(lik.n_layers), int(lik.width)):
+        raise NotImplementedError(f"likelihood {name}({lik.n_layers}, {lik.width}): the HIP kernels hold 1 .. 4 hidden layers of width 1 .. 32")
+    return True
+
+
 def switch(model, attr: Optional[str], env: str, default: bool = False, env_adds: bool = False) -> bool:
     """One on / off switch of the engine: `model.<attr>` where it is set (not None), else the environment variable `env` ("1" on, "0"
     off), else `default`.  `env_adds`: the variable also switches on what the attribute leaves off (`deterministic`)."""
@@ -405,6 +441,21 @@ class DetBuffers:
 
 
 @dataclass
+class NlikBuffers:
+    """A neural likelihood, per observation set (`ObsData.nlik` / `ObsChunks.nlik`, `ElboEngine._nlik_attach`): the set's rows in the
+    caller's order -- the mean of delta couples them all, also where `ObsChunks` cuts the set into pieces."""
+    n: int
+    iobs: torch.Tensor                  # [n] raw Iobs, SigIobs in the caller's row order
+    sigiobs: torch.Tensor
+    sigpred: torch.Tensor               # [n + TILE]: cl_nlik_forward's output; the tail keeps the 1.0 of a plain layout's padding rows
+    ws: torch.Tensor                    # cl_nlik_workspace_bytes
+    ipred: Optional[torch.Tensor] = None        # [n][S]: the data term's ipred_out when the caller brings none
+    image_key: Optional[tuple] = None   # what `image` / `pos` were built for: per piece, the layout's own order or a frozen scaler's sorted rows
+    image: Optional[torch.Tensor] = None        # the pieces' sig-shaped images, one behind the other (None: every piece reads sigpred itself)
+    pos: Optional[torch.Tensor] = None  # int32 [n]: position of row i in `image`
+
+
+@dataclass
 class PeelBuffers:
     """A peeled first layer, per observation set (`ObsData.peel`, `ElboEngine._peel_bufs`), feature-major like meta_t."""
     u: torch.Tensor                     # the layer's pre-activations
@@ -436,6 +487,7 @@ class ElboEngine(WidePath, FrozenPath):
             import torch.distributed as dist
             self.force_allreduce = dist.is_available() and dist.is_initialized()
         self._read_plugins(model, inputs)
+        check_neural_likelihood(self.lik, self.laue, shard.world if shard is not None else 1, self.lib)
         self._reflection_constants()
         two_pass = self._plan(inputs)
         if self.deterministic:
@@ -468,6 +520,7 @@ class ElboEngine(WidePath, FrozenPath):
         self.ref_prior = prior_kind(prior) == _lib.CL_PRIOR_REFERENCE
         from careless_amd.models.likelihoods.laue import LaueBase
         self.laue = BaseModel.is_laue(inputs)
+        self.neural = check_neural_likelihood(lik, self.laue, lib=self.lib)
         if self.laue != isinstance(lik, LaueBase):
             raise ValueError("Laue inputs (8-tuple with harmonic_id) need a careless_amd.models.likelihoods.laue likelihood, "
                              "monochromatic inputs a careless_amd.models.likelihoods.mono one")
@@ -555,9 +608,13 @@ class ElboEngine(WidePath, FrozenPath):
     def _bind_parameters(self):
         """The flat parameter vector and Adam's moments; the plugin objects become views into the parameters (`bind_flat`)."""
         mlp, img, imgl, dev = self.mlp, self.img, self.imgl, self.device
+        if self.neural:
+            self.lik.build()
         self.layout = lay = make_layout(self.R, self.d, self.w, self.L, img.max_images - 1 if img is not None else 0, 3 if self.ev11 else 0,
                                         int(self.prior.r_raw.numel()) if self.dw_trainable else 0,
-                                        imgl=(imgl.n_image_layers, imgl.max_images) if imgl is not None else None)
+                                        imgl=(imgl.n_image_layers, imgl.max_images) if imgl is not None else None,
+                                        lik_dense=self.lik.layer_slices() if self.neural else None)
+        assert not self.neural or lay.n_ev11 == self.lik.param_count() == int(self.lib.cl_nlik_param_count(self.lik.n_layers, self.lik.width))
         assert lay.P == mlp.param_count(self.d) == int(self.lib.cl_mlp_param_count(self.d, self.w, self.L))
         self.params = torch.empty(lay.n, dtype=torch.float32, device=dev)
         bind_flat(self.params, lay, self.q, mlp, img, imgl, self.lik, self.prior)
@@ -637,6 +694,8 @@ class ElboEngine(WidePath, FrozenPath):
                 o.rows = np.asarray(rows, dtype=np.int64)
         if self.deterministic:
             self._det_attach(o, pieces)
+        if self.neural:
+            self._nlik_attach(o, pieces, inputs)
         if self.blocks is not None:
             o.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         return o
@@ -683,6 +742,101 @@ class ElboEngine(WidePath, FrozenPath):
         for k, p in enumerate(pieces):
             p.det_parent, p.det_index = obs, k
 
+    # -- neural likelihood (csrc/elbo_nlik.hip) ------------------------------------------------------------------
+    def _nlik_attach(self, obs, pieces, inputs):
+        """Buffers of the neural likelihood for one observation set: Iobs / SigIobs of all its rows in the order the set's eta and ipred_out
+        are in -- the caller's rows, whatever order a packed layout stores them in; the image order of the wide path's sorted layout, whose
+        eta / ipred_out follow `obs.rows` (`_noise_to_device`, `VariationalMergingModel.call`) --, sigpred and the kernels' workspace."""
+        dev, lik = self.device, self.lik
+        rows = np.concatenate([np.asarray(p.rows, dtype=np.int64) if p.rows is not None else np.arange(p.start, p.start + p.N, dtype=np.int64)
+                               for p in pieces])
+        col = lambda a: torch.as_tensor(np.ascontiguousarray(_np(a).reshape(-1)[rows].astype(np.float32)), device=dev)
+        n = int(len(rows))
+        nbytes = int(self.lib.cl_nlik_workspace_bytes(n, lik.n_layers, lik.width))
+        sigpred = torch.ones(n + TILE, dtype=torch.float32, device=dev)
+        obs.nlik = NlikBuffers(n, col(BaseModel.get_intensities(inputs)), col(BaseModel.get_uncertainties(inputs)), sigpred,
+                               torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev))
+        assert obs.nlik.ws.data_ptr() % 16 == 0
+        for p in pieces:
+            p.sig_now = None                # this step's sigpred in the order the piece's launches read sig (`_nlik_image`, `_sig`)
+
+    def _nlik_image(self, obs, pieces, forms):
+        """`nlik.image` / `nlik.pos` of the set for the forms its pieces' data terms take now, and every piece's `sig_now`: the sig-shaped
+        array in the order its launch reads.  The pos map of a piece: none where sig is stored in the order of ipred_out (the plain layout;
+        the wide path's image-sorted one, whose ipred_out is in that order too), the inverse of `row_map` (packed by image) or of a frozen
+        scaler's sort by reflection (`SortedRows.key` - start)."""
+        from careless_amd.frozen import FrozenForm
+        nb = obs.nlik
+        key = tuple(("sorted", self._frozen_epoch) if f is FrozenForm.SORTED_ROWS else "layout" for f in forms)
+        if nb.image_key == key:
+            return
+        dev, owns, poss = self.device, [], []
+        for p, f in zip(pieces, forms):
+            pos = None
+            if f is FrozenForm.SORTED_ROWS:
+                fz = self._sorted_rows(p)
+                own, src, dst = fz.sig, fz.key.long() - int(p.start), None
+            elif p.row_map is not None:
+                own, dst = p.sig, torch.nonzero(p.row_map >= 0).flatten()
+                src = p.row_map.long().index_select(0, dst)
+            else:
+                own, src = p.sig, None
+            if src is not None:
+                pos = torch.empty(p.N, dtype=torch.int64, device=dev)
+                pos[src] = torch.arange(p.N, dtype=torch.int64, device=dev) if dst is None else dst
+                assert int(src.numel()) == p.N and int(pos.min()) >= 0 and int(pos.max()) < int(own.numel())
+            owns.append(own); poss.append(pos)
+        if all(q is None for q in poss):
+            nb.image = nb.pos = None
+            for p in pieces:
+                p.sig_now = nb.sigpred[p.row0:]                     # (a piece's padding rows: the next piece's rows, or the tail of ones)
+        else:
+            offs = list(accumulate([int(o.numel()) for o in owns], initial=0))
+            nb.image = torch.cat([o.clone() for o in owns])         # padding positions keep the layout's own 1.0
+            nb.pos = torch.cat([(torch.arange(p.N, dtype=torch.int64, device=dev) if q is None else q) + off
+                                for p, q, off in zip(pieces, poss, offs)]).to(torch.int32).contiguous()
+            for p, a, b in zip(pieces, offs, offs[1:]):
+                p.sig_now = nb.image[a:b]
+        nb.image_key = key
+
+    def _nlik_args(self, obs) -> NlikArgs:
+        nb, lik = obs.nlik, self.lik
+        a = NlikArgs()
+        a.iobs, a.sigiobs, a.net = ptr(nb.iobs), ptr(nb.sigiobs), self._param_ptr("ev11")
+        a.L, a.w, a.leak, a.n = lik.n_layers, lik.width, lik.leakiness, nb.n
+        a.sigpred, a.pos, a.sig_image, a.workspace = ptr(nb.sigpred), ptr(nb.pos), ptr(nb.image), ptr(nb.ws)
+        a.stop_flag = ptr(self.stop_flag)
+        return a
+
+    def _nlik_forward(self, obs, injected: bool, st):
+        """sigpred of all rows of the set -- the mean of delta is over the whole set, also when it is cut into pieces -- in the caller's order
+        and in the order every piece's data term reads (`_sig`)."""
+        pieces = obs.children if isinstance(obs, ObsChunks) else [obs]
+        self._nlik_image(obs, pieces, [self._frozen_form(p, injected=injected) for p in pieces])
+        check(self.lib.cl_nlik_forward(C.byref(self._nlik_args(obs)), st), "cl_nlik_forward")
+
+    def _nlik_backward(self, obs, ipred_out, st):
+        """The network's gradient from the step's predictions (`ipred_out`, [n][S] in the caller's order) into the likelihood's slice of
+        the flat gradient."""
+        a = self._nlik_args(obs)
+        a.ipred, a.S, a.w_ll, a.d_net = ptr(ipred_out), self.S, self._w_ll(obs), self._grad_ptr("ev11")
+        check(self.lib.cl_nlik_backward(C.byref(a), st), "cl_nlik_backward")
+
+    def _nlik_ipred(self, obs) -> torch.Tensor:
+        nb = obs.nlik
+        if nb.ipred is None:
+            nb.ipred = torch.empty(nb.n * self.S, dtype=torch.float32, device=self.device)
+        return nb.ipred
+
+    def _sig(self, obs: ObsData, own: torch.Tensor) -> torch.Tensor:
+        """THE hand-over of the likelihood's sigma to a data-term launch (`_mlp_args`, `_slot_args`, `_frozen_rows`): `own`, the observation
+        image's SigIobs in the order the launch reads -- or, under a neural likelihood, this step's sigpred in the same order
+        (`_nlik_forward` set `obs.sig_now`; before the first step -- a routing question -- there is none and the pointer is not read)."""
+        if not self.neural or getattr(obs, "sig_now", None) is None:
+            return own
+        assert obs.sig_now.numel() >= own.numel()
+        return obs.sig_now
+
     def _max_images(self):
         if self.img is not None:
             return self.img.max_images
@@ -708,6 +862,8 @@ class ElboEngine(WidePath, FrozenPath):
             if owner == "q" and not self.q.trainable:
                 fr[k] = 1
             if owner == "scaler" and not m.scaling_model.trainable:
+                fr[k] = 1
+            if owner == "likelihood" and not getattr(self.lik, "trainable", True):
                 fr[k] = 1
         self.any_frozen = bool(fr.any())
         self.frozen.copy_(torch.as_tensor(fr))
@@ -807,7 +963,7 @@ class ElboEngine(WidePath, FrozenPath):
         obs = self.obs if obs is None else obs
         a = self._step_fields(MlpArgs(), obs, step)
         a.refl_id = ptr(obs.refl_id); a.image_id = ptr(obs.image_id); a.meta_t = ptr(obs.meta_t)
-        a.iobs = ptr(obs.iobs); a.sig = ptr(obs.sig)
+        a.iobs = ptr(obs.iobs); a.sig = ptr(self._sig(obs, obs.sig))
         a.n_obs, a.n_pad = obs.N, obs.n_pad
         a.obs_offset = obs.start
         if obs.fused_laue:
@@ -917,7 +1073,7 @@ class ElboEngine(WidePath, FrozenPath):
         # cl_tn_backward; a's and b's gradient follows when that kernel is done.  (Not with a trainable double-Wilson r: its gradient
         # sits in the tail and comes out of cl_tn_backward.)
         split = dist_on and not self.owner and not self.dw_trainable and switch(self.model, "split_message", "CARELESS_HIP_SPLIT_MESSAGE")
-        self._data_term(self.obs, step, eta, ipred_out, st, defer_reduce=not split)
+        self._data_term(self.obs, step, eta, ipred_out, st, defer_reduce=not split, train=True)
         tail_work = None
         if split:
             import torch.distributed as dist
@@ -985,17 +1141,24 @@ class ElboEngine(WidePath, FrozenPath):
             a.ev11_part, a.n_ev11, a.d_ev11 = ptr(det.ev11), int(det.ev11.numel()) // 3, self._grad_ptr("ev11")
         check(self.lib.cl_det_reduce(C.byref(a), st), "cl_det_reduce")
 
-    def _data_term(self, obs, step: int, eta, ipred_out, st, defer_reduce: bool = False):
+    def _data_term(self, obs, step: int, eta, ipred_out, st, defer_reduce: bool = False, train: bool = False):
         """NLL of `obs` into scalars[NLL] and its gradient into dz_f / the flat gradient (scaler + image scales): one launch sequence per
         piece of the set, then -- deterministic mode -- the fixed-order sums over the whole set.  `defer_reduce`: a single fused launch
-        leaves its partial reduction to the caller (`self._pending_reduce`: forward_backward hands it to the step's cl_tn_backward launch)."""
+        leaves its partial reduction to the caller (`self._pending_reduce`: forward_backward hands it to the step's cl_tn_backward launch).
+        A neural likelihood: cl_nlik_forward over the whole set in front (the pieces then read sigpred for SigIobs: `_sig`, and write their
+        predictions), and -- `train`: a training step -- cl_nlik_backward behind."""
         if obs.empty:
             return
         chunked = isinstance(obs, ObsChunks)
+        if self.neural:
+            ipred_out = self._nlik_ipred(obs) if ipred_out is None else ipred_out
+            self._nlik_forward(obs, True, st)
         for piece in (obs.children if chunked else [obs]):
             self._data_term_launch(piece, step, eta, ipred_out, st, defer_reduce and not chunked)
         if self.deterministic:
             self._det_reduce(obs, st)
+        if self.neural and train and getattr(self.lik, "trainable", True):
+            self._nlik_backward(obs, ipred_out, st)
 
     def _data_term_launch(self, obs: ObsData, step: int, eta, ipred_out, st, defer_reduce: bool):
         """The data term of one `ObsData`: exactly one path, then the reduction of the weight-gradient partials that goes with it."""
@@ -1175,7 +1338,7 @@ class ElboEngine(WidePath, FrozenPath):
         n = obs.N - a if n is None else n
         off = lambda t, size: None if t is None else t.data_ptr() + size * a
         la.refl_id, la.image_id, la.harmonic_id = off(obs.refl_id, 4), off(obs.image_id, 4), off(obs.harmonic_id, 4)
-        la.loc, la.sigma, la.iobs, la.sig = off(obs.laue_loc, 4), off(obs.laue_sig, 4), off(obs.iobs, 4), off(obs.sig, 4)
+        la.loc, la.sigma, la.iobs, la.sig = off(obs.laue_loc, 4), off(obs.laue_sig, 4), off(obs.iobs, 4), off(self._sig(obs, obs.sig), 4)
         la.n_obs, la.obs_offset = n, obs.start + a
         la.img, la.use_img, la.d_img = ma.img, ma.use_img, ma.d_img
         la.eta, la.ipred_out = off(eta, 4 * self.S), off(ipred_out, 4 * self.S)
@@ -1325,7 +1488,8 @@ class ElboEngine(WidePath, FrozenPath):
 
     def grad_tensors(self) -> List[torch.Tensor]:
         """Gradients split per trainable tensor, in the oracle's order and Keras shapes
-        [q_loc_raw, q_scale_raw, W_0 (in,out), b_0, ..., W_o, b_o, image scales, per-image layers, Ev11, double-Wilson r]."""
+        [q_loc_raw, q_scale_raw, W_0 (in,out), b_0, ..., W_o, b_o, image scales, per-image layers, Ev11 | the neural likelihood's
+        network (Keras shapes), double-Wilson r]."""
         return self._split(self.grads)
 
     def param_tensors(self) -> List[torch.Tensor]:

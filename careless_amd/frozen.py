@@ -236,7 +236,7 @@ class FrozenPath:
         that cross a wave border.  The image scales are part of the frozen scaling model: their gradient is not computed either."""
         fz = self._sorted_rows(obs)
         fa = self._frozen_args(fz, obs, step, eta, ipred_out)
-        fa.refl_id, fa.iobs, fa.sig, fa.n = ptr(fz.refl), ptr(fz.iobs), ptr(fz.sig), int(obs.N)
+        fa.refl_id, fa.iobs, fa.sig, fa.n = ptr(fz.refl), ptr(fz.iobs), ptr(self._sig(obs, fz.sig)), int(obs.N)
         # (several launches into one dz_f -- the pieces of a chunked shard -- and the double-Wilson prior, whose dlog p / dz is in dz_f
         #  before the data term: add with atomics instead of storing)
         fa.accumulate = 1 if (obs.is_piece or self.double_wilson) else 0

@@ -1,0 +1,1 @@
+from careless_amd.models.likelihoods.mono import NeuralLikelihood, NeuralNormalLikelihood  # noqa: F401

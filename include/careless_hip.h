@@ -563,6 +563,51 @@ int cl_frozen_edge_floats(long long n, int S);     /* floats of edge_val */
 int cl_frozen_grid(long long n);                   /* workgroups of the launch (nll_part / ev11_part slots) */
 size_t cl_frozen_args_size(void);                  /* sizeof(cl_frozen_args) as the library was compiled (binding check, like cl_abi_sizes) */
 
+/* --- neural likelihood: an error model learned from the data (csrc/elbo_nlik.hip) ---------------------------------------------------
+ * replaces: NeuralLikelihood.__init__ / .call and NeuralNormalLikelihood.base_dist (careless/models/likelihoods/mono.py:75-110) inside
+ *           VariationalMergingModel.call (careless/models/merging/variational.py:141-183), and tape.gradient through the network
+ *           (variational.py:197-202).  Monochromatic only: the reference has no Laue form.
+ * The network is L Dense(w, LeakyReLU(leak)) layers on the two raw columns (iobs, sigiobs) and a Dense(1, softplus) head, `net` in the
+ * scaler's W^T layout on d = 2 columns with a one-row head: per layer the kernel transposed [w][fan-in], then its bias [w]; the head
+ * [1][w], then 1 bias: cl_nlik_param_count(L, w) = 3 w + (L - 1)(w w + w) + w + 1 floats.
+ *     delta_i = network(iobs_i, sigiobs_i)         sigpred_i = sigiobs_i delta_i / m,   m = mean of delta over the n rows of the call
+ * cl_nlik_forward writes sigpred[i] in the caller's row order and, `pos` given, sig_image[pos[i]] = sigpred[i] as well (the observation
+ * layout's own sig-shaped image: positions no row maps to -- padding -- are never written).  The data-term entry points then run
+ * unchanged with `sig` = that image and `ipred_out` set.  cl_nlik_backward, behind them, takes ipred [n][S] in the caller's row order:
+ *     g_i = w_ll sum_s [1 / sigpred_i - (ipred_is - iobs_i)^2 / sigpred_i^3]      T = sum_i g_i sigpred_i (fp64)
+ *     dL/ddelta_k = (g_k sigiobs_k - T / n) / m      dL/dz_k = dL/ddelta_k sigmoid(z_k) (z: the head's pre-activation)
+ * and d_net += the network's gradient.  No floor on delta or sigpred and no float atomics: fp32 arithmetic, the two global sums in fp64,
+ * every sum in a fixed order -- two calls on the same inputs agree bit for bit; a NaN in iobs / sigiobs makes every sigpred and every
+ * gradient entry NaN.  `workspace` (cl_nlik_workspace_bytes(n, L, w) bytes, 16-byte aligned) holds, in this order: delta [n] (kept by the
+ * forward call for the backward call of the same step), g [n], then per-workgroup partials.  stop_flag non-zero: nothing is written.
+ * -1: a NULL iobs / sigiobs / net / sigpred / workspace, a misaligned workspace, n < 1, exactly one of pos / sig_image, and for the
+ * backward call a NULL ipred / d_net or S < 1.  -2: cl_nlik_supports(L, w) == 0 (it holds 1 .. 4 hidden layers of width 1 .. 32).  Both
+ * answers come before anything touches the device.                                                                                    */
+typedef struct cl_nlik_args {
+    const float* iobs;          /* [n] in the caller's row order, raw (un-normalised)                              */
+    const float* sigiobs;       /* [n]                                                                             */
+    const float* net;           /* [cl_nlik_param_count(L, w)]                                                     */
+    int L, w;
+    float leak;                 /* LeakyReLU slope (tf_keras default 0.3)                                          */
+    long long n;
+    float* sigpred;             /* [n] forward: out; backward: in                                                  */
+    const int* pos;             /* optional [n]: position of row i in sig_image                                    */
+    float* sig_image;           /* with pos                                                                        */
+    void* workspace;
+    const float* ipred;         /* backward: [n][S] predictions of the step (the data term's ipred_out)            */
+    int S;
+    float w_ll;                 /* backward: weight of one log-likelihood term                                     */
+    float* d_net;               /* backward: [cl_nlik_param_count(L, w)] +=                                        */
+    const int* stop_flag;
+} cl_nlik_args;
+int cl_nlik_forward(const cl_nlik_args* args, void* stream);
+int cl_nlik_backward(const cl_nlik_args* args, void* stream);
+int cl_nlik_supports(int L, int w);                /* 1: the kernels hold L hidden layers of width w                   */
+size_t cl_nlik_param_count(int L, int w);
+size_t cl_nlik_workspace_bytes(long long n, int L, int w);
+int cl_nlik_grid(long long n);                     /* workgroups of every launch = rows of the partial buffers         */
+size_t cl_nlik_args_size(void);                    /* sizeof(cl_nlik_args) as the library was compiled                 */
+
 /* --- gradient norm, sanitise, clip, Adam -------------------------------------------------------------------------
  * replaces: tf.linalg.global_norm, tf.where(is_finite), optimizer.apply_gradients (variational.py:202-209)
  *           tfk.optimizers.Adam(lr, b1, b2, clipnorm, clipvalue, global_clipnorm) (careless/io/manager.py:494-501)
