@@ -66,6 +66,38 @@ def test_truncated_normal_element(hm):
     assert err(6, g[2].numpy(), np.maximum(np.abs(g[2].numpy()), 1.0 / sc)) < 2e-4
 
 
+@pytest.mark.parametrize("family", ["wide", "tiny", "dw"])
+def test_truncated_normal_element_on_the_direct_kernel_tests_families(hm, family):
+    """The comparison above on the inputs of tests/test_q_kernels_gpu.py (tests/ref_q.py): loc / scale from 1e-3 to 1e3, scales down to
+    2 eps, uniforms on the device's grid.  z is normalised by loc + scale (at loc << scale the sample's size is the scale's)."""
+    from tests import ref_q as Q
+    prior = "dw" if family == "dw" else "wilson"
+    T = lambda v: torch.as_tensor(np.asarray(v, dtype=np.float64))
+    for R, S in ((1100, 9), (513, 8)):
+        x = Q.make_inputs(Q.case(family, R, S, prior=prior))
+        n = R * S
+        a, b, low = (np.ascontiguousarray(np.repeat(v, S)) for v in (x.a, x.b, x.low))
+        u = np.ascontiguousarray(x.u.ravel())
+        out = np.empty((n, 10), np.float32)
+        hm.hm_tn(n, fp(a), fp(b), fp(low), ctypes.c_float(1e10), ctypes.c_float(1e-7), fp(u), fp(out))
+        loc, scale = O.tn_loc_scale(T(a), T(b), float(np.float32(1e-7)))
+        ll, sl = loc.clone().requires_grad_(True), scale.clone().requires_grad_(True)
+        z = O.tn_sample(ll, sl, T(low), T(float(np.float32(1e10))), T(u)[None, :])[0]
+        gl, gs = torch.autograd.grad(z.sum(), [ll, sl])
+        zd = z.detach().clone().requires_grad_(True)
+        lq = O.tn_log_prob(zd, ll, sl, T(low), T(float(np.float32(1e10))))
+        g = torch.autograd.grad(lq.sum(), [zd, ll, sl])
+        sc = scale.numpy()
+        def err(k, ref, nat):
+            return np.max(np.abs(out[:, k] - ref) / nat)
+        e = [err(0, z.detach().numpy(), (loc + scale).numpy()), err(1, lq.detach().numpy(), np.maximum(np.abs(lq.detach().numpy()), 1.0)),
+             err(2, gl.numpy(), 1.0), err(3, gs.numpy(), np.maximum(np.abs(gs.numpy()), 1.0)),
+             err(4, g[0].numpy(), np.maximum(np.abs(g[0].numpy()), 1.0 / sc)), err(5, g[1].numpy(), np.maximum(np.abs(g[1].numpy()), 1.0 / sc)),
+             err(6, g[2].numpy(), np.maximum(np.abs(g[2].numpy()), 1.0 / sc))]
+        print(family, R, S, ["%.1e" % v for v in e])
+        assert e[0] < 1e-5 and e[1] < 1e-4 and e[2] < 1e-5 and e[3] < 1e-5 and e[4] < 1e-4 and e[5] < 1e-4 and e[6] < 2e-4, (family, e)
+
+
 def test_wilson_likelihood_bijector(hm):
     rng = np.random.default_rng(2)
     n = 5000
