@@ -187,9 +187,11 @@ class FrozenPath:
         scales = torch.cat([torch.ones(1, dtype=torch.float32, device=self.device), self.params[lay.off_img: lay.off_img + lay.n_img].detach()])
         return scales.index_select(0, image_id)
 
-    def _edge_buffers(self, n: int, slack: int = 0):
-        """(edge_rid, edge_val) of a `cl_frozen_rows` launch over n sorted rows"""
-        return (torch.empty(2 * ((n + 63) // 64) + slack, dtype=torch.int32, device=self.device),
+    def _edge_buffers(self, n: int):
+        """(edge_rid, edge_val) of a `cl_frozen_rows` launch over n sorted rows, at the sizes the header documents: both forms that write
+        edges (ROWS, SUMS) stay inside 2 * ceil(n / 64) ints and `cl_frozen_edge_floats` floats (tests/test_rows_kernels_gpu.py runs them on
+        guarded workspaces of exactly these sizes)"""
+        return (torch.empty(2 * ((n + 63) // 64), dtype=torch.int32, device=self.device),
                 torch.empty(max(int(self.lib.cl_frozen_edge_floats(n, self.S)), 1), dtype=torch.float32, device=self.device))
 
     def _sorted_rows(self, obs: ObsData) -> SortedRows:
@@ -217,7 +219,7 @@ class FrozenPath:
             rmc, key, _, dst, refl_sorted, n2 = group_row_order(obs.refl_id, obs.row_map, obs.start, obs.noise_row)
             fz = obs.frozen_sorted = GroupRows(self._frozen_epoch, loc, sigma, loc.index_select(0, rmc).contiguous(), sigma.index_select(0, rmc).contiguous(),
                                                self._row_image_scales(obs.image_id.long().clamp(min=0)), key, dst, refl_sorted, n2,
-                                               torch.zeros(max(n2, 1) * self.S, dtype=torch.float32, device=self.device), *self._edge_buffers(n2, slack=2))
+                                               torch.zeros(max(n2, 1) * self.S, dtype=torch.float32, device=self.device), *self._edge_buffers(n2))
         return fz
 
     def _frozen_args(self, fz, obs: ObsData, step: int, eta, ipred_out) -> FrozenArgs:

@@ -470,7 +470,10 @@ typedef struct cl_laue_args {
     float* dz_f;                /* [R][S] +=                                 */
     float* d_img;               /* [M-1] +=                                  */
     float* dO;                  /* [n_obs][2] dL/d(loc, sigma) for cl_mlp_backward_ext; cl_laue_backward takes NULL (a frozen scaling model:
-                                   dz_f only, d_img untouched) */
+                                   dz_f only, d_img untouched).  Where dO is filled by atomics -- cl_laue_backward, and cl_slot_rows when S
+                                   does not divide 64 -- the call clears it first with a memset on the stream, in front of the launch:
+                                   that memset runs whatever *stop_flag says (the host does not read the flag), so a stopped call leaves
+                                   dO zero and every other output as it was.  Nothing consumes dO of a stopped step. */
     double* scalars;
     float* ipred_out;           /* optional [n_obs][S]                       */
     const int* stop_flag;
