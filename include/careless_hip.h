@@ -183,7 +183,8 @@ size_t cl_rw_args_size(void);                      /* sizeof(cl_rw_args) as the 
 typedef struct cl_mlp_args {
     const int* refl_id;         /* [n_obs]                                    */
     const int* image_id;        /* [n_obs]                                    */
-    const float* meta_t;        /* [cl_mlp_meta_rows(d)][n_pad]               */
+    const float* meta_t;        /* [cl_mlp_meta_rows(d)][n_pad]; rows >= d and observations >= n_obs are finite ZEROS from the caller (they
+                                 * enter the weight gradient's MFMAs beside a zero gradient: a NaN there is a NaN gradient) */
     const float* iobs;          /* [n_obs]                                    */
     const float* sig;           /* [n_obs]                                    */
     int n_obs, n_pad;
@@ -207,7 +208,8 @@ typedef struct cl_mlp_args {
     unsigned long long seed; unsigned step;
     float* dz_f;                /* [R][S] += dL/dz_f                           */
     float* d_img;               /* [M-1]  += dL/d(image scale)                 */
-    float* partials;            /* [grid][P] per-workgroup scaler gradient partials (workspace) */
+    float* partials;            /* [grid][P] per-workgroup scaler gradient partials (workspace).  A grid above n_pad / CL_MLP_TILE is clamped to it:
+                                 * only the first n_pad / CL_MLP_TILE rows are written (the same for nll_part and ev11_part), the rows behind keep their bytes */
     double* scalars;            /* [CL_SC_COUNT]: adds NLL into scalars[CL_SC_NLL] */
     float* ipred_out;           /* optional [n_obs][S]                         */
     float* loc_out;             /* cl_mlp_forward: [n_obs]                     */
@@ -223,7 +225,8 @@ typedef struct cl_mlp_args {
      * The observation axis must then be PACKED: every 128-observation tile holds rows of ONE image (tile_img), rows of an
      * image are padded to whole tiles with refl_id = -1, sig = 1, metadata 0; n_obs == n_pad.  row_map gives the caller's
      * row of every packed row (-1: padding): eta / ipred_out / loc_out / sig_out / dO_ext and the noise key
-     * (obs_offset + row) stay in the caller's row order.                                                          */
+     * (obs_offset + row) stay in the caller's row order: under row_map these arrays, dzf_obs and dimg_obs have one entry per CALLER's
+     * row (1 + the largest row_map entry), not per packed position.                                                */
     const float* imgl;
     float* d_imgl;              /* += dL/d(imgl)                                                               */
     int n_imgl, n_images;
@@ -244,7 +247,10 @@ typedef struct cl_mlp_args {
      *   cl_mlp_forward      with act_out : `mlp` holds L Dense layers and NO Dense(2) head; writes the last layer's activations
      *   cl_mlp_backward_ext with dH_ext  : same parameters; gradient w.r.t. those activations comes in (instead of dO_ext)
      *   dX_out (any backward launch)     : also write dL/d(metadata) -- the dH_ext of the block before
-     * The scaler-gradient partials of a head-less block have cl_mlp_param_count(d, w, L) - 2 w - 2 entries.               */
+     * The scaler-gradient partials of a head-less block have cl_mlp_param_count(d, w, L) - 2 w - 2 entries.
+     * act_out and dX_out are STORED for observations < n_obs only (their padding feature rows, [w, meta_rows(w)) and [d, meta_rows(d)),
+     * as zeros); the columns [n_obs, n_pad) are never written.  act_out is the next block's meta_t: the caller clears the buffer once
+     * (finite zeros behind n_obs, as for meta_t).  dH_ext is read for observations < n_obs only.                          */
     float* act_out;             /* [cl_mlp_meta_rows(w)][n_pad]                                                        */
     const float* dH_ext;        /* [cl_mlp_meta_rows(w)][n_pad]                                                        */
     float* dX_out;              /* [cl_mlp_meta_rows(d)][n_pad]                                                        */
