@@ -250,7 +250,11 @@ typedef struct cl_mlp_args {
      * The scaler-gradient partials of a head-less block have cl_mlp_param_count(d, w, L) - 2 w - 2 entries.
      * act_out and dX_out are STORED for observations < n_obs only (their padding feature rows, [w, meta_rows(w)) and [d, meta_rows(d)),
      * as zeros); the columns [n_obs, n_pad) are never written.  act_out is the next block's meta_t: the caller clears the buffer once
-     * (finite zeros behind n_obs, as for meta_t).  dH_ext is read for observations < n_obs only.                          */
+     * (finite zeros behind n_obs, as for meta_t).  dH_ext is read for observations < n_obs only.
+     * A block on the lane kernel (cl_mlp_route: CL_ROUTE_LANE_BLOCK) stores act_out by whole 64-observation wave tiles and its data rows
+     * only: the columns [n_obs, 64 ceil(n_obs / 64)) of the rows < w receive the FINITE activations of the zero metadata behind n_obs
+     * (the next block masks those observations, and they meet a zero gradient in its weight-gradient MFMAs); the rows
+     * [w, meta_rows(w)) and the columns behind the last wave tile are never written -- the caller's zeros stay.              */
     float* act_out;             /* [cl_mlp_meta_rows(w)][n_pad]                                                        */
     const float* dH_ext;        /* [cl_mlp_meta_rows(w)][n_pad]                                                        */
     float* dX_out;              /* [cl_mlp_meta_rows(d)][n_pad]                                                        */
@@ -270,10 +274,17 @@ typedef struct cl_mlp_args {
                                    records contiguously instead of gathering them; the scattered STORES cost the kernel nothing it waits for */
     float* dZ0_out;             /* optional [cl_mlp_meta_rows(w)][n_pad] (round 5): cl_elbo_mono_fwd_bwd also STORES dL/d(pre-activations of the FIRST Dense
                                    layer), feature-major like meta_t -- what cl_peel_backward turns into a peeled first layer's weight gradient.
-                                   The default scaler's kernels only (elbo_lane.hip, elbo_narrow.hip): any other routing returns -2            */
+                                   The default scaler's kernels only (elbo_lane.hip, elbo_narrow.hip): any other routing returns -2.
+                                   Stored by whole wave tiles (64 observations; 32 on elbo_narrow.hip) in the rows < w: every element below n_obs, and
+                                   exact ZEROS in the columns [n_obs, end of the last wave tile).  The columns behind that tile and the rows
+                                   [w, cl_mlp_meta_rows(w)) are never written, and cl_peel_backward reads every column up to n_pad ("padding
+                                   observations carry dZ_0 = 0"; cl_chain_dx reads below n_obs only): the CALLER CLEARS the buffer once, before
+                                   the first launch                                                                                            */
     float* ev11_part;           /* deterministic mode with the Evans-2011 error model (round 4): every wave of the launch STORES its share of dL/d raw
                                    (Sdfac, Sdadd, SdB) at ev11_part[3 * (CL_EV11_WAVES * workgroup + wave)] instead of three float atomics on d_ev11;
-                                   [3 * CL_EV11_WAVES * grid] floats, cl_det_reduce adds them in index order                                          */
+                                   [3 * CL_EV11_WAVES * grid] floats, cl_det_reduce adds them in index order -- ALL CL_EV11_WAVES slots of every
+                                   workgroup.  A kernel of four waves (elbo_lane.hip) stores the slots 0 .. 3 of a workgroup and never touches
+                                   4 .. 7: the CALLER CLEARS the buffer once, before the first launch                                                 */
 } cl_mlp_args;
 
 #define CL_EV11_WAVES 8          /* wave slots per workgroup in ev11_part (the kernels run four or eight waves) */
@@ -691,8 +702,9 @@ int cl_adam_grid(const cl_adam_args* args);
  *                   (elbo_lane.hip / elbo_narrow.hip store it).  zero_ptr[0 .. zero_n): cleared on the way (the caller's grad_peel).
  * cl_peel_backward: grad_mlp[layer 0] += dZ_0^T X, sum dZ_0 (per-workgroup partials [nparts][w d + w], nparts <= cl_peel_parts(n_obs), summed
  *                   in index order), grad_mlp[behind layer 0] += grad_peel[behind its layer 0] (grad_peel = cl_reduce_partials of the launch).
- * `mlp` / `grad_mlp` point at the scaler's slice of the flat parameter / gradient vector (W^T layout).  cl_peel_supported: d > w, w <= 15,
- * w (d + 1) <= 1280.                                                                                                                     */
+ * `mlp` / `grad_mlp` point at the scaler's slice of the flat parameter / gradient vector (W^T layout).  cl_peel_supported: 1 <= w <= 15,
+ * w < d <= 79 (five 16-column blocks of the weight-gradient kernel hold 79 metadata columns and the ones column), L >= 1; -2 otherwise.
+ * dz0_t is read in EVERY column up to n_pad (rows < w): zeros behind n_obs (cl_mlp_args.dZ0_out).                                          */
 int cl_peel_supported(int d, int w, int L);
 int cl_peel_parts(long long n_obs);
 int cl_peel_forward(const float* meta_t, int n_obs, int n_pad, int d, int w, int L, const float* mlp, float* u_t, float* mlp_peel,

@@ -75,18 +75,22 @@ def unpack(mlp, d, w, L, head=True):
 
 # ---- cases ---------------------------------------------------------------------------------------------------------------------------------
 def case(unit, mode, w, d, L, n=5 * TILE + 37, grid=2, S=3, lik="normal", bij="exp", img="off", noise="eta", ipred=False, ev11=False, head=True,
-         dX=False, det_slot=False, groups=False, noise_row=False, tag=""):
+         dX=False, det_slot=False, groups=False, noise_row=False, tag="", kernel="mlp", dz0=False):
     """One launch.  unit: one of UNITS; img: off / sorted (image borders inside a wave's 16 rows) / unsorted; noise: eta (injected) / philox
     (drawn in the kernel: the reference takes cl_debug_noise(kind = 1)); head False: a head-less block of a chain (act_out in mode 1, dH_ext in
-    mode 2); dX: dX_out given; groups: gmeta / tile_gmax (packed units); n: the caller's rows (active rows of a packed layout)."""
+    mode 2); dX: dX_out given; groups: gmeta / tile_gmax (packed units); n: the caller's rows (active rows of a packed layout).  kernel: whose
+    launch geometry the case has (WAVES: elbo_mlp.hip's 128-row tiles, or the 64- / 32-row wave tiles of elbo_lane.hip / elbo_narrow.hip, strided
+    over all waves of the launch: tests/ref_lane.py); dz0: dZ0_out given (those two kernels only)."""
     c = SimpleNamespace(unit=unit, mode=mode, w=w, d=d, L=L, n=n, grid=grid, S=S, lik=lik, bij=bij, img=img, noise=noise, ipred=ipred, ev11=ev11,
-                        head=head, dX=dX, det_slot=det_slot, groups=groups, noise_row=noise_row, tag=tag)
+                        head=head, dX=dX, det_slot=det_slot, groups=groups, noise_row=noise_row, tag=tag, kernel=kernel, dz0=dz0)
     c.packed, c.det, c.chain = unit.startswith("packed"), unit.endswith("det"), unit.startswith("chain")
-    assert unit in UNITS and (head or c.chain) and (not dX or c.chain) and (not groups or (c.packed and mode == 0))
+    assert unit in UNITS and (head or c.chain) and (not dX or c.chain) and (not groups or (c.packed and mode == 0)) and kernel in WAVES
+    assert not dz0 or (kernel != "mlp" and mode == 0)
     assert not (lik == "laplace" and ev11) and (mode == 0 or not (ipred or ev11))
     c.id = (f"{unit}-m{mode}-{L}x{w}-d{d}-n{n}-g{grid}-S{S}-{lik}-{bij}" + ("" if img == "off" else f"-img{img}") + ("" if noise == "eta" else "-philox") +
             ("-ipred" if ipred else "") + ("-ev11" if ev11 else "") + ("" if head else "-nohead") + ("-dX" if dX else "") + ("-slot" if det_slot else "") +
-            ("-groups" if groups else "") + ("-noiserow" if noise_row else "") + (f"-{tag}" if tag else ""))
+            ("-groups" if groups else "") + ("-noiserow" if noise_row else "") + ("-dz0" if dz0 else "") + ("" if kernel == "mlp" else f"-{kernel}") +
+            (f"-{tag}" if tag else ""))
     return c
 
 
@@ -111,6 +115,8 @@ def set_fields(c):
         f |= {"partials", "dO_ext" if c.head else "dH_ext"}
     if c.dX:
         f.add("dX_out")
+    if c.dz0:
+        f.add("dZ0_out")
     if c.packed:
         f.add("row_map")
         if c.groups:
@@ -233,7 +239,7 @@ def instance_cases(lib=None):
 
 def _like(c, **kw):
     f = dict(n=c.n, grid=c.grid, S=c.S, lik=c.lik, bij=c.bij, img=c.img, noise=c.noise, ipred=c.ipred, ev11=c.ev11, head=c.head, dX=c.dX, det_slot=c.det_slot,
-             groups=c.groups, noise_row=c.noise_row, tag=c.tag)
+             groups=c.groups, noise_row=c.noise_row, tag=c.tag, kernel=c.kernel, dz0=c.dz0)
     f.update(kw)
     return case(c.unit, c.mode, c.w, c.d, c.L, **f)
 
@@ -412,6 +418,26 @@ def forward(X, mlp, d, w, L, head, bij_kind, eps):
     return f
 
 
+# (waves of a workgroup, rows of a wave's tile) of the kernel a case runs on
+WAVES = {"mlp": (EV11_WAVES, 16), "lane": (4, 64), "narrow": (8, 32)}
+
+
+def partition(c, npos, grid_eff, ntiles):
+    """(workgroup, wave) of every position.  elbo_mlp.hip: 128-row tiles strided over the grid (the packed layout: one contiguous range of tiles
+    per workgroup), wave = the tile's 16-row slice.  The lane and narrow kernels: wave tiles strided over ALL waves of the launch, in either layout."""
+    pos = np.arange(npos)
+    nw, wt = WAVES[c.kernel]
+    if c.kernel != "mlp":
+        gw = (pos // wt) % (grid_eff * nw)
+        return gw // nw, gw % nw
+    tile_of = pos // TILE
+    wg_of = tile_of % grid_eff
+    if c.packed:                                                        # tile t belongs to the g with g nt / G <= t < (g + 1) nt / G (integer division)
+        begin = np.array([g * ntiles // grid_eff for g in range(grid_eff + 1)])
+        wg_of = np.searchsorted(begin, tile_of, side="right") - 1
+    return wg_of, (pos % TILE) // 16
+
+
 def packed_layout(c, seed):
     """positions of a packed layout by the header's contract: groups of 1 .. 16 rows inside 16-row granules (ref_rows.groups_layout), padding
     positions with refl_id = -1, the whole padded to tiles; the caller's rows are a permutation of the active positions"""
@@ -459,11 +485,7 @@ def make_inputs(c, seed=0):
     x.ntiles = x.n_pad // TILE
     x.grid_eff = min(c.grid, x.ntiles)
     # a workgroup's tiles: strided over the grid in the plain layout, ONE contiguous range in the packed one (image changes are then rare)
-    tile_of = np.arange(x.np_) // TILE
-    wg_of = tile_of % x.grid_eff
-    if c.packed:                                                        # tile t belongs to the g with g nt / G <= t < (g + 1) nt / G (integer division)
-        begin = np.array([g * x.ntiles // x.grid_eff for g in range(x.grid_eff + 1)])
-        wg_of = np.searchsorted(begin, tile_of, side="right") - 1
+    wg_of, x.wave_of = partition(c, x.np_, x.grid_eff, x.ntiles)
     x.wg_of = wg_of
     x.wg_rows = [np.flatnonzero((wg_of == g) & x.act) for g in range(x.grid_eff)]
     if c.mode == 1:
@@ -474,6 +496,8 @@ def make_inputs(c, seed=0):
             x.dO[:] = RW.normals(rng, c.n, 2) * F32(0.7)
         else:
             x.dH = np.zeros((meta_rows(c.w), x.n_pad), F32)
+            if c.kernel != "mlp":                                       # dH_ext is read below n_obs and in the rows < w only: numbers a launch must not use everywhere else
+                x.dH[:] = F32(1e3)
             x.dH[:c.w, :x.np_] = (RW.normals(rng, c.w, x.np_) * F32(0.7)) * x.act
         x.grad_pre = None
         return x
@@ -625,7 +649,7 @@ def ev11_wave_reference(x, g, wv):
     xx = rows_view(x)
     m = np.zeros(x.np_, bool)
     rows = x.wg_rows[g]
-    m[rows[(rows % TILE) // 16 == wv]] = True
+    m[rows[x.wave_of[rows] == wv]] = True
     sub = copy.copy(xx)
     sub.count = xx.count & m
     if not sub.count.any():
@@ -728,6 +752,9 @@ def ratios(x, ref, pre, got):
     if have("grad"):                                                    # behind cl_reduce_partials, on top of the preload
         stored = RW.f64(pre.grad) + ref.grad
         out["reduced grad"] = RR._worst_grad(np.abs(RW.f64(got.grad) - stored), ref.M_grad, stored)
+    if have("dz0"):                                                     # dL/d(pre-activations of layer 0), feature-major, every element below n_obs
+        dz0 = RW.f64(got.dz0)[:x.w, :x.np_].T
+        out["dZ0_out"] = RR._worst_grad(np.abs(dz0 - ref.b.dZ[0]), ref.b.MZ[0], ref.b.dZ[0])
     if have("dX"):
         dX = RW.f64(got.dX)[:x.d, :x.np_].T
         out["dX_out"] = RR._worst_grad(np.abs(dX - ref.b.dX), ref.b.MX, ref.b.dX)
@@ -741,6 +768,9 @@ MUTANTS = ("rows_behind_n_obs_counted", "last_tile_left_out_of_wgrad", "wg1_part
            "head_rows_swapped_in_backward", "image_0_not_pinned", "shift_outside_image_scale", "second_sample_dropped", "eta_read_as_S_n",
            "obs_offset_left_out_of_noise_key", "w_ll_lost", "dX_without_first_layer_mask", "act_out_row_major", "group_sum_over_tile_gmax",
            "det_slot_not_times_S")
+# ... of the lane and narrow kernels' launches (tests/ref_lane.py, tests/test_ref_lane.py)
+LANE_MUTANTS = ("rows_behind_n_obs_counted", "second_wave_tile_skipped", "ninth_sample_dropped", "head_wgrad_from_one_wave", "dz0_without_first_slope",
+                "tile_shares_a_reflection_by_store", "dH_ext_read_behind_n_obs")
 
 
 def _mm(a, b):
@@ -748,7 +778,7 @@ def _mm(a, b):
 
 
 def _wg(x, npos, act):
-    wg_of = np.concatenate([x.wg_of, (np.arange(x.np_, npos) // TILE) % x.grid_eff])
+    wg_of = x.wg_of if npos == x.np_ else partition(x.case, npos, x.grid_eff, x.ntiles)[0]      # (more positions: the plain layout's padding rows)
     return [np.flatnonzero((wg_of == g) & act) for g in range(x.grid_eff)]
 
 
@@ -759,7 +789,7 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
     layers, head = unpack(x.mlp, x.d, x.w, x.L, x.head)
     act = x.act.copy()
     X = x.X.copy()
-    if mutant == "rows_behind_n_obs_counted" and not c.packed:          # the padding rows of the last tile take part (metadata 0)
+    if mutant in ("rows_behind_n_obs_counted", "dH_ext_read_behind_n_obs") and not c.packed:      # the padding rows of the last tile take part (metadata 0)
         npos = x.n_pad
         X = np.zeros((npos, x.d), F32)
         X[:x.np_] = x.X
@@ -845,6 +875,8 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
         live = act[:, None] & np.ones((1, S), bool)
         if mutant == "second_sample_dropped":                          # a lane's samples s and s + 4: the second one never evaluated
             live = live & (np.arange(S)[None, :] < 4)
+        if mutant == "ninth_sample_dropped":                           # the lane kernel's batches of eight samples: the second batch one short
+            live = live & (np.arange(S)[None, :] != 8)
         nll_rows = -(np.where(live & cnt[:, None], ll, F32(0)) * w_ll).astype(np.float64).sum(1)
         gi = np.where(live, -dll * w_ll, F32(0)).astype(F32)
         rec = (gi * zs * F32(2) * zf).astype(F32)
@@ -875,7 +907,13 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
                 got.dimg_obs[rows] = pda[:x.np_][x.act]
         else:
             got.dz = pre.dz.copy()
-            np.add.at(got.dz, (rid[act][:, None], np.arange(S)[None, :]), rec[act])
+            add = act
+            if mutant == "tile_shares_a_reflection_by_store":          # the rows of one wave tile that share a reflection: the last one's record alone arrives
+                key = (np.arange(npos) // WAVES[c.kernel][1]) * x.R + rid
+                last = np.zeros(npos, bool)
+                last[npos - 1 - np.unique(key[::-1], return_index=True)[1]] = True
+                add = act & last
+            np.add.at(got.dz, (rid[add][:, None], np.arange(S)[None, :]), rec[add])
             if x.img is not None:
                 got.d_img = pre.d_img.copy()
                 if mutant == "image_0_not_pinned":
@@ -887,10 +925,11 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
             sgm = RR.sigmoid32(hm, x.ev11)
             e = np.stack([-(np.where(live & cnt[:, None], v.reshape(npos, S), F32(0)) * w_ll).sum(1, dtype=F32) for v in (gf, ga, gb)], 1)      # Sdfac, Sdadd, SdB
             if c.det:
+                wave_of = partition(c, npos, x.grid_eff, x.ntiles)[1]
                 got.ev11_part = np.zeros((EV11_WAVES * c.grid, 3), F32)
                 for g, r in enumerate(wg):
                     for wv in range(EV11_WAVES):
-                        got.ev11_part[EV11_WAVES * g + wv] = e[r[(r % TILE) // 16 == wv]].sum(0, dtype=F32) * sgm
+                        got.ev11_part[EV11_WAVES * g + wv] = e[r[wave_of[r] == wv]].sum(0, dtype=F32) * sgm
                 got.ev11_part = got.ev11_part.ravel()
             else:
                 got.d_ev11 = (pre.d_ev11 + e[act].sum(0, dtype=F32) * sgm).astype(F32)
@@ -910,13 +949,19 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
     else:
         dH = np.zeros((npos, x.w), F32)
         dH[:x.np_] = x.dH[:x.w, :x.np_].T
+        if mutant == "dH_ext_read_behind_n_obs":                       # a block's backward launch that reads whole wave tiles of dH_ext
+            dH[:] = x.dH[:x.w, :npos].T
     dZ = [None] * x.L
     for l in range(x.L - 1, -1, -1):
         dZ[l] = (dH * slope[l]).astype(F32)
+        dH0 = dH                                                       # (behind the loop: dL/d(activations of layer 0))
         if l == 0 and mutant == "dX_without_first_layer_mask":
             dH = _mm(dH, layers[0][0])
         else:
             dH = _mm(dZ[l], layers[l][0])
+    if c.dz0:
+        got.dz0 = np.zeros((meta_rows(x.w), x.n_pad), F32)
+        got.dz0[:x.w, :x.np_] = (dH0 if mutant == "dz0_without_first_slope" else dZ[0])[:x.np_].T
     if c.dX:
         got.dX = np.zeros((meta_rows(x.d), x.n_pad), F32)
         got.dX[:x.d, :x.np_] = dH[:x.np_].T
@@ -924,6 +969,14 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
     for g, rows in enumerate(wg):
         if mutant == "last_tile_left_out_of_wgrad" and len(rows):
             rows = rows[rows // TILE != (rows // TILE).max()] if len(np.unique(rows // TILE)) > 1 else rows[:0]
+        hrows = rows
+        if mutant in ("second_wave_tile_skipped", "head_wgrad_from_one_wave"):
+            nw, wt = WAVES[c.kernel]
+            if mutant == "second_wave_tile_skipped":                   # wave tiles are strided over all waves of the launch: every wave's second one
+                rows = rows[(rows // wt) // (x.grid_eff * nw) != 1]
+                hrows = rows
+            else:                                                      # the head's per-wave sums: wave 0's alone
+                hrows = rows[((rows // wt) % (x.grid_eff * nw)) % nw == 0]
         v = []
         for l in range(x.L):
             db = dZ[l][rows].sum(0, dtype=F32)
@@ -933,7 +986,7 @@ def emulate(x, hm, pre, mutant=None, eta_shifted=None):
                 db = dZ[l][rows[(rows % TILE) // 16 != 7]].sum(0, dtype=F32)
             v += [_mm(dZ[l][rows].T, H[l][rows]).ravel(), db]
         if x.head:
-            v += [_mm(g0[rows][None, :], H[-1][rows]).ravel(), _mm(g1[rows][None, :], H[-1][rows]).ravel(), np.array([g0[rows].sum(dtype=F32), g1[rows].sum(dtype=F32)], F32)]
+            v += [_mm(g0[hrows][None, :], H[-1][hrows]).ravel(), _mm(g1[hrows][None, :], H[-1][hrows]).ravel(), np.array([g0[hrows].sum(dtype=F32), g1[hrows].sum(dtype=F32)], F32)]
         row = 0 if (mutant == "wg1_partial_to_row_0" and g == 1) else g
         parts[row] = np.concatenate(v)
     got.partials = parts

@@ -78,7 +78,37 @@ def inputs_of(c):
 
 
 class Run:
-    """the operands of one case in a guarded allocation and the cl_mlp_args that point at them"""
+    """the operands of one case in a guarded allocation and the cl_mlp_args that point at them.  (The hooks -- stored_columns, ev11_waves,
+    more_operands, more_args, check_instance -- are what tests/test_lane_kernels_gpu.py replaces for the lane and narrow kernels.)"""
+
+    def stored_columns(self):
+        """columns of act_out / dX_out the launch may store: the observations below n_obs"""
+        return self.x.np_
+
+    def act_mask(self, live):
+        """elements of act_out the launch may store: every row of the padded feature block (the padding rows: zeros) in the stored columns"""
+        return np.broadcast_to(live, (RM.meta_rows(self.x.w), self.x.n_pad))
+
+    def check_act(self, act):
+        """data rows written, padding rows exactly zero, columns behind n_obs left alone (the mask)"""
+        x = self.x
+        assert np.all(act[:x.w, :x.np_] != F32(RM.SENT)) and np.all(act[x.w:, :x.np_] == 0.0), self.c.id
+
+    EV11_FILL = 0.0                                                    # what the wave slots the kernel never stores hold: the caller's zeros (cl_det_reduce adds them)
+
+    def ev11_waves(self):
+        """wave slots of a workgroup's CL_EV11_WAVES in ev11_part that the kernel stores"""
+        return RM.EV11_WAVES
+
+    def more_operands(self, g):
+        pass
+
+    def more_args(self, A, opt):
+        pass
+
+    def check_instance(self, route, inst):
+        c = self.c
+        assert route == ROUTE[c.unit] and inst == RM.expected_instance(c) == getattr(c, "instance", inst), (c.id, route, inst, RM.expected_instance(c))
 
     def __init__(self, x, ref, stop=False, act_zero=False):
         c = x.case
@@ -86,7 +116,7 @@ class Run:
         self.pre = pre = RM.preloads(x, ref) if c.mode != 1 else None
         n, S, grid, P = x.n, x.S, c.grid, x.P
         live = np.zeros(x.n_pad, bool)
-        live[:x.np_] = True
+        live[:self.stored_columns()] = True
         g = ref_step.Guarded(DEV).add("meta_t", x.meta_t).add("mlp", x.mlp).add("stop", np.array([1 if stop else 0], np.int32))
         part_mask = np.zeros((grid, P), bool)
         part_mask[:x.grid_eff] = True                                  # the launch clamps the grid: the rows behind n_pad / 128 keep their bits
@@ -108,8 +138,9 @@ class Run:
                 g.add("ev11", x.ev11).add("d_ev11", pre.d_ev11, True)
                 if c.det:
                     m = np.zeros((grid, 3 * RM.EV11_WAVES), bool)
-                    m[:x.grid_eff] = True
-                    g.add("ev11_part", np.full((grid, 3 * RM.EV11_WAVES), RM.SENT, F32), m)
+                    m[:x.grid_eff, :3 * self.ev11_waves()] = True
+                    g.add("ev11_part", np.where(m | (np.arange(grid) >= x.grid_eff)[:, None], F32(RM.SENT), F32(self.EV11_FILL)), m)      # (slots the kernel has no wave for: the caller's zeros)
+                    self.ev11_mask = m
             if c.det:
                 g.add("dzf_obs", np.full((n, S), RM.SENT, F32), True).add("nll_part", np.full(grid, -7.5e300), np.arange(grid) < x.grid_eff)
                 if x.img is not None:
@@ -120,7 +151,7 @@ class Run:
             if c.head:
                 g.add("loc_out", np.full(n, RM.SENT, F32), True).add("sig_out", np.full(n, RM.SENT, F32), True)
             else:
-                g.add("act_out", np.full((RM.meta_rows(x.w), x.n_pad), 0.0 if act_zero else RM.SENT, F32), np.broadcast_to(live, (RM.meta_rows(x.w), x.n_pad)))
+                g.add("act_out", np.full((RM.meta_rows(x.w), x.n_pad), 0.0 if act_zero else RM.SENT, F32), self.act_mask(live))
         if c.mode == 2:
             g.add("dO_ext", x.dO) if c.head else g.add("dH_ext", x.dH)
         if c.mode != 1:
@@ -133,6 +164,7 @@ class Run:
                 g.add("gmeta", x.gmeta).add("tile_gmax", x.tile_gmax)
         if x.case.noise_row:
             g.add("noise_row", x.noise_row)
+        self.more_operands(g)
         self.g = g.build()
         A = _lib.MlpArgs()
         A.meta_t, A.mlp, A.stop_flag = g.ptr("meta_t"), g.ptr("mlp"), g.ptr("stop")
@@ -150,6 +182,7 @@ class Run:
             A.dzf_obs, A.dimg_obs, A.nll_part, A.det_slot = opt("dzf_obs"), opt("dimg_obs"), opt("nll_part"), opt("det_slot")
         A.loc_out, A.sig_out, A.act_out, A.dO_ext, A.dH_ext, A.dX_out = (opt(k) for k in ("loc_out", "sig_out", "act_out", "dO_ext", "dH_ext", "dX_out"))
         A.partials, A.row_map, A.gmeta, A.tile_gmax, A.noise_row = (opt(k) for k in ("partials", "row_map", "gmeta", "tile_gmax", "noise_row"))
+        self.more_args(A, opt)
         self.A = A
 
     def instance(self):
@@ -161,7 +194,7 @@ class Run:
     def launch(self, untouched=False):
         lib, c = _lib.get_lib(), self.c
         route, inst = self.instance()
-        assert route == ROUTE[c.unit] and inst == RM.expected_instance(c) == getattr(c, "instance", inst), (c.id, route, inst, RM.expected_instance(c))
+        self.check_instance(route, inst)
         assert int(lib.cl_mlp_check(C.byref(self.A), c.mode, c.grid)) == 0, c.id
         ret = int(getattr(lib, ENTRY[c.mode])(C.byref(self.A), c.grid, None))
         try:
@@ -187,12 +220,12 @@ class Run:
             assert getattr(out, k) is None or np.all(getattr(out, k) != sent), (c.id, k)
         if out.partials is not None:
             assert np.all(out.partials[:x.grid_eff] != sent), c.id
-        if out.act is not None:                                        # data rows written, padding columns exactly zero, rows behind n_obs left alone (the mask)
-            assert np.all(out.act[:x.w, :x.np_] != sent) and np.all(out.act[x.w:, :x.np_] == 0.0), c.id
+        if out.act is not None:
+            self.check_act(out.act)
         if out.dX is not None:
             assert np.all(out.dX[:x.d, :x.np_] != sent) and np.all(out.dX[x.d:, :x.np_] == 0.0), c.id
         if out.ev11_part is not None:
-            assert np.all(out.ev11_part[:x.grid_eff] != sent), c.id
+            assert np.all(out.ev11_part[self.ev11_mask] != sent), c.id
             out.ev11_part = out.ev11_part[:x.grid_eff].ravel()
         if c.mode == 0 and not c.det:
             out.dz, out.d_img, out.d_ev11 = get("dz_f"), get("d_img"), get("d_ev11")
