@@ -32,8 +32,10 @@ LANE_TABLE = [("elbo_lane0", "DISPATCH", None, True), ("elbo_lane1", "PACKED_REG
               ("elbo_lane_b20", "BLOCK", None, True)]
 LANE_UNITS = [("elbo_lane.hip", stem, [f"-DCL_LANE_UNIT=CL_LANE_UNIT_{kind}"] + ([f"-DCL_LANE_NL={D}"] if D else []) + (LANE_FLAG if flag else []) + NNAN)
               for stem, kind, D, flag in LANE_TABLE]
-# (source, object stem, extra flags): elbo_mlp.hip is compiled twice -- Dense-only scalers and the per-image-layer variant
-UNITS = [("cl_api.hip", "cl_api", []), ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=0"] + NNAN), ("elbo_mlp.hip", "elbo_mlp_imgl", ["-DCL_IMGL=1"] + NNAN),
+# (source, object stem, extra flags): elbo_mlp.hip is compiled seven times, once per cl_route it serves (the list at the head of the source);
+# mlp_launch.hip is the host code that picks among them and the lane and narrow kernels
+UNITS = [("cl_api.hip", "cl_api", []), ("mlp_launch.hip", "mlp_launch", []),
+         ("elbo_mlp.hip", "elbo_mlp", ["-DCL_IMGL=0"] + NNAN), ("elbo_mlp.hip", "elbo_mlp_imgl", ["-DCL_IMGL=1"] + NNAN),
          ("elbo_mlp.hip", "elbo_mlp_packed", ["-DCL_IMGL=2"] + NNAN),
          ("elbo_mlp.hip", "elbo_mlp_chain", ["-DCL_CHAIN=1"] + NNAN),
          ("elbo_mlp.hip", "elbo_mlp_det", ["-DCL_DET=1"] + NNAN),               # deterministic mode: the epilogue's atomics as stores
@@ -124,7 +126,7 @@ def _build(LIB: str, extra, verbose: bool) -> str:
             cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17"] + list(extra) + flags + ["-c", os.path.join(CSRC, s), "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
-            while sum(1 for _, p in procs if p.poll() is None) >= jobs:      # (58 units: not all compilers at once on a small box)
+            while sum(1 for _, p in procs if p.poll() is None) >= jobs:      # (60 units: not all compilers at once on a small box)
                 time.sleep(0.2)
             procs.append((cmd, subprocess.Popen(cmd)))
             objs.append(o)

@@ -49,48 +49,11 @@ size_t cl_mlp_param_count(int d, int w, int L) {
     return (size_t)w * d + w + (size_t)(L - 1) * ((size_t)w * w + w) + 2 * (size_t)w + 2;
 }
 
-static int check_mlp(const cl_mlp_args* a) {
-    if (a == nullptr) return -1;
-    if (a->meta_t == nullptr || a->mlp == nullptr) return -1;
-    if (a->n_obs <= 0 || a->n_pad < a->n_obs || a->n_pad % CL_MLP_TILE != 0) return -1;
-    return 0;
-}
-
-// the entry checks of the three scaler calls, by mode (0 = cl_elbo_mono_fwd_bwd, 1 = cl_mlp_forward, 2 = cl_mlp_backward_ext)
-static int check_mlp_entry(const cl_mlp_args* a, int mode) {
-    if (int e = check_mlp(a)) return e;
-    switch (mode) {
-        case 0:
-            if (a->refl_id == nullptr || a->iobs == nullptr || a->sig == nullptr || a->z_f == nullptr || a->dz_f == nullptr ||
-                a->partials == nullptr || a->scalars == nullptr || a->S < 1 || a->R < 1)
-                return -1;
-            if (a->use_img && (a->image_id == nullptr || a->img == nullptr || a->d_img == nullptr)) return -1;
-            return cl_lik_check(a->lik_kind, a->ev11, a->d_ev11, a->ev11_part, true);
-        case 1: return (a->act_out == nullptr && (a->loc_out == nullptr || a->sig_out == nullptr)) ? -1 : 0;
-        case 2: return ((a->dO_ext == nullptr && a->dH_ext == nullptr) || a->partials == nullptr) ? -1 : 0;
-    }
-    return -1;
-}
-
-int cl_elbo_mono_fwd_bwd(const cl_mlp_args* a, int grid, void* stream) {
-    if (int e = check_mlp_entry(a, 0)) return e;
-    return cl_launch_mlp(*a, 0, grid, (hipStream_t)stream);
-}
-
-int cl_mlp_forward(const cl_mlp_args* a, int grid, void* stream) {
-    if (int e = check_mlp_entry(a, 1)) return e;
-    return cl_launch_mlp(*a, 1, grid, (hipStream_t)stream);
-}
-
-int cl_mlp_backward_ext(const cl_mlp_args* a, int grid, void* stream) {
-    if (int e = check_mlp_entry(a, 2)) return e;
-    return cl_launch_mlp(*a, 2, grid, (hipStream_t)stream);
-}
-
-int cl_mlp_check(const cl_mlp_args* a, int mode, int grid) {
-    if (int e = check_mlp_entry(a, mode)) return e;
-    return mlp_check(*a, mode, grid, mlp_route(*a, mode));
-}
+// the three scaler calls and the code they would return (mlp_launch.hip: entry check, route, argument check, launch)
+int cl_elbo_mono_fwd_bwd(const cl_mlp_args* a, int grid, void* stream) { return cl_launch_mlp(a, 0, grid, (hipStream_t)stream); }
+int cl_mlp_forward(const cl_mlp_args* a, int grid, void* stream) { return cl_launch_mlp(a, 1, grid, (hipStream_t)stream); }
+int cl_mlp_backward_ext(const cl_mlp_args* a, int grid, void* stream) { return cl_launch_mlp(a, 2, grid, (hipStream_t)stream); }
+int cl_mlp_check(const cl_mlp_args* a, int mode, int grid) { return cl_launch_mlp(a, mode, grid, nullptr, false); }
 
 int cl_mlp_route(const cl_mlp_args* a, int mode) {
     if (a == nullptr || mode < 0 || mode > 2) return -1;

@@ -7,7 +7,7 @@
 #include <cstdio>
 #include "../../include/careless_hip.h"
 
-// What a lane / narrow launch path hands down to the leaf that picks the kernel instance.  With a name sink the leaf prints the
+// What a scaler launch path hands down to the leaf that picks the kernel instance.  With a name sink the leaf prints the
 // instance's own template parameters there and returns the length (cl_mlp_kernel_name: the name comes from the code that selects
 // the instance) without touching the runtime; without one it launches on `grid` workgroups of stream `st`.
 struct cl_launch_ctx {
@@ -17,20 +17,18 @@ struct cl_launch_ctx {
     size_t name_n = 0;
 };
 
-// A scaler launch: route, argument check, grid clamp, dispatch (elbo_mlp.hip).  The launchers below it check nothing.
-int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st);
-cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // the launcher cl_launch_mlp hands a launch to
-cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r);                // the epilogue of the instance that launcher runs (cl_mlp_epilogue)
-int mlp_check(const cl_mlp_args& a, int mode, int grid, cl_route r);                 // 0, or the negative code of the launch (every argument check of every route)
+// A scaler launch: entry check, route, argument check, grid clamp, dispatch (mlp_launch.hip).  The units below it check nothing.
+// `launch` false: the code the launch would return, without launching (cl_mlp_check).
+int cl_launch_mlp(const cl_mlp_args* a, int mode, int grid, hipStream_t st, bool launch = true);
+cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // the unit or launcher cl_launch_mlp hands a launch to
+cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r);                // the epilogue of the instance it runs (cl_mlp_epilogue)
 int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // the name of the instance the launch runs
-// the eight compilations of elbo_mlp.hip (build.py), one launcher each
-int cl_launch_mlp_plain(const cl_mlp_args& a, int mode, int grid, hipStream_t st);  // -DCL_IMGL=0
-int cl_launch_mlp_imgl(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // -DCL_IMGL=1: per-image layers
-int cl_launch_mlp_packed(const cl_mlp_args& a, int mode, int grid, hipStream_t st); // -DCL_IMGL=2: packed layout (single-pass Laue)
-int cl_launch_mlp_chain(const cl_mlp_args& a, int mode, int grid, hipStream_t st);  // -DCL_CHAIN=1: a block of a layer-block chain
-int cl_launch_mlp_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // -DCL_DET=1: deterministic mode (no atomics), plain layout, full step
-int cl_launch_mlp_packed_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);   // -DCL_IMGL=2 -DCL_DET=1
-int cl_launch_mlp_chain_det(const cl_mlp_args& a, int mode, int grid, hipStream_t st);    // -DCL_CHAIN=1 -DCL_DET=1: a chain's LAST block (the forward-only and backward-only launches have no atomics and keep the chain unit)
+// The seven compilations of elbo_mlp.hip (build.py), one cl_route each: -DCL_IMGL=0 CL_ROUTE_MLP, -DCL_IMGL=1 _IMGL (per-image layers),
+// -DCL_IMGL=2 _PACKED (single-pass Laue), -DCL_CHAIN=1 _CHAIN (a block of a layer-block chain), -DCL_DET=1 _DET (deterministic mode: no
+// atomics; plain layout, full step), -DCL_IMGL=2 -DCL_DET=1 _PACKED_DET, -DCL_CHAIN=1 -DCL_DET=1 _CHAIN_DET (a chain's LAST block: the
+// forward-only and backward-only launches have no atomics and keep the chain unit).  One entry point, specialised in the unit of the route.
+template <cl_route R>
+int cl_mlp_unit(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
 int cl_launch_det_reduce(const cl_det_args& a, hipStream_t st);                     // elbo_elem.hip: fixed-order sums of the deterministic mode
 // The *_supports functions describe the shapes a kernel family holds; the A/B switches that keep shapes off a family are read by mlp_route only.
 int cl_narrow_supports(const cl_mlp_args& a);                                       // elbo_narrow.hip: width <= 15, metadata <= 15, plain layout
@@ -82,6 +80,45 @@ static inline int cl_lik_check(int lik_kind, const void* ev11, const void* d_ev1
     if (lik_kind == CL_LIK_LAPLACE_ && (ev11 != nullptr || d_ev11 != nullptr || ev11_part != nullptr)) return -1;
     if (lik_kind == CL_LIK_LAPLACE_ && !has_laplace) return -2;
     return 0;
+}
+
+// Instantiated geometries of elbo_mlp.hip: the padded width WP fixes how many layers of activations + weight-gradient blocks fit in the
+// 256-register budget of a wave: w <= 15 -> up to 20 layers (the CLI default scaler is 20 x 10), w <= 32 -> 10, w <= 64 -> 5.
+// Per-image layers on more than 32 metadata columns at hidden width <= 15: the 16-wide instance <16, 64, 24, IMGL> (864 - 880 bytes of
+// scratch per lane, the largest of the library) ends in a GPU memory fault when a workgroup walks more than one tile and crosses an
+// image border (found by a random draw late in round 6: scripts/probe/imgl_abort_probe.py, NOTEBOOK R6.4; the forward-only launch
+// is not affected).  Those shapes take the 32-wide instance, which holds up to CL_MLP_LMAX_W32 layers (deeper: the caller's
+// layer-by-layer path, as for any scaler deeper than one launch).
+// One helper for every unit's launch_mode and for mlp_route / mlp_epilogue (mlp_launch.hip); `imgl_unit`: the per-image-layer compilation
+// (CL_IMGL == 1).  WP = 0: no instance holds the shape.
+struct MlpGeom { int WP, DP, LMAX, KS; };
+static inline MlpGeom mlp_geom(const cl_mlp_args& a, int mode, bool imgl_unit) {
+    if (a.L < 1 || a.w < 1 || a.d < 1 || a.w > 64 || a.d > 64) return {0, 0, 0, 0};
+    const int imgl = imgl_unit ? a.n_imgl : 0;
+    const bool imgl_d64 = imgl_unit && mode != 1 && a.n_imgl > 0 && a.d > 32;
+    MlpGeom g{0, a.d <= 8 ? 8 : (a.d <= 32 ? 32 : 64), 0, 4};
+    if (a.w <= 15 && !imgl_d64) {
+        // the narrow instance comes in three step counts (hidden width <= 8, <= 12, <= 15); the forward-only launch keeps all four
+        g.WP = 16, g.LMAX = imgl_unit ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16;
+        if (mode != 1) g.KS = a.w <= 8 ? 2 : (a.w <= 12 ? 3 : 4);
+    } else if (a.w == 16 && !imgl_unit) {
+        g.WP = 16, g.LMAX = CL_MLP_LMAX_W16, g.KS = 5;         // (per-image layers keep the 32-wide instance)
+    } else if (a.w <= 32) {
+        g.WP = 32, g.LMAX = a.L + imgl <= 5 ? 5 : CL_MLP_LMAX_W32;
+    } else {
+        g.WP = 64, g.LMAX = CL_MLP_LMAX_W64;
+    }
+    if (a.L + imgl > g.LMAX) g.WP = 0;
+    return g;
+}
+// The launches the plain epilogue is compiled for (template parameter EPI): a full step that draws its noise in the kernel keyed by the
+// row itself, returns no predictions, has no Evans-2011 error model and at most two MC samples per epilogue lane.  Arguments only: which
+// instances HAVE a plain epilogue (the 64-wide ones of the plain unit) and the A/B switch are mlp_epilogue's.
+static inline cl_epilogue epi_plain(const cl_mlp_args& a, int mode) {
+    if (mode != 0 || a.eta != nullptr || a.noise_row != nullptr || a.ipred_out != nullptr || a.S > 8) return CL_EPI_GENERIC;
+    if (a.ev11 != nullptr || a.d_ev11 != nullptr || a.ev11_part != nullptr) return CL_EPI_GENERIC;
+    if (a.lik_kind == CL_LIK_NORMAL_) return CL_EPI_PLAIN_NORMAL;
+    return a.lik_kind == CL_LIK_STUDENTT_ ? CL_EPI_PLAIN_STUDENTT : CL_EPI_GENERIC;
 }
 
 // What the entry checks of wide_gemm.hip and elbo_frozen.hip ask of their required pointers.
@@ -232,7 +269,7 @@ __device__ __forceinline__ float cl_wave_sum(float v) {
 // out[i] += sum over the `nparts` per-workgroup partials of element i, in index order (deterministic): the work of ONE 256-thread
 // workgroup -- 32 consecutive elements x 8 chunks of the partial list; a thread sums its chunk (coalesced 128-B rows, eight rows in
 // flight: a one-at-a-time loop is a chain of dependent HBM / MALL latencies), the 8 chunk sums are combined through LDS in chunk order.
-// Shared by reduce_partials_kernel (elbo_mlp.hip) and the extra workgroups of tn_backward_kernel (elbo_elem.hip).
+// Shared by reduce_partials_kernel and the extra workgroups of tn_backward_kernel (both elbo_elem.hip).
 __device__ __forceinline__ void cl_reduce_partials_block(const float* __restrict__ partials, int nparts, int P, float* __restrict__ out, int block) {
     __shared__ float sh[8][33];
     const int e = threadIdx.x & 31, c = threadIdx.x >> 5;

@@ -542,6 +542,18 @@ int cl_launch_tn_backward(const cl_tn_args& a, hipStream_t st) {
     hipLaunchKernelGGL(tn_backward_kernel, dim3((nr + 255) / 256 + nred), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
+// sum of the per-workgroup partials of a scaler launch in a fixed order -> MLP slice of the flat gradient buffer (the work of a workgroup
+// is cl_reduce_partials_block, cl_kernels.h: shared with the cl_tn_backward launch above, which can carry it)
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partials, int nparts, int P,
+                                                               float* __restrict__ out, const int* stop_flag) {
+    if (stop_flag != nullptr && *stop_flag != 0) return;
+    cl_reduce_partials_block(partials, nparts, P, out, (int)blockIdx.x);
+}
+int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st) {
+    (void)hipGetLastError();   // drop any stale error of an unrelated earlier runtime call
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((P + 31) / 32), dim3(256), 0, st, partials, nparts, P, out, stop_flag);
+    return (int)hipGetLastError();
+}
 int cl_launch_rw_forward(const cl_rw_args& a, hipStream_t st) {
     if (a.tn.R <= 0 || a.tn.S <= 0) return -1;
     (void)hipGetLastError();

@@ -36,15 +36,15 @@
 //     B.  Every wave executes the same barriers in the same order; the first tile needs no seam barrier (the __syncthreads() behind the
 //     weight staging), the last is followed by the flush's.  Every other instance keeps barrier A at the top of the layer step and the
 //     seam barrier in front of the backward pass (the 16-wide ones as wave-local ordering): the early form costs them spilled registers.
-// The file is compiled eight times (build.py): plain; packed layout + per-image layers (-DCL_IMGL=1, NeuralImageScaler); packed layout only
+// The file is compiled seven times (build.py): plain; packed layout + per-image layers (-DCL_IMGL=1, NeuralImageScaler); packed layout only
 // (-DCL_IMGL=2, single-pass Laue: harmonic group sums as lane reductions in the epilogue); layer-block chains (-DCL_CHAIN=1, scalers deeper
 // than one launch holds); and the plain, packed and chain forms once more with the epilogue's atomics turned into stores (-DCL_DET=1, the
-// deterministic mode of include/careless_hip.h: dzf_obs / dimg_obs / nll_part).
+// deterministic mode of include/careless_hip.h: dzf_obs / dimg_obs / nll_part).  Each compilation is one cl_route and ends in its
+// cl_mlp_unit<route>; which route a launch takes, its argument checks and the A/B switches are mlp_launch.hip's.
 // Roofline: fp32 MFMA (157.3 TFLOP/s); algorithmic flops per observation 6 (d w + (L-1) w^2 + 2 w).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdio>
-#include <cstdlib>
 #include "cl_math.h"
 #include "cl_kernels.h"
 
@@ -59,6 +59,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef CL_DET
 #define CL_DET 0             // 1: the deterministic compilation (build.py: elbo_mlp_det) -- the epilogue's float atomics (dz_f, image scales) and
 #endif                       // the NLL's fp64 atomic become per-observation / per-workgroup STORES that cl_det_reduce sums in a fixed order
+#ifndef CL_IMGL
+#define CL_IMGL 0            // 1: packed layout + per-image layers, 2: packed layout only
+#endif
+#ifndef CL_CHAIN
+#define CL_CHAIN 0           // 1: a block of a layer-block chain
+#endif
+#define CL_PLAIN_UNIT (!CL_IMGL && !CL_CHAIN && !CL_DET)      // the one unit that compiles the plain-epilogue 64-wide instances
 #define CL_TILE CL_MLP_TILE
 #define CL_NW 8              // waves per workgroup
 #define CL_WOBS 16           // observations per wave in forward / dgrad
@@ -154,7 +161,7 @@ struct AccPlan {
 // they would be the same symbols as the plain unit's and the linker would keep one of the two)
 // EPI: the sampling epilogue (enum cl_epilogue).  CL_EPI_GENERIC decides per MC sample what is uniform for the whole launch (likelihood
 //     kind, Evans-2011 model, injected noise or Philox, noise_row, ipred_out, any S); the two plain values compile the common launch --
-//     in-kernel noise keyed by the row, none of the optional buffers, S <= 8 (epi_plain, below), the likelihood kind a constant -- as
+//     in-kernel noise keyed by the row, none of the optional buffers, S <= 8 (epi_plain, cl_kernels.h), the likelihood kind a constant -- as
 //     straight-line code for the lane's two samples.  64-wide full-step instances of the plain unit only.
 //     CL_EPI_GENERIC_LAPLACE (internal, not a value of the public enum): the generic epilogue with the Laplace likelihood compiled in
 //     (no Evans-2011 terms) -- an instance of its own, so that the instances Normal and Student-T launches run are what they were.
@@ -1305,29 +1312,20 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// sum of the per-workgroup partials in a fixed order -> MLP slice of the flat gradient buffer
+// This unit's launch path, host code: cl_mlp_unit<route> -> launch_mode (the instance, by mlp_geom) -> launch_dp -> launch_one, the leaf
 // ---------------------------------------------------------------------------------------------------------
-// (the work of a workgroup is cl_reduce_partials_block, cl_kernels.h: shared with the step's cl_tn_backward launch, which can carry it)
-#if !CL_IMGL && !CL_CHAIN && !CL_DET
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partials, int nparts, int P,
-                                                               float* __restrict__ out, const int* stop_flag) {
-    if (stop_flag != nullptr && *stop_flag != 0) return;
-    cl_reduce_partials_block(partials, nparts, P, out, (int)blockIdx.x);
-}
-#endif
+// The route this compilation serves (mlp_dispatch calls each unit by it), and the suffix its instances carry in their name
+constexpr cl_route UNIT_ROUTE = CL_DET ? (CL_IMGL == 2 ? CL_ROUTE_MLP_PACKED_DET : (CL_CHAIN ? CL_ROUTE_MLP_CHAIN_DET : CL_ROUTE_MLP_DET))
+                                       : (CL_CHAIN ? CL_ROUTE_MLP_CHAIN : (CL_IMGL == 2 ? CL_ROUTE_MLP_PACKED : (CL_IMGL ? CL_ROUTE_MLP_IMGL : CL_ROUTE_MLP)));
+constexpr const char* UNIT_SUFFIX[] = {"", ", packed", ", image layers", ", chain", ", deterministic", ", packed deterministic", ", chain deterministic"};
+static_assert(CL_ROUTE_MLP_CHAIN_DET - CL_ROUTE_MLP == 6, "UNIT_SUFFIX: one entry per route of this file, in cl_route's order");
 
-// ---------------------------------------------------------------------------------------------------------
-// host-side dispatch
-// ---------------------------------------------------------------------------------------------------------
-#ifndef CL_IMGL
-#define CL_IMGL 0            // the file is compiled three times: plain (-DCL_IMGL=0 -DCL_CHAIN=0), packed layouts / per-image layers
-#endif                       // (-DCL_IMGL=1) and layer-block chains (-DCL_CHAIN=1)
-#ifndef CL_CHAIN
-#define CL_CHAIN 0
-#endif
-
+// The leaf: with a name sink it prints this instance's template parameters and the unit (EPI and the Laplace instance stay out of the
+// name), without one it launches.
 template <int WP, int DP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC>
-static int launch_one(const cl_mlp_args& a, int grid, hipStream_t st) {
+static int launch_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
+    if (c.name != nullptr)
+        return snprintf(c.name, c.name_n, "elbo_mlp_kernel<%d, %d, %d, %d%s, KS=%d>", WP, DP, LMAX, MODE, UNIT_SUFFIX[UNIT_ROUTE - CL_ROUTE_MLP], KS);
     using SL = SmemLayout<WP, DP, LMAX>;
     const size_t sm_tiles = (size_t)SL::total * sizeof(float);
     const size_t P = (size_t)a.w * a.d + a.w + (size_t)(a.L - 1) * (a.w * a.w + a.w) + 2 * a.w + 2;
@@ -1336,260 +1334,48 @@ static int launch_one(const cl_mlp_args& a, int grid, hipStream_t st) {
     if (MODE != 1 && flush > sm) sm = flush;
     using AP = AccPlan<WP, DP, LMAX, MODE, (CL_IMGL == 1)>;
     if (AP::NACC > 0) sm = (size_t)AP::total * sizeof(float);                                       // + LDS-resident accumulators
-    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0), EPI>>(dim3(grid), dim3(512), sm, st, a);
-}
-
-// Instantiated geometries: the padded width WP fixes how many layers of activations + weight-gradient blocks fit in the
-// 256-register budget of a wave: w <= 15 -> up to 20 layers (the CLI default scaler is 20 x 10), w <= 32 -> 10, w <= 64 -> 5.
-// Per-image layers on more than 32 metadata columns at hidden width <= 15: the 16-wide instance <16, 64, 24, IMGL> (864 - 880 bytes of
-// scratch per lane, the largest of the library) ends in a GPU memory fault when a workgroup walks more than one tile and crosses an
-// image border (found by a random draw late in round 6: scripts/probe/imgl_abort_probe.py, NOTEBOOK R6.4; the forward-only launch
-// is not affected).  Those shapes take the 32-wide instance, which holds up to CL_MLP_LMAX_W32 layers (deeper: the caller's
-// layer-by-layer path, as for any scaler deeper than one launch).
-// One helper for launch_mode and cl_mlp_kernel_name_of; `imgl_unit`: the per-image-layer compilation (CL_IMGL == 1).  WP = 0: no instance holds the shape.
-struct MlpGeom { int WP, DP, LMAX, KS; };
-static inline MlpGeom mlp_geom(const cl_mlp_args& a, int mode, bool imgl_unit) {
-    if (a.L < 1 || a.w < 1 || a.d < 1 || a.w > 64 || a.d > 64) return {0, 0, 0, 0};
-    const int imgl = imgl_unit ? a.n_imgl : 0;
-    const bool imgl_d64 = imgl_unit && mode != 1 && a.n_imgl > 0 && a.d > 32;
-    MlpGeom g{0, a.d <= 8 ? 8 : (a.d <= 32 ? 32 : 64), 0, 4};
-    if (a.w <= 15 && !imgl_d64) {
-        // the narrow instance comes in three step counts (hidden width <= 8, <= 12, <= 15); the forward-only launch keeps all four
-        g.WP = 16, g.LMAX = imgl_unit ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16;
-        if (mode != 1) g.KS = a.w <= 8 ? 2 : (a.w <= 12 ? 3 : 4);
-    } else if (a.w == 16 && !imgl_unit) {
-        g.WP = 16, g.LMAX = CL_MLP_LMAX_W16, g.KS = 5;         // (per-image layers keep the 32-wide instance)
-    } else if (a.w <= 32) {
-        g.WP = 32, g.LMAX = a.L + imgl <= 5 ? 5 : CL_MLP_LMAX_W32;
-    } else {
-        g.WP = 64, g.LMAX = CL_MLP_LMAX_W64;
-    }
-    if (a.L + imgl > g.LMAX) g.WP = 0;
-    return g;
-}
-// The launches the plain epilogue is compiled for (template parameter EPI): a full step that draws its noise in the kernel keyed by the
-// row itself, returns no predictions, has no Evans-2011 error model and at most two MC samples per epilogue lane.  Arguments only: which
-// instances HAVE a plain epilogue (the 64-wide ones of the plain unit) and the A/B switch are mlp_epilogue's.
-static inline cl_epilogue epi_plain(const cl_mlp_args& a, int mode) {
-    if (mode != 0 || a.eta != nullptr || a.noise_row != nullptr || a.ipred_out != nullptr || a.S > 8) return CL_EPI_GENERIC;
-    if (a.ev11 != nullptr || a.d_ev11 != nullptr || a.ev11_part != nullptr) return CL_EPI_GENERIC;
-    if (a.lik_kind == CL_LIK_NORMAL) return CL_EPI_PLAIN_NORMAL;
-    return a.lik_kind == CL_LIK_STUDENTT ? CL_EPI_PLAIN_STUDENTT : CL_EPI_GENERIC;
+    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0), EPI>>(dim3(c.grid), dim3(512), sm, c.st, a);
 }
 
 template <int WP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC>
-static int launch_dp(const cl_mlp_args& a, int dp, int grid, hipStream_t st) {
-    if (dp == 8) return launch_one<WP, 8, LMAX, MODE, KS, EPI>(a, grid, st);
-    if (dp == 32) return launch_one<WP, 32, LMAX, MODE, KS, EPI>(a, grid, st);
-    return launch_one<WP, 64, LMAX, MODE, KS, EPI>(a, grid, st);
+static int launch_dp(const cl_mlp_args& a, int dp, const cl_launch_ctx& c) {
+    if (dp == 8) return launch_one<WP, 8, LMAX, MODE, KS, EPI>(a, c);
+    if (dp == 32) return launch_one<WP, 32, LMAX, MODE, KS, EPI>(a, c);
+    return launch_one<WP, 64, LMAX, MODE, KS, EPI>(a, c);
 }
-
-#define CL_PLAIN_UNIT (!CL_IMGL && !CL_CHAIN && !CL_DET)
-#if CL_PLAIN_UNIT
-// The A/B switches (bisection and measurement runs; unset or anything but "0" = on), read here and nowhere else.  Each keeps shapes off
-// a kernel family, which then go to the next kernel down mlp_route's order:
-//   CARELESS_HIP_LANE=0         every shape off the lane-per-observation kernel (elbo_lane.hip)
-//   CARELESS_HIP_NARROW=0       every shape off elbo_narrow.hip
-//   CARELESS_HIP_LANE_W12=0     widths 11, 12 off the lane kernel (the narrow kernel they ran on until round 6)
-//   CARELESS_HIP_LANE_DEPTHS=0  depths other than the default off the lane kernel (until round 5)
-//   CARELESS_HIP_LANE_BLOCKS=0  the head-less blocks of a chain off the lane kernel (the chain unit of this file)
-// and one keeps launches off an instance of the kernel the route names:
-//   CARELESS_HIP_EPI=0          the 64-wide instances off their plain epilogue (the generic one: every launch until this switch came)
-struct RouteSwitches { bool lane, narrow, w12, depths, blocks, epi; };
-static bool switch_on(const char* name) { const char* e = getenv(name); return !(e != nullptr && e[0] == '0'); }
-static const RouteSwitches& route_switches() {
-    static const RouteSwitches s{switch_on("CARELESS_HIP_LANE"), switch_on("CARELESS_HIP_NARROW"), switch_on("CARELESS_HIP_LANE_W12"),
-                                 switch_on("CARELESS_HIP_LANE_DEPTHS"), switch_on("CARELESS_HIP_LANE_BLOCKS"), switch_on("CARELESS_HIP_EPI")};
-    return s;
-}
-// The epilogue of the instance a launch on route `r` runs (cl_mlp_epilogue; launch_mode picks the instance by it).
-cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r) {
-    if (r != CL_ROUTE_MLP || !route_switches().epi || mlp_geom(a, mode, false).WP != 64) return CL_EPI_GENERIC;
-    return epi_plain(a, mode);
-}
-#endif
-
 
 // GEN: the generic epilogue's instance -- CL_EPI_GENERIC, or, for a full step under the Laplace likelihood, CL_EPI_GENERIC_LAPLACE
 template <int MODE, int GEN = CL_EPI_GENERIC>
-static int launch_mode(const cl_mlp_args& a, int grid, hipStream_t st) {
+static int launch_mode(const cl_mlp_args& a, const cl_launch_ctx& c) {
     const MlpGeom g = mlp_geom(a, MODE, CL_IMGL == 1);
     constexpr int L16 = (CL_IMGL == 1 ? CL_MLP_LMAX_W16_IMGL : CL_MLP_LMAX_W16);
     if (g.WP == 0) return -2;
     if (g.WP == 16) {
-        if (g.KS == 2) return launch_dp<16, L16, MODE, 2, GEN>(a, g.DP, grid, st);
-        if (g.KS == 3) return launch_dp<16, L16, MODE, 3, GEN>(a, g.DP, grid, st);
+        if (g.KS == 2) return launch_dp<16, L16, MODE, 2, GEN>(a, g.DP, c);
+        if (g.KS == 3) return launch_dp<16, L16, MODE, 3, GEN>(a, g.DP, c);
 #if CL_IMGL != 1
-        if (g.KS == 5) return launch_dp<16, CL_MLP_LMAX_W16, MODE, 5, GEN>(a, g.DP, grid, st);
+        if (g.KS == 5) return launch_dp<16, CL_MLP_LMAX_W16, MODE, 5, GEN>(a, g.DP, c);
 #endif
-        return launch_dp<16, L16, MODE, 4, GEN>(a, g.DP, grid, st);
+        return launch_dp<16, L16, MODE, 4, GEN>(a, g.DP, c);
     }
-    if (g.WP == 32) return g.LMAX == 5 ? launch_dp<32, 5, MODE, 4, GEN>(a, g.DP, grid, st) : launch_dp<32, CL_MLP_LMAX_W32, MODE, 4, GEN>(a, g.DP, grid, st);
+    if (g.WP == 32) return g.LMAX == 5 ? launch_dp<32, 5, MODE, 4, GEN>(a, g.DP, c) : launch_dp<32, CL_MLP_LMAX_W32, MODE, 4, GEN>(a, g.DP, c);
 #if CL_PLAIN_UNIT
     if constexpr (MODE == 0 && GEN == CL_EPI_GENERIC) {
         const cl_epilogue e = mlp_epilogue(a, MODE, CL_ROUTE_MLP);
-        if (e == CL_EPI_PLAIN_NORMAL) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_NORMAL>(a, g.DP, grid, st);
-        if (e == CL_EPI_PLAIN_STUDENTT) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_STUDENTT>(a, g.DP, grid, st);
+        if (e == CL_EPI_PLAIN_NORMAL) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_NORMAL>(a, g.DP, c);
+        if (e == CL_EPI_PLAIN_STUDENTT) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_STUDENTT>(a, g.DP, c);
     }
 #endif
-    return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, GEN>(a, g.DP, grid, st);
+    return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, GEN>(a, g.DP, c);
 }
 
-// This compilation's launcher (cl_kernels.h lists the eight; cl_launch_mlp has checked the arguments and clamped the grid)
-#if CL_DET && CL_IMGL == 2
-#define CL_MLP_UNIT cl_launch_mlp_packed_det
-#elif CL_DET && CL_CHAIN
-#define CL_MLP_UNIT cl_launch_mlp_chain_det
-#elif CL_DET
-#define CL_MLP_UNIT cl_launch_mlp_det
-#elif CL_CHAIN
-#define CL_MLP_UNIT cl_launch_mlp_chain
-#elif CL_IMGL == 2
-#define CL_MLP_UNIT cl_launch_mlp_packed
-#elif CL_IMGL
-#define CL_MLP_UNIT cl_launch_mlp_imgl
-#else
-#define CL_MLP_UNIT cl_launch_mlp_plain
-#endif
-int CL_MLP_UNIT(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
+// This compilation's entry point (cl_kernels.h; cl_launch_mlp has checked the arguments and clamped the grid)
+template <>
+int cl_mlp_unit<UNIT_ROUTE>(const cl_mlp_args& a, int mode, const cl_launch_ctx& c) {
     switch (mode) {
-        case 0: return a.lik_kind == CL_LIK_LAPLACE ? launch_mode<0, CL_EPI_GENERIC_LAPLACE>(a, grid, st) : launch_mode<0>(a, grid, st);
-        case 1: return launch_mode<1>(a, grid, st);
-        case 2: return launch_mode<2>(a, grid, st);
+        case 0: return a.lik_kind == CL_LIK_LAPLACE ? launch_mode<0, CL_EPI_GENERIC_LAPLACE>(a, c) : launch_mode<0>(a, c);
+        case 1: return launch_mode<1>(a, c);
+        case 2: return launch_mode<2>(a, c);
     }
     return -1;
 }
-
-#if CL_PLAIN_UNIT
-// Which launcher takes the launch: the one routing decision of the scaler launches (cl_launch_mlp, cl_mlp_kernel_name_of, cl_mlp_route).
-// Shape, optional buffers and mode only: n_pad, the grid and the buffers a route requires are mlp_check's.
-cl_route mlp_route(const cl_mlp_args& a, int mode) {
-    const RouteSwitches& sw = route_switches();
-    const bool lane_depth = sw.depths || a.L == CL_MLP_LMAX_W16;
-    const bool lane = mode == 0 && sw.lane && lane_depth && (sw.w12 || a.w <= CL_LANE_WMAX) && cl_lane_supports(a);
-    const bool narrow = mode == 0 && sw.narrow && cl_narrow_supports(a);
-    const bool lane_imgl = mode == 0 && a.n_imgl > 0 && sw.lane && lane_depth && cl_lane_imgl_supports(a);
-    cl_route r;
-    if (a.dzf_obs != nullptr && (mode == 0 || (a.act_out == nullptr && a.dH_ext == nullptr))) {
-        // deterministic mode: full steps only, with the Evans-2011 gradients in their per-wave slots.  The default scaler's shapes keep their
-        // own kernels (round 4: elbo_lane.hip / elbo_narrow.hip store per observation when dzf_obs is given), per-image layers the lane
-        // kernel's instances only (round 6: one wave per image; the IMGL instances of this file keep their float atomics), every other width
-        // <= 64 runs the deterministic compilations of this file.  (The forward-only and backward-only launches of a layer-block chain have
-        // no float atomics: they take the chain unit.)
-        if (mode != 0 || (a.ev11 != nullptr && a.ev11_part == nullptr)) return CL_ROUTE_NONE;
-        if (a.n_imgl > 0) r = lane_imgl ? CL_ROUTE_LANE_IMGL : CL_ROUTE_NONE;
-        else if (a.dX_out != nullptr) r = (a.row_map != nullptr || a.act_out != nullptr || a.dH_ext != nullptr) ? CL_ROUTE_NONE : CL_ROUTE_MLP_CHAIN_DET;
-        else if (lane) r = CL_ROUTE_LANE;
-        else if (narrow) r = CL_ROUTE_NARROW;
-        else if (a.row_map != nullptr && a.n_imgl == 0) r = CL_ROUTE_MLP_PACKED_DET;            // single-pass Laue, wider than 15
-        else r = (a.row_map != nullptr || a.act_out != nullptr || a.dH_ext != nullptr) ? CL_ROUTE_NONE : CL_ROUTE_MLP_DET;
-    } else if ((a.act_out != nullptr || a.dH_ext != nullptr) && sw.lane && sw.blocks && cl_lane_block_supports(a, mode)) {
-        r = CL_ROUTE_LANE_BLOCK;              // the first block of a chained narrow scaler: the lane kernel's forward-only / external-gradient instances (round 6)
-    } else if (a.act_out != nullptr || a.dH_ext != nullptr || a.dX_out != nullptr) {
-        r = (a.row_map != nullptr || a.n_imgl > 0) ? CL_ROUTE_NONE : CL_ROUTE_MLP_CHAIN;        // (chains use the plain layout)
-    } else if (a.n_imgl > 0) {
-        r = lane_imgl ? CL_ROUTE_LANE_IMGL : CL_ROUTE_MLP_IMGL;       // packed layout + per-image layers: the default scaler's shapes on the lane kernel (round 5)
-    } else if (lane) {
-        r = CL_ROUTE_LANE;                    // the default scaler's shape: lane = observation
-    } else if (narrow) {
-        r = CL_ROUTE_NARROW;                  // hidden width <= 15: one wave per SIMD
-    } else {
-        r = a.row_map != nullptr ? CL_ROUTE_MLP_PACKED : CL_ROUTE_MLP;
-    }
-    // dZ0_out (the launch behind a peeled first layer, elbo_peel.hip) is stored by the default scaler's kernels only: a launch elsewhere
-    // would ignore it and leave the peeled layer a zero gradient without any error
-    if (a.dZ0_out != nullptr && r != CL_ROUTE_LANE && r != CL_ROUTE_NARROW && r != CL_ROUTE_LANE_IMGL) return CL_ROUTE_NONE;
-    if (r >= CL_ROUTE_MLP && mlp_geom(a, mode, r == CL_ROUTE_MLP_IMGL).WP == 0) return CL_ROUTE_NONE;     // wider / deeper than this file's instances
-    return r;
-}
-// Every argument check of a scaler launch, in one place: what cl_launch_mlp tests between the route and the dispatch (and what
-// cl_mlp_check answers without launching).  Precedence: -1 tile / grid, -2 no route, the route's own -1 clauses, the -4 bounds.
-// The kernels address with 32-bit byte offsets: a float array of `elems` elements must stay below 4 GiB (shard further across GPUs otherwise).
-static inline bool over_4gib(unsigned long long elems) { return 4ull * elems >= (1ull << 32); }
-static inline bool meta_over(const cl_mlp_args& a) { return over_4gib((unsigned long long)((a.d + 3) & ~3) * (unsigned long long)a.n_pad); }   // meta_t
-static inline bool refl_over(const cl_mlp_args& a) { return over_4gib((unsigned long long)a.R * (unsigned long long)a.S); }                     // z_f, dz_f
-static inline bool obs_over(const cl_mlp_args& a) { return over_4gib((unsigned long long)a.n_pad * (unsigned long long)a.S); }                  // eta, ipred_out, dzf_obs
-
-int mlp_check(const cl_mlp_args& a, int mode, int grid, cl_route r) {
-    if (a.n_pad % CL_TILE != 0 || a.n_pad <= 0 || grid < 1) return -1;
-    if (r == CL_ROUTE_NONE) return -2;
-    const bool packed = a.row_map != nullptr || r == CL_ROUTE_MLP_IMGL;      // (the route keeps row_map off the plain-layout launchers)
-    // deterministic mode: the routes with per-observation stores (the lane and narrow kernels store when dzf_obs is given)
-    const bool det = r == CL_ROUTE_MLP_DET || r == CL_ROUTE_MLP_PACKED_DET || r == CL_ROUTE_MLP_CHAIN_DET ||
-                     (a.dzf_obs != nullptr && (r == CL_ROUTE_LANE || r == CL_ROUTE_LANE_IMGL || r == CL_ROUTE_NARROW));
-    if (r == CL_ROUTE_MLP_PACKED_DET && a.n_obs != a.n_pad) return -2;      // (this unit's answer to a padded packed layout has always been -2)
-    if (packed) {                                                           // packed layout: no padding rows behind n_obs, group sizes with their tile maxima, full step only
-        if (a.row_map == nullptr || a.n_obs != a.n_pad || a.n_imgl < 0) return -1;
-        if (a.gmeta != nullptr && (a.tile_gmax == nullptr || mode != 0)) return -1;
-    }
-    if (r == CL_ROUTE_MLP_IMGL) {                                           // per-image layers: their weights, the tiles' images, and no image scale beside them
-        if (a.imgl == nullptr || a.tile_img == nullptr || a.n_images < 1 || a.use_img) return -1;
-        if (mode != 1 && a.d_imgl == nullptr) return -1;
-    }
-    if (r == CL_ROUTE_MLP_CHAIN) {                                          // a block's activations leave the forward launch, its gradient enters the backward one
-        if (a.act_out != nullptr && mode != 1) return -1;
-        if (a.dH_ext != nullptr && mode != 2) return -1;
-    }
-    if (det && (a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr))) return -1;      // the store targets
-    if (meta_over(a)) return -4;
-    if (r != CL_ROUTE_LANE_BLOCK && refl_over(a)) return -4;                 // (a head-less block reads no reflection)
-    if ((det || (packed && (a.eta != nullptr || a.ipred_out != nullptr))) && obs_over(a)) return -4;
-    return 0;
-}
-
-// The launcher the route names.  With a name sink in `c` (cl_mlp_kernel_name_of) the lane and narrow paths print their instance.
-static int mlp_dispatch(const cl_mlp_args& a, int mode, cl_route r, const cl_launch_ctx& c) {
-    switch (r) {
-        case CL_ROUTE_NONE: break;
-        case CL_ROUTE_LANE: return cl_launch_lane(a, c);
-        case CL_ROUTE_LANE_IMGL: return cl_launch_lane_imgl(a, c);
-        case CL_ROUTE_LANE_BLOCK: return cl_launch_lane_block(a, mode, c);
-        case CL_ROUTE_NARROW: return cl_launch_narrow(a, c);
-        case CL_ROUTE_MLP: return cl_launch_mlp_plain(a, mode, c.grid, c.st);
-        case CL_ROUTE_MLP_PACKED: return cl_launch_mlp_packed(a, mode, c.grid, c.st);
-        case CL_ROUTE_MLP_IMGL: return cl_launch_mlp_imgl(a, mode, c.grid, c.st);
-        case CL_ROUTE_MLP_CHAIN: return cl_launch_mlp_chain(a, mode, c.grid, c.st);
-        case CL_ROUTE_MLP_DET: return cl_launch_mlp_det(a, mode, c.grid, c.st);
-        case CL_ROUTE_MLP_PACKED_DET: return cl_launch_mlp_packed_det(a, mode, c.grid, c.st);
-        case CL_ROUTE_MLP_CHAIN_DET: return cl_launch_mlp_chain_det(a, mode, c.grid, c.st);
-    }
-    return -2;
-}
-
-int cl_launch_mlp(const cl_mlp_args& a, int mode, int grid, hipStream_t st) {
-    const cl_route r = mlp_route(a, mode);
-    if (int e = mlp_check(a, mode, grid, r)) return e;
-    if (grid > a.n_pad / CL_TILE) grid = a.n_pad / CL_TILE;
-    return mlp_dispatch(a, mode, r, {grid, st});
-}
-
-// Name of the kernel instance cl_launch_mlp(a, mode, ...) runs (bench.py and the profiling scripts label their rows with it instead of
-// guessing): for shapes, not for valid buffers -- the same dispatch without mlp_check.  The lane and narrow paths print the name at the
-// leaf that picks the instance; this file's instances share mlp_geom between launch and name.  Returns the length written (snprintf semantics).
-int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n) {
-    const cl_route r = mlp_route(a, mode);
-    const char* unit = "";
-    switch (r) {
-        case CL_ROUTE_NONE: return snprintf(out, n, "(unsupported)");
-        case CL_ROUTE_LANE:
-        case CL_ROUTE_LANE_IMGL:
-        case CL_ROUTE_LANE_BLOCK:
-        case CL_ROUTE_NARROW: return mlp_dispatch(a, mode, r, {0, nullptr, out, n});
-        case CL_ROUTE_MLP_CHAIN: unit = ", chain"; break;
-        case CL_ROUTE_MLP: break;
-        case CL_ROUTE_MLP_PACKED: unit = ", packed"; break;
-        case CL_ROUTE_MLP_IMGL: unit = ", image layers"; break;
-        case CL_ROUTE_MLP_DET: unit = ", deterministic"; break;
-        case CL_ROUTE_MLP_PACKED_DET: unit = ", packed deterministic"; break;
-        case CL_ROUTE_MLP_CHAIN_DET: unit = ", chain deterministic"; break;
-    }
-    const MlpGeom g = mlp_geom(a, mode, r == CL_ROUTE_MLP_IMGL);
-    return snprintf(out, n, "elbo_mlp_kernel<%d, %d, %d, %d%s, KS=%d>", g.WP, g.DP, g.LMAX, mode, unit, g.KS);
-}
-
-int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st) {
-    (void)hipGetLastError();   // drop any stale error of an unrelated earlier runtime call
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((P + 31) / 32), dim3(256), 0, st, partials, nparts, P, out, stop_flag);
-    return (int)hipGetLastError();
-}
-#endif

@@ -301,7 +301,7 @@ int cl_elbo_mono_fwd_bwd(const cl_mlp_args* args, int grid, void* stream);
 int cl_mlp_forward(const cl_mlp_args* args, int grid, void* stream);
 int cl_mlp_backward_ext(const cl_mlp_args* args, int grid, void* stream);
 /* Which launcher the three calls above hand these arguments to (mode 0 = cl_elbo_mono_fwd_bwd, 1 = cl_mlp_forward,
- * 2 = cl_mlp_backward_ext): the library's one routing decision.  It depends on the shape, the optional buffers set and the mode
+ * 2 = cl_mlp_backward_ext): the library's one routing decision (csrc/mlp_launch.hip).  It depends on the shape, the optional buffers set and the mode
  * only (pointer fields count as set / NULL, n_pad and the grid are not looked at), and on the A/B switches CARELESS_HIP_LANE,
  * _NARROW, _LANE_W12, _LANE_DEPTHS and _LANE_BLOCKS (CARELESS_HIP_EPI picks an instance, not a route: cl_mlp_epilogue).  CL_ROUTE_NONE: no kernel takes the launch -- the call returns -2.
  * Returns < 0 for bad arguments.  Needs no device. */

@@ -162,7 +162,7 @@ UNIT_MODES = {"plain": (0, 1, 2), "chain": (0, 1, 2), "packed": (0, 1, 2), "det"
 
 def enumerate_instances():
     """Every instance of elbo_mlp.hip outside the per-image-layer unit that direct arguments reach, from the rules of mlp_geom / mlp_route
-    (csrc/elbo_mlp.hip) restated: {instance name: (unit, mode, WP, DP, LMAX, KS, variant)}.
+    (csrc/cl_kernels.h, csrc/mlp_launch.hip) restated: {instance name: (unit, mode, WP, DP, LMAX, KS, variant)}.
       * seven width forms; the forward-only launch keeps all four k-steps at width <= 15 (KS = 4 for every such width);
       * three metadata capacities; three modes on the plain, chain and packed units, full steps only on the deterministic ones;
       * a full step has a Laplace instance beside the generic one; the 64-wide full step of the plain unit also the two plain epilogues;
@@ -320,7 +320,7 @@ def stop_cases():
 
 
 def expected_instance(c):
-    """the instance a case of this file's units must run, from the rules of mlp_geom / epi_plain (csrc/elbo_mlp.hip) restated: what every launch
+    """the instance a case of this file's units must run, from the rules of mlp_geom / epi_plain (csrc/cl_kernels.h) restated: what every launch
     of the GPU tests and every case of the list is compared with (the library's answer is the other side)"""
     DP = 8 if c.d <= 8 else (32 if c.d <= 32 else 64)
     if c.w <= 15:

@@ -402,9 +402,35 @@ def test_lane_instance_table_matches_the_record():
     assert blocks > 0
 
 
+def test_mlp_instance_table_matches_the_record():
+    """What the scaler launch layer (csrc/mlp_launch.hip) and the units of csrc/elbo_mlp.hip under it answer, as data: `scripts/mlp_table.py`
+    walks widths 8 .. 65, columns 8 .. 65 and depths 1 .. 25 on both sides of every threshold `mlp_geom`, `epi_plain` and `mlp_route`
+    test, in every layout, with the options that pick another route, instance or epilogue, and the forward-only / external-gradient
+    launches (29 160 launch descriptions), and asks the library for route, epilogue, return code (`cl_mlp_check`, grid 2) and name.
+    tests/golden/mlp_instances.json is that record taken on the library BEFORE the layer moved out of the kernel file and the names of
+    the seven units moved to the leaf that launches: every entry equals it.  The record reaches every route of elbo_mlp.hip and both plain
+    epilogues.  Host only."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("mlp_table", os.path.join(ROOT, "scripts", "mlp_table.py"))
+    mlp_table = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mlp_table)
+    assert not [k for k in os.environ if k.startswith(mlp_table.SWITCHES)]
+    with open(os.path.join(ROOT, "tests", "golden", "mlp_instances.json")) as f:
+        want = mlp_table.decode(json.load(f))
+    got = mlp_table.table(_lib.get_lib())
+    assert len(got) == len(want) == mlp_table.ENTRIES == 29160
+    differ = [(mode, kw, g, w_) for (mode, kw), g, w_ in zip(mlp_table.walk(), got, want) if g != w_]
+    assert not differ, (len(differ), differ[:5])
+    assert {r for r, _, _, _ in want} >= set(range(_lib.CL_ROUTE_MLP, _lib.CL_ROUTE_MLP_CHAIN_DET + 1))
+    assert {e for _, e, _, _ in want} >= {_lib.CL_EPI_PLAIN_NORMAL, _lib.CL_EPI_PLAIN_STUDENTT}
+    for route, _, _, name in want:          # (the name's family follows the route: a unit of elbo_mlp.hip prints elbo_mlp_kernel<...>)
+        assert name.startswith("elbo_mlp_kernel<") == (route >= _lib.CL_ROUTE_MLP), (route, name)
+
+
 def test_one_argument_check_answers_for_every_route():
     """`cl_mlp_check`: the return code a scaler launch would give, without the launch -- the entry checks of the call, the route, and
-    `mlp_check`, the one table of argument checks every route shares (csrc/elbo_mlp.hip).  For each of the twelve routes an accepted
+    `mlp_check`, the one table of argument checks every route shares (csrc/mlp_launch.hip).  For each of the twelve routes an accepted
     launch and a rejected one per clause that applies to it, with the exact code; precedence: -1 tile / grid, -2 no route, the route's
     -1 clauses, the -4 bounds.  Pointer fields are only tested against NULL and nothing is launched: holds with or without a GPU."""
     import ctypes as C
