@@ -180,10 +180,15 @@ class AdamArgs(C.Structure):
     ]
 
 
+# every argument struct of include/careless_hip.h and its mirror: get_lib() compares the sizes with the library's (cl_abi_sizeof),
+# tests/test_abi_layout.py every field's offset and size with the header's
+ABI_STRUCTS = {"cl_tn_args": TnArgs, "cl_mlp_args": MlpArgs, "cl_adam_args": AdamArgs, "cl_laue_args": LaueArgs, "cl_det_args": DetArgs,
+               "cl_frozen_args": FrozenArgs, "cl_refprior_args": RefPriorArgs, "cl_rw_args": RwArgs, "cl_nlik_args": NlikArgs}
+
 EXPORTS = {
     # name: (restype, argtypes)
     "cl_version": (C.c_char_p, []),
-    "cl_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
+    "cl_abi_sizeof": (C.c_size_t, [C.c_char_p]),
     "cl_mlp_default_grid": (C.c_int, []),
     "cl_mlp_param_count": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "cl_mlp_meta_rows": (C.c_int, [C.c_int]),
@@ -232,12 +237,9 @@ EXPORTS = {
     "cl_frozen_rows": (C.c_int, [C.POINTER(FrozenArgs), _vp]),
     "cl_frozen_edge_floats": (C.c_int, [C.c_longlong, C.c_int]),
     "cl_frozen_grid": (C.c_int, [C.c_longlong]),
-    "cl_frozen_args_size": (C.c_size_t, []),
     "cl_ref_prior": (C.c_int, [C.POINTER(RefPriorArgs), _vp]),
-    "cl_refprior_args_size": (C.c_size_t, []),
     "cl_rw_forward": (C.c_int, [C.POINTER(RwArgs), _vp]),
     "cl_rw_backward": (C.c_int, [C.POINTER(RwArgs), _vp]),
-    "cl_rw_args_size": (C.c_size_t, []),
     "cl_rw_moments": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp]),
     "cl_nlik_forward": (C.c_int, [C.POINTER(NlikArgs), _vp]),
     "cl_nlik_backward": (C.c_int, [C.POINTER(NlikArgs), _vp]),
@@ -245,7 +247,6 @@ EXPORTS = {
     "cl_nlik_param_count": (C.c_size_t, [C.c_int, C.c_int]),
     "cl_nlik_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
     "cl_nlik_grid": (C.c_int, [C.c_longlong]),
-    "cl_nlik_args_size": (C.c_size_t, []),
     "cl_reduce_partials": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "cl_grad_sqnorm": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cl_adam_step": (C.c_int, [C.POINTER(AdamArgs), _vp]),
@@ -296,19 +297,11 @@ def get_lib() -> C.CDLL:
             raise CarelessHipError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = res
         fn.argtypes = args
-    sizes = (C.c_size_t * 5)()
-    lib.cl_abi_sizes(sizes)
-    mine = (C.sizeof(TnArgs), C.sizeof(MlpArgs), C.sizeof(AdamArgs), C.sizeof(LaueArgs), C.sizeof(DetArgs))
-    if tuple(sizes) != mine:
-        raise CarelessHipError(f"ABI mismatch between careless_amd/_lib.py {mine} and the library {tuple(sizes)}")
-    if int(lib.cl_frozen_args_size()) != C.sizeof(FrozenArgs):
-        raise CarelessHipError(f"ABI mismatch: cl_frozen_args is {int(lib.cl_frozen_args_size())} bytes in the library, {C.sizeof(FrozenArgs)} in careless_amd/_lib.py")
-    if int(lib.cl_refprior_args_size()) != C.sizeof(RefPriorArgs):
-        raise CarelessHipError(f"ABI mismatch: cl_refprior_args is {int(lib.cl_refprior_args_size())} bytes in the library, {C.sizeof(RefPriorArgs)} in careless_amd/_lib.py")
-    if int(lib.cl_rw_args_size()) != C.sizeof(RwArgs):
-        raise CarelessHipError(f"ABI mismatch: cl_rw_args is {int(lib.cl_rw_args_size())} bytes in the library, {C.sizeof(RwArgs)} in careless_amd/_lib.py")
-    if int(lib.cl_nlik_args_size()) != C.sizeof(NlikArgs):
-        raise CarelessHipError(f"ABI mismatch: cl_nlik_args is {int(lib.cl_nlik_args_size())} bytes in the library, {C.sizeof(NlikArgs)} in careless_amd/_lib.py")
+    for name, mirror in ABI_STRUCTS.items():
+        theirs = int(lib.cl_abi_sizeof(name.encode()))
+        if theirs != C.sizeof(mirror):
+            raise CarelessHipError(f"ABI mismatch: {name} is {theirs} bytes in the library, {C.sizeof(mirror)} in careless_amd/_lib.py "
+                                   f"({mirror.__name__}); 0: the library does not know the struct -- rebuild it")
     _lib = lib
     return lib
 

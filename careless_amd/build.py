@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libcareless_hip.so")
 # every one of them, without it emits the one v_max_f32 -- an instruction it KNOWS, so that its hazard recognizer pads the two wait
 # states gfx950 wants in front of an MFMA that reads the result (until round 6 the bare instruction was inline assembly, which it does
 # not see: NOTEBOOK R6.1).  The units must still CARRY a NaN from a poisoned observation to the gradient entries it touches (the non-finite
-# stop is taken on the gradient norm, in elbo_elem.hip): tests/test_nonfinite.py holds every route to the oracle's non-finite mask.
+# stop is taken on the gradient norm, in elbo_step.hip): tests/test_nonfinite.py holds every route to the oracle's non-finite mask.
 NNAN = ["-fno-honor-nans"]
 # The lane kernel's 4x4x1 MFMA results feed vector code: kept in architectural registers, no accumulator-register detour.  Internal LLVM
 # option (validated on ROCm 7.2.0 / AMD clang 22); probed before use
@@ -43,7 +43,9 @@ UNITS = [("cl_api.hip", "cl_api", []), ("mlp_launch.hip", "mlp_launch", []),
          ("elbo_mlp.hip", "elbo_mlp_chain_det", ["-DCL_CHAIN=1", "-DCL_DET=1"] + NNAN),    # ... for the last block of a layer-block chain
          ("elbo_narrow.hip", "elbo_narrow", ["-fno-slp-vectorize"] + NNAN),     # (packed fp32 math costs more than it saves beside MFMAs)
          *LANE_UNITS,
-         ("elbo_elem.hip", "elbo_elem", []), ("elbo_laue.hip", "elbo_laue", []), ("wide_gemm.hip", "wide_gemm", []),
+         # the small kernels of the step, one unit per role (NaNs honoured): posterior and priors, optimizer half, deterministic sums, output step
+         ("elbo_q.hip", "elbo_q", []), ("elbo_step.hip", "elbo_step", []), ("elbo_det.hip", "elbo_det", []), ("elbo_output.hip", "elbo_output", []),
+         ("elbo_laue.hip", "elbo_laue", []), ("wide_gemm.hip", "wide_gemm", []),
          ("elbo_peel.hip", "elbo_peel", []), ("elbo_frozen.hip", "elbo_frozen", []),
          ("elbo_nlik.hip", "elbo_nlik", []),        # the neural likelihood's network: NaNs honoured, so that a poisoned row reaches every sigpred
 

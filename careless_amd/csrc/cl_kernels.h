@@ -1,5 +1,6 @@
-// Internal launch interface between the C-ABI layer (cl_api.hip) and the kernels (the argument structs are the public ones of
-// include/careless_hip.h), the one launch helper of the kernels with dynamic LDS, and the device helpers the kernel files share.
+// What crosses compilation units below the C ABI (the argument structs are the public ones of include/careless_hip.h; every kernel file
+// owns its extern "C" entry points: argument check, then launch), the one launch helper of the library, and the device helpers the
+// kernel files share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,7 +30,6 @@ int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n); 
 // forward-only and backward-only launches have no atomics and keep the chain unit).  One entry point, specialised in the unit of the route.
 template <cl_route R>
 int cl_mlp_unit(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
-int cl_launch_det_reduce(const cl_det_args& a, hipStream_t st);                     // elbo_elem.hip: fixed-order sums of the deterministic mode
 // The *_supports functions describe the shapes a kernel family holds; the A/B switches that keep shapes off a family are read by mlp_route only.
 int cl_narrow_supports(const cl_mlp_args& a);                                       // elbo_narrow.hip: width <= 15, metadata <= 15, plain layout
 int cl_launch_narrow(const cl_mlp_args& a, const cl_launch_ctx& c);                 // ... the full ELBO step on that kernel
@@ -42,33 +42,8 @@ int cl_launch_lane_imgl(const cl_mlp_args& a, const cl_launch_ctx& c);
 int cl_lane_block_supports(const cl_mlp_args& a, int mode);                          // ... a head-less layer block's forward / backward launch
 int cl_launch_lane_block(const cl_mlp_args& a, int mode, const cl_launch_ctx& c);
 int cl_launch_lane(const cl_mlp_args& a, const cl_launch_ctx& c);                   // ... the full ELBO step on that kernel
+// elbo_step.hip: out[i] += the nparts partial rows of element i in index order (cl_reduce_partials; elbo_peel.hip and elbo_nlik.hip end in it)
 int cl_launch_reduce_partials(const float* partials, int nparts, int P, float* out, const int* stop_flag, hipStream_t st);
-int cl_launch_tn_forward(const cl_tn_args& a, hipStream_t st);
-int cl_launch_tn_backward(const cl_tn_args& a, hipStream_t st);
-int cl_launch_rw_forward(const cl_rw_args& a, hipStream_t st);             // elbo_elem.hip: the Rice-Woolfson posterior's instances of the two
-int cl_launch_rw_backward(const cl_rw_args& a, hipStream_t st);
-int cl_launch_rw_moments(const float* a, const float* b, const unsigned char* centric, int R, float eps, float* mean, float* sd, double* m4,
-                         hipStream_t st);
-int cl_launch_dw_forward(const cl_tn_args& a, hipStream_t st);
-int cl_launch_ref_prior(const cl_refprior_args& a, hipStream_t st);        // elbo_elem.hip: empirical reference priors
-int cl_launch_grad_sqnorm(const float* g, int n, const int* seg_off, int nseg, double* seg_sq, double* scalars,
-                          const unsigned char* frozen, const int* stop_flag, hipStream_t st);
-int cl_launch_adam(const cl_adam_args& a, hipStream_t st);
-int cl_launch_owner_qnorm(const float* g, int R, int r_begin, int r_end, float* out, double* scratch, const int* stop_flag, hipStream_t st);
-int cl_launch_finalize(double* scalars, float klw, double* history, int step_index, int hist_stride, int* stop_flag,
-                       const double* norm_part, int n_norm_part, hipStream_t st);
-int cl_adam_grid_of(const cl_adam_args& a);
-int cl_launch_predict_moments(const float* smean, const float* sstd, const int* refl_id, long long n, const float* fmean, const float* fstd,
-                              const double* fm4, int R, double* iexp, double* ivar, hipStream_t st);      // elbo_elem.hip: output step, per observation
-int cl_launch_tn_moments(const float* a, const float* b, const float* low, int R, double high, double high4, float eps, float* mean, float* sd,
-                         double* m4, hipStream_t st);                                // elbo_elem.hip: moments of q for the output step
-int cl_launch_noise(unsigned long long seed, unsigned step, int S, long long n, long long offset, int kind, float* out,
-                    hipStream_t st);
-int cl_launch_laue_predict(const cl_laue_args& a, hipStream_t st);
-int cl_launch_laue_likelihood(const cl_laue_args& a, hipStream_t st);
-int cl_launch_laue_backward(const cl_laue_args& a, hipStream_t st);
-int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st);
-int cl_launch_frozen_rows(const cl_frozen_args& a, hipStream_t st);      // elbo_frozen.hip (round 6)
 
 // The likelihood of a launch, checked by every entry that evaluates one.  -1: a kind nobody compiles (it would run as Student-T), or
 // Laplace beside an Evans-2011 buffer (cl_lik_ev11 has no Laplace form: the reference has no such class).  -2: Laplace at an entry whose
@@ -125,7 +100,9 @@ static inline cl_epilogue epi_plain(const cl_mlp_args& a, int mode) {
 template <class... P>
 static inline bool any_null(const P*... p) { return ((p == nullptr) || ...); }
 
-// Launch of a kernel instance with `sm` bytes of dynamic LDS: -3 above the 160 KB of a gfx950 workgroup, else 0 or the hipError_t.
+// THE launch of the library -- no other file holds a launch statement or reads the runtime's last error.  A kernel instance with `sm`
+// bytes of dynamic LDS: -3 above the 160 KB of a gfx950 workgroup, else 0 or the hipError_t.  A call that issues several launches
+// returns the first non-zero code and issues nothing behind it.
 // The kernel is a template ARGUMENT, so the mark below -- the largest dynamic-LDS size the instance has been configured for -- is one
 // per instance: the lane, narrow and 16/32/64-wide kernels share one function-pointer type, and a mark keyed by type would publish
 // one instance's size for another.  One process drives one device; host threads may race here: setting the attribute twice is
@@ -143,6 +120,11 @@ static inline int cl_launch_lds(dim3 grid, dim3 block, size_t sm, hipStream_t st
     (void)hipGetLastError();   // drop any stale error of an unrelated earlier runtime call
     hipLaunchKernelGGL(Kern, grid, block, sm, st, args...);
     return (int)hipGetLastError();
+}
+// ... of a kernel without dynamic LDS
+template <auto Kern, class... A>
+static inline int cl_launch(dim3 grid, dim3 block, hipStream_t st, const A&... args) {
+    return cl_launch_lds<Kern>(grid, block, 0, st, args...);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -227,6 +209,20 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// block-wide double sum -> one atomic per block
+__device__ __forceinline__ void block_atomic_add_d(double v, double* dst) {
+    __shared__ double sh[16];
+    v = wave_sum_d(v);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) sh[wv] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += sh[i];
+        atomicAdd(dst, s);
+    }
+}
+
 // The kernel arguments, re-read from the kernarg segment behind an opaque pointer.  hipcc loads every field of a by-value argument
 // struct at kernel entry and keeps it in SGPRs for the whole kernel (more than the ~100 there are: it then parks them in VGPR lanes
 // and pays v_readlane / v_writelane in the per-tile code); fields that only one phase of a tile uses are loaded there instead, by
@@ -269,7 +265,7 @@ __device__ __forceinline__ float cl_wave_sum(float v) {
 // out[i] += sum over the `nparts` per-workgroup partials of element i, in index order (deterministic): the work of ONE 256-thread
 // workgroup -- 32 consecutive elements x 8 chunks of the partial list; a thread sums its chunk (coalesced 128-B rows, eight rows in
 // flight: a one-at-a-time loop is a chain of dependent HBM / MALL latencies), the 8 chunk sums are combined through LDS in chunk order.
-// Shared by reduce_partials_kernel and the extra workgroups of tn_backward_kernel (both elbo_elem.hip).
+// Shared by reduce_partials_kernel (elbo_step.hip) and the extra workgroups of the posterior backward kernels (elbo_q_kernels.h).
 __device__ __forceinline__ void cl_reduce_partials_block(const float* __restrict__ partials, int nparts, int P, float* __restrict__ out, int block) {
     __shared__ float sh[8][33];
     const int e = threadIdx.x & 31, c = threadIdx.x >> 5;

@@ -225,33 +225,34 @@ int frozen_check(const cl_frozen_args& a, frozen_form f) {
 // (the size of nll_part / ev11_part).  The kernel is a template ARGUMENT, so the cache of its resident grid is one per instance (as
 // cl_launch_lds' mark: cl_kernels.h).  One process drives one device: the cache is filled for the device current at the first call.
 template <auto Kern>
-void frozen_launch(const cl_frozen_args& a, hipStream_t st) {
+int frozen_launch(const cl_frozen_args& a, hipStream_t st) {
     static std::atomic<int> resident{0};
     int g = resident.load(std::memory_order_relaxed), dev = 0, cus = 0, per = 0;
     if (g == 0 && hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, Kern, FB, 0) == hipSuccess && per >= 1 && cus >= 1)
         resident.store(g = per * cus, std::memory_order_relaxed);
     const int cap = cl_frozen_grid(a.n);
-    hipLaunchKernelGGL(Kern, dim3((unsigned)(g > 0 && g < cap ? g : cap)), dim3(FB), 0, st, a);
+    return cl_launch<Kern>(dim3((unsigned)(g > 0 && g < cap ? g : cap)), dim3(FB), st, a);
 }
 
 }  // namespace
 
-int cl_launch_frozen_rows(const cl_frozen_args& a, hipStream_t st) {
+extern "C" int cl_frozen_rows(const cl_frozen_args* ap, void* stream) {
+    if (ap == nullptr) return -1;
+    const cl_frozen_args& a = *ap;
     const frozen_form f = frozen_form_of(a);
     if (int e = frozen_check(a, f)) return e;
-    (void)hipGetLastError();
+    hipStream_t st = (hipStream_t)stream;
     // S = 1 (--mc-samples 1, the default) has its own instances; Laplace is an instance, Normal / Student-T a run-time kind (cl_math.h);
     // SUMS evaluates no likelihood and runs the run-time-kind instance whatever lik_kind says
     const bool one = a.S == 1, lap = a.lik_kind == CL_LIK_LAPLACE_ && f != frozen_form::SUMS;
     if (f == frozen_form::GROUPS) {
-        if (lap) one ? frozen_launch<frozen_laue_laplace_kernel<1>>(a, st) : frozen_launch<frozen_laue_laplace_kernel<8>>(a, st);
-        else one ? frozen_launch<frozen_laue_kernel<1>>(a, st) : frozen_launch<frozen_laue_kernel<8>>(a, st);
-        return (int)hipGetLastError();
+        if (lap) return one ? frozen_launch<frozen_laue_laplace_kernel<1>>(a, st) : frozen_launch<frozen_laue_laplace_kernel<8>>(a, st);
+        return one ? frozen_launch<frozen_laue_kernel<1>>(a, st) : frozen_launch<frozen_laue_kernel<8>>(a, st);
     }
-    if (lap) one ? frozen_launch<frozen_rows_laplace_kernel<1>>(a, st) : frozen_launch<frozen_rows_laplace_kernel<8>>(a, st);
-    else one ? frozen_launch<frozen_rows_kernel<1>>(a, st) : frozen_launch<frozen_rows_kernel<8>>(a, st);
+    const int e = lap ? (one ? frozen_launch<frozen_rows_laplace_kernel<1>>(a, st) : frozen_launch<frozen_rows_laplace_kernel<8>>(a, st))
+                      : (one ? frozen_launch<frozen_rows_kernel<1>>(a, st) : frozen_launch<frozen_rows_kernel<8>>(a, st));
+    if (e) return e;
     const long long t = ((a.n + 63) / 64) * a.S;
-    hipLaunchKernelGGL(frozen_edges_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    return cl_launch<frozen_edges_kernel>(dim3((unsigned)((t + 255) / 256)), dim3(256), st, a);
 }

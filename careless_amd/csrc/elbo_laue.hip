@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void laue_likelihood_laplace_kernel(const cl_l
 // consecutive floats of dz_f (one request) -- with a thread per row and a loop over the samples every instruction sent 64 lanes to 64
 // different lines, the pattern the memory side serialises (0.52 ms per step at 2 M rows x 4 samples; csrc/elbo_lane.hip has the same
 // story).  The row's sums over its samples (dL/dloc, dL/dsigma, image-scale gradient) are segmented lane reductions; the first lane
-// of a row's segment inside a wave adds them into dO (zeroed by the caller side of this launch: see cl_launch_laue_backward).
+// of a row's segment inside a wave adds them into dO (zeroed by the caller side of this launch: see cl_laue_backward).
 __global__ __launch_bounds__(256) void laue_backward_kernel(const cl_laue_args A) {
     if (A.stop_flag != nullptr && *A.stop_flag != 0) return;
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -299,26 +299,35 @@ static int laue_check(const cl_laue_args& a) {
     return 0;
 }
 
-int cl_launch_laue_predict(const cl_laue_args& a, hipStream_t st) {
-    if (int e = laue_check(a)) return e;
-    const long long n = (long long)a.n_obs * a.S;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(laue_predict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+// workgroups of a thread-per-(row, sample) launch, and of the grid-stride launches that end in one NLL atomic per workgroup
+static dim3 laue_grid(const cl_laue_args& a, bool bounded) {
+    long long blocks = ((long long)a.n_obs * a.S + 255) / 256;
+    if (bounded && blocks > CL_LAUE_LIK_MAX_BLOCKS) blocks = CL_LAUE_LIK_MAX_BLOCKS;
+    return dim3((unsigned)blocks);
 }
-int cl_launch_laue_likelihood(const cl_laue_args& a, hipStream_t st) {
+
+extern "C" {
+
+int cl_laue_predict(const cl_laue_args* ap, void* stream) {
+    if (ap == nullptr) return -1;
+    const cl_laue_args& a = *ap;
+    if (int e = laue_check(a)) return e;
+    return cl_launch<laue_predict_kernel>(laue_grid(a, false), dim3(256), (hipStream_t)stream, a);
+}
+
+int cl_laue_likelihood(const cl_laue_args* ap, void* stream) {
+    if (ap == nullptr) return -1;
+    const cl_laue_args& a = *ap;
     // needs the slot arrays only (it is also called on the padded slots alone by the single-pass path)
     if (a.n_obs <= 0 || a.S <= 0 || a.iconv == nullptr || a.iobs == nullptr || a.sig == nullptr || a.scalars == nullptr) return -1;
     if (int e = cl_lik_check(a.lik_kind, a.ev11, a.d_ev11, a.ev11_part, true)) return e;
-    const long long n = (long long)a.n_obs * a.S;
-    (void)hipGetLastError();
-    long long blocks = (n + 255) / 256;
-    if (blocks > CL_LAUE_LIK_MAX_BLOCKS) blocks = CL_LAUE_LIK_MAX_BLOCKS;
-    if (a.lik_kind == CL_LIK_LAPLACE_) hipLaunchKernelGGL(laue_likelihood_laplace_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(laue_likelihood_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    if (a.lik_kind == CL_LIK_LAPLACE_) return cl_launch<laue_likelihood_laplace_kernel>(laue_grid(a, true), dim3(256), (hipStream_t)stream, a);
+    return cl_launch<laue_likelihood_kernel>(laue_grid(a, true), dim3(256), (hipStream_t)stream, a);
 }
-int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st) {
+
+int cl_slot_rows(const cl_laue_args* ap, void* stream) {
+    if (ap == nullptr) return -1;
+    const cl_laue_args& a = *ap;
     if (int e = laue_check(a)) return e;
     if (a.harmonic_id != nullptr) return -2;           // rows that share slots need the three passes (group sums between them)
     if (a.iobs == nullptr || a.sig == nullptr || a.scalars == nullptr || a.dz_f == nullptr || a.dO == nullptr || (a.use_img && a.d_img == nullptr)) return -1;
@@ -327,30 +336,29 @@ int cl_launch_slot_rows(const cl_laue_args& a, hipStream_t st) {
         if (64 % a.S != 0) return -2;
         if (a.nll_part == nullptr || (a.use_img && a.dimg_obs == nullptr) || (a.ev11 != nullptr && a.ev11_part == nullptr)) return -1;
     }
-    (void)hipGetLastError();
+    hipStream_t st = (hipStream_t)stream;
     const int store = (64 % a.S == 0) ? 1 : 0;
     if (!store) {
         hipError_t e = hipMemsetAsync(a.dO, 0, sizeof(float) * 2 * (size_t)a.n_obs, st);
         if (e != hipSuccess) return (int)e;
     }
-    const long long n = (long long)a.n_obs * a.S;
-    long long blocks = (n + 255) / 256;
-    if (blocks > CL_LAUE_LIK_MAX_BLOCKS) blocks = CL_LAUE_LIK_MAX_BLOCKS;
-    if (a.lik_kind == CL_LIK_LAPLACE_) hipLaunchKernelGGL(slot_rows_laplace_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, store);
-    else hipLaunchKernelGGL(slot_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, store);
-    return (int)hipGetLastError();
+    if (a.lik_kind == CL_LIK_LAPLACE_) return cl_launch<slot_rows_laplace_kernel>(laue_grid(a, true), dim3(256), st, a, store);
+    return cl_launch<slot_rows_kernel>(laue_grid(a, true), dim3(256), st, a, store);
 }
-int cl_launch_laue_backward(const cl_laue_args& a, hipStream_t st) {
+
+int cl_laue_backward(const cl_laue_args* ap, void* stream) {
+    if (ap == nullptr) return -1;
+    const cl_laue_args& a = *ap;
     if (int e = laue_check(a)) return e;
     if (a.dz_f == nullptr || (a.dO != nullptr && a.use_img && a.d_img == nullptr)) return -1;
-    (void)hipGetLastError();
+    hipStream_t st = (hipStream_t)stream;
     // dO receives the rows' sums by atomics: cleared here, on the same stream (part of the call).  dO NULL (round 6): the scaling model
     // is frozen -- only dz_f is taken, no clearing, no per-row reductions
     if (a.dO != nullptr) {
         hipError_t e = hipMemsetAsync(a.dO, 0, sizeof(float) * 2 * (size_t)a.n_obs, st);
         if (e != hipSuccess) return (int)e;
     }
-    const long long n = (long long)a.n_obs * a.S;
-    hipLaunchKernelGGL(laue_backward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    return cl_launch<laue_backward_kernel>(laue_grid(a, false), dim3(256), st, a);
 }
+
+}  // extern "C"

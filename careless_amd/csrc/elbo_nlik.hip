@@ -437,7 +437,6 @@ int cl_nlik_supports(int L, int w) { return L >= 1 && L <= NLIK_LMAX && w >= 1 &
 size_t cl_nlik_param_count(int L, int w) { return (L < 1 || w < 1) ? 0 : (size_t)3 * w + (size_t)(L - 1) * ((size_t)w * w + w) + w + 1; }
 int cl_nlik_grid(long long n) { return n < 1 ? 0 : nlik_grid(n); }
 size_t cl_nlik_workspace_bytes(long long n, int L, int w) { return (n < 1 || !cl_nlik_supports(L, w)) ? 0 : nlik_carve(nullptr, n, L, w).bytes; }
-size_t cl_nlik_args_size(void) { return sizeof(cl_nlik_args); }
 
 int cl_nlik_forward(const cl_nlik_args* a, void* stream) {
     if (int e = nlik_check(a)) return e;
@@ -445,9 +444,7 @@ int cl_nlik_forward(const cl_nlik_args* a, void* stream) {
     const NlikWs ws = nlik_carve(a->workspace, a->n, a->L, a->w);
     const int G = nlik_grid(a->n);
     if (int e = nlik_delta(*a, ws, G, st)) return e;
-    hipLaunchKernelGGL(nlik_sigpred_kernel, dim3(G), dim3(NLIK_T), 0, st, a->sigiobs, (const float*)ws.delta, (const double*)ws.dpart, G, a->n, a->sigpred,
-                       a->pos, a->sig_image, a->stop_flag);
-    return (int)hipGetLastError();
+    return cl_launch<nlik_sigpred_kernel>(dim3(G), dim3(NLIK_T), st, a->sigiobs, ws.delta, ws.dpart, G, a->n, a->sigpred, a->pos, a->sig_image, a->stop_flag);
 }
 
 int cl_nlik_backward(const cl_nlik_args* a, void* stream) {
@@ -456,9 +453,7 @@ int cl_nlik_backward(const cl_nlik_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const NlikWs ws = nlik_carve(a->workspace, a->n, a->L, a->w);
     const int G = nlik_grid(a->n);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(nlik_g_kernel, dim3(G), dim3(NLIK_T), 0, st, a->iobs, (const float*)a->sigpred, a->ipred, a->S, a->w_ll, a->n, ws.g, ws.tpart, a->stop_flag);
-    if (int e = (int)hipGetLastError()) return e;
+    if (int e = cl_launch<nlik_g_kernel>(dim3(G), dim3(NLIK_T), st, a->iobs, a->sigpred, a->ipred, a->S, a->w_ll, a->n, ws.g, ws.tpart, a->stop_flag)) return e;
     if (int e = nlik_wgrad(*a, ws, G, st)) return e;
     return cl_launch_reduce_partials(ws.wpart, G, nlik_P(a->L, a->w), a->d_net, a->stop_flag, st);       // index order: deterministic
 }

@@ -170,9 +170,7 @@ extern "C" {
 int cl_chain_dx(const float* dz0_t, const float* Wt, int n_obs, int n_pad, int w_out, int w_in, float* dx_t, const int* stop_flag, void* stream) {
     if (dz0_t == nullptr || Wt == nullptr || dx_t == nullptr || n_obs < 1 || n_pad < n_obs) return -1;
     if (w_out < 1 || w_out > 15 || w_in < 1 || w_in > 15) return -2;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(chain_dx_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dz0_t, Wt, n_obs, n_pad, w_out, w_in, dx_t, stop_flag);
-    return (int)hipGetLastError();
+    return cl_launch<chain_dx_kernel>(dim3((unsigned)((n_pad + 255) / 256)), dim3(256), (hipStream_t)stream, dz0_t, Wt, n_obs, n_pad, w_out, w_in, dx_t, stop_flag);
 }
 
 int cl_peel_supported(int d, int w, int L) {
@@ -198,15 +196,13 @@ int cl_peel_forward(const float* meta_t, int n_obs, int n_pad, int d, int w, int
     const dim3 grid((unsigned)((n_pad + PEEL_T - 1) / PEEL_T));
     const int WQ = (w + 3) & ~3;
     const size_t lds = (size_t)(d + 1) * WQ * sizeof(float);
-    (void)hipGetLastError();
     hipStream_t st = (hipStream_t)stream;
-#define PEEL_FWD(Q) hipLaunchKernelGGL(peel_forward_kernel<Q>, grid, dim3(PEEL_T), lds, st, meta_t, n_pad, d, w, mlp, n_tail, u_t, u_rows, mlp_peel, zero_ptr, zero_n, stop_flag)
-    if (WQ == 4) PEEL_FWD(4);
-    else if (WQ == 8) PEEL_FWD(8);
-    else if (WQ == 12) PEEL_FWD(12);
-    else PEEL_FWD(16);
+#define PEEL_FWD(Q) cl_launch_lds<peel_forward_kernel<Q>>(grid, dim3(PEEL_T), lds, st, meta_t, n_pad, d, w, mlp, n_tail, u_t, u_rows, mlp_peel, zero_ptr, zero_n, stop_flag)
+    if (WQ == 4) return PEEL_FWD(4);
+    if (WQ == 8) return PEEL_FWD(8);
+    if (WQ == 12) return PEEL_FWD(12);
+    return PEEL_FWD(16);
 #undef PEEL_FWD
-    return (int)hipGetLastError();
 }
 
 int cl_peel_backward(const float* meta_t, int n_obs, int n_pad, int d, int w, int L, const float* dz0_t, const float* grad_peel, float* grad_mlp,
@@ -218,21 +214,20 @@ int cl_peel_backward(const float* meta_t, int n_obs, int n_pad, int d, int w, in
     const int nout = w * d + w;
     const long long n_tail = (long long)(L - 1) * ((long long)w * w + w) + 2 * w + 2;
     hipStream_t st = (hipStream_t)stream;
-    (void)hipGetLastError();
     const int NB = (d + 1 + 15) / 16;
-#define PEEL_WG(B) hipLaunchKernelGGL(peel_wgrad_kernel<B>, dim3(nparts), dim3(PEEL_T), 0, st, meta_t, n_pad, d, w, dz0_t, partials, stop_flag)
+    int e;
+#define PEEL_WG(B) cl_launch<peel_wgrad_kernel<B>>(dim3(nparts), dim3(PEEL_T), st, meta_t, n_pad, d, w, dz0_t, partials, stop_flag)
     switch (NB) {
-        case 1: PEEL_WG(1); break;
-        case 2: PEEL_WG(2); break;
-        case 3: PEEL_WG(3); break;
-        case 4: PEEL_WG(4); break;
-        default: PEEL_WG(5); break;
+        case 1: e = PEEL_WG(1); break;
+        case 2: e = PEEL_WG(2); break;
+        case 3: e = PEEL_WG(3); break;
+        case 4: e = PEEL_WG(4); break;
+        default: e = PEEL_WG(5); break;
     }
 #undef PEEL_WG
-    if (int e = (int)hipGetLastError()) return e;
-    if (int e = cl_launch_reduce_partials(partials, nparts, nout, grad_mlp, stop_flag, st)) return e;      // fixed order: deterministic
-    hipLaunchKernelGGL(peel_tail_kernel, dim3((unsigned)((n_tail + 255) / 256)), dim3(256), 0, st, grad_peel + (w * w + w), n_tail, grad_mlp + nout, stop_flag);
-    return (int)hipGetLastError();
+    if (e) return e;
+    if ((e = cl_launch_reduce_partials(partials, nparts, nout, grad_mlp, stop_flag, st)) != 0) return e;      // fixed order: deterministic
+    return cl_launch<peel_tail_kernel>(dim3((unsigned)((n_tail + 255) / 256)), dim3(256), st, grad_peel + (w * w + w), n_tail, grad_mlp + nout, stop_flag);
 }
 
 }  // extern "C"

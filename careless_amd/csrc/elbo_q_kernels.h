@@ -1,9 +1,9 @@
-// The text of the two surrogate-posterior kernels of csrc/elbo_elem.hip, included there once per posterior: as tn_forward_kernel /
+// The text of the two surrogate-posterior kernels of csrc/elbo_q.hip, included there once per posterior: as tn_forward_kernel /
 // tn_backward_kernel (truncated normal, argument cl_tn_args) and as rw_forward_kernel / rw_backward_kernel (Rice-Woolfson, argument cl_rw_args).
 // Two expansions of one text, as elbo_frozen_rows.h, rather than a body function called from two kernels: the truncated-normal kernels
 // must stay what they were, instruction for instruction (a shared body moved their reads of the launch geometry), under their old names.
 // Workspace clearing, KL parts, owned range, prior arms, the ride-along reduction and the stop flag are this text's; the posterior
-// (CL_Q_POST: tn_post / rw_post of elbo_elem.hip) supplies load / sample / log_prob / grads.
+// (CL_Q_POST: tn_post / rw_post of elbo_q.hip) supplies load / sample / log_prob / grads.
 //   #define CL_Q_FORWARD_KERNEL <name>   #define CL_Q_BACKWARD_KERNEL <name>   #define CL_Q_ARGS <kernel argument type>
 //   #define CL_Q_TN(KA) <its cl_tn_args>   #define CL_Q_POST <posterior type>   #define CL_Q_POST_OF(KA) <the posterior of a launch>
 __global__ __launch_bounds__(256) void CL_Q_FORWARD_KERNEL(const CL_Q_ARGS KA) {

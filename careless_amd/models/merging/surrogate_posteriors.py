@@ -217,7 +217,7 @@ class TrainableRiceWoolfson(SurrogatePosterior):
     `VariationalMergingModel(RiceWoolfson(loc_var, scale_var, centric), ...)` trains there.  Made by `RiceWoolfson.from_loc_and_scale`.
 
     Sampling, log-density and their gradients on the training path run in the HIP kernels `cl_rw_forward` / `cl_rw_backward`
-    (csrc/elbo_elem.hip): a centric draw is |loc + scale n1| + eps32 (reference :166), an acentric one sqrt((scale n1)^2 + (loc + scale n2)^2)
+    (csrc/elbo_q.hip): a centric draw is |loc + scale n1| + eps32 (reference :166), an acentric one sqrt((scale n1)^2 + (loc + scale n2)^2)
     (careless/utils/distributions.py:252-258), differentiated pathwise.  `sample`, `mean`, `stddev`, `variance` and `moment_4` run on the
     GPU (`cl_rw_forward`, `cl_rw_moments`) and raise `CarelessHipError` without one; `log_prob` is torch arithmetic on the host.
 

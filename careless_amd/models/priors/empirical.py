@@ -4,7 +4,7 @@ Miller indices.
 Mirror of `careless/models/priors/empirical.py:9-131` (reference): `ReferencePrior`, `LaplaceReferencePrior`, `NormalReferencePrior`,
 `StudentTReferencePrior`, `RiceWoolfsonReferencePrior`, with the reference's constructor signatures.  `Fobs` / `SigFobs` (and `centric`)
 hold one entry per OBSERVED reflection when `observed` is given, and are stored as float32.  Like the Wilson priors, on the hot path a
-reference prior is only a description: its log-density and z-derivative are evaluated by `cl_ref_prior` (careless_amd/csrc/elbo_elem.hip:
+reference prior is only a description: its log-density and z-derivative are evaluated by `cl_ref_prior` (careless_amd/csrc/elbo_q.hip:
 ref_prior_kernel) from the arrays of the "what the engine consumes" block below; `log_prob`, `mean` and `stddev` are host-side numpy
 (float64 arithmetic, float32 results) for users and tests.
 """

@@ -2,7 +2,7 @@
 
 Mirror of `careless/models/priors/wilson.py:13-80` (reference).  On the hot path the prior is only a *description*
 (centric flags, multiplicity, Sigma): its log-density and gradient are evaluated inside the HIP kernels
-`cl_tn_forward` / `cl_tn_backward` (careless_amd/csrc/elbo_elem.hip).  `mean` / `stddev` seed the surrogate posterior
+`cl_tn_forward` / `cl_tn_backward` (careless_amd/csrc/elbo_q.hip).  `mean` / `stddev` seed the surrogate posterior
 exactly as `DataManager.build_model` does (reference `careless/io/manager.py:432`), `log_prob` / `prob` are host-side
 conveniences for users and tests.
 """

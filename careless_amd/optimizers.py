@@ -2,7 +2,7 @@
 
 The reference builds `tfk.optimizers.Adam(lr, beta_1, beta_2, clipnorm=, clipvalue=, global_clipnorm=)`
 (careless/io/manager.py:494-501) and hands it to `model.compile`.  Here `Adam` only carries the hyper-parameters; the
-update itself is the fused HIP kernel `cl_adam_step` (careless_amd/csrc/elbo_elem.hip).  Defaults follow tf_keras
+update itself is the fused HIP kernel `cl_adam_step` (careless_amd/csrc/elbo_step.hip).  Defaults follow tf_keras
 (epsilon 1e-7) and the careless CLI (args/optimizer.py: lr 1e-3, beta_1 0.9, beta_2 0.99).
 """
 from __future__ import annotations

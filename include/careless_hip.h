@@ -151,7 +151,6 @@ typedef struct cl_refprior_args {
 } cl_refprior_args;
 enum { CL_REFPRIOR_NORMAL = 0, CL_REFPRIOR_LAPLACE = 1, CL_REFPRIOR_STUDENTT = 2, CL_REFPRIOR_RICE_WOOLFSON = 3 };
 int cl_ref_prior(const cl_refprior_args* args, void* stream);
-size_t cl_refprior_args_size(void);                /* sizeof(cl_refprior_args) as the library was compiled (binding check, like cl_abi_sizes) */
 
 /* --- Rice-Woolfson surrogate posterior ---------------------------------------------------------------------------------
  * replaces: RiceWoolfson.sample / .log_prob (careless/models/merging/surrogate_posteriors.py:133-172), Rice._sample_n / .log_prob and
@@ -172,7 +171,6 @@ typedef struct cl_rw_args {
 } cl_rw_args;
 int cl_rw_forward(const cl_rw_args* args, void* stream);
 int cl_rw_backward(const cl_rw_args* args, void* stream);
-size_t cl_rw_args_size(void);                      /* sizeof(cl_rw_args) as the library was compiled */
 
 /* --- scaler + likelihood -----------------------------------------------------------------------------------------
  * replaces: MLPScaler.call / MetadataScaler / NormalLayer        (careless/models/scaling/nn.py:10-120)
@@ -581,7 +579,6 @@ typedef struct cl_frozen_args {
 int cl_frozen_rows(const cl_frozen_args* args, void* stream);
 int cl_frozen_edge_floats(long long n, int S);     /* floats of edge_val */
 int cl_frozen_grid(long long n);                   /* workgroups of the launch (nll_part / ev11_part slots) */
-size_t cl_frozen_args_size(void);                  /* sizeof(cl_frozen_args) as the library was compiled (binding check, like cl_abi_sizes) */
 
 /* --- neural likelihood: an error model learned from the data (csrc/elbo_nlik.hip) ---------------------------------------------------
  * replaces: NeuralLikelihood.__init__ / .call and NeuralNormalLikelihood.base_dist (careless/models/likelihoods/mono.py:75-110) inside
@@ -626,7 +623,6 @@ int cl_nlik_supports(int L, int w);                /* 1: the kernels hold L hidd
 size_t cl_nlik_param_count(int L, int w);
 size_t cl_nlik_workspace_bytes(long long n, int L, int w);
 int cl_nlik_grid(long long n);                     /* workgroups of every launch = rows of the partial buffers         */
-size_t cl_nlik_args_size(void);                    /* sizeof(cl_nlik_args) as the library was compiled                 */
 
 /* --- gradient norm, sanitise, clip, Adam -------------------------------------------------------------------------
  * replaces: tf.linalg.global_norm, tf.where(is_finite), optimizer.apply_gradients (variational.py:202-209)
@@ -783,8 +779,10 @@ int cl_host_crystfel_parse(const char* buf, long long nbytes, long long n_rows, 
 
 /* --- diagnostics -------------------------------------------------------------------------------------------------- */
 const char* cl_version(void);
-/* sizeof(cl_tn_args), sizeof(cl_mlp_args), sizeof(cl_adam_args), sizeof(cl_laue_args), sizeof(cl_det_args): lets a binding verify its mirrors */
-void cl_abi_sizes(size_t out[5]);
+/* The binding handshake: sizeof(<struct_name>) as the library was compiled, for every argument struct of this header -- "cl_tn_args",
+ * "cl_mlp_args", "cl_adam_args", "cl_laue_args", "cl_det_args", "cl_frozen_args", "cl_refprior_args", "cl_rw_args", "cl_nlik_args" --,
+ * 0 for a name the library does not know (or NULL).  A binding compares each of its mirrors once, at load time.                       */
+size_t cl_abi_sizeof(const char* struct_name);
 /* out[n][S]: kind 0 = the uniforms of cl_tn_*, kind 1 = the normals of cl_elbo_mono_fwd_bwd, for (seed, step);
  * kind 2 = the normal pairs (n1, n2) of cl_rw_*: out[n][S][2] */
 int cl_debug_noise(unsigned long long seed, unsigned step, int S, long long n, long long offset, int kind, float* out,

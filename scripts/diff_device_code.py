@@ -7,7 +7,7 @@ A change that touches host code only -- or moves a device helper from one file t
 speed of the kernels is the parent's by construction.  Both libraries are unbundled and disassembled (the tools of
 scripts/check_lane_isa.py); kernels are matched by name (demangled where llvm-cxxfilt is installed), without the suffix the compiler
 derives from the source path for kernels with internal linkage.  Compared per kernel: the instruction sequence (mnemonic and operands; addresses and the comments
-derived from them are dropped) and the kernel descriptor's resources (register counts, scratch and LDS size).  Exit code 1 and one
+derived from them are dropped, and so is the fill behind a kernel's last instruction) and the kernel descriptor's resources (register counts, scratch and LDS size).  Exit code 1 and one
 line per kernel that is missing, extra or different.
 """
 from __future__ import annotations
@@ -45,6 +45,16 @@ def resources(co: str) -> dict:
     return {k: tuple(v.get(f) for f in RESOURCES) for k, v in out.items()}
 
 
+def _without_padding(texts: list) -> tuple:
+    """The disassembler counts the `s_nop 0` fill behind a kernel's last instruction -- up to the next kernel's alignment, and a longer run
+    behind the LAST kernel of a code object -- as that kernel's: how long the run is says where the kernel stands in its file, not what it
+    executes (nothing behind its final `s_endpgm` or branch).  Dropped, so that a kernel moved to another file compares equal."""
+    n = len(texts)
+    while n > 0 and texts[n - 1] == "s_nop 0":
+        n -= 1
+    return tuple(texts[:n])
+
+
 def kernels_of(lib: str) -> dict:
     """demangled name (path-derived suffix stripped) -> sorted list of (resources, instruction texts), one per code object that holds it"""
     out = defaultdict(list)
@@ -54,7 +64,7 @@ def kernels_of(lib: str) -> dict:
             ks = {k: v for k, v in parse_objdump(txt).items() if v[1]}
             res = resources(co)
             for k, name in demangle(list(ks)).items():
-                out[_UNIQUE.sub("", name)].append((res.get(k), tuple(i.text for i in ks[k][1])))
+                out[_UNIQUE.sub("", name)].append((res.get(k), _without_padding([i.text for i in ks[k][1]])))
     return {k: sorted(v, key=repr) for k, v in out.items()}
 
 

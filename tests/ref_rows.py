@@ -1,5 +1,5 @@
 """The row-level data-term kernels -- cl_frozen_rows in its three forms (csrc/elbo_frozen.hip, csrc/elbo_frozen_rows.h), cl_laue_predict /
-cl_laue_likelihood / cl_laue_backward and cl_slot_rows (csrc/elbo_laue.hip), cl_det_reduce (csrc/elbo_elem.hip) -- restated ONCE in torch
+cl_laue_likelihood / cl_laue_backward and cl_slot_rows (csrc/elbo_laue.hip), cl_det_reduce (csrc/elbo_det.hip) -- restated ONCE in torch
 fp64 from the contract (include/careless_hip.h: the comments on cl_frozen_args, cl_laue_args, cl_det_args), with a summand size M beside
 every output element, the bounds the direct kernel tests hold the device to (tests/test_rows_kernels_gpu.py), the inputs and the case list
 of those tests, and an fp32 emulation of each kernel's arithmetic in the kernel's own order through the host build of csrc/cl_math.h

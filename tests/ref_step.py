@@ -1,5 +1,5 @@
 """fp64 restatements of the optimizer half of the training step -- cl_grad_sqnorm, cl_owner_qnorm, cl_adam_step, cl_step_finalize
-(csrc/elbo_elem.hip) -- with an a-priori bound per element, the inputs of the direct kernel tests (tests/test_step_kernels.py), and the
+(csrc/elbo_step.hip) -- with an a-priori bound per element, the inputs of the direct kernel tests (tests/test_step_kernels.py), and the
 guarded-buffer harness their device operands are carved from.
 
 Written from the contract in include/careless_hip.h ("gradient norm, sanitise, clip, Adam") and the reference's

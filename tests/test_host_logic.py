@@ -804,7 +804,7 @@ def test_round6_entry_points_host_side():
     assert lib.cl_frozen_edge_floats(0, 3) == 0 and lib.cl_frozen_edge_floats(1, 3) == 6 and lib.cl_frozen_edge_floats(64, 1) == 2
     assert lib.cl_frozen_edge_floats(65, 8) == 32 and lib.cl_frozen_edge_floats(10_000_000, 8) == 2 * 156250 * 8
     assert lib.cl_frozen_grid(1) == 1 and lib.cl_frozen_grid(257) == 2 and lib.cl_frozen_grid(10_000_000) == _lib.CL_LAUE_LIK_MAX_BLOCKS
-    assert int(lib.cl_frozen_args_size()) == C.sizeof(_lib.FrozenArgs)
+    assert int(lib.cl_abi_sizeof(b"cl_frozen_args")) == C.sizeof(_lib.FrozenArgs)
     assert lib.cl_frozen_rows(None, None) == -1
     fa = _lib.FrozenArgs()
     fa.n, fa.S = 100, 2

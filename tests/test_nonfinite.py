@@ -2,7 +2,7 @@
 kernel route a training step can take: the global gradient norm is taken BEFORE anything is sanitised (so it is non-finite), the
 non-finite gradient entries are then zeroed one by one and that step's Adam update is still applied, the step is recorded and the loop
 breaks.  In this package that rests on every fused kernel carrying a NaN from ONE poisoned observation to the gradient entries that
-observation touches -- and to no others --, to the norm (csrc/elbo_elem.hip) and to the `stop_flag` every later launch reads; the fused
+observation touches -- and to no others --, to the norm (csrc/elbo_step.hip) and to the `stop_flag` every later launch reads; the fused
 scaler units are compiled with -fno-honor-nans (careless_amd/build.py), under which the compiler may fold a select or compare that sees
 a NaN, so nothing but a test holds it.
 

@@ -171,15 +171,19 @@ def test_bare_reference_prior_has_no_base_distribution():
 
 
 # ---- the C-ABI ---------------------------------------------------------------------------------------------------------------------------
-PARENT_ABI_SIZES = (304, 392, 168, 272, 136)      # cl_tn_args, cl_mlp_args, cl_adam_args, cl_laue_args, cl_det_args before cl_ref_prior existed
+PINNED_STRUCTS = ("cl_tn_args", "cl_mlp_args", "cl_adam_args", "cl_laue_args", "cl_det_args")
+PARENT_ABI_SIZES = (304, 392, 168, 272, 136)      # ... before cl_ref_prior existed
+
+
+def pinned_abi_sizes(lib):
+    """The library's sizes of PINNED_STRUCTS, asked by name (cl_abi_sizeof)."""
+    return tuple(int(lib.cl_abi_sizeof(n.encode())) for n in PINNED_STRUCTS)
 
 
 def test_abi_sizes():
     lib = _lib.get_lib()
-    assert int(lib.cl_refprior_args_size()) == C.sizeof(_lib.RefPriorArgs)
-    sizes = (C.c_size_t * 5)()
-    lib.cl_abi_sizes(sizes)
-    assert tuple(sizes) == PARENT_ABI_SIZES             # the feature added a struct of its own: none of the pinned ones grew
+    assert int(lib.cl_abi_sizeof(b"cl_refprior_args")) == C.sizeof(_lib.RefPriorArgs)
+    assert pinned_abi_sizes(lib) == PARENT_ABI_SIZES    # the feature added a struct of its own: none of the pinned ones grew
     assert (_lib.CL_PRIOR_WILSON, _lib.CL_PRIOR_DOUBLE_WILSON, _lib.CL_PRIOR_REFERENCE) == (0, 1, 2)
 
 
@@ -191,7 +195,7 @@ def _accepted():
 
 
 def test_ref_prior_entry_checks_answer_without_a_launch():
-    """One rejecting call per clause of the entry check; every one returns before the launch (csrc/cl_api.hip: cl_ref_prior), so the
+    """One rejecting call per clause of the entry check; every one returns before the launch (csrc/elbo_q.hip: cl_ref_prior), so the
     made-up pointers are never dereferenced -- whoever reorders that check must keep it ahead of the launch."""
     lib = _lib.get_lib()
     assert lib.cl_ref_prior(None, None) == -1

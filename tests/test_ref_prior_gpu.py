@@ -1,4 +1,4 @@
-"""Empirical reference priors on the GPU: `cl_ref_prior` (csrc/elbo_elem.hip: ref_prior_kernel) called directly, one launch per case, on
+"""Empirical reference priors on the GPU: `cl_ref_prior` (csrc/elbo_q.hip: ref_prior_kernel) called directly, one launch per case, on
 operands carved from one guarded allocation, and whole training steps of the engine under the four prior classes, both against the fp64
 restatement of tests/ref_prior.py (the unchanged oracle with the Wilson term traded for the reference prior's).
 

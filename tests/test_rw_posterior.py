@@ -14,10 +14,10 @@ import torch
 
 from careless_amd import _lib
 from tests import ref_rw as RR
-from tests.test_ref_prior import PARENT_ABI_SIZES
+from tests.test_ref_prior import PARENT_ABI_SIZES, pinned_abi_sizes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-NEW_SYMBOLS = ("cl_rw_forward", "cl_rw_backward", "cl_rw_args_size", "cl_rw_moments")
+NEW_SYMBOLS = ("cl_rw_forward", "cl_rw_backward", "cl_rw_moments")
 
 
 def _params(n, seed, lo=-3.0, hi=3.0):
@@ -192,10 +192,8 @@ def test_header_declares_and_library_exports_the_new_symbols():
 
 def test_abi_sizes():
     lib = _lib.get_lib()
-    assert int(lib.cl_rw_args_size()) == C.sizeof(_lib.RwArgs) == C.sizeof(_lib.TnArgs) + 16
-    sizes = (C.c_size_t * 5)()
-    lib.cl_abi_sizes(sizes)
-    assert tuple(sizes) == PARENT_ABI_SIZES             # the feature added a struct of its own: none of the pinned ones grew
+    assert int(lib.cl_abi_sizeof(b"cl_rw_args")) == C.sizeof(_lib.RwArgs) == C.sizeof(_lib.TnArgs) + 16
+    assert pinned_abi_sizes(lib) == PARENT_ABI_SIZES    # the feature added a struct of its own: none of the pinned ones grew
 
 
 def _accepted(**over):
@@ -219,7 +217,7 @@ SHARED_CLAUSES = [dict(q_centric=None), dict(q_loc_raw=None), dict(q_scale_raw=N
 
 
 def test_entry_checks_answer_without_a_launch():
-    """One rejecting call per clause of the entry checks of cl_rw_forward, cl_rw_backward and cl_rw_moments (csrc/cl_api.hip); every one
+    """One rejecting call per clause of the entry checks of cl_rw_forward, cl_rw_backward (csrc/elbo_q.hip) and cl_rw_moments (csrc/elbo_output.hip); every one
     returns before the launch, so the made-up pointers are never dereferenced."""
     lib = _lib.get_lib()
     p = 0x10000

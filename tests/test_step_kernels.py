@@ -1,10 +1,10 @@
-"""The optimizer half of the training step -- cl_grad_sqnorm, cl_owner_qnorm, cl_adam_step, cl_step_finalize (csrc/elbo_elem.hip) -- called
+"""The optimizer half of the training step -- cl_grad_sqnorm, cl_owner_qnorm, cl_adam_step, cl_step_finalize (csrc/elbo_step.hip) -- called
 directly through careless_amd._lib, one call of one entry point per case, against the fp64 references of tests/ref_step.py at their
 a-priori bounds, on operands carved from one guarded allocation (ref_step.Guarded: every byte the contract says is not written --
 g, elements outside the ranges, frozen tensors, scalars[NLL, KL], the other history records and the record's three spare doubles, all
 guard bands -- bit-identical after the call).
 
-Shape -> grid, from the launchers in elbo_elem.hip (workgroups of 256 threads):
+Shape -> grid, from the entry points in elbo_step.hip (workgroups of 256 threads):
   cl_adam_grid_of: `int grid = (work + 1023) / 1024;` (work = n, or the sum of the range lengths, at least 1),
       `const int cap = (a.n >= (1 << 22) || a.norm_out == nullptr || a.norm_part != nullptr) ? 1024 : 256; if (grid > cap) grid = cap;`
       the kernel then walks rounds of `U * stride` = 4 x grid x 256 elements: 262 144 per round at 256 workgroups (262 145 and
@@ -185,7 +185,7 @@ REFUSED = {
 
 @pytest.mark.parametrize("name", list(REFUSED))
 def test_adam_step_refuses(name):
-    """cl_api.hip's checks: -1 and not a byte written"""
+    """elbo_step.hip's entry checks: -1 and not a byte written"""
     kw, spoil = REFUSED[name]
     c = small_case(**kw)
     a = adam_arena(c, R.adam_step(c))
