@@ -28,6 +28,8 @@ CL_EV11_WAVES = 8               # wave slots per workgroup in ev11_part (include
 
 # cl_mlp_epilogue: the sampling epilogue of the instance a scaler launch runs (enum cl_epilogue)
 CL_EPI_GENERIC, CL_EPI_PLAIN_NORMAL, CL_EPI_PLAIN_STUDENTT = range(3)
+# cl_mlp_instance_traits: first-layer k-steps in the low byte, the compile-time-depth bit
+CL_TRAIT_K1_MASK, CL_TRAIT_FIXED_DEPTH = 0xFF, 0x100
 
 _vp = C.c_void_p
 
@@ -201,6 +203,7 @@ EXPORTS = {
     "cl_mlp_backward_ext": (C.c_int, [C.POINTER(MlpArgs), C.c_int, _vp]),
     "cl_mlp_route": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
     "cl_mlp_epilogue": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
+    "cl_mlp_instance_traits": (C.c_int, [C.POINTER(MlpArgs), C.c_int]),
     "cl_mlp_kernel_name": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_char_p, C.c_size_t]),
     "cl_mlp_check": (C.c_int, [C.POINTER(MlpArgs), C.c_int, C.c_int]),
     "cl_wide_ld": (C.c_int, [C.c_int]),
@@ -338,6 +341,16 @@ def mlp_epilogue(lib, mode: int, **fields) -> int:
     """`cl_mlp_epilogue` of a launch with these `cl_mlp_args` fields (as `mlp_route`); no device needed."""
     a = MlpArgs(**fields)
     return int(lib.cl_mlp_epilogue(C.byref(a), mode))
+
+
+def mlp_instance_traits(lib, mode: int, **fields) -> tuple:
+    """`cl_mlp_instance_traits` of a launch with these `cl_mlp_args` fields (as `mlp_route`): (first-layer k-steps, depth compiled
+    in); no device needed."""
+    a = MlpArgs(**fields)
+    t = int(lib.cl_mlp_instance_traits(C.byref(a), mode))
+    if t < 0:
+        raise ValueError(f"cl_mlp_instance_traits: code {t}")
+    return t & CL_TRAIT_K1_MASK, bool(t & CL_TRAIT_FIXED_DEPTH)
 
 
 def ptr(t) -> Optional[int]:

@@ -58,6 +58,14 @@ int cl_mlp_epilogue(const cl_mlp_args* a, int mode) {
     return (int)mlp_epilogue(*a, mode, mlp_route(*a, mode));
 }
 
+int cl_mlp_instance_traits(const cl_mlp_args* a, int mode) {
+    if (a == nullptr || mode < 0 || mode > 2) return -1;
+    const cl_route r = mlp_route(*a, mode);
+    if (r == CL_ROUTE_NONE) return -2;
+    const MlpTraits t = mlp_traits(*a, mode, r);
+    return t.K1 | (t.fixed_depth ? CL_TRAIT_FIXED_DEPTH : 0);
+}
+
 int cl_mlp_kernel_name(const cl_mlp_args* a, int mode, char* out, size_t n) {
     if (a == nullptr || out == nullptr || n == 0 || mode < 0 || mode > 2) return -1;
     return cl_mlp_kernel_name_of(*a, mode, out, n);

@@ -23,6 +23,8 @@ struct cl_launch_ctx {
 int cl_launch_mlp(const cl_mlp_args* a, int mode, int grid, hipStream_t st, bool launch = true);
 cl_route mlp_route(const cl_mlp_args& a, int mode);                                  // the unit or launcher cl_launch_mlp hands a launch to
 cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r);                // the epilogue of the instance it runs (cl_mlp_epilogue)
+struct MlpTraits { int K1; bool fixed_depth; };                                      // first-layer k-steps with real columns; depth compiled in
+MlpTraits mlp_traits(const cl_mlp_args& a, int mode, cl_route r);                    // ... of the instance it runs (cl_mlp_instance_traits)
 int cl_mlp_kernel_name_of(const cl_mlp_args& a, int mode, char* out, size_t n);     // the name of the instance the launch runs
 // The seven compilations of elbo_mlp.hip (build.py), one cl_route each: -DCL_IMGL=0 CL_ROUTE_MLP, -DCL_IMGL=1 _IMGL (per-image layers),
 // -DCL_IMGL=2 _PACKED (single-pass Laue), -DCL_CHAIN=1 _CHAIN (a block of a layer-block chain), -DCL_DET=1 _DET (deterministic mode: no

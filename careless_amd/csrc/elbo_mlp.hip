@@ -165,9 +165,16 @@ struct AccPlan {
 //     straight-line code for the lane's two samples.  64-wide full-step instances of the plain unit only.
 //     CL_EPI_GENERIC_LAPLACE (internal, not a value of the public enum): the generic epilogue with the Laplace likelihood compiled in
 //     (no Evans-2011 terms) -- an instance of its own, so that the instances Normal and Student-T launches run are what they were.
+// K1: k-steps of the first layer that hold real metadata columns (0: all DP / 4 of them).  The plain-epilogue instances on DP = 32 exist
+//     with K1 = 6 too, for 8 < d <= 24 (the headline has d = 21): the first layer's forward issues 4 K1 MFMAs instead of 32, the metadata
+//     prefetch and the layer-0 staging writes touch K1 feature groups instead of 8.  DP, the LDS layout and the wgrad plan are the same.
+// FIXL: the launch runs all LMAX layers (A.L == LMAX, the host's promise: mlp_traits, mlp_launch.hip), so the depth is a constant of the
+//     instance: no per-tile opaque layer count, no `l < Lt` guards, one copy of the Dense(2) head and of the top layer's backward arm
+//     instead of LMAX.  Plain-epilogue 64-wide instances on DP <= 32; a launch with fewer layers keeps the run-time-depth instance.
+// Neither is part of the kernel's printed name (like EPI); cl_mlp_instance_traits answers both, CARELESS_HIP_EXACT=0 turns both off.
 #define CL_EPI_GENERIC_LAPLACE 100
 template <int WP, int DP, int LMAX, int MODE, bool IMGL, bool CHAIN = false, bool ILAY = IMGL, int KS = 4, bool DET = (CL_DET != 0),
-          int EPI = CL_EPI_GENERIC>
+          int EPI = CL_EPI_GENERIC, int K1 = 0, bool FIXL = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void elbo_mlp_kernel(const cl_mlp_args A) {
     constexpr bool EPI_GEN = (EPI == CL_EPI_GENERIC || EPI == CL_EPI_GENERIC_LAPLACE);       // every option decided per MC sample
@@ -175,7 +182,9 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
     static_assert(EPI_GEN || (WP == 64 && MODE == 0 && !IMGL && !CHAIN && !DET), "plain epilogue: 64-wide full step of the plain unit");
     using SL = SmemLayout<WP, DP, LMAX>;
     constexpr int FB = WP / 16;          // 16-feature blocks of a hidden layer
-    constexpr int KS1 = DP / 4;          // MFMA k-steps of the first layer (4 metadata features per step)
+    constexpr int KS1 = (K1 > 0) ? K1 : DP / 4;     // MFMA k-steps of the first layer (4 metadata features per step): those with real columns
+    static_assert(KS1 <= DP / 4 && (K1 == 0 || (!EPI_GEN && DP == 32)), "trimmed metadata k-steps: plain-epilogue instances on 32 padded columns");
+    static_assert(!FIXL || (!EPI_GEN && DP <= 32), "compile-time depth: plain-epilogue instances on up to 32 padded columns");
     constexpr int IB1 = (DP + 15) / 16;  // 16-feature blocks of the metadata
     constexpr int PW = SL::PW, PW1 = SL::PW1, PB = CL_PB;
     // Width <= 15: a layer has ONE 16x16 weight-gradient block and the plan below splits its 128-observation contraction into
@@ -228,8 +237,8 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
     auto acc_slot = [&](int l) -> f32x4& { return sAcc[(l >= LREG ? l - LREG : 0) * (CL_NW * 64)]; };
 
     const int d = A.d, w = A.w;
-    const int Ld = A.L;                              // Dense layers (parameters in A.mlp)
-    const int L = ILAY ? A.L + A.n_imgl : A.L;       // all hidden layers (Dense + per-image)
+    const int Ld = FIXL ? LMAX : A.L;                // Dense layers (parameters in A.mlp)
+    const int L = ILAY ? A.L + A.n_imgl : Ld;        // all hidden layers (Dense + per-image)
     const float leak = A.leak;
     const bool no_head = CHAIN && ((MODE == 1 && A.act_out != nullptr) || (MODE == 2 && A.dH_ext != nullptr));
 
@@ -442,7 +451,8 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
         // the layer count, made opaque once per tile: otherwise hipcc hoists every `l == L - 1` / `l < L` test of the unrolled layer
         // loops out of the tile loop, runs out of SGPRs, parks the masks in VGPR lanes and pays v_readlane / v_writelane round trips
         // (plus bool -> VGPR -> bool conversions) inside every layer
-        const int Lt = opaque_uniform(L);
+        // (FIXL: the depth is the instance's LMAX -- every layer test below folds when the layer loops are unrolled)
+        const int Lt = FIXL ? LMAX : opaque_uniform(L);
         const int gobs = tile * CL_TILE + CL_WOBS * wv + j;      // this lane's observation (all four k-groups)
         if (ILAY && A.n_imgl > 0) {
             const int im = __builtin_amdgcn_readfirstlane(A.tile_img[tile]);
@@ -837,10 +847,11 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
         // EARLY: "l is the top layer" as a bit test, not as `l == Lt - 1`.  Inside a block guarded by that equality hipcc rewrites hs[l] as
         // hs[Lt - 1] BEFORE it unrolls the layer loop -- an index known only at run time, which takes the whole activation array out of
         // registers into scratch memory (20 stores and 12 loads of 16 bytes per lane and tile) once the seam barrier is gone
-        const unsigned top_bit = EARLY ? (unsigned)opaque_uniform(1 << (Lt - 1)) : 0u;
+        // (FIXL: the top layer is l == LMAX - 1, a constant of the unrolled loop, and hs[] never sees a run-time index)
+        const unsigned top_bit = (EARLY && !FIXL) ? (unsigned)opaque_uniform(1 << (Lt - 1)) : 0u;
 #pragma unroll
         for (int l = LMAX - 1; l >= 0; --l) {
-            const bool is_top = EARLY ? (((top_bit >> l) & 1u) != 0u) : (l == Lt - 1);
+            const bool is_top = FIXL ? (l == LMAX - 1) : (EARLY ? (((top_bit >> l) & 1u) != 0u) : (l == Lt - 1));
             if (is_top && no_head) {
                 // head-less block of a chain: dL/dH_L comes from the next block (feature-major, like the metadata)
 #pragma unroll
@@ -876,6 +887,12 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                     }
                     woacc0 = wo[0]; woacc1 = wo[1];
                 }
+                // FIXL: without the run-time depth's branch around this arm hipcc sinks the sums above to the end of the tile, where the
+                // accumulators are next read, and keeps their 48 operand registers live through the whole backward pass: the values are pinned here
+                // (this pin and the two on bacc[l] below are all that keeps the FIXL instances out of scratch -- without them 44 spilled
+                // VGPRs, 116 B -- and that rests on this compiler's scheduling, which no test sees: after a compiler update rebuild the
+                // table of profiles/exact_instance_device_code.txt and check scratch 0 and the VGPR counts of the "depth" rows)
+                if (FIXL) asm volatile("" : "+v"(woacc0), "+v"(woacc1));
                 wave_lds_sync();
                 STAMP(4);
             }
@@ -959,6 +976,9 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
                     // the metadata stay in registers through the backward pass: re-reading the tile here (an L2 hit) still puts a
                     // vector-memory round trip in front of the staging writes of every wave at the same time (measured: +2.2 %
                     // on cfg3 without it, at the price of ~20 more spilled registers in the d <= 32 instance)
+                    // K1 < DP / 4: rows 4 KS1 .. DP - 1 of sH are not written here and hold the H of the layer step before (finite, or NaN
+                    // from a poisoned observation) during the layer-0 wgrad.  They reach accumulator columns i >= 4 KS1 >= d only, which
+                    // the flush never stores (it tests i < in_dim): no zero fill.
 #pragma unroll
                     for (int t = 0; t < KS1; ++t) sH[(4 * t + q) * PB + CL_WOBS * wv + j] = h0[t];
                     if (CHAIN && A.dX_out != nullptr) {
@@ -1092,6 +1112,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) sb += (z4[e][0] + z4[e][1]) + (z4[e][2] + z4[e][3]);
                             if (lane < WP) bacc[l] += sb;
+                            if (FIXL) asm volatile("" : "+v"(bacc[l]));          // (as woacc above: the row sums stay here, z4 dies here)
                         }
                         a4 = na; b4 = nb; c4 = nc;
                     }
@@ -1154,6 +1175,7 @@ void elbo_mlp_kernel(const cl_mlp_args A) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) sb += (z4[e][0] + z4[e][1]) + (z4[e][2] + z4[e][3]);
                             if (lane < WP) bacc[l] += sb;
+                            if (FIXL) asm volatile("" : "+v"(bacc[l]));          // (as woacc above: the row sums stay here, z4 dies here)
                         }
                         a4 = na; b4 = nb; c4 = nc;
                     }
@@ -1321,8 +1343,8 @@ constexpr const char* UNIT_SUFFIX[] = {"", ", packed", ", image layers", ", chai
 static_assert(CL_ROUTE_MLP_CHAIN_DET - CL_ROUTE_MLP == 6, "UNIT_SUFFIX: one entry per route of this file, in cl_route's order");
 
 // The leaf: with a name sink it prints this instance's template parameters and the unit (EPI and the Laplace instance stay out of the
-// name), without one it launches.
-template <int WP, int DP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC>
+// name, and so do K1 and FIXL), without one it launches.
+template <int WP, int DP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC, int K1 = 0, bool FIXL = false>
 static int launch_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
     if (c.name != nullptr)
         return snprintf(c.name, c.name_n, "elbo_mlp_kernel<%d, %d, %d, %d%s, KS=%d>", WP, DP, LMAX, MODE, UNIT_SUFFIX[UNIT_ROUTE - CL_ROUTE_MLP], KS);
@@ -1334,7 +1356,7 @@ static int launch_one(const cl_mlp_args& a, const cl_launch_ctx& c) {
     if (MODE != 1 && flush > sm) sm = flush;
     using AP = AccPlan<WP, DP, LMAX, MODE, (CL_IMGL == 1)>;
     if (AP::NACC > 0) sm = (size_t)AP::total * sizeof(float);                                       // + LDS-resident accumulators
-    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0), EPI>>(dim3(c.grid), dim3(512), sm, c.st, a);
+    return cl_launch_lds<elbo_mlp_kernel<WP, DP, LMAX, MODE, (CL_IMGL != 0), (CL_CHAIN != 0), (CL_IMGL == 1), KS, (CL_DET != 0), EPI, K1, FIXL>>(dim3(c.grid), dim3(512), sm, c.st, a);
 }
 
 template <int WP, int LMAX, int MODE, int KS = 4, int EPI = CL_EPI_GENERIC>
@@ -1343,6 +1365,22 @@ static int launch_dp(const cl_mlp_args& a, int dp, const cl_launch_ctx& c) {
     if (dp == 32) return launch_one<WP, 32, LMAX, MODE, KS, EPI>(a, c);
     return launch_one<WP, 64, LMAX, MODE, KS, EPI>(a, c);
 }
+
+#if CL_PLAIN_UNIT
+// The 64-wide plain-epilogue instances (full step): by padded metadata width, and on DP <= 32 by mlp_traits -- the first layer's real
+// k-steps (DP = 32: 6 for d <= 24) and the compile-time depth (A.L == LMAX)
+template <int EPI>
+static int launch_plain64(const cl_mlp_args& a, int dp, const cl_launch_ctx& c) {
+    constexpr int LM = CL_MLP_LMAX_W64;
+    const MlpTraits t = mlp_traits(a, 0, CL_ROUTE_MLP);
+    if (dp == 8) return t.fixed_depth ? launch_one<64, 8, LM, 0, 4, EPI, 0, true>(a, c) : launch_one<64, 8, LM, 0, 4, EPI>(a, c);
+    if (dp == 32) {
+        if (t.K1 == 6) return t.fixed_depth ? launch_one<64, 32, LM, 0, 4, EPI, 6, true>(a, c) : launch_one<64, 32, LM, 0, 4, EPI, 6>(a, c);
+        return t.fixed_depth ? launch_one<64, 32, LM, 0, 4, EPI, 0, true>(a, c) : launch_one<64, 32, LM, 0, 4, EPI>(a, c);
+    }
+    return launch_one<64, 64, LM, 0, 4, EPI>(a, c);
+}
+#endif
 
 // GEN: the generic epilogue's instance -- CL_EPI_GENERIC, or, for a full step under the Laplace likelihood, CL_EPI_GENERIC_LAPLACE
 template <int MODE, int GEN = CL_EPI_GENERIC>
@@ -1362,8 +1400,8 @@ static int launch_mode(const cl_mlp_args& a, const cl_launch_ctx& c) {
 #if CL_PLAIN_UNIT
     if constexpr (MODE == 0 && GEN == CL_EPI_GENERIC) {
         const cl_epilogue e = mlp_epilogue(a, MODE, CL_ROUTE_MLP);
-        if (e == CL_EPI_PLAIN_NORMAL) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_NORMAL>(a, g.DP, c);
-        if (e == CL_EPI_PLAIN_STUDENTT) return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, CL_EPI_PLAIN_STUDENTT>(a, g.DP, c);
+        if (e == CL_EPI_PLAIN_NORMAL) return launch_plain64<CL_EPI_PLAIN_NORMAL>(a, g.DP, c);
+        if (e == CL_EPI_PLAIN_STUDENTT) return launch_plain64<CL_EPI_PLAIN_STUDENTT>(a, g.DP, c);
     }
 #endif
     return launch_dp<64, CL_MLP_LMAX_W64, MODE, 4, GEN>(a, g.DP, c);

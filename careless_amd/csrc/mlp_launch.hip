@@ -1,10 +1,11 @@
 // The launch layer of the scaler kernels (host code only, no kernel): every cl_elbo_mono_fwd_bwd / cl_mlp_forward / cl_mlp_backward_ext
 // call is decided here -- entry check, mlp_route, mlp_check, grid clamp, mlp_dispatch -- and handed to the lane kernel's launch layer
 // (elbo_lane.hip), the narrow kernel (elbo_narrow.hip) or the unit of elbo_mlp.hip that compiles the route (cl_mlp_unit<route>).
-// cl_mlp_route, cl_mlp_epilogue, cl_mlp_check and cl_mlp_kernel_name answer from the same functions without launching.
+// cl_mlp_route, cl_mlp_epilogue, cl_mlp_instance_traits, cl_mlp_check and cl_mlp_kernel_name answer from the same functions without launching.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "cl_kernels.h"
 
 // The A/B switches (bisection and measurement runs; unset or anything but "0" = on), read here and nowhere else.  Each keeps shapes off
@@ -14,19 +15,38 @@
 //   CARELESS_HIP_LANE_W12=0     widths 11, 12 off the lane kernel (the narrow kernel they ran on until round 6)
 //   CARELESS_HIP_LANE_DEPTHS=0  depths other than the default off the lane kernel (until round 5)
 //   CARELESS_HIP_LANE_BLOCKS=0  the head-less blocks of a chain off the lane kernel (the chain unit of elbo_mlp.hip)
-// and one keeps launches off an instance of the kernel the route names:
+// and two keep launches off an instance of the kernel the route names:
 //   CARELESS_HIP_EPI=0          the 64-wide instances off their plain epilogue (the generic one: every launch until this switch came)
-struct RouteSwitches { bool lane, narrow, w12, depths, blocks, epi; };
+//   CARELESS_HIP_EXACT=0        the plain-epilogue instances off their exact forms (mlp_traits): all DP / 4 metadata k-steps and the
+//                               run-time depth, every launch's instance until this switch came.  Measurement only, for telling the two apart:
+//                               exactly "k1" keeps the trimmed k-steps alone, exactly "depth" the compile-time depth alone
+struct RouteSwitches { bool lane, narrow, w12, depths, blocks, epi, exact_k1, exact_depth; };
 static bool switch_on(const char* name) { const char* e = getenv(name); return !(e != nullptr && e[0] == '0'); }
+// (one part of a two-part switch: off with the switch, and when the value is exactly the OTHER part's word -- measurement runs only)
+static bool switch_part(const char* name, const char* other) { const char* e = getenv(name); return switch_on(name) && !(e != nullptr && strcmp(e, other) == 0); }
 static const RouteSwitches& route_switches() {
     static const RouteSwitches s{switch_on("CARELESS_HIP_LANE"), switch_on("CARELESS_HIP_NARROW"), switch_on("CARELESS_HIP_LANE_W12"),
-                                 switch_on("CARELESS_HIP_LANE_DEPTHS"), switch_on("CARELESS_HIP_LANE_BLOCKS"), switch_on("CARELESS_HIP_EPI")};
+                                 switch_on("CARELESS_HIP_LANE_DEPTHS"), switch_on("CARELESS_HIP_LANE_BLOCKS"), switch_on("CARELESS_HIP_EPI"),
+                                 switch_part("CARELESS_HIP_EXACT", "depth"), switch_part("CARELESS_HIP_EXACT", "k1")};
     return s;
 }
 // The epilogue of the instance a launch on route `r` runs (cl_mlp_epilogue; the plain unit's launch_mode picks the instance by it).
 cl_epilogue mlp_epilogue(const cl_mlp_args& a, int mode, cl_route r) {
     if (r != CL_ROUTE_MLP || !route_switches().epi || mlp_geom(a, mode, false).WP != 64) return CL_EPI_GENERIC;
     return epi_plain(a, mode);
+}
+// What the instance a launch on route `r` runs is compiled for beyond its printed name (cl_mlp_instance_traits; the plain unit's
+// launch_plain64 picks the instance by it).  The plain-epilogue 64-wide instances come in exact forms: on 32 padded metadata columns
+// with the 6 k-steps that 8 < d <= 24 real columns fill, and on up to 32 with the depth compiled in when the launch runs all LMAX layers.
+MlpTraits mlp_traits(const cl_mlp_args& a, int mode, cl_route r) {
+    if (r < CL_ROUTE_MLP) return {0, false};                             // (the lane and narrow kernels: no MFMA k-steps of this kind)
+    const MlpGeom g = mlp_geom(a, mode, r == CL_ROUTE_MLP_IMGL);
+    MlpTraits t{g.DP / 4, false};
+    if (mlp_epilogue(a, mode, r) == CL_EPI_GENERIC) return t;
+    const RouteSwitches& sw = route_switches();
+    if (sw.exact_k1 && g.DP == 32 && a.d <= 24) t.K1 = 6;
+    if (sw.exact_depth && g.DP <= 32 && a.L == g.LMAX) t.fixed_depth = true;
+    return t;
 }
 
 // Which launcher takes the launch: the one routing decision of the scaler launches (cl_launch_mlp, cl_mlp_kernel_name_of, cl_mlp_route).

@@ -329,6 +329,17 @@ typedef enum cl_epilogue {
     CL_EPI_PLAIN_STUDENTT        /* plain epilogue, Student-T likelihood */
 } cl_epilogue;
 int cl_mlp_epilogue(const cl_mlp_args* args, int mode);
+/* What that instance is compiled for beyond the name cl_mlp_kernel_name prints.  The plain-epilogue 64-wide instances come in exact
+ * forms: (a) on 32 padded metadata columns, the first layer runs the 6 MFMA k-steps that 8 < d <= 24 real columns fill instead of all 8;
+ * (b) on up to 32 padded columns, a launch with L = cl_mlp_max_layers(w) layers runs an instance with the depth compiled in.  The
+ * scaler gradient is the same element for element (zeros may differ in sign), everything else up to the order of the float atomics.
+ * Returns the number of first-layer k-steps (4 metadata columns each; 0 on the lane and narrow kernels' routes) in the low byte, OR-ed
+ * with CL_TRAIT_FIXED_DEPTH when the depth is compiled in; -2 for CL_ROUTE_NONE, -1 for bad arguments.  CARELESS_HIP_EXACT=0 keeps
+ * every launch on the instances with all k-steps and a run-time depth (A/B runs); the values "k1" and "depth", matched as whole words,
+ * keep form (a) or (b) alone and are for measuring the two apart, not for use.  Needs no device. */
+#define CL_TRAIT_K1_MASK 0xff
+#define CL_TRAIT_FIXED_DEPTH 0x100
+int cl_mlp_instance_traits(const cl_mlp_args* args, int mode);
 /* Diagnostics: the name of the kernel instance the launch cl_mlp_route chose runs, e.g. "elbo_lane_kernel<10, 0, false, false>": what a
  * rocprofv3 kernel trace lists; "(unsupported)" for CL_ROUTE_NONE.  The lane kernel's names leave out trailing template parameters at
  * their defaults; the launches of a layer block (CL_ROUTE_LANE_BLOCK) print all of them, the mode last:
