@@ -17,39 +17,49 @@ HBM layout owned by the engine (see include/careless_hip.h):
     observation shard      : refl_id i32, image_id i32, meta_t [d][n_pad], iobs, sig [, noise_row]   (immutable)
 PyTorch is used for device memory, streams and torch.distributed only.
 
-Round 4: the observation layouts and the data-parallel splits live in careless_amd/obs.py, the layer-by-layer path of scalers wider
-than 64 in careless_amd/wide.py, the data term of a step behind a frozen scaler in careless_amd/frozen.py (mixins of `ElboEngine`); this file keeps the flat parameter layout, the step schedule and the helpers
-behind the plugin protocol methods.
+What lives where (one role per module; every class below is a mixin of `ElboEngine`, none of the modules imports this one):
+    obs.py      the observation layouts and the data-parallel splits
+    flat.py     the flat parameter vector and the step workspace
+    plan.py     every decision taken without a device, and THE route of a piece's data term (`data_term_route`)
+    fused.py    `FusedPath`: the fused scaler launches (plain, peeled, two-pass Laue, chain) and their argument fill
+    wide.py     `WidePath`: scalers wider than 64, layer by layer
+    frozen.py   `FrozenPath`: the data term behind a frozen scaler
+    slots.py    `SlotPath`: the slot likelihood those three routes share
+    det.py      `DetPath`: deterministic mode's buffers and fixed-order sums
+    nlik.py     `NlikPath`: the neural likelihood's buffers and launches
+This file keeps the engine itself -- the constructor's named steps, the posterior launches, the step schedule (`forward_backward`,
+`_data_term`, the route question `_route`), the optimizer, the history, the validation NLL -- and the stand-alone helpers behind the
+plugin protocol methods.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-from dataclasses import dataclass
-from functools import cached_property
-from itertools import accumulate
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 from careless_amd import _lib
-from careless_amd._lib import AdamArgs, DetArgs, LaueArgs, MlpArgs, NlikArgs, RefPriorArgs, RwArgs, TnArgs, check, ptr
-from careless_amd.frozen import FrozenPath
+from careless_amd._lib import AdamArgs, MlpArgs, RefPriorArgs, RwArgs, TnArgs, check, ptr
 from careless_amd.models.base import BaseModel
-from careless_amd.models.scaling.image import image_layer_layout
-from careless_amd.models.scaling.nn import dense_layout, dense_slices
-# (re-exported: the tests, bench.py and scripts import the sharding / layout names from here)
+from careless_amd.models.scaling.nn import dense_layout
+# (re-exported, here and below: the tests, bench.py, the scripts and the plugin classes import these names from this module)
 from careless_amd.obs import (GRANULE, ObsChunks, ObsData, Shard, _EmptyObs, _ShardRows, _np, _tiles, image_order, laue_group_shard,  # noqa: F401
                               launch_row_limit, make_shard, meta_by_image, meta_feature_major, meta_row_major, owner_bounds, owner_shard,
                               pack_by_image, pack_laue)
+from careless_amd.flat import FLAT_GROUPS, FlatLayout, Workspace, bind_flat, carve_workspace, make_layout, split_flat  # noqa: F401
+from careless_amd.plan import (BIJ_KINDS, REFPRIOR_KINDS, LayerBlock, Route, ScalerPlan, chain_plan, check_deterministic,  # noqa: F401
+                               check_neural_likelihood, data_term_route, plan_scaler, posterior_kind, prior_kind, reference_prior_arrays,
+                               switch, wants_owner_shard)
+from careless_amd.det import DetBuffers, DetPath  # noqa: F401
+from careless_amd.frozen import FrozenPath
+from careless_amd.fused import FusedPath, PeelBuffers, _copy_args, block_fields, scaler_fields  # noqa: F401
+from careless_amd.nlik import NlikBuffers, NlikPath  # noqa: F401
+from careless_amd.slots import SlotPath
 from careless_amd.wide import WidePath, WideShape, hidden_forward, row_chunks
 
 TILE = _lib.CL_MLP_TILE
-REFPRIOR_KINDS = {"normal": _lib.CL_REFPRIOR_NORMAL, "laplace": _lib.CL_REFPRIOR_LAPLACE, "studentt": _lib.CL_REFPRIOR_STUDENTT,
-                  "rice_woolfson": _lib.CL_REFPRIOR_RICE_WOOLFSON}       # ReferencePrior.engine_kind -> cl_refprior_args.kind
-BIJ_KINDS = {"exp": _lib.CL_BIJ_EXP, "softplus": _lib.CL_BIJ_SOFTPLUS}       # MetadataScaler.scale_bijector -> cl_mlp_args.bij_kind
 FORWARD_CHUNK_BYTES = 256 << 20       # `scaler_forward`, layer by layer: bytes of its two alternating hidden buffers; sizes the row chunk
 HISTORY_KEYS = ("loss", "F KLDiv", "NLL", "Grad Norm")
 
@@ -66,409 +76,10 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _copy_args(ma: MlpArgs) -> MlpArgs:
-    a = MlpArgs()
-    C.memmove(C.byref(a), C.byref(ma), C.sizeof(MlpArgs))
-    return a
-
-
-def scaler_fields(a: MlpArgs, mlp, d: int, pmlp: int, imgl=None, pimgl=None, tile_img=None, row_map=None) -> MlpArgs:
-    """The scaler's own fields of `cl_mlp_args`, filled in one place for the training step (`ElboEngine._mlp_args`) and the forward-only
-    path (`scaler_forward`): the Dense stack at `pmlp`, the per-image layers `imgl` at `pimgl`, and what a packed layout adds (`a.n_pad` is set)."""
-    a.mlp = pmlp
-    a.d, a.w, a.L, a.leak = d, mlp.width, mlp.n_layers, mlp.leakiness
-    a.bij_kind, a.eps = BIJ_KINDS[mlp.scale_bijector], mlp.epsilon
-    if row_map is not None:
-        a.n_obs, a.row_map = a.n_pad, ptr(row_map)       # packed: validity is per row (row_map / refl_id = -1)
-    if imgl is not None:
-        a.imgl, a.n_imgl, a.n_images, a.tile_img = pimgl, imgl.n_image_layers, imgl.max_images, ptr(tile_img)
-    return a
-
-
-def block_fields(a: MlpArgs, b: "LayerBlock", pmlp: int, x: int) -> MlpArgs:
-    """`a` turned into the launch of block `b` of a chain: its slice of the parameters at `pmlp`, its input `x` (metadata or the previous block's output)."""
-    a.mlp = pmlp + 4 * b.off
-    a.d, a.L, a.meta_t = b.d_in, b.l1 - b.l0, x
-    return a
-
-
-# ------------------------------------------------------------------------------------------------------------
-# layout of the flat parameter vector
-# ------------------------------------------------------------------------------------------------------------
-FLAT_GROUPS = ("q_loc", "q_scale", "mlp", "img", "imgl", "ev11", "dwr")      # the groups of the flat vector, in storage order
-
-
-@dataclass
-class FlatLayout:
-    """The flat parameter vector (`groups`).  The group "ev11" holds the likelihood's trainable floats: the three scalars of the Evans-2011
-    error model, or the network of a neural likelihood (`lik_dense`, its Dense slices) -- never both."""
-    R: int
-    P: int
-    n_img: int                 # M - 1 trainable image scales (0 when image scales are off)
-    seg_off: List[int]         # tensor boundaries (Keras trainable-variable granularity) for per-tensor clipnorm
-    seg_owner: List[str]       # "q" | "scaler" | "likelihood" per tensor (for --freeze-*)
-    n_ev11: int = 0            # the likelihood's trainable floats: 3 with the Evans-2011 error model, P_lik with a neural likelihood
-    n_dwr: int = 0             # number of ASUs with --optimize-double-wilson-r
-    n_imgl: int = 0            # floats of the per-image layers (NeuralImageScaler: `image_layer_layout`)
-    lik_dense: Optional[list] = None      # a neural likelihood's Dense slices [(kernel offset, out, in, bias offset)] inside its group
-
-    @cached_property
-    def groups(self) -> Tuple[Tuple[str, int, int], ...]:
-        """THE table of the flat vector: (name, offset, count) of its groups in storage order; an absent group has count 0.  Every
-        offset below, `n`, the binding of the plugin objects (`bind_flat`) and the per-tensor split (`split_flat`) come from it."""
-        counts = (self.R, self.R, self.P, self.n_img, self.n_imgl, self.n_ev11, self.n_dwr)
-        return tuple(zip(FLAT_GROUPS, accumulate(counts, initial=0), counts))
-
-    @cached_property
-    def _span(self) -> Dict[str, Tuple[int, int]]:
-        return {name: (off, cnt) for name, off, cnt in self.groups}
-
-    def off(self, group: str) -> int:
-        return self._span[group][0]
-
-    def view(self, flat: torch.Tensor, group: str) -> torch.Tensor:
-        off, cnt = self._span[group]
-        return flat[off:off + cnt]
-
-    n = property(lambda self: sum(self.groups[-1][1:]))
-    off_mlp = property(lambda self: self.off("mlp"))
-    off_img = property(lambda self: self.off("img"))
-    off_imgl = property(lambda self: self.off("imgl"))
-    off_ev11 = property(lambda self: self.off("ev11"))
-    off_dwr = property(lambda self: self.off("dwr"))
-
-
-def make_layout(R: int, d: int, w: int, L: int, n_img: int, n_ev11: int = 0, n_dwr: int = 0, imgl=None, lik_dense=None) -> FlatLayout:
-    """`imgl` = (K, M): K per-image layers over M images (NeuralImageScaler).  `lik_dense`: the Dense slices of a neural likelihood's
-    network (`NeuralLikelihood.layer_slices`) -- the likelihood's group then holds the network, one segment per kernel and per bias."""
-    if lik_dense is not None and n_ev11:
-        raise NotImplementedError("a neural likelihood and the Evans-2011 error model are mutually exclusive (the reference has no such class)")
-    seg, owner = [0, R, 2 * R], ["q", "q"]
-    for _, out, _, ob in dense_slices(d, w, L):       # kernel and bias of every Dense layer, then of the head
-        seg += [2 * R + ob, 2 * R + ob + out]; owner += ["scaler", "scaler"]
-    off = seg[-1]
-    P = off - 2 * R
-    if n_img > 0:
-        off += n_img; seg.append(off); owner.append("scaler")
-    n_imgl = 0
-    if imgl is not None:
-        K, M = imgl
-        blocks, n_imgl = image_layer_layout(K, M, w)
-        for ow, ob in blocks:                # ImageLayer kernel (M, w, w) and bias (M, w) (image.py:76-88)
-            seg += [off + ob, off + ob + M * w]; owner += ["scaler", "scaler"]
-        off += n_imgl
-    for _ in range(n_ev11):              # Sdfac, Sdadd, SdB: three scalar variables (mono.py:42-44)
-        off += 1; seg.append(off); owner.append("likelihood")
-    if lik_dense is not None:            # kernel and bias of every Dense layer of the likelihood's network, then of its head (mono.py:79-92)
-        for _, out, _, ob in lik_dense:
-            seg += [off + ob, off + ob + out]; owner += ["likelihood", "likelihood"]
-        n_ev11 = seg[-1] - off
-        off = seg[-1]
-    if n_dwr > 0:                        # the double-Wilson r vector (wilson.py:105-110)
-        off += n_dwr; seg.append(off); owner.append("prior")
-    return FlatLayout(R, P, n_img, seg, owner, n_ev11, n_dwr, n_imgl, None if lik_dense is None else list(lik_dense))
-
-
-def bind_flat(flat: torch.Tensor, lay: FlatLayout, q, mlp, img=None, imgl=None, lik=None, prior=None) -> None:
-    """The plugin objects become views into `flat`: the tensor that holds each group of `lay` is copied into it and the plugin attribute
-    rebound to that slice, in one loop over (group, holder, attribute).  (A group whose count is 0 is passed over: its holder may be
-    None.)  Any device: needs no engine."""
-    for group, holder, attr in (("q_loc", q, "loc_raw"), ("q_scale", q, "scale_raw"), ("mlp", mlp, "flat"), ("img", img, "_scales"),
-                                ("imgl", imgl, "flat"), ("ev11", lik, "raw"), ("dwr", prior, "r_raw")):
-        view = lay.view(flat, group)
-        if view.numel() > 0:
-            view[:] = getattr(holder, attr).to(flat.device)
-            setattr(holder, attr, view)
-
-
-def split_flat(g: torch.Tensor, lay: FlatLayout, dense, imgl_views=None) -> List[torch.Tensor]:
-    """`g`, a vector laid out like the parameters, per trainable tensor in the oracle's order and Keras shapes: the groups of `lay` in
-    order, the Dense stack by `dense` (`MetadataScaler.layer_slices`) as kernel (in, out) and bias per layer, the per-image block by
-    `imgl_views` (`NeuralImageScaler.layer_views`), a neural likelihood's network by `lay.lik_dense` like the Dense stack."""
-    out = []
-    for name, off, cnt in lay.groups:
-        v = g[off:off + cnt]
-        if name == "mlp":
-            for ow, o, i, ob in dense:
-                out += [v[ow:ow + o * i].view(o, i).t(), v[ob:ob + o]]
-        elif name == "imgl" and cnt > 0:
-            out += imgl_views(v)
-        elif name == "ev11" and cnt > 0 and lay.lik_dense is not None:
-            for ow, o, i, ob in lay.lik_dense:
-                out += [v[ow:ow + o * i].view(o, i).t(), v[ob:ob + o]]
-        elif cnt > 0:
-            out.append(v)
-    return out
-
-
-@dataclass(frozen=True)
-class Workspace:
-    """The step workspace in floats, as (offset, count) per region (`carve_workspace`).  `dz_f`, `grads`, the four floats of slack behind
-    them, `msg_norm`, `scalars` (4 doubles), `seg_sq` (nseg doubles) and `own_scratch` (5 doubles) follow each other without overlap;
-    `msg` (what an owner-mode step all-reduces: the gradient behind a and b, the slack, the norm terms) and `ws_step` (what such a step
-    clears: everything from the gradient's padding on) are spans over them."""
-    owner: bool
-    dz_f: Tuple[int, int]
-    grads: Tuple[int, int]
-    msg: Tuple[int, int]
-    msg_norm: Tuple[int, int]
-    scalars: Tuple[int, int]
-    seg_sq: Tuple[int, int]
-    own_scratch: Tuple[int, int]
-    ws_step: Tuple[int, int]
-    total: int
-
-    @property
-    def aligned(self) -> bool:
-        """In a 16-byte aligned allocation the buffer a data-parallel step all-reduces -- the flat gradient (row split) or the message
-        (reflection-owner split) -- and `ws_step` start on 16-byte boundaries, the doubles on 8-byte ones."""
-        reduced = self.msg if self.owner else self.grads
-        return reduced[0] % 4 == 0 and self.ws_step[0] % 4 == 0 and all(r[0] % 2 == 0 for r in (self.scalars, self.seg_sq, self.own_scratch))
-
-
-def carve_workspace(R: int, S: int, n: int, nseg: int, owner: bool) -> Workspace:
-    """Offsets of the step workspace for R reflections, S samples, n parameters in nseg tensors.  The buffer a step all-reduces starts on
-    a 16-byte boundary: the flat gradient (row split), or -- reflection-owner split -- what lies behind a and b in it (two floats of
-    padding in front of the gradient when 2 R is not a multiple of four)."""
-    pad = (-2 * R) % 4 if owner else 0
-    g = (R * S + 3) // 4 * 4 + pad
-    sc = (g + n + 8 + 3) // 4 * 4           # 4 floats of slack, then the 4 norm terms of the owner-mode message; 16-byte aligned
-    seg = sc + 8                            # 4 doubles = 8 floats
-    own = seg + 2 * nseg                    # owner mode: 4 double accumulators + the block ticket of cl_owner_qnorm
-    total = own + 10
-    return Workspace(owner, dz_f=(0, R * S), grads=(g, n), msg=(g + 2 * R, n + 8 - 2 * R), msg_norm=(g + n + 4, 4), scalars=(sc, 8),
-                     seg_sq=(seg, 2 * nseg), own_scratch=(own, 10), ws_step=(g - pad, total - (g - pad)), total=total)
-
-
-@dataclass
-class LayerBlock:
-    """One launch of a chained scaler: Dense layers [l0, l1) of the stack; the last block also carries the Dense(2) head."""
-    l0: int
-    l1: int
-    d_in: int          # width of the block's input: the metadata width for the first block, the hidden width for the others
-    off: int           # offset of the block's parameters inside the scaler's flat W^T layout
-    P: int             # number of parameters of the block (what its gradient partials hold)
-    final: bool
-
-
-def chain_plan(d: int, w: int, L: int, max_layers: int, last: int = 0) -> List[LayerBlock]:
-    """Split a scaler of L Dense layers into the fewest, evenly sized blocks of at most `max_layers` layers (one block = one
-    launch of the fused kernel, include/careless_hip.h: act_out / dH_ext / dX_out).  `last` > 0: the last block has exactly that many
-    layers (round 6: 20 of them on the default scaler's lane kernel), the layers in front of it are split evenly."""
-    if last > 0 and L > last:
-        K = -(-(L - last) // max_layers)
-        sizes = [(L - last) // K + (1 if i < (L - last) % K else 0) for i in range(K)] + [last]
-        K += 1
-    else:
-        K = -(-L // max_layers)
-        sizes = [L // K + (1 if i < L % K else 0) for i in range(K)]
-    layers, head = dense_layout(d, w, L)
-    off_of = lambda l: layers[l][0] if l < L else head
-    blocks, l0 = [], 0
-    for k, n in enumerate(sizes):
-        l1 = l0 + n
-        final = k == K - 1
-        P = off_of(l1) - off_of(l0) + (2 * w + 2 if final else 0)
-        blocks.append(LayerBlock(l0, l1, d if k == 0 else w, off_of(l0), P, final))
-        l0 = l1
-    return blocks
-
-
-@dataclass
-class ScalerPlan:
-    wide: bool                             # layer by layer (careless_amd/wide.py): no fused launch holds the scaler
-    peel: bool                             # the first Dense layer runs in front of the training launch (csrc/elbo_peel.hip; DESIGN 4.4)
-    blocks: Optional[List[LayerBlock]]     # a chain of layer blocks: deeper than one launch holds
-    chain_lane: bool                       # ... whose last block runs on the lane kernel (dZ_0 out, then cl_chain_dx)
-    route: int                             # cl_mlp_route of the training launch (`ElboEngine.training_launch`); CL_ROUTE_NONE when wide
-
-
-def plan_scaler(lib, d: int, w: int, L: int, K: int = 0, laue: bool = False, two_pass: bool = False, gmax: int = 1, ev11: bool = False,
-                deterministic: bool = False, lik_kind: int = 0) -> ScalerPlan:
-    """How `ElboEngine` runs L Dense layers of width w on d columns with K per-image layers (`gmax`: the largest harmonic group): the plan
-    chooses the launches -- peel the first layer, cut a deep scaler into blocks, go layer by layer --, the library's routes decide."""
-    NONE, LANE, NARROW, LANE_IMGL = _lib.CL_ROUTE_NONE, _lib.CL_ROUTE_LANE, _lib.CL_ROUTE_NARROW, _lib.CL_ROUTE_LANE_IMGL
-    proto = dict(d=d, w=w, L=L, S=1, refl_id=1, meta_t=1, iobs=1, sig=1, mlp=1, z_f=1, dz_f=1, partials=1, scalars=1, stop_flag=1,
-                 ev11=int(ev11), d_ev11=int(ev11), lik_kind=lik_kind)      # (the lane and the narrow kernel refuse CL_LIK_LAPLACE: the routes say so)
-    det = dict(dzf_obs=1, dimg_obs=1, nll_part=1, det_slot=1, ev11_part=int(ev11)) if deterministic else {}
-    route = lambda mode, **kw: _lib.mlp_route(lib, mode, **{**proto, **kw})
-    if w > 64 or d > 64:        # a layer's activations no longer fit a wave's registers next to the weight-gradient blocks
-        return ScalerPlan(True, False, None, False, NONE)
-    max_plain = int(lib.cl_mlp_max_layers(w))
-    if K == 0 and L > max_plain:
-        # a chain of layer blocks, activations exchanged through HBM.  The LAST 20 layers (widths 11, 12: 19, the deepest twelve-wide instance
-        # without spilled registers) and the head on the lane kernel where it takes them, dZ_0 out, `cl_chain_dx` turns it into the gradient
-        # of the block's input (round 6: 24 x 10 at 4 M observations 3.13 -> 1.4 ms per step).  Laue data: the two-pass path.
-        last = 19 if w in (11, 12) else 20
-        chain_lane = not laue and route(0, d=w, L=last, dZ0_out=1) == LANE
-        blocks = chain_plan(d, w, L, min(max_plain, last) if chain_lane else max_plain, last=last if chain_lane else 0)
-        last_block = dict(d=w, L=blocks[-1].l1 - blocks[-1].l0, **({"dZ0_out": 1} if chain_lane else {"dX_out": 1}))
-        return ScalerPlan(False, False, blocks, chain_lane, route(0, **last_block, **det))
-    # Laue rows the fused kernel cannot take as harmonic groups: the two-pass path, cl_mlp_forward + cl_mlp_backward_ext on the scaler itself
-    two_pass = laue and (two_pass or gmax > GRANULE)
-    layout = dict(dict(row_map=1, tile_img=1, imgl=1, d_imgl=1, n_imgl=K, n_images=1) if K else {},
-                  **(dict(row_map=1, gmeta=1, tile_gmax=1) if laue and not two_pass else {}))
-    unpeeled, peeled = route(0, **layout), route(0, **layout, d=w, dZ0_out=1)
-    if K:       # (the lane kernel's per-image-layer instances behind the peeled layer)
-        peel = unpeeled != LANE_IMGL and peeled == LANE_IMGL
-    else:
-        # more columns than the lane / narrow kernel holds: cl_peel_forward computes the first layer's pre-activations, the fused kernel runs
-        # on them (w "metadata columns") with an identity first layer and hands back dZ_0 for cl_peel_backward (DESIGN 4.4).  (Widths 13 .. 15
-        # are no faster on the narrow kernel than on elbo_mlp.hip's 16-wide instance: profiles/r5_envelope.txt, 20 x 15 on 37 columns 2.02 vs 2.19 ms.)
-        peel = unpeeled not in (LANE, NARROW) and peeled in (LANE, NARROW) and w <= 12
-    peel = peel and bool(lib.cl_peel_supported(d, w, L))
-    train = dict(layout, d=w, dZ0_out=1) if peel else layout          # (the two-pass path has no peeled launch)
-    launches = [route(1, **layout, loc_out=1, sig_out=1), route(2, **layout, dO_ext=1)] if two_pass else [route(0, **train)]
-    if NONE in launches:
-        return ScalerPlan(True, False, None, False, NONE)
-    return ScalerPlan(False, peel, None, False, launches[-1] if two_pass else route(0, **train, **det))
-
-
-def prior_kind(prior, owner: bool = False) -> int:
-    """CL_PRIOR_* under which the engine runs `prior` (`owner`: on a reflection-owner split); NotImplementedError for what it does not
-    run.  Host logic: needs no device."""
-    from careless_amd.models.priors.empirical import ReferencePrior
-    from careless_amd.models.priors.wilson import DoubleWilsonPrior, WilsonPrior
-    if isinstance(prior, ReferencePrior):
-        if prior.base_dist is None or prior.engine_kind not in REFPRIOR_KINDS:
-            raise NotImplementedError(f"prior {type(prior).__name__} has no base distribution the HIP engine evaluates (use one of its subclasses: "
-                                      "Normal-, Laplace-, StudentT- or RiceWoolfsonReferencePrior)")
-        if owner:
-            raise NotImplementedError(f"the reflection-owner split runs the Wilson prior only, not {type(prior).__name__}: use the row split")
-        return _lib.CL_PRIOR_REFERENCE
-    if isinstance(prior, DoubleWilsonPrior):
-        return _lib.CL_PRIOR_DOUBLE_WILSON
-    if isinstance(prior, WilsonPrior):
-        return _lib.CL_PRIOR_WILSON
-    raise NotImplementedError(f"prior {type(prior).__name__} is not supported by the HIP engine yet")
-
-
-def posterior_kind(q) -> str:
-    """The surrogate posteriors the engine samples: "truncated_normal" (cl_tn_forward / _backward) or "rice_woolfson" (cl_rw_forward /
-    _backward: the trainable class of `RiceWoolfson.from_loc_and_scale`); NotImplementedError for anything else -- the host-side
-    `RiceWoolfson(loc, scale, centric)` of the reference priors included."""
-    from careless_amd.models.merging.surrogate_posteriors import TrainableRiceWoolfson, TruncatedNormal
-    if isinstance(q, TruncatedNormal):
-        return "truncated_normal"
-    if isinstance(q, TrainableRiceWoolfson):
-        return "rice_woolfson"
-    raise NotImplementedError(f"surrogate posterior {type(q).__name__} is not supported by the HIP engine")
-
-
-def check_neural_likelihood(lik, laue: bool, world: int = 1, lib=None) -> bool:
-    """Is `lik` a neural likelihood (`NeuralNormalLikelihood`: an error model learned from the data, csrc/elbo_nlik.hip)?  NotImplementedError
-    for what the engine does not run it on: Laue data (the reference has no Laue form), the Evans-2011 error model beside it (the
-    reference has no such class), more than one rank (the mean of delta over all rows would take two more collectives per step: DESIGN 7),
-    a network the kernels do not hold.  Host logic: needs no device (`lib`: the loaded library, for `cl_nlik_supports`)."""
-    if not getattr(lik, "neural", False):
-        return False
-    name = type(lik).__name__
-    if laue:
-        raise NotImplementedError(f"likelihood {name}: the neural likelihood is monochromatic only (the reference has no Laue form)")
-    if getattr(lik, "ev11", False):
-        raise NotImplementedError(f"likelihood {name}: a neural likelihood and the Evans-2011 error model are mutually exclusive (the reference has no such class)")
-    if world > 1:
-        raise NotImplementedError(f"likelihood {name}: the neural likelihood runs on one rank (its mean over all rows would need two more "
-                                  f"collectives per step); got a shard of {world} ranks")
-    lib = _lib.get_lib() if lib is None else lib
-    if not lib.cl_nlik_supports(int(lik.n_layers), int(lik.width)):
-        raise NotImplementedError(f"likelihood {name}({lik.n_layers}, {lik.width}): the HIP kernels hold 1 .. 4 hidden layers of width 1 .. 32")
-    return True
-
-
-def switch(model, attr: Optional[str], env: str, default: bool = False, env_adds: bool = False) -> bool:
-    """One on / off switch of the engine: `model.<attr>` where it is set (not None), else the environment variable `env` ("1" on, "0"
-    off), else `default`.  `env_adds`: the variable also switches on what the attribute leaves off (`deterministic`)."""
-    want = getattr(model, attr, None) if attr is not None else None
-    if want is None or (env_adds and not want):
-        env = os.environ.get(env, "")
-        want = (env != "0") if default else (env == "1")
-    return bool(want)
-
-
-def check_deterministic(plan: ScalerPlan, laue: bool, two_pass: bool, imgl: bool, S: int, dw_trainable: bool) -> None:
-    """NotImplementedError for what the deterministic mode does not cover, of a scaler run by `plan` on `laue` data (`two_pass`: asked for
-    by the model) with per-image layers (`imgl`), S samples and a trainable double-Wilson r (`dw_trainable`).  Host logic: needs no device."""
-    # (wide scalers: monochromatic rows only -- they are their own slots and one kernel holds every float atomic of the path --, with a
-    #  sample count that divides 64, so that a row's samples sit inside one wave)
-    wide_det_ok = plan.wide and not laue and 64 % S == 0
-    # (per-image layers: where the training launch has a route with the deterministic stores -- the lane kernel's instances, one wave per image)
-    imgl_det_ok = plan.route != _lib.CL_ROUTE_NONE
-    if two_pass or (plan.wide and not wide_det_ok) or (imgl and not imgl_det_ok) or (plan.blocks is not None and laue) or dw_trainable:
-        raise NotImplementedError("deterministic mode covers monochromatic and single-pass Laue data, the Wilson and the double-Wilson prior "
-                                  "(fixed r), Normal / Student-T likelihoods with or without the Evans-2011 error model, the Laplace likelihood, scalers of any depth up to "
-                                  "width 64, up to three per-image layers on 2 .. 20 Dense layers of width 5 .. 10 (two on 19; the default scaler's kernels) and, "
-                                  "for monochromatic data with a sample count that divides 64, scalers wider than 64; the two-pass "
-                                  "Laue path (also under a chained scaler), a trainable double-Wilson r and every other shape with per-image layers "
-                                  "keep their float atomics")
-
-
-def wants_owner_shard(want: bool, prior, world: int, owner_given: bool, laue: bool, double_wilson: bool, wide: bool, imgl: bool,
-                      deterministic: bool) -> bool:
-    """Does an engine asked for the reflection-owner split (`want`) on `world` ranks cut its rows by reflection (`owner_shard`)?  Not on one
-    rank, not when its shard already is an owner's (`owner_given`), not for Laue data (a harmonic group mixes reflections), the
-    double-Wilson prior (a child's parent may live on another rank), wide scalers, per-image layers or the deterministic mode: they keep
-    the row split.  NotImplementedError where the split is asked for or given and the prior is not one it runs.  Host logic: needs no device."""
-    if owner_given or (want and world > 1):
-        prior_kind(prior, owner=True)                # (the reflection-owner split is Wilson-only: raises for a reference prior)
-    return bool(want and world > 1 and not laue and not double_wilson and not wide and not imgl and not deterministic and not owner_given)
-
-
-def reference_prior_arrays(prior, R: int) -> dict:
-    """What `cl_ref_prior` takes from an empirical reference prior, expanded to all R reflections (host arrays); ValueError where the
-    prior's lengths do not match R or a Student-t prior has no positive dof."""
-    out = dict(kind=REFPRIOR_KINDS[prior.engine_kind], dof=float(prior.dof), loc=prior.loc_full(R), scale=prior.scale_full(R),
-               observed=prior.observed_mask(R), centric=prior.centric_full(R))
-    if out["kind"] == _lib.CL_REFPRIOR_STUDENTT and not out["dof"] > 0.0:
-        raise ValueError(f"{type(prior).__name__} needs dof > 0 (got {prior.dof})")
-    return out
-
-
-@dataclass
-class DetBuffers:
-    """Deterministic mode, per observation set (`ObsData.det`, `ElboEngine._det_attach`): the per-observation stores of the kernels and the
-    sort orders `cl_det_reduce` walks."""
-    slot: Optional[torch.Tensor]        # position of every observation in reflection order (cl_mlp_args.det_slot); None past the 32-bit byte offset
-    dzf: torch.Tensor                   # amplitude gradient per (observation, sample)
-    dimg: torch.Tensor                  # image-scale term per observation
-    nll: torch.Tensor                   # NLL per workgroup: `grid` slots per piece, then the slot / padded-slot likelihood launch's
-    refl: Tuple[torch.Tensor, torch.Tensor]     # (permutation, segment starts) by reflection
-    img: Tuple[torch.Tensor, torch.Tensor]      # ... by image
-    M: int                              # number of images
-    pieces: int                         # launches the set is cut into
-    grid: int                           # workgroups of one of them
-    ev11: Optional[torch.Tensor] = None         # Evans-2011 gradients: three floats per wave of every launch
-
-
-@dataclass
-class NlikBuffers:
-    """A neural likelihood, per observation set (`ObsData.nlik` / `ObsChunks.nlik`, `ElboEngine._nlik_attach`): the set's rows in the
-    caller's order -- the mean of delta couples them all, also where `ObsChunks` cuts the set into pieces."""
-    n: int
-    iobs: torch.Tensor                  # [n] raw Iobs, SigIobs in the caller's row order
-    sigiobs: torch.Tensor
-    sigpred: torch.Tensor               # [n + TILE]: cl_nlik_forward's output; the tail keeps the 1.0 of a plain layout's padding rows
-    ws: torch.Tensor                    # cl_nlik_workspace_bytes
-    ipred: Optional[torch.Tensor] = None        # [n][S]: the data term's ipred_out when the caller brings none
-    image_key: Optional[tuple] = None   # what `image` / `pos` were built for: per piece, the layout's own order or a frozen scaler's sorted rows
-    image: Optional[torch.Tensor] = None        # the pieces' sig-shaped images, one behind the other (None: every piece reads sigpred itself)
-    pos: Optional[torch.Tensor] = None  # int32 [n]: position of row i in `image`
-
-
-@dataclass
-class PeelBuffers:
-    """A peeled first layer, per observation set (`ObsData.peel`, `ElboEngine._peel_bufs`), feature-major like meta_t."""
-    u: torch.Tensor                     # the layer's pre-activations
-    dz0: torch.Tensor                   # their gradient
-    parts: torch.Tensor                 # weight-gradient partials of cl_peel_backward
-    nparts: int
-
-
 # ------------------------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------------------------
-class ElboEngine(WidePath, FrozenPath):
-    SLOT_ROWS_ONE_LAUNCH = True      # rows that are their own slot: predict + log-prob + gradient in one `cl_slot_rows` launch (tests flip it)
+class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
     local_only = False               # test hook: a rank shard on one device, the per-rank partial gradient stays in place (no collective call)
     force_allreduce = False          # CARELESS_FORCE_DIST=1: a one-rank run makes every collective call of the multi-GPU step
 
@@ -700,143 +311,6 @@ class ElboEngine(WidePath, FrozenPath):
             o.alloc_chain(self.lib, self.blocks, self.w, self.device, self.chain_lane)
         return o
 
-    def _det_attach(self, obs, pieces):
-        """Buffers of the deterministic mode for one observation set: the per-observation stores of the fused kernel and the sort
-        orders (by reflection, by image; stable, so sums run in row order) that `cl_det_reduce` walks."""
-        dev = self.device
-        if pieces[0].row_map is not None:
-            # packed layout (single-pass Laue; per-image layers, round 6): the kernels store by the caller's local row (row_map), so the ids go back to that order
-            p0 = pieces[0]
-            if self.laue and not p0.fused_laue:
-                raise NotImplementedError("deterministic mode: harmonic groups of more than 16 rows take the two-pass Laue path, which keeps its float atomics")
-            rm = p0.row_map.cpu().numpy()
-            ok = rm >= 0
-            rid, img = np.zeros(p0.N, dtype=np.int64), np.zeros(p0.N, dtype=np.int64)
-            rid[rm[ok]] = p0.refl_id.cpu().numpy()[ok]
-            img[rm[ok]] = p0.image_id.cpu().numpy()[ok]
-        else:
-            rid = torch.cat([p.refl_id[: p.N] for p in pieces]).cpu().numpy()
-            img = torch.cat([p.image_id[: p.N] for p in pieces]).cpu().numpy()
-        n = len(rid)
-
-        def order(ids, nbins):
-            perm = np.argsort(ids, kind="stable").astype(np.int32)
-            seg = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=nbins))]).astype(np.int32)
-            return torch.as_tensor(perm, device=dev), torch.as_tensor(seg, device=dev)
-        M = self._max_images() or 1
-        # slot[i] = position of observation i in the reflection-sorted order: the kernels store its record THERE (cl_mlp_args.det_slot),
-        # so that the per-reflection sums read contiguous records instead of gathering ~30 random ones each (DESIGN 4.12)
-        perm_r, seg_r = order(rid, self.R)
-        slot = None
-        if 4 * n * self.S < (1 << 32):          # (the kernels address a record with a 32-bit byte offset from the buffer's start)
-            slot = torch.empty(n, dtype=torch.int32, device=dev)
-            slot[perm_r.long()] = torch.arange(n, dtype=torch.int32, device=dev)
-        obs.det = DetBuffers(slot=slot, dzf=torch.zeros(n * self.S, dtype=torch.float32, device=dev), dimg=torch.zeros(n, dtype=torch.float32, device=dev),
-                             nll=torch.zeros(len(pieces) * pieces[0].grid + (_lib.CL_LAUE_LIK_MAX_BLOCKS if (self.laue or self.wide) else 0),
-                                             dtype=torch.float64, device=dev),
-                             refl=(perm_r, seg_r), img=order(img, M), M=M, pieces=len(pieces), grid=pieces[0].grid)
-        if self.ev11:
-            # Evans-2011 gradients: one slot of three floats per wave of every launch (the fused launches' CL_EV11_WAVES per workgroup, then
-            # four per workgroup of the slot / padded-slot likelihood launch), summed in slot order by cl_det_reduce
-            obs.det.ev11 = torch.zeros(3 * (_lib.CL_EV11_WAVES * len(pieces) * pieces[0].grid + 4 * _lib.CL_LAUE_LIK_MAX_BLOCKS), dtype=torch.float32, device=dev)
-        for k, p in enumerate(pieces):
-            p.det_parent, p.det_index = obs, k
-
-    # -- neural likelihood (csrc/elbo_nlik.hip) ------------------------------------------------------------------
-    def _nlik_attach(self, obs, pieces, inputs):
-        """Buffers of the neural likelihood for one observation set: Iobs / SigIobs of all its rows in the order the set's eta and ipred_out
-        are in -- the caller's rows, whatever order a packed layout stores them in; the image order of the wide path's sorted layout, whose
-        eta / ipred_out follow `obs.rows` (`_noise_to_device`, `VariationalMergingModel.call`) --, sigpred and the kernels' workspace."""
-        dev, lik = self.device, self.lik
-        rows = np.concatenate([np.asarray(p.rows, dtype=np.int64) if p.rows is not None else np.arange(p.start, p.start + p.N, dtype=np.int64)
-                               for p in pieces])
-        col = lambda a: torch.as_tensor(np.ascontiguousarray(_np(a).reshape(-1)[rows].astype(np.float32)), device=dev)
-        n = int(len(rows))
-        nbytes = int(self.lib.cl_nlik_workspace_bytes(n, lik.n_layers, lik.width))
-        sigpred = torch.ones(n + TILE, dtype=torch.float32, device=dev)
-        obs.nlik = NlikBuffers(n, col(BaseModel.get_intensities(inputs)), col(BaseModel.get_uncertainties(inputs)), sigpred,
-                               torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev))
-        assert obs.nlik.ws.data_ptr() % 16 == 0
-        for p in pieces:
-            p.sig_now = None                # this step's sigpred in the order the piece's launches read sig (`_nlik_image`, `_sig`)
-
-    def _nlik_image(self, obs, pieces, forms):
-        """`nlik.image` / `nlik.pos` of the set for the forms its pieces' data terms take now, and every piece's `sig_now`: the sig-shaped
-        array in the order its launch reads.  The pos map of a piece: none where sig is stored in the order of ipred_out (the plain layout;
-        the wide path's image-sorted one, whose ipred_out is in that order too), the inverse of `row_map` (packed by image) or of a frozen
-        scaler's sort by reflection (`SortedRows.key` - start)."""
-        from careless_amd.frozen import FrozenForm
-        nb = obs.nlik
-        key = tuple(("sorted", self._frozen_epoch) if f is FrozenForm.SORTED_ROWS else "layout" for f in forms)
-        if nb.image_key == key:
-            return
-        dev, owns, poss = self.device, [], []
-        for p, f in zip(pieces, forms):
-            pos = None
-            if f is FrozenForm.SORTED_ROWS:
-                fz = self._sorted_rows(p)
-                own, src, dst = fz.sig, fz.key.long() - int(p.start), None
-            elif p.row_map is not None:
-                own, dst = p.sig, torch.nonzero(p.row_map >= 0).flatten()
-                src = p.row_map.long().index_select(0, dst)
-            else:
-                own, src = p.sig, None
-            if src is not None:
-                pos = torch.empty(p.N, dtype=torch.int64, device=dev)
-                pos[src] = torch.arange(p.N, dtype=torch.int64, device=dev) if dst is None else dst
-                assert int(src.numel()) == p.N and int(pos.min()) >= 0 and int(pos.max()) < int(own.numel())
-            owns.append(own); poss.append(pos)
-        if all(q is None for q in poss):
-            nb.image = nb.pos = None
-            for p in pieces:
-                p.sig_now = nb.sigpred[p.row0:]                     # (a piece's padding rows: the next piece's rows, or the tail of ones)
-        else:
-            offs = list(accumulate([int(o.numel()) for o in owns], initial=0))
-            nb.image = torch.cat([o.clone() for o in owns])         # padding positions keep the layout's own 1.0
-            nb.pos = torch.cat([(torch.arange(p.N, dtype=torch.int64, device=dev) if q is None else q) + off
-                                for p, q, off in zip(pieces, poss, offs)]).to(torch.int32).contiguous()
-            for p, a, b in zip(pieces, offs, offs[1:]):
-                p.sig_now = nb.image[a:b]
-        nb.image_key = key
-
-    def _nlik_args(self, obs) -> NlikArgs:
-        nb, lik = obs.nlik, self.lik
-        a = NlikArgs()
-        a.iobs, a.sigiobs, a.net = ptr(nb.iobs), ptr(nb.sigiobs), self._param_ptr("ev11")
-        a.L, a.w, a.leak, a.n = lik.n_layers, lik.width, lik.leakiness, nb.n
-        a.sigpred, a.pos, a.sig_image, a.workspace = ptr(nb.sigpred), ptr(nb.pos), ptr(nb.image), ptr(nb.ws)
-        a.stop_flag = ptr(self.stop_flag)
-        return a
-
-    def _nlik_forward(self, obs, injected: bool, st):
-        """sigpred of all rows of the set -- the mean of delta is over the whole set, also when it is cut into pieces -- in the caller's order
-        and in the order every piece's data term reads (`_sig`)."""
-        pieces = obs.children if isinstance(obs, ObsChunks) else [obs]
-        self._nlik_image(obs, pieces, [self._frozen_form(p, injected=injected) for p in pieces])
-        check(self.lib.cl_nlik_forward(C.byref(self._nlik_args(obs)), st), "cl_nlik_forward")
-
-    def _nlik_backward(self, obs, ipred_out, st):
-        """The network's gradient from the step's predictions (`ipred_out`, [n][S] in the caller's order) into the likelihood's slice of
-        the flat gradient."""
-        a = self._nlik_args(obs)
-        a.ipred, a.S, a.w_ll, a.d_net = ptr(ipred_out), self.S, self._w_ll(obs), self._grad_ptr("ev11")
-        check(self.lib.cl_nlik_backward(C.byref(a), st), "cl_nlik_backward")
-
-    def _nlik_ipred(self, obs) -> torch.Tensor:
-        nb = obs.nlik
-        if nb.ipred is None:
-            nb.ipred = torch.empty(nb.n * self.S, dtype=torch.float32, device=self.device)
-        return nb.ipred
-
-    def _sig(self, obs: ObsData, own: torch.Tensor) -> torch.Tensor:
-        """THE hand-over of the likelihood's sigma to a data-term launch (`_mlp_args`, `_slot_args`, `_frozen_rows`): `own`, the observation
-        image's SigIobs in the order the launch reads -- or, under a neural likelihood, this step's sigpred in the same order
-        (`_nlik_forward` set `obs.sig_now`; before the first step -- a routing question -- there is none and the pointer is not read)."""
-        if not self.neural or getattr(obs, "sig_now", None) is None:
-            return own
-        assert obs.sig_now.numel() >= own.numel()
-        return obs.sig_now
-
     def _max_images(self):
         if self.img is not None:
             return self.img.max_images
@@ -950,63 +424,6 @@ class ElboEngine(WidePath, FrozenPath):
         """Pointer to the rows of `obs` inside a per-(row, sample) array of its whole shard (eta, ipred_out): a piece of a chunked shard starts at row0."""
         return None if t is None else t.data_ptr() + 4 * self.S * obs.row0
 
-    def _det_parts(self, obs: ObsData, k: int):
-        """(nll_part, ev11_part) of part k of the shard `obs` belongs to (deterministic mode): the fused launches of its pieces store into parts
-        0 .. pieces - 1 -- det.grid NLL slots, CL_EV11_WAVES Evans-2011 slots of three floats per workgroup --, the slot / padded-slot
-        likelihood launch behind them (k = det.pieces)."""
-        det = obs.det_parent.det
-        return (det.nll.data_ptr() + 8 * det.grid * k,
-                det.ev11.data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det.grid * k if self.ev11 else None)
-
-    def _mlp_args(self, step: int, eta, ipred_out=None, obs: Optional[ObsData] = None) -> MlpArgs:
-        lay = self.layout
-        obs = self.obs if obs is None else obs
-        a = self._step_fields(MlpArgs(), obs, step)
-        a.refl_id = ptr(obs.refl_id); a.image_id = ptr(obs.image_id); a.meta_t = ptr(obs.meta_t)
-        a.iobs = ptr(obs.iobs); a.sig = ptr(self._sig(obs, obs.sig))
-        a.n_obs, a.n_pad = obs.N, obs.n_pad
-        a.obs_offset = obs.start
-        if obs.fused_laue:
-            a.gmeta, a.tile_gmax = ptr(obs.gmeta), ptr(obs.tile_gmax)
-        a.noise_row = ptr(obs.noise_row)
-        scaler_fields(a, self.mlp, self.d, self._param_ptr("mlp"), self.imgl, self._param_ptr("imgl"), obs.tile_img, obs.row_map)
-        if self.imgl is not None:
-            a.d_imgl = self._grad_ptr("imgl")
-        a.use_img = 1 if lay.n_img > 0 else 0
-        a.img = self._param_ptr("img") if lay.n_img > 0 else None
-        a.eta, a.ipred_out = self._shard_rows(obs, eta), self._shard_rows(obs, ipred_out)
-        a.d_img = self._grad_ptr("img") if lay.n_img > 0 else None
-        a.partials = ptr(obs.partials)
-        if self.deterministic:
-            det = obs.det_parent.det
-            if det.slot is not None:
-                a.dzf_obs = det.dzf.data_ptr()                  # (records by slot: positions inside the whole shard, not the piece)
-                a.det_slot = det.slot.data_ptr() + 4 * obs.row0
-            else:
-                a.dzf_obs = det.dzf.data_ptr() + 4 * self.S * obs.row0
-            a.dimg_obs = det.dimg.data_ptr() + 4 * obs.row0
-            a.nll_part, a.ev11_part = self._det_parts(obs, obs.det_index)
-        return a
-
-    def _likelihood_args(self, ma: MlpArgs, obs: ObsData, mode: int = 0):
-        """From `_mlp_args` of `obs`: (arguments, mode) of the scaler launch that computes the likelihood -- the launch `plan.route` is the
-        route of: the last block of a chain with its dZ_0 (lane kernel) or dX out, the backward launch of the two-pass Laue path (mode 2,
-        dL/d(loc, sigma) in), the launch behind a peeled first layer, else the fused launch on the scaler itself.  The data term launches
-        with it, `training_launch` asks about it."""
-        if self.blocks is not None:
-            K = len(self.blocks)
-            ma = self._block_args(ma, obs, K - 1)
-            if self.chain_lane:
-                ma.dZ0_out = ptr(obs.chain_dz0)       # dZ_0 of the block's first layer; `cl_chain_dx` turns it into the gradient of the block's input
-            else:
-                ma.dX_out = ptr(obs.chain_dact[K - 2])
-        elif self.laue and not obs.fused_laue:
-            mode = 2 if mode == 0 else mode
-            ma.dO_ext = ptr(obs.laue_dO)
-        elif self.peel and mode == 0:
-            ma = self._peel_args(ma, obs)
-        return ma, mode
-
     def kernel_name(self, mode: int = 0) -> str:
         """Name of the kernel instance the scaler launches of this engine run (`cl_mlp_kernel_name`: the library's own routing):
         what a rocprofv3 kernel trace lists for the dominant kernel."""
@@ -1018,10 +435,6 @@ class ElboEngine(WidePath, FrozenPath):
         buf = C.create_string_buffer(128)
         check(min(0, self.lib.cl_mlp_kernel_name(C.byref(ma), mode, buf, 128)), "cl_mlp_kernel_name")
         return buf.value.decode()
-
-    def training_launch(self, mode: int = 0):         # (arguments, mode) of the launch kernel_name names; plan.route is its cl_mlp_route
-        obs = self.obs.children[0] if isinstance(self.obs, ObsChunks) else self.obs
-        return self._likelihood_args(self._mlp_args(0, None, None, obs), obs, mode)
 
     def _w_ll(self, obs: ObsData) -> float:
         """Weight of one log-likelihood term: sum / S, or with `kl_weight` the mean over the S x N terms of the observation set
@@ -1126,21 +539,6 @@ class ElboEngine(WidePath, FrozenPath):
         self.dz_f[r0 * self.S:r1 * self.S].zero_()
         self.ws_step.zero_()
 
-    def _det_reduce(self, obs, st):
-        det, lay = obs.det, self.layout
-        a = DetArgs()
-        # (records stored in reflection order -- det_slot -- need no gather list)
-        a.dzf_obs, a.perm_refl, a.seg_refl = ptr(det.dzf), (None if det.slot is not None else ptr(det.refl[0])), ptr(det.refl[1])
-        a.R, a.S, a.dz_f = self.R, self.S, ptr(self.dz_f)
-        if lay.n_img > 0:
-            a.dimg_obs, a.perm_img, a.seg_img = ptr(det.dimg), ptr(det.img[0]), ptr(det.img[1])
-            a.n_images, a.d_img = det.M, self._grad_ptr("img")
-        a.nll_part, a.nparts, a.scalars = ptr(det.nll), int(det.nll.numel()), ptr(self.scalars)
-        a.stop_flag = ptr(self.stop_flag)
-        if self.ev11:
-            a.ev11_part, a.n_ev11, a.d_ev11 = ptr(det.ev11), int(det.ev11.numel()) // 3, self._grad_ptr("ev11")
-        check(self.lib.cl_det_reduce(C.byref(a), st), "cl_det_reduce")
-
     def _data_term(self, obs, step: int, eta, ipred_out, st, defer_reduce: bool = False, train: bool = False):
         """NLL of `obs` into scalars[NLL] and its gradient into dz_f / the flat gradient (scaler + image scales): one launch sequence per
         piece of the set, then -- deterministic mode -- the fixed-order sums over the whole set.  `defer_reduce`: a single fused launch
@@ -1160,129 +558,30 @@ class ElboEngine(WidePath, FrozenPath):
         if self.neural and train and getattr(self.lik, "trainable", True):
             self._nlik_backward(obs, ipred_out, st)
 
+    def _route(self, obs: ObsData, form=None, wide: bool = False, chained: Optional[bool] = None) -> Route:
+        """THE route question (`plan.data_term_route`) for `obs` on this engine's plan.  `_data_term_launch` puts it whole -- `form`, the
+        frozen scaler's answer for the step, and the plan's `wide`.  Left at their defaults the answer is the route of the fused scaler
+        launch alone, which the frozen and the layer-by-layer route do not have (`_likelihood_args` behind `training_launch`);
+        `chained=False`: of a chain's last block taken by itself."""
+        return data_term_route(form, wide, self.blocks is not None if chained is None else chained, self.laue, obs.fused_laue, self.peel)
+
     def _data_term_launch(self, obs: ObsData, step: int, eta, ipred_out, st, defer_reduce: bool):
-        """The data term of one `ObsData`: exactly one path, then the reduction of the weight-gradient partials that goes with it."""
-        lib, lay = self.lib, self.layout
+        """The data term of one `ObsData`: the route question, then the route's method -- each ends with the reduction of the
+        weight-gradient partials that goes with it (`defer_reduce`: the two routes of a single reduction may leave it to the caller)."""
         form = self._frozen_form(obs, injected=eta is not None or ipred_out is not None)
-        if form is not None:
+        route = self._route(obs, form, self.wide)
+        if route is Route.FROZEN:
             self._data_term_frozen(form, obs, step, eta, ipred_out, st)       # (no scaler gradient: nothing to reduce)
-            return
-        if self.wide:
+        elif route is Route.WIDE:
             self._data_term_wide(obs, step, eta, ipred_out, st)               # (reduces layer by layer)
-            return
-        ma = self._mlp_args(step, eta, ipred_out, obs)
-        if self.blocks is not None:
-            self._data_term_chain(ma, obs, step, eta, ipred_out, st)          # (reduces block by block)
-            return
-        a, mode = self._likelihood_args(ma, obs)
-        if mode == 2:
-            self._laue_passes(a, obs, step, eta, ipred_out, st)
+        elif route is Route.CHAIN:
+            self._data_term_chain(obs, step, eta, ipred_out, st)              # (reduces block by block)
+        elif route is Route.TWO_PASS:
+            self._data_term_two_pass(obs, step, eta, ipred_out, st, defer_reduce)
+        elif route is Route.PEEL:
+            self._data_term_peel(obs, step, eta, ipred_out, st)               # (`_peel_reduce`)
         else:
-            # (deterministic mode: every workgroup of the launch STORES its NLL slot, det.grid slots per piece -- nothing to clear;
-            #  the slots a short last piece leaves unwritten were zero-initialised and are never touched)
-            self._fused_step_launch(a, obs, st)
-            if obs.fused_laue:
-                # single pass: the harmonic group sums happen inside the fused kernel; the padded slots (no rows, iconv = 0,
-                # reference formatter.py:637-640 / laue.py:24) only add their constant -- and, with Ev11, its gradient
-                self._laue_pad_slots(a, obs, st)
-        if self.peel and mode == 0:
-            self._peel_reduce(obs, st, a.n_obs)
-        elif defer_reduce and not self.deterministic:
-            self._pending_reduce = (ptr(obs.partials), obs.grid, lay.P, self._grad_ptr("mlp"))
-        else:
-            check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, lay.P, self._grad_ptr("mlp"), ptr(self.stop_flag), st), "cl_reduce_partials")
-
-    def _laue_pad_slots(self, ma, obs: ObsData, st):
-        """The padded slots of a packed Laue observation set (no rows, iconv = 0: reference formatter.py:637-640 / laue.py:24) add their
-        constant to the NLL -- and, with Ev11, its gradient -- through one small `cl_laue_likelihood` launch.  `ma`: the arguments of the
-        rows' own launch (`cl_mlp_args` or `cl_frozen_args`: its w_ll, ev11, d_ev11).  (Of the per-step constants this launch reads the
-        likelihood's alone: the other shared fields stay zero.)"""
-        lib = self.lib
-        npad = int(obs.pad_iobs.numel())
-        if npad <= 0:
-            return
-        nslot = 1 if obs.pad_uniform else npad                  # all padded slots alike: one slot, weight x their number
-        obs.pad_iconv[: nslot * self.S].zero_()
-        la = LaueArgs()
-        la.iobs, la.sig, la.iconv = ptr(obs.pad_iobs), ptr(obs.pad_sig), ptr(obs.pad_iconv)
-        la.n_obs, la.S = nslot, self.S
-        la.lik_kind, la.dof, la.lik_const = self.lik_kind, self.dof, self.lik_const
-        la.w_ll = ma.w_ll * (npad if obs.pad_uniform else 1)
-        la.scalars, la.stop_flag = ptr(self.scalars), ptr(self.stop_flag)
-        la.ev11, la.d_ev11 = ma.ev11, ma.d_ev11
-        if self.deterministic:      # the padded slots' workgroups store their NLL behind the fused launch's parts
-            la.nll_part, la.ev11_part = self._det_parts(obs, obs.det_parent.det.pieces)
-        check(lib.cl_laue_likelihood(C.byref(la), st), "cl_laue_likelihood")
-
-    def _peel_bufs(self, obs: ObsData):
-        """Buffers of the peeled first layer for one observation set: its pre-activations and dZ_0 (feature-major, like meta_t), the
-        weight-gradient partials; per engine: the peeled scaler's parameters and reduced gradient."""
-        if obs.peel is None:
-            rows = int(self.lib.cl_mlp_meta_rows(self.w))
-            nparts = int(self.lib.cl_peel_parts(obs.n_pad))     # (packed layouts: every row of the padded axis may be a real one)
-            obs.peel = PeelBuffers(u=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
-                                   dz0=torch.zeros(rows * obs.n_pad, dtype=torch.float32, device=self.device),
-                                   parts=torch.empty(nparts * (self.w * self.d + self.w), dtype=torch.float32, device=self.device), nparts=nparts)
-        if self.peel_params is None:
-            Pp = int(self.lib.cl_mlp_param_count(self.w, self.w, self.L))
-            self.peel_params = torch.zeros(Pp, dtype=torch.float32, device=self.device)
-            self.peel_grad = torch.zeros(Pp, dtype=torch.float32, device=self.device)
-        return obs.peel
-
-    def _peel_args(self, ma: MlpArgs, obs: ObsData) -> MlpArgs:
-        """The fused launch behind the peeled first layer: the layer's pre-activations as metadata, identity first layer, dZ_0 out."""
-        pb = self._peel_bufs(obs)
-        a = _copy_args(ma)
-        a.meta_t, a.d, a.mlp, a.dZ0_out = ptr(pb.u), self.w, ptr(self.peel_params), ptr(pb.dz0)
-        return a
-
-    def _fused_step_launch(self, a: MlpArgs, obs: ObsData, st):
-        """cl_elbo_mono_fwd_bwd on `_likelihood_args`' arguments, behind cl_peel_forward when the first layer is peeled (self.peel)."""
-        if self.peel:
-            check(self.lib.cl_peel_forward(ptr(obs.meta_t), a.n_obs, obs.n_pad, self.d, self.w, self.L, self._param_ptr("mlp"), ptr(obs.peel.u),
-                                           ptr(self.peel_params), ptr(self.peel_grad), int(self.peel_grad.numel()), ptr(self.stop_flag), st), "cl_peel_forward")
-        check(self.lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
-
-    def _peel_reduce(self, obs: ObsData, st, n_obs: int):
-        """Gradient of a step with a peeled first layer: the launch's partials -> the peeled scaler's gradient; layer 0's own gradient
-        from dZ_0 and the metadata, everything behind it copied over (cl_peel_backward)."""
-        pb = obs.peel
-        check(self.lib.cl_reduce_partials(ptr(obs.partials), obs.grid, int(self.peel_grad.numel()), ptr(self.peel_grad), ptr(self.stop_flag), st),
-              "cl_reduce_partials")
-        check(self.lib.cl_peel_backward(ptr(obs.meta_t), n_obs, obs.n_pad, self.d, self.w, self.L, ptr(pb.dz0), ptr(self.peel_grad),
-                                        self._grad_ptr("mlp"), ptr(pb.parts), pb.nparts, ptr(self.stop_flag), st), "cl_peel_backward")
-
-    def _block_args(self, ma: MlpArgs, obs: ObsData, k: int) -> MlpArgs:
-        """Arguments of block k of the chain: its slice of the parameters, its input (metadata or the previous block's output)."""
-        return block_fields(_copy_args(ma), self.blocks[k], self._param_ptr("mlp"), ptr(obs.meta_t) if k == 0 else ptr(obs.chain_act[k - 1]))
-
-    def _data_term_chain(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
-        """Scaler deeper than one launch: forward through the head-less blocks (activations to HBM), the last block does the
-        likelihood and its own backward (recomputing its forward), then the blocks are walked back, each recomputing its
-        forward from its stored input.  8 P_mm flops per observation instead of 6, plus 2 x 8 w bytes per block boundary."""
-        lib, K = self.lib, len(self.blocks)
-        gptr = lambda k: self._grad_ptr("mlp", self.blocks[k].off)
-        for k in range(K - 1):
-            a = self._block_args(ma, obs, k)
-            a.act_out = ptr(obs.chain_act[k])
-            check(lib.cl_mlp_forward(C.byref(a), obs.grid, st), "cl_mlp_forward")
-        a, _ = self._likelihood_args(ma, obs)
-        if self.laue:
-            a.dO_ext = ptr(obs.laue_dO)
-            self._laue_passes(a, obs, step, eta, ipred_out, st)
-        else:
-            check(lib.cl_elbo_mono_fwd_bwd(C.byref(a), obs.grid, st), "cl_elbo_mono_fwd_bwd")
-            if self.chain_lane:     # the last block on the lane kernel handed back dZ_0 of its first layer: dX = W_0^T dZ_0
-                check(lib.cl_chain_dx(ptr(obs.chain_dz0), a.mlp, a.n_obs, obs.n_pad, self.w, self.w, ptr(obs.chain_dact[K - 2]), ptr(self.stop_flag), st), "cl_chain_dx")
-        check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, self.blocks[K - 1].P, gptr(K - 1), ptr(self.stop_flag), st),
-              "cl_reduce_partials")
-        for k in range(K - 2, -1, -1):
-            a = self._block_args(ma, obs, k)
-            a.dH_ext = ptr(obs.chain_dact[k])
-            a.dX_out = ptr(obs.chain_dact[k - 1]) if k > 0 else None
-            check(lib.cl_mlp_backward_ext(C.byref(a), obs.grid, st), "cl_mlp_backward_ext")
-            check(lib.cl_reduce_partials(ptr(obs.partials), obs.grid, self.blocks[k].P, gptr(k), ptr(self.stop_flag), st),
-                  "cl_reduce_partials")
+            self._data_term_fused(obs, step, eta, ipred_out, st, defer_reduce)
 
     def evaluate_nll(self, obs: ObsData, key: int, u_f=None, eta=None) -> float:
         """NLL of another observation set under the current parameters with fresh Monte-Carlo noise -- what
@@ -1319,57 +618,6 @@ class ElboEngine(WidePath, FrozenPath):
         if o.d != self.d:
             raise ValueError("validation metadata width differs from the training data")
         return o
-
-    def _laue_passes(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
-        """Harmonic deconvolution (reference likelihoods/laue.py:9-47): scaler forward, predict + group sums, likelihood on
-        the slots, gradient broadcast back to the rows, scaler backward from dL/d(loc, sigma).  `ma`: the backward launch's arguments
-        (`dO_ext` set: `_likelihood_args`); the forward launch runs on a copy without it."""
-        lib = self.lib
-        ma.loc_out, ma.sig_out = ptr(obs.laue_loc), ptr(obs.laue_sig)
-        fwd = _copy_args(ma)
-        fwd.dO_ext = None
-        check(lib.cl_mlp_forward(C.byref(fwd), obs.grid, st), "cl_mlp_forward")
-        self._slot_likelihood(ma, obs, step, eta, ipred_out, st)
-        check(lib.cl_mlp_backward_ext(C.byref(ma), obs.grid, st), "cl_mlp_backward_ext")
-
-    def _slot_args(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, a: int = 0, n: Optional[int] = None) -> LaueArgs:
-        """Arguments of the slot likelihood kernels for the rows [a, a + n) of `obs` (default: all of them)."""
-        la = self._step_fields(LaueArgs(), obs, step)
-        n = obs.N - a if n is None else n
-        off = lambda t, size: None if t is None else t.data_ptr() + size * a
-        la.refl_id, la.image_id, la.harmonic_id = off(obs.refl_id, 4), off(obs.image_id, 4), off(obs.harmonic_id, 4)
-        la.loc, la.sigma, la.iobs, la.sig = off(obs.laue_loc, 4), off(obs.laue_sig, 4), off(obs.iobs, 4), off(self._sig(obs, obs.sig), 4)
-        la.n_obs, la.obs_offset = n, obs.start + a
-        la.img, la.use_img, la.d_img = ma.img, ma.use_img, ma.d_img
-        la.eta, la.ipred_out = off(eta, 4 * self.S), off(ipred_out, 4 * self.S)
-        la.iconv, la.dO = off(obs.laue_iconv, 4 * self.S), off(obs.laue_dO, 8)
-        la.row_index = off(obs.row_index, 8)
-        return la
-
-    def _slot_likelihood(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st, frozen: bool = False):
-        """From (loc, sigma) per row in obs.laue_loc / laue_sig: sample, predict, group sums, slot likelihood (NLL into the
-        scalars), its gradient back on the rows -> dz_f, d(image scales), obs.laue_dO = dL/d(loc, sigma) per row."""
-        lib = self.lib
-        if obs.harmonic_id is not None:
-            obs.laue_iconv.zero_()          # (group sums accumulate by atomics; rows that are their own slot -- harmonic_id None -- store)
-        la = self._slot_args(ma, obs, step, eta, ipred_out)
-        if self.deterministic and obs.harmonic_id is None:
-            # no float atomics: the amplitude gradient of every (row, sample) and the image-scale term of every row are stored (records in
-            # reflection order: det_slot), every workgroup stores its NLL; cl_det_reduce sums them in a fixed order after the backward pass
-            det = obs.det_parent.det
-            la.dzf_obs, la.dimg_obs, la.det_slot = ptr(det.dzf), ptr(det.dimg), ptr(det.slot)
-            la.nll_part, la.ev11_part = self._det_parts(obs, det.pieces)
-            check(lib.cl_slot_rows(C.byref(la), st), "cl_slot_rows")
-            return
-        if obs.harmonic_id is None and self.SLOT_ROWS_ONE_LAUNCH:
-            # every row its own slot (monochromatic data on the layer-by-layer path): one launch, no round trip through iconv
-            check(lib.cl_slot_rows(C.byref(la), st), "cl_slot_rows")
-            return
-        check(lib.cl_laue_predict(C.byref(la), st), "cl_laue_predict")
-        check(lib.cl_laue_likelihood(C.byref(la), st), "cl_laue_likelihood")
-        if frozen:
-            la.dO = None                # nobody takes dL/d(loc, sigma) of a frozen scaler: amplitude gradients only (no clearing, no row sums)
-        check(lib.cl_laue_backward(C.byref(la), st), "cl_laue_backward")
 
     def _allreduce(self):
         from careless_amd.distributed import allreduce_flat_

@@ -11,9 +11,10 @@ Two decisions, each written once:
                   packing by image), and which `_build_obs` keywords that changes;
     step time     `_frozen_form`: which form a step's data term takes on one `ObsData` -- none (the fused / wide / chain step), rows sorted
                   by reflection (`cl_frozen_rows`, csrc/elbo_frozen.hip), harmonic groups (the two-call form of `cl_frozen_rows`), or
-                  round 5's slot kernels (`ElboEngine._slot_likelihood`).
+                  round 5's slot kernels (`SlotPath._slot_likelihood`, careless_amd/slots.py).
 The per-training state of the two `cl_frozen_rows` forms is one record each (`SortedRows`, `GroupRows`) at `obs.frozen_sorted`; the slot
-form reads `obs.laue_*` through `_slot_args` like the two-pass Laue path.  The index arithmetic of both records is in two functions of
+form reads `obs.laue_*` through `_slot_args` like the two-pass Laue path.  Defined elsewhere and used here: `_slot_likelihood` and
+`_laue_pad_slots` (slots.py), `_mlp_args` (fused.py), `_sig` (nlik.py), `_step_fields` / `_shard_rows` (engine.py).  The index arithmetic of both records is in two functions of
 torch tensors (`sorted_row_order`, `group_row_order`) that run on any device without an engine.
 """
 from __future__ import annotations

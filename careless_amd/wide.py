@@ -2,6 +2,8 @@
 fused launch takes): the layer-by-layer path of the engine on the GEMM kernels of csrc/wide_gemm.hip, as a mixin of `ElboEngine`
 (split out of careless_amd/engine.py in round 4).  Reference: `MetadataScaler.call` (careless/models/scaling/nn.py:55-68, 92-120),
 `ImageLayer` (scaling/image.py:66-125) and the tape gradient of both (models/merging/variational.py:197-202).
+Defined elsewhere and used here: the likelihood between the forward and the backward pass is `SlotPath._slot_likelihood` / `_slot_args`
+(careless_amd/slots.py) on (loc, sigma) per row; `_mlp_args` (fused.py) supplies the image-scale fields; `_param_ptr` / `_grad_ptr` (engine.py).
 """
 from __future__ import annotations
 

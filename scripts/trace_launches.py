@@ -45,9 +45,12 @@ class Tracer:
             launch = bool(argtypes) and argtypes[-1] is C.c_void_p and res is C.c_int and not name.startswith("cl_host_")      # (its last argument is the stream)
             setattr(lib, name, self._wrap(name, getattr(lib, name), res, argtypes, dry and launch))
         if dry:
-            from careless_amd import engine
-            engine.require_gpu = lambda what: torch.device("cpu")
-            engine._stream = lambda: 0
+            import careless_amd.engine  # noqa: F401      (the stubs go on every loaded module of the package that holds the name)
+            stubs = dict(require_gpu=lambda what: torch.device("cpu"), _stream=lambda: 0)
+            for mod in [m for n, m in list(sys.modules.items()) if n.startswith("careless_amd.") and m is not None]:
+                for name, stub in stubs.items():
+                    if hasattr(mod, name):
+                        setattr(mod, name, stub)
             torch.cuda.synchronize = lambda *a: None
             torch.cuda.mem_get_info = lambda *a: (64 << 30, 64 << 30)
 

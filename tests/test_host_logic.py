@@ -1121,3 +1121,87 @@ def test_switch_model_attribute_then_environment_then_default(monkeypatch):
     assert switch(NS(x=True), "x", env, env_adds=True) is True and switch(NS(), "x", env) is False
     monkeypatch.setenv(env, "yes")                                          # only "1" switches on, only "0" off
     assert switch(NS(), "x", env) is False and switch(NS(), "x", env, default=True) is True
+
+
+# --- the engine's modules: one route decision, host modules that need no engine ------------------------------
+ENGINE_MODULES = ("flat", "plan", "fused", "slots", "det", "nlik")
+# every name another file of the repository imports from, or reads on, careless_amd.engine
+ENGINE_EXPORTS = ("ElboEngine", "ObsChunks", "ObsData", "make_shard", "owner_bounds", "owner_shard", "laue_group_shard", "launch_row_limit",
+                  "debug_noise", "tn_sample", "tn_moments", "predict_moments", "scaler_forward", "_forward_layers", "require_gpu", "_stream",
+                  "FORWARD_CHUNK_BYTES", "plan_scaler", "chain_plan", "ScalerPlan", "check_deterministic", "wants_owner_shard", "switch",
+                  "check_neural_likelihood", "posterior_kind", "prior_kind", "reference_prior_arrays", "REFPRIOR_KINDS", "make_layout",
+                  "FLAT_GROUPS", "FlatLayout", "bind_flat", "split_flat", "carve_workspace", "GRANULE", "TILE", "pack_by_image", "pack_laue")
+
+
+def test_data_term_route_precedence():
+    """frozen before wide, before chain, before two-pass (Laue rows not packed for the single-pass kernels), before peel, before fused --
+    over every combination of the six arguments."""
+    from itertools import product
+    from careless_amd.frozen import FrozenForm
+    from careless_amd.plan import Route, data_term_route
+    assert [r.name for r in Route] == ["FROZEN", "WIDE", "CHAIN", "TWO_PASS", "PEEL", "FUSED"]
+    n = 0
+    for form, wide, chained, laue, fused_laue, peel in product((None, *FrozenForm), *[(False, True)] * 5):
+        table = ((form is not None, Route.FROZEN), (wide, Route.WIDE), (chained, Route.CHAIN), (laue and not fused_laue, Route.TWO_PASS),
+                 (peel, Route.PEEL), (True, Route.FUSED))
+        want = next(route for holds, route in table if holds)
+        assert data_term_route(form, wide, chained, laue, fused_laue, peel) is want, (form, wide, chained, laue, fused_laue, peel)
+        n += 1
+    assert n == 4 * 32
+    # the precedence that is easy to get wrong: the plan says `peel`, `pack_laue` declined to pack the rows -- no peeled launch
+    assert data_term_route(None, False, False, True, False, True) is Route.TWO_PASS
+    assert data_term_route(None, False, False, True, True, True) is Route.PEEL
+    assert data_term_route(None, False, True, True, False, True) is Route.CHAIN
+    assert data_term_route(FrozenForm.SLOTS, True, True, True, False, True) is Route.FROZEN
+
+
+def test_engine_modules_do_not_import_the_engine():
+    """`careless_amd.flat` and `careless_amd.plan` -- and the four mixin modules -- import without `careless_amd.engine`: imported afresh
+    with the engine taken out of `sys.modules`, none brings it back; and none names it in an import statement, a function's own included."""
+    import ast
+    import importlib
+    import sys
+    import careless_amd
+    names = ["careless_amd." + m for m in ENGINE_MODULES]
+    for m in ENGINE_MODULES:
+        tree = ast.parse(open(os.path.join(ROOT, "careless_amd", m + ".py")).read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Import):
+                assert not any(a.name.startswith("careless_amd.engine") for a in node.names), (m, node.lineno)
+            elif isinstance(node, ast.ImportFrom):
+                assert not (node.module or "").startswith("careless_amd.engine"), (m, node.lineno)
+                assert not (node.module == "careless_amd" and any(a.name == "engine" for a in node.names)), (m, node.lineno)
+    saved = {n: sys.modules.pop(n) for n in names + ["careless_amd.engine"] if n in sys.modules}
+    attrs = {n: getattr(careless_amd, n) for n in ENGINE_MODULES + ("engine",) if hasattr(careless_amd, n)}
+    try:
+        for n in names:
+            importlib.import_module(n)
+            assert "careless_amd.engine" not in sys.modules, n
+    finally:
+        for n in names:
+            sys.modules.pop(n, None)
+        sys.modules.update(saved)
+        for n, mod in attrs.items():
+            setattr(careless_amd, n, mod)
+
+
+def test_engine_keeps_its_names():
+    """`careless_amd.engine` exposes every name other files import from it, as the object its new home defines; `ElboEngine` keeps the class
+    flags tests flip and the methods tests and scripts call."""
+    from careless_amd import det, engine, flat, frozen, fused, nlik, plan, slots, wide
+    missing = [n for n in ENGINE_EXPORTS if not hasattr(engine, n)]
+    assert not missing, missing
+    for mod in (flat, plan):
+        for n in ENGINE_EXPORTS:
+            assert not hasattr(mod, n) or getattr(mod, n) is getattr(engine, n), (mod.__name__, n)
+    E = engine.ElboEngine
+    assert [c for c in (fused.FusedPath, wide.WidePath, frozen.FrozenPath, slots.SlotPath, det.DetPath, nlik.NlikPath) if not issubclass(E, c)] == []
+    for flag in ("SLOT_ROWS_ONE_LAUNCH", "FROZEN_LAUE_PACKED", "FROZEN_SORTED_ROWS", "FUSE_PRE", "FUSE_WG0", "FUSE_HEADB", "FUSE_LIK"):
+        assert getattr(E, flag) is True, flag
+    assert E.local_only is False
+    for method in ("_mlp_args", "_block_args", "_nlik_args", "_data_term", "_data_term_launch", "_noise_to_device", "_likelihood_args",
+                   "training_launch", "kernel_name", "_slot_args", "_slot_likelihood", "_laue_pad_slots", "_laue_passes", "_sig", "_det_parts",
+                   "_det_attach", "_det_reduce", "_peel_bufs", "_peel_args", "_peel_reduce", "_fused_step_launch", "_data_term_chain",
+                   "_nlik_attach", "_nlik_forward", "_nlik_backward", "_step_fields", "_shard_rows", "_param_ptr", "_grad_ptr", "_tn_args",
+                   "_q_launch", "_ref_prior", "forward_backward", "optimizer_step", "evaluate_nll", "make_obs"):
+        assert callable(getattr(E, method, None)), method
