@@ -5,6 +5,13 @@ This file is a CPU restatement, in plain PyTorch-CPU (fp64 by default) + scipy, 
 kernels under `careless_amd/csrc/`; it is never imported by the product package.  Only `tests/`,
 `__graft_entry__.smoke()` and the `cpu_baseline` leg of `bench.py` may import it.
 
+The model it states, one independent choice each (`ElboConfig`), as the engine runs them:
+    likelihood   normal | studentt | laplace | neural          (Evans-2011 error model on the first two)
+    prior        wilson | double_wilson | reference            (an empirical reference prior: `RefPrior` on `ElboInputs.ref`)
+    posterior    truncated_normal | rice_woolfson
+The default configuration -- Normal, Wilson, truncated normal -- performs the arithmetic of the committed golden vectors,
+operation for operation.
+
 PARITY STATUS -- "parity unpinned by the reference":
   the reference's arithmetic lives in un-vendored third-party packages (tensorflow==2.18.0,
   tensorflow-probability==0.25, tf_keras; reference `pyproject.toml:14-19`) that are absent from the
@@ -16,7 +23,10 @@ PARITY STATUS -- "parity unpinned by the reference":
     * scipy.stats closed forms for every density used (truncnorm, norm, t, halfnorm, weibull_min,
       rice, foldnorm);
     * a finite-difference check of the truncated-normal pathwise gradient;
-    * committed golden vectors produced by this file (tests/golden/, generator committed beside them).
+    * committed golden vectors produced by this file (tests/golden/, generator committed beside them);
+    * for the later families, the scipy / torch.distributions and finite-difference tests of tests/test_laplace.py,
+      tests/test_nlik.py, tests/test_ref_prior.py and tests/test_rw_posterior.py, and the swap identities of
+      tests/test_oracle_families.py, which derive each family's step from the golden-pinned default step.
 
 Every function cites the reference file:line it follows (paths relative to the reference checkout).
 Statements about TF / TFP internals are recalled from the pinned versions and marked [3P].
@@ -25,7 +35,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -44,7 +54,7 @@ class ElboConfig:
     """Static configuration of one ELBO graph (what `DataManager.build_model` wires up,
     reference `careless/io/manager.py:380-507`)."""
     mc_samples: int = 1                 # --mc-samples (args/common.py:11-15)
-    likelihood: str = "normal"          # "normal" | "studentt"  (manager.py:438-443)
+    likelihood: str = "normal"          # "normal" | "studentt" | "laplace" | "neural"  (manager.py:438-443; mono.py:20-23, 75-110)
     dof: Optional[float] = None         # --studentt-likelihood-dof
     scale_bijector: str = "exp"         # --scale-bijector (args/scaling.py:47-52)
     epsilon: float = 1e-7               # --epsilon: q scale shift AND scaler sigma shift (manager.py:436,453,460)
@@ -54,7 +64,8 @@ class ElboConfig:
     leakiness: float = 0.01             # nn.py:31
     high: float = 1e10                  # surrogate_posteriors.py:105
     laue: bool = False                  # len(inputs) >= 8 (models/base.py:39-47)
-    prior: str = "wilson"               # "wilson" | "double_wilson"
+    prior: str = "wilson"               # "wilson" | "double_wilson" | "reference" (priors/empirical.py; arrays in ElboInputs.ref)
+    posterior: str = "truncated_normal" # "truncated_normal" | "rice_woolfson"  (surrogate_posteriors.py:45-131, 133-172)
     ev11: bool = False                  # --refine-uncertainties: Evans-2011 error model (likelihoods/mono.py:39-73)
     optimize_dw_r: bool = False         # --optimize-double-wilson-r (priors/wilson.py:105-110)
     image_layers: int = 0               # --image-layers: NeuralImageScaler (scaling/image.py:98-125); replaces the image scales
@@ -66,6 +77,11 @@ class ElboConfig:
     clipnorm: Optional[float] = None
     clipvalue: Optional[float] = None
     global_clipnorm: Optional[float] = None
+
+
+def f64(a):
+    """`a` (array-like or tensor) as an fp64 tensor."""
+    return torch.as_tensor(np.asarray(a), dtype=torch.float64) if not torch.is_tensor(a) else a.to(torch.float64)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -261,6 +277,76 @@ def double_wilson_log_prob(z, centric, multiplicity, sigma, parent_ids, root, as
 
 
 # --------------------------------------------------------------------------------------------------
+# surrogate posterior q(F): Rice-Woolfson  (surrogate_posteriors.py:133-172 on careless/utils/distributions.py:228-348)
+# --------------------------------------------------------------------------------------------------
+def rw_sample(loc, scale, centric, n):
+    """n: (2, S, R) standard normals.  Centric: |loc + scale n1| + eps32 (surrogate_posteriors.py:166; n2 unused); acentric:
+    sqrt((scale n1)^2 + (loc + scale n2)^2) (distributions.py:252-258: s1 alone, s2 + nu).  Differentiable: the pathwise gradient is autograd's
+    (the gradient of abs is sign, 0 at 0, as TensorFlow's)."""
+    n1, n2 = n[0], n[1]
+    zc = torch.abs(loc + scale * n1) + EPS_F32
+    za = torch.sqrt((scale * n1) ** 2 + (loc + scale * n2) ** 2)
+    return torch.where(centric, zc, za)
+
+
+def rw_log_prob(z, loc, scale, centric):
+    """tf.where(centric, FoldedNormal.log_prob, Rice.log_prob) (surrogate_posteriors.py:168-169)."""
+    return torch.where(centric, folded_normal_log_prob(z, loc, scale), rice_log_prob(z, loc, scale))
+
+
+def rw_moments(loc, scale, centric):
+    """(mean, variance, fourth raw moment) in fp64 numpy: `RiceWoolfson._moments` of the package's host class (pinned to scipy by
+    tests/test_ref_prior.py) and the two closed-form fourth moments."""
+    from careless_amd.models.merging.surrogate_posteriors import RiceWoolfson
+    loc, scale, c = np.asarray(loc, dtype=np.float64), np.asarray(scale, dtype=np.float64), np.asarray(centric, dtype=bool)
+    host = RiceWoolfson(loc, scale, c)
+    host.loc, host.scale = loc, scale                      # (the constructor rounds to fp32: keep the fp64 values)
+    (wm, rm), (wv, rv) = host._moments()
+    m4 = np.where(c, loc ** 4 + 6 * loc ** 2 * scale ** 2 + 3 * scale ** 4, loc ** 4 + 8 * scale ** 2 * loc ** 2 + 8 * scale ** 4)
+    return np.where(c, wm, rm), np.where(c, wv, rv), m4
+
+
+# --------------------------------------------------------------------------------------------------
+# empirical reference priors  (careless/models/priors/empirical.py:9-131)
+# --------------------------------------------------------------------------------------------------
+class RefPrior(NamedTuple):
+    """An empirical reference prior as `ref_log_prob` takes it: full-length (R,) arrays."""
+    kind: str                          # "normal" | "laplace" | "studentt" | "rice_woolfson"
+    loc: object                        # (R,) the BASE distribution's parameters (Laplace: scale = SigFobs / sqrt 2)
+    scale: object
+    observed: object = None            # (R,) bool, None: every reflection
+    centric: object = None             # (R,) bool, rice_woolfson only
+    dof: Optional[float] = None        # studentt only
+
+
+def base_log_prob(kind, z, loc, scale, centric=None, dof=None):
+    """log-density of the base distribution at z (..., R); loc / scale (R,) are the BASE distribution's parameters (Laplace: b = SigFobs / sqrt 2)."""
+    if kind == "normal":                                # tfd.Normal (empirical.py:85)
+        return normal_log_prob(z, loc, scale)
+    if kind == "laplace":                               # tfd.Laplace (empirical.py:64): -|z - loc| / b - log(2 b)
+        return -torch.abs(z - loc) / scale - torch.log(2.0 * scale)
+    if kind == "studentt":                              # tfd.StudentT (empirical.py:108)
+        return studentt_log_prob(z, float(dof), loc, scale)
+    if kind == "rice_woolfson":                         # RiceWoolfson.log_prob (surrogate_posteriors.py:168-169)
+        return rw_log_prob(z, loc, scale, centric)
+    raise ValueError(kind)
+
+
+def ref_log_prob(kind, z, loc, scale, observed=None, centric=None, dof=None):
+    """`ReferencePrior.log_prob` (empirical.py:33-43) with FULL-length (R,) parameter arrays: the base density on observed reflections,
+    exact zeros elsewhere (the parameters of unobserved reflections are not looked at).  Differentiable in z."""
+    z, loc, scale = f64(z), f64(loc), f64(scale)
+    if centric is not None:
+        centric = torch.as_tensor(np.asarray(centric), dtype=torch.bool) if not torch.is_tensor(centric) else centric.bool()
+    if observed is None:
+        return base_log_prob(kind, z, loc, scale, centric, dof)
+    obs = torch.as_tensor(np.asarray(observed), dtype=torch.bool) if not torch.is_tensor(observed) else observed.bool()
+    one = torch.ones_like(loc)
+    lp = base_log_prob(kind, z, torch.where(obs, loc, one), torch.where(obs, scale, one), centric, dof)
+    return torch.where(obs, lp, torch.zeros_like(lp))
+
+
+# --------------------------------------------------------------------------------------------------
 # scaling model  (careless/models/scaling/nn.py, image.py)
 # --------------------------------------------------------------------------------------------------
 def mlp_identity_init(d: int, width: int, n_layers: int, dtype=np.float32):
@@ -359,6 +445,51 @@ def studentt_log_prob(x, df: float, loc, scale):
             - 0.5 * math.log(math.pi) - math.lgamma(0.5 * df) + math.lgamma(0.5 * (df + 1.0)))
 
 
+class _AbsResidual(torch.autograd.Function):
+    """|d| with the gradient g sign(d) -- 0 at 0, as TensorFlow's -- and NaN where d is NaN: a non-finite observation or prediction reaches
+    the gradient through the Laplace term as it does through the Normal and Student-t ones (their d appears in the derivative itself), which
+    is what the engine's kernels do and what the non-finite step contract of tests/test_nonfinite.py is stated on.  (torch.abs gives 0 there.)"""
+
+    @staticmethod
+    def forward(ctx, d):
+        ctx.save_for_backward(d)
+        return torch.abs(d)
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return g * torch.where(torch.isnan(d), d, torch.sign(d))
+
+
+def laplace_log_prob(x, loc, sig):
+    """`tfd.Laplace(loc, sig / sqrt 2).log_prob(x)` (mono.py:20-23, laue.py:76-81): -|x - loc| / b - log(2 b)."""
+    b = sig / math.sqrt(2.0)
+    return -_AbsResidual.apply(x - loc) / b - torch.log(2.0 * b)
+
+
+NLIK_LEAK = 0.3           # tfk.layers.LeakyReLU()'s default slope
+
+
+def nlik_forward(net, iobs, sigiobs):
+    """The neural likelihood's network (mono.py:75-110): mlp_layers x Dense(mlp_width, LeakyReLU(0.3)) -> Dense(1, softplus) on
+    concat(iobs, sigiobs) gives delta; sigpred = sigiobs * delta / mean(delta), the mean over all rows of the set.  `net`: Keras-ordered
+    tensors [W_0 (2, w), b_0, ..., W_head (w, 1), b_head (1,)].  Returns (delta (N,), sigpred (N,), head pre-activation (N,), kink): kink is
+    the smallest |hidden pre-activation| relative to its layer's largest -- a unit of an fp32 engine can sit on the other branch of its
+    LeakyReLU only where that is at rounding level."""
+    h = torch.stack([f64(iobs).reshape(-1), f64(sigiobs).reshape(-1)], dim=1)
+    kink = math.inf
+    for k in range(len(net) // 2 - 1):
+        z = h @ net[2 * k] + net[2 * k + 1]
+        with torch.no_grad():
+            fin = z[torch.isfinite(z)].abs()
+            if fin.numel():
+                kink = min(kink, float(fin.min() / fin.max()))
+        h = torch.where(z > 0, z, NLIK_LEAK * z)
+    zh = (h @ net[-2] + net[-1])[:, 0]
+    delta = torch.nn.functional.softplus(zh)
+    return delta, f64(sigiobs).reshape(-1) * delta / delta.mean(), zh, kink
+
+
 def laue_convolve(value, harmonic_id):
     """`ConvolvedLikelihood.convolve` (laue.py:17-25): scatter_nd(harmonic_id, value^T, shape (N,S))^T -- duplicates sum,
     untouched slots stay 0.  value: (S, N) or (N,)."""
@@ -380,6 +511,7 @@ class ElboParams:
     ev11_raw: Optional[torch.Tensor] = None  # (3,) pre-softplus Sdfac, Sdadd, SdB (mono.py:42-44), only with cfg.ev11
     imgl_w: Optional[List[torch.Tensor]] = None   # K x (M, w, w) per-image kernels, only with cfg.image_layers (image.py:76-82)
     imgl_b: Optional[List[torch.Tensor]] = None   # K x (M, w)
+    nlik: Optional[List[torch.Tensor]] = None     # the neural likelihood's network, Keras order (see `nlik_forward`), only with likelihood "neural"
 
     def tensors(self) -> List[torch.Tensor]:
         """Trainable tensors in the flat-buffer order the HIP engine uses."""
@@ -392,6 +524,7 @@ class ElboParams:
             out += [w, b]
         if self.ev11_raw is not None:
             out.append(self.ev11_raw)
+        out += self.nlik or []             # the likelihood's slot: the neural likelihood excludes the Evans-2011 model
         if self.dw_r_raw is not None:
             out.append(self.dw_r_raw)
         return out
@@ -407,7 +540,8 @@ class ElboParams:
         return ElboParams(c(self.q_loc_raw), c(self.q_scale_raw), [c(w) for w in self.mlp_w],
                           [c(b) for b in self.mlp_b], c(self.img_raw), c(self.dw_r_raw), c(self.ev11_raw),
                           None if self.imgl_w is None else [c(w) for w in self.imgl_w],
-                          None if self.imgl_b is None else [c(b) for b in self.imgl_b])
+                          None if self.imgl_b is None else [c(b) for b in self.imgl_b],
+                          None if self.nlik is None else [c(t) for t in self.nlik])
 
 
 @dataclass
@@ -429,20 +563,53 @@ class ElboInputs:
     root: Optional[torch.Tensor] = None
     asu_ids: Optional[torch.Tensor] = None
     dw_r: Optional[torch.Tensor] = None
+    ref: Optional[RefPrior] = None               # the empirical reference prior's arrays, only with prior "reference"
+    q_centric: Optional[torch.Tensor] = None     # (R,) bool: the Rice-Woolfson posterior's own centric flag; None: `centric`
+
+
+def _posterior(x: ElboInputs, cfg: ElboConfig, loc):
+    """(sample(loc, scale, noise), log_prob(z, loc, scale)) of q(F)."""
+    if cfg.posterior == "truncated_normal":
+        high = torch.as_tensor(cfg.high, dtype=loc.dtype)
+        return (lambda loc, scale, u: tn_sample(loc, scale, x.low, high, u),
+                lambda z, loc, scale: tn_log_prob(z, loc, scale, x.low, high))
+    if cfg.posterior == "rice_woolfson":
+        c = x.centric if x.q_centric is None else x.q_centric
+        return (lambda loc, scale, n: rw_sample(loc, scale, c, n),
+                lambda z, loc, scale: rw_log_prob(z, loc, scale, c))
+    raise ValueError(cfg.posterior)
+
+
+def _posterior_moments(p: ElboParams, x: ElboInputs, cfg: ElboConfig):
+    """(mean, variance, fourth raw moment) of q(F), (R,) each.  Truncated normal: `tfd.TruncatedNormal.mean` / `.variance` [3P] and
+    `moment_4(method='scipy')` = scipy.stats.truncnorm.moment(4) (surrogate_posteriors.py:75-83; high = inf, :85).  Rice-Woolfson: `rw_moments`."""
+    loc, scale = tn_loc_scale(p.q_loc_raw, p.q_scale_raw, cfg.epsilon)
+    if cfg.posterior == "truncated_normal":
+        from scipy.stats import truncnorm
+        high = torch.as_tensor(cfg.high, dtype=loc.dtype)
+        a = ((x.low - loc) / scale).numpy()
+        return (tn_mean(loc, scale, x.low, high), tn_variance(loc, scale, x.low, high),
+                torch.as_tensor(truncnorm.moment(4, a, np.inf, loc.numpy(), scale.numpy())))
+    if cfg.posterior == "rice_woolfson":
+        c = x.centric if x.q_centric is None else x.q_centric
+        return tuple(torch.as_tensor(m) for m in rw_moments(loc.numpy(), scale.numpy(), c.numpy()))
+    raise ValueError(cfg.posterior)
 
 
 def elbo_forward(p: ElboParams, x: ElboInputs, cfg: ElboConfig, u_f: torch.Tensor, eta: torch.Tensor,
                  kl_mask: Optional[torch.Tensor] = None, flips=None, near=None):
     """One forward pass of `VariationalMergingModel.call` (variational.py:141-183).
 
-    u_f: (S, R) uniforms for the truncated normal; eta: (S, N) standard normals for the scale sample.
+    u_f: (S, R) uniforms for the truncated normal, (2, S, R) standard normals n1, n2 for the Rice-Woolfson posterior;
+    eta: (S, N) standard normals for the scale sample.
     kl_mask: optional (R,) bool -- restrict the KL sum to these reflections (used by the data-parallel shard
     tests so the KL is counted once across ranks).
-    Returns dict(loss, nll, kl, ipred, z_f)."""
+    Returns dict(loss, nll, kl, ipred, z_f, ipred_l) -- ipred_l is what the likelihood saw (S, N) -- and, under the neural
+    likelihood, sigpred, delta and kink (see `nlik_forward`)."""
     S = cfg.mc_samples
     loc, scale = tn_loc_scale(p.q_loc_raw, p.q_scale_raw, cfg.epsilon)
-    high = torch.as_tensor(cfg.high, dtype=loc.dtype)
-    z_f = tn_sample(loc, scale, x.low, high, u_f)                              # variational.py:154
+    q_sample, q_log_prob = _posterior(x, cfg, loc)
+    z_f = q_sample(loc, scale, u_f)                                            # variational.py:154
 
     out = mlp_forward(x.metadata, p.mlp_w, p.mlp_b, cfg.leakiness,            # variational.py:156 -> nn.py:106-120
                       x.image_id, p.imgl_w or (), p.imgl_b or (),             # --image-layers: image.py:116-125
@@ -460,7 +627,7 @@ def elbo_forward(p: ElboParams, x: ElboInputs, cfg: ElboConfig, u_f: torch.Tenso
         ipred_l = laue_convolve(ipred, x.harmonic_id)                          # laue.py:33-34
     else:
         ipred_l = ipred
-    sig_l = x.sigiobs[None, :]
+    sig_l, extra = x.sigiobs[None, :], {}
     if cfg.ev11:                                                                # Ev11Likelihood.corrected_sigiobs (mono.py:51-59)
         sd = torch.nn.functional.softplus(p.ev11_raw)
         sp = torch.nn.functional.softplus(ipred_l)
@@ -469,16 +636,26 @@ def elbo_forward(p: ElboParams, x: ElboInputs, cfg: ElboConfig, u_f: torch.Tenso
         ll = normal_log_prob(ipred_l, x.iobs[None, :], sig_l)
     elif cfg.likelihood == "studentt":
         ll = studentt_log_prob(ipred_l, float(cfg.dof), x.iobs[None, :], sig_l)
+    elif cfg.likelihood == "laplace" and not cfg.ev11:
+        ll = laplace_log_prob(ipred_l, x.iobs[None, :], sig_l)
+    elif cfg.likelihood == "neural" and not cfg.ev11 and not cfg.laue:
+        delta, sigpred, _, kink = nlik_forward(p.nlik, x.iobs, x.sigiobs)
+        extra = dict(sigpred=sigpred, delta=delta, kink=kink)
+        ll = normal_log_prob(ipred_l, x.iobs[None, :], sigpred[None, :])
     else:
-        raise ValueError(cfg.likelihood)
+        raise ValueError((cfg.likelihood, cfg.ev11, cfg.laue))
 
-    log_q = tn_log_prob(z_f, loc, scale, x.low, high)                          # variational.py:128
+    log_q = q_log_prob(z_f, loc, scale)                                        # variational.py:128
     if cfg.prior == "wilson":
         log_p = wilson_log_prob(z_f, x.centric, x.multiplicity, x.sigma)
-    else:
+    elif cfg.prior == "double_wilson":
         dw_r = torch.sigmoid(p.dw_r_raw) if p.dw_r_raw is not None else x.dw_r        # wilson.py:105-110
         log_p = double_wilson_log_prob(z_f, x.centric, x.multiplicity, x.sigma, x.parent_ids, x.root,
                                        x.asu_ids, dw_r)
+    elif cfg.prior == "reference":
+        log_p = ref_log_prob(x.ref.kind, z_f, x.ref.loc, x.ref.scale, x.ref.observed, x.ref.centric, x.ref.dof)
+    else:
+        raise ValueError(cfg.prior)
     kl_e = log_q - log_p
     if kl_mask is not None:
         kl_e = kl_e[:, kl_mask]
@@ -491,7 +668,7 @@ def elbo_forward(p: ElboParams, x: ElboInputs, cfg: ElboConfig, u_f: torch.Tenso
         kl = kl_e.mean()
         nll = -ll.mean()
         loss = nll + cfg.kl_weight * kl
-    return dict(loss=loss, nll=nll, kl=kl, ipred=ipred, z_f=z_f)
+    return dict(loss=loss, nll=nll, kl=kl, ipred=ipred, z_f=z_f, ipred_l=ipred_l, **extra)
 
 
 def elbo_value_and_grads(p: ElboParams, x: ElboInputs, cfg: ElboConfig, u_f, eta, kl_mask=None, flips=None, near=None):
@@ -501,7 +678,7 @@ def elbo_value_and_grads(p: ElboParams, x: ElboInputs, cfg: ElboConfig, u_f, eta
     ts = q.tensors()
     grads = torch.autograd.grad(out["loss"], ts, allow_unused=True)
     grads = [torch.zeros_like(t) if g is None else g for g, t in zip(grads, ts)]
-    return {k: v.detach() for k, v in out.items()}, grads
+    return {k: v.detach() if torch.is_tensor(v) else v for k, v in out.items()}, grads
 
 
 # --------------------------------------------------------------------------------------------------
@@ -567,7 +744,7 @@ def train_step(p: ElboParams, x: ElboInputs, cfg: ElboConfig, st: AdamState, u_f
     grads = clip_grads(grads, cfg)
     adam_apply(p.tensors(), grads, st, cfg)
     return {"loss": float(out["loss"]), "F KLDiv": float(out["kl"]), "NLL": float(out["nll"]),
-            "Grad Norm": float(gnorm)}
+            "Grad Norm": float(gnorm), **{k: out[k] for k in ("kink",) if k in out}}
 
 
 # --------------------------------------------------------------------------------------------------
@@ -599,15 +776,11 @@ def prediction_mean_stddev(p: ElboParams, x: ElboInputs, cfg: ElboConfig):
     """`VariationalMergingModel.prediction_mean_stddev` (variational.py:80-121): <I> = <Sigma><F^2>,
     var(I) = <F^4><Sigma^2> - <I>^2, <F^4> from `moment_4(method='scipy')` = scipy.stats.truncnorm.moment(4)
     (surrogate_posteriors.py:75-83; high = inf, :85), Laue: both convolved before the square root (:113-119)."""
-    from scipy.stats import truncnorm
     with torch.no_grad():
-        loc, scale = tn_loc_scale(p.q_loc_raw, p.q_scale_raw, cfg.epsilon)
-        high = torch.as_tensor(cfg.high, dtype=loc.dtype)
         smean, ssd = _scale_moments(p, x, cfg)
-        f2 = tn_mean(loc, scale, x.low, high) ** 2 + tn_variance(loc, scale, x.low, high)
+        mean, var, f4 = _posterior_moments(p, x, cfg)
+        f2 = mean ** 2 + var
         iexp = smean * f2[x.refl_id]
-        a = ((x.low - loc) / scale).numpy()
-        f4 = torch.as_tensor(truncnorm.moment(4, a, np.inf, loc.numpy(), scale.numpy()))
         s2 = smean ** 2 + ssd ** 2
         ivar = f4[x.refl_id] * s2 - iexp * iexp
         if cfg.laue:
@@ -618,15 +791,10 @@ def prediction_mean_stddev(p: ElboParams, x: ElboInputs, cfg: ElboConfig):
 def merged_results(p: ElboParams, x: ElboInputs, cfg: ElboConfig, max_intensity_snr: float = 1e-5):
     """`DataManager.get_results` numerics (io/manager.py:188-197): F, SigF = TN mean / stddev, I = SigF^2 + F^2,
     SigI = sqrt(max((I snr)^2, <F^4> - I^2))."""
-    from scipy.stats import truncnorm
     with torch.no_grad():
-        loc, scale = tn_loc_scale(p.q_loc_raw, p.q_scale_raw, cfg.epsilon)
-        high = torch.as_tensor(cfg.high, dtype=loc.dtype)
-        F = tn_mean(loc, scale, x.low, high)
-        SigF = torch.sqrt(tn_variance(loc, scale, x.low, high))
+        F, var, f4 = _posterior_moments(p, x, cfg)
+        SigF = torch.sqrt(var)
         I = SigF * SigF + F * F
-        a = ((x.low - loc) / scale).numpy()
-        f4 = torch.as_tensor(truncnorm.moment(4, a, np.inf, loc.numpy(), scale.numpy()))
         SigI = torch.sqrt(torch.maximum((I * max_intensity_snr) ** 2, f4 - I * I))
     return dict(F=F, SigF=SigF, I=I, SigI=SigI)
 

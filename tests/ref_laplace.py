@@ -1,18 +1,11 @@
-"""fp64 restatement of the Laplace likelihood (reference careless/models/likelihoods/mono.py:20-23, laue.py:76-81:
-tfd.Laplace(Iobs, SigIobs / sqrt 2)) and of a whole ELBO step under it, for tests/test_laplace.py and tests/test_laplace_gpu.py.
-
-The whole-step reference sits ON TOP of the unchanged oracle, like tests/ref_prior.py: `O.elbo_forward` computes the step under the
-Normal likelihood, and because the likelihood enters the loss only through  nll = -w sum ll(ipred),  trading the Normal term for the
-Laplace one on the SAME attached predictions -- through `O.laue_convolve` for Laue data, over all N slots, the padded ones included, as
-the oracle's own `ll` -- gives the step under the Laplace likelihood:
-    nll_laplace  = nll  + w sum (normal_log_prob - laplace_log_prob)(ipred),      loss_laplace = loss + (the same)
-with w = 1 / S, or 1 / (S N) under `kl_weight`.  Gradients by torch.autograd.grad (the gradient of abs is sign, 0 at 0, as TensorFlow's).
+"""The problems of the Laplace-likelihood tests (tests/test_laplace.py, tests/test_laplace_gpu.py).  The density and the whole step under it
+are the oracle's (`O.laplace_log_prob`, `ElboConfig.likelihood = "laplace"`; the gradient of abs is sign, 0 at 0, as TensorFlow's).
 
 The problems of util.make_problem put every prediction far below its observation: every residual has one sign and the derivative of the
 Laplace term is one constant.  `rewrite_observations` moves the observations onto the predictions (see there)."""
 from __future__ import annotations
 
-import math
+from dataclasses import replace
 
 import numpy as np
 import torch
@@ -23,52 +16,9 @@ GUARD_REL = 1e-4          # the guard round the kink, relative to gmax * max|ipr
                           # sum over a harmonic group of gmax rows is within one guard and no sample outside the guard changes sides
 
 
-def f64(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.float64) if not torch.is_tensor(a) else a.to(torch.float64)
-
-
-def laplace_log_prob(x, loc, sig):
-    """`tfd.Laplace(loc, sig / sqrt 2).log_prob(x)`: -|x - loc| / b - log(2 b)."""
-    b = sig / math.sqrt(2.0)
-    return -torch.abs(x - loc) / b - torch.log(2.0 * b)
-
-
-def convolved(ipred, x, cfg):
-    return O.laue_convolve(ipred, x.harmonic_id) if cfg.laue else ipred
-
-
-def elbo_value_and_grads(params, x, cfg, u_f, eta, kl_mask=None, flips=None, near=None):
-    """Loss terms and gradients of one step under the Laplace likelihood (module docstring); signature and return value of
-    `O.elbo_value_and_grads`, plus out["ipred_l"], what the likelihood saw (S, N)."""
-    assert cfg.likelihood == "normal" and not cfg.ev11
-    q = params.clone(requires_grad=True)
-    out = O.elbo_forward(q, x, cfg, f64(u_f), f64(eta), kl_mask, flips=flips, near=near)
-    ipl = convolved(out["ipred"], x, cfg)
-    S, N = ipl.shape
-    swap = O.normal_log_prob(ipl, x.iobs[None, :], x.sigiobs[None, :]) - laplace_log_prob(ipl, x.iobs[None, :], x.sigiobs[None, :])
-    w = 1.0 / S if cfg.kl_weight is None else 1.0 / (S * N)
-    tot = w * swap.sum()
-    out = dict(out, nll=out["nll"] + tot, loss=out["loss"] + tot, ipred_l=ipl)
-    ts = q.tensors()
-    grads = torch.autograd.grad(out["loss"], ts, allow_unused=True)
-    grads = [torch.zeros_like(t) if g is None else g for g, t in zip(grads, ts)]
-    return {k: v.detach() for k, v in out.items()}, grads
-
-
-def train_step(p, x, cfg, st, u_f, eta):
-    """`O.train_step` with this module's gradients: global norm before the sanitise, non-finite -> 0, clipping, Adam (variational.py:185-224)."""
-    out, grads = elbo_value_and_grads(p, x, cfg, u_f, eta)
-    gnorm = O.global_norm(grads)
-    grads = [torch.where(torch.isfinite(g), g, torch.zeros_like(g)) for g in grads]
-    grads = O.clip_grads(grads, cfg)
-    O.adam_apply(p.tensors(), grads, st, cfg)
-    return {"loss": float(out["loss"]), "F KLDiv": float(out["kl"]), "NLL": float(out["nll"]), "Grad Norm": float(gnorm)}
-
-
-def validation_nll(p, x_val, cfg, u_f, eta, n_train):
-    """`O.validation_nll` under the Laplace likelihood."""
-    out, _ = elbo_value_and_grads(p, x_val, cfg, u_f, eta)
-    return float(out["nll"]) * n_train / int(x_val.refl_id.shape[0])
+def under(cfg):
+    """`cfg` with the Laplace likelihood."""
+    return replace(cfg, likelihood="laplace")
 
 
 # ---- the problem: observations on both sides of the predictions, none on the kink -----------------------------------------------------------
@@ -87,8 +37,8 @@ def predictions(data, cfg, params, u_f, eta):
     """(ipred (S, N), what the likelihood sees (S, N)) of the fp64 reference: independent of Iobs / SigIobs."""
     x = O.inputs_from_numpy(data)
     with torch.no_grad():
-        out = O.elbo_forward(params, x, cfg, f64(u_f), f64(eta))
-    return out["ipred"].numpy(), convolved(out["ipred"], x, cfg).numpy()
+        out = O.elbo_forward(params, x, cfg, O.f64(u_f), O.f64(eta))
+    return out["ipred"].numpy(), out["ipred_l"].numpy()
 
 
 def rewrite_observations(data, cfg, params, noises, seed=0):

@@ -11,7 +11,7 @@ order:
     ipred[i][s] = aim_i (loc_i + sigma_i eta[i][s] + shift) z_f[refl_i][s]^2            0 on rows with refl_id < 0
     iconv       = O.laue_convolve(ipred, slot)                                           (ipred itself without a slot map)
     NLL         = -w_ll sum over the COUNTED slots and samples of log p(iconv | iobs, sig)
-log p from O.normal_log_prob / O.studentt_log_prob / ref_laplace.laplace_log_prob; under the Evans-2011 error model sig is the oracle's
+log p from O.normal_log_prob / O.studentt_log_prob / O.laplace_log_prob; under the Evans-2011 error model sig is the oracle's
 (O.elbo_forward: sd[0] sqrt(sig^2 + sd[2] sp + sd[1] sp^2), sd = softplus(raw), sp = softplus(iconv); tests/test_ref_rows.py holds the whole
 reference against O.elbo_value_and_grads).  Which slots count: every active row (monochromatic), every slot 0 .. n_obs - 1 (Laue: the slots
 past the last group keep iconv = 0 and still count, elbo_laue.hip:1-6), member 0 of every group (the GROUPS form: the padded slots' constant
@@ -53,7 +53,7 @@ import numpy as np
 import torch
 
 from oracle import elbo_oracle as O
-from tests import ref_laplace, ref_step
+from tests import ref_step
 from tests.ref_q import host_lib, fp          # the host build of csrc/cl_math.h (tests/host_math_check.cpp)
 
 F32 = np.float32
@@ -306,7 +306,7 @@ def _log_prob(kind, dof, v, io, sc):
         return O.normal_log_prob(v, io, sc)
     if kind == "studentt":
         return O.studentt_log_prob(v, float(dof), io, sc)
-    return ref_laplace.laplace_log_prob(v, io, sc)
+    return O.laplace_log_prob(v, io, sc)
 
 
 def reference(x, values_only=False):

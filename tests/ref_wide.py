@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests.ref_step import f64
+
 U = 2.0 ** -24
 BIJ_EXP, BIJ_SOFTPLUS = 0, 1
 BIJ_RTOL = 1e-5
@@ -23,10 +25,6 @@ BIJ_RTOL = 1e-5
 
 def gamma(m):
     return m * U / (1.0 - m * U)
-
-
-def f64(a):
-    return np.asarray(a, dtype=np.float64)
 
 
 def slope(h, leak):

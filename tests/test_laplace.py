@@ -1,4 +1,4 @@
-"""The Laplace likelihood without a GPU: the fp64 reference of tests/ref_laplace.py and the two plugin classes against torch and scipy, the
+"""The Laplace likelihood without a GPU: the oracle's fp64 restatement of it and the two plugin classes against torch and scipy, the
 reference's own unit tests restated (careless tests/models/likelihoods/test_mono.py:25-36, test_laue.py:38-66), a host build of
 csrc/cl_math.h -- cl_lik_laplace_log_prob against fp64, the Normal and Student-T results of the three two-way forms bit for bit against the
 expressions they had before --, the constants, the entry checks that need no launch, and the problem construction the GPU tests stand on."""
@@ -38,8 +38,8 @@ def test_reference_density_is_torch_and_scipy_laplace():
     rng = np.random.default_rng(0)
     loc, sig = rng.normal(size=500) * 30, 0.1 + 5 * rng.random(500)
     x = loc + sig * rng.normal(size=(3, 500)) * 2
-    got = RL.laplace_log_prob(RL.f64(x), RL.f64(loc), RL.f64(sig)).numpy()
-    a = torch.distributions.Laplace(RL.f64(loc), RL.f64(sig) / SQRT2).log_prob(RL.f64(x)).numpy()
+    got = O.laplace_log_prob(O.f64(x), O.f64(loc), O.f64(sig)).numpy()
+    a = torch.distributions.Laplace(O.f64(loc), O.f64(sig) / SQRT2).log_prob(O.f64(x)).numpy()
     b = stats.laplace.logpdf(x, loc=loc, scale=sig / SQRT2)
     assert np.allclose(got, a, rtol=1e-13, atol=1e-13) and np.allclose(got, b, rtol=1e-13, atol=1e-13)
     # the issue's second form
@@ -211,14 +211,14 @@ def test_rewritten_observations_put_the_kink_inside_the_data(kw):
         assert np.array_equal(new["iobs"][G:], data["iobs"][G:]) and np.array_equal(new["sigiobs"][G:], data["sigiobs"][G:]) and G < len(new["iobs"])
     # the step under the Laplace likelihood differs from the Normal step, and its data gradient is finite
     xn = O.inputs_from_numpy(new)
-    out, grads = RL.elbo_value_and_grads(params, xn, cfg, u_f, eta)
-    on, _ = O.elbo_value_and_grads(params, xn, cfg, RL.f64(u_f), RL.f64(eta))
+    out, grads = O.elbo_value_and_grads(params, xn, RL.under(cfg), O.f64(u_f), O.f64(eta))
+    on, _ = O.elbo_value_and_grads(params, xn, cfg, O.f64(u_f), O.f64(eta))
     assert abs(float(out["nll"]) - float(on["nll"])) > 1e-2 * abs(float(on["nll"]))
     assert abs(float(out["kl"]) - float(on["kl"])) == 0.0 and all(torch.isfinite(g).all() for g in grads)
     # ... and is the hand-written derivative: d nll / d ipred_l = w sign(d) sqrt2 / sig
     S = cfg.mc_samples
     ipl_t = torch.as_tensor(ipl).requires_grad_(True)
-    (g,) = torch.autograd.grad(-RL.laplace_log_prob(ipl_t, xn.iobs[None, :], xn.sigiobs[None, :]).sum() / S, ipl_t)
+    (g,) = torch.autograd.grad(-O.laplace_log_prob(ipl_t, xn.iobs[None, :], xn.sigiobs[None, :]).sum() / S, ipl_t)
     d = ipl - new["iobs"].astype(np.float64)[None, :]
     assert np.allclose(g.numpy(), np.sign(d) * SQRT2 / new["sigiobs"].astype(np.float64)[None, :] / S, rtol=1e-12)
 

@@ -1,5 +1,5 @@
-"""The Laplace likelihood on the GPU: whole training steps of the engine against the fp64 restatement of tests/ref_laplace.py (the
-unchanged oracle with the Normal term traded for the Laplace one), deterministic mode, the frozen scaler, row-split and reflection-owner
+"""The Laplace likelihood on the GPU: whole training steps of the engine against the fp64 oracle under its Laplace likelihood
+(`ElboConfig.likelihood = "laplace"`), deterministic mode, the frozen scaler, row-split and reflection-owner
 shards, NLL_val, an Adam trajectory, the non-finite step contract and the slot kernels' Laplace instances called directly.
 
 The cases are the rows of tests/test_nonfinite.py's MATRIX (its keyword dictionaries, routes and kernel-name fragments; the four Ev11 /
@@ -144,13 +144,13 @@ def assert_grads(g_hip, grads, prob, name):
     data, cfg, params, u_f, eta = prob
     x = O.inputs_from_numpy(data)
     near = []
-    RL.elbo_value_and_grads(params, x, cfg, u_f, eta, near=near)
+    O.elbo_value_and_grads(params, x, RL.under(cfg), O.f64(u_f), O.f64(eta), near=near)
     near.sort()
     cand = [(l, r, u) for _, l, r, u in near[:P.MAX_FLIP_CANDIDATES]]
     assert cand, f"{name}: gradient errors {errs} and no LeakyReLU pre-activation within fp32 rounding of zero: not a branch flip"
     for k in range(1, len(cand) + 1):
         for sub in itertools.combinations(cand, k):
-            _, gf = RL.elbo_value_and_grads(params, x, cfg, u_f, eta, flips=sub)
+            _, gf = O.elbo_value_and_grads(params, x, RL.under(cfg), O.f64(u_f), O.f64(eta), flips=sub)
             if max(util.rel_err(a, b.numpy()) for a, b in zip(g_hip, gf[:n])) < P.RTOL_GRAD:
                 print(f"{name}: gradients match with the LeakyReLU unit(s) {list(sub)} on the engine's branch")
                 return
@@ -162,7 +162,7 @@ def assert_grads(g_hip, grads, prob, name):
 def test_whole_step_matches_the_fp64_reference(name):
     case, kw, opts, _, data, cfg, params, u_f, eta = problem(name)
     x = O.inputs_from_numpy(data)
-    out, grads = RL.elbo_value_and_grads(params, x, cfg, u_f, eta)
+    out, grads = O.elbo_value_and_grads(params, x, RL.under(cfg), O.f64(u_f), O.f64(eta))
     gap, pos = RL.assert_conditions(data, out["ipred"].numpy(), out["ipred_l"].numpy())
     print(f"{name}: smallest gap {gap:.2f} guards, {100 * pos:.0f} % positive residuals")
     model = laplace_model(case, kw, opts, data, cfg, params)
@@ -183,7 +183,7 @@ def test_whole_step_matches_the_fp64_reference(name):
         g_hip = g_hip[:2]
     assert_grads(g_hip, grads, (data, cfg, params, u_f, eta), name)
     # the likelihood matters: the same step under the Normal likelihood has another NLL
-    nll_n = float(O.elbo_value_and_grads(params, x, cfg, RL.f64(u_f), RL.f64(eta))[0]["nll"])
+    nll_n = float(O.elbo_value_and_grads(params, x, cfg, O.f64(u_f), O.f64(eta))[0]["nll"])
     assert abs(float(out["nll"]) - nll_n) > 1e-2 * abs(nll_n)
 
 
@@ -292,7 +292,7 @@ def test_validation_nll_matches_the_reference():
     rng = np.random.default_rng(12)
     noise = (u_f, eta[:, :n_tr])                             # the training rows' share of the noise the observations were rewritten under
     vnoise = (rng.random((2, 48)).astype(np.float32), rng.normal(size=(2, kw["N"] - n_tr)).astype(np.float32))
-    out, _ = RL.elbo_value_and_grads(params, x_tr, cfg, *noise)
+    out, _ = O.elbo_value_and_grads(params, x_tr, RL.under(cfg), *map(O.f64, noise))
     RL.assert_conditions(d_tr, out["ipred"].numpy(), out["ipred_l"].numpy())
     probe = fresh()                                          # the first step's predictions: no sample on the other side of its observation
     assert util.rel_err(probe(train, u_f=noise[0], eta=noise[1]).cpu().numpy(), out["ipred"].numpy()) < 1e-4
@@ -300,9 +300,9 @@ def test_validation_nll_matches_the_reference():
     hist = model.train_model(train, 1, progress=False, validation_data=test, validation_frequency=1, noise=lambda i: noise,
                              validation_noise=lambda i: vnoise)
     p = params.clone()
-    rec = RL.train_step(p, x_tr, cfg, O.AdamState.zeros_like(p.tensors()), *noise)
-    ref = RL.validation_nll(p, x_te, cfg, vnoise[0], vnoise[1], n_tr)
-    normal = O.validation_nll(p, x_te, cfg, RL.f64(vnoise[0]), RL.f64(vnoise[1]), n_tr)
+    rec = O.train_step(p, x_tr, RL.under(cfg), O.AdamState.zeros_like(p.tensors()), *map(O.f64, noise))
+    ref = O.validation_nll(p, x_te, RL.under(cfg), O.f64(vnoise[0]), O.f64(vnoise[1]), n_tr)
+    normal = O.validation_nll(p, x_te, cfg, O.f64(vnoise[0]), O.f64(vnoise[1]), n_tr)
     print("NLL_val", hist["NLL_val"], "reference", ref, "under the Normal likelihood", normal)
     assert len(hist["NLL_val"]) == 1 and abs(hist["NLL_val"][0] - ref) <= P.RTOL_LOSS * abs(ref)
     assert abs(hist["NLL"][0] - rec["NLL"]) <= P.RTOL_LOSS * abs(rec["NLL"]) and abs(ref - normal) > 1e-2 * abs(normal)
@@ -323,11 +323,11 @@ def _trajectory(seed, steps=5):
     st = O.AdamState.zeros_like(p.tensors())
     ref, worst, first = [], np.inf, None
     for u, e in noises:
-        out, _ = RL.elbo_value_and_grads(p, x, cfg, u, e)
+        out, _ = O.elbo_value_and_grads(p, x, RL.under(cfg), O.f64(u), O.f64(e))
         first = out if first is None else first
         gap, pos = RL.assert_conditions(data, out["ipred"].numpy(), out["ipred_l"].numpy())
         worst = min(worst, gap)
-        ref.append(RL.train_step(p, x, cfg, st, u, e))
+        ref.append(O.train_step(p, x, RL.under(cfg), st, O.f64(u), O.f64(e)))
 
     def fresh():
         m = util.build_model(data, cfg, params, kw["L"], kw["w"])
@@ -356,10 +356,10 @@ def test_adam_trajectory_matches_the_reference_loop():
 def _reference_of_a_poisoned_step(name, poison):
     case, kw, opts, clean, data, cfg, params, u_f, eta = problem(name, poison, "inner")
     # the clean twin meets the two conditions; the poisoned step's LeakyReLU branches are not in doubt (tests/test_nonfinite.py: `_oracle_grads`)
-    co, _ = RL.elbo_value_and_grads(params, O.inputs_from_numpy(clean), cfg, u_f, eta)
+    co, _ = O.elbo_value_and_grads(params, O.inputs_from_numpy(clean), RL.under(cfg), O.f64(u_f), O.f64(eta))
     RL.assert_conditions(clean, co["ipred"].numpy(), co["ipred_l"].numpy())
     near = []
-    out, grads = RL.elbo_value_and_grads(params, O.inputs_from_numpy(data), cfg, u_f, eta, near=near)
+    out, grads = O.elbo_value_and_grads(params, O.inputs_from_numpy(data), RL.under(cfg), O.f64(u_f), O.f64(eta), near=near)
     near = [t for t in near if np.isfinite(t[0])]
     assert not near, sorted(near)[:5]
     assert float(out["z_f"].min()) >= 1e-2
@@ -401,7 +401,7 @@ def test_training_stops_after_the_sanitised_step(name, poison):
     inputs = util.reference_inputs(data)
     assert_route(model.engine(inputs), case, plan_of(case, kw, opts, data, cfg))
     p = params.clone()
-    rec = RL.train_step(p, O.inputs_from_numpy(data), cfg, O.AdamState.zeros_like(p.tensors()), u_f, eta)
+    rec = O.train_step(p, O.inputs_from_numpy(data), RL.under(cfg), O.AdamState.zeros_like(p.tensors()), O.f64(u_f), O.f64(eta))
     after = [t.numpy() for t in p.tensors()]
     hist = model.train_model(inputs, 4, progress=False, noise=lambda i: (u_f, eta))
     eng = model._engine
@@ -463,8 +463,8 @@ def test_cl_laue_likelihood_laplace_instance_and_its_entry_checks():
         assert rc == -1 and np.array_equal(out, iconv, equal_nan=True) and not scal.any(), (kind, with_ev)
     rc, out, scal = call(_lib.CL_LIK_LAPLACE)
     assert rc == 0
-    x = RL.f64(iconv).requires_grad_(True)
-    lp = RL.laplace_log_prob(x, RL.f64(iobs)[:, None], RL.f64(sig)[:, None])
+    x = O.f64(iconv).requires_grad_(True)
+    lp = O.laplace_log_prob(x, O.f64(iobs)[:, None], O.f64(sig)[:, None])
     fin = np.ones((n, S), bool); fin[11] = False
     (g,) = torch.autograd.grad(lp[torch.as_tensor(fin)].sum(), x)
     ref = -np.float64(np.float32(w)) * g.numpy()
@@ -474,7 +474,7 @@ def test_cl_laue_likelihood_laplace_instance_and_its_entry_checks():
     iobs[11] = iconv[11, 0]
     t_iobs = dev(iobs)
     rc, out, scal = call(_lib.CL_LIK_LAPLACE)
-    nll = -np.float64(np.float32(w)) * float(RL.laplace_log_prob(RL.f64(iconv), RL.f64(iobs)[:, None], RL.f64(sig)[:, None]).sum())
+    nll = -np.float64(np.float32(w)) * float(O.laplace_log_prob(O.f64(iconv), O.f64(iobs)[:, None], O.f64(sig)[:, None]).sum())
     assert rc == 0 and abs(scal[_lib.CL_SC_NLL] - nll) <= P.RTOL_LOSS * abs(nll) and np.isfinite(out).all()
 
 
@@ -510,5 +510,5 @@ def test_cl_slot_rows_entry_checks_and_laplace_instance():
         rc, dzf, dO, scal = call(kind, with_ev)
         assert rc == -1 and not dzf.any() and not dO.any() and not scal.any(), (kind, with_ev)
     rc, dzf, dO, scal = call(_lib.CL_LIK_LAPLACE)
-    nll = -0.5 * float(RL.laplace_log_prob(RL.f64(ipred), RL.f64(iobs)[:, None], RL.f64(sig)[:, None]).sum())
+    nll = -0.5 * float(O.laplace_log_prob(O.f64(ipred), O.f64(iobs)[:, None], O.f64(sig)[:, None]).sum())
     assert rc == 0 and abs(scal[_lib.CL_SC_NLL] - nll) <= P.RTOL_LOSS * abs(nll) and dzf.any() and np.isfinite(dzf).all()

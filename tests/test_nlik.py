@@ -1,5 +1,5 @@
 """The neural likelihood off the GPU: the plugin class, its place in the flat parameter vector, the engine's refusals, the entry checks of
-cl_nlik_forward / cl_nlik_backward, and the fp64 reference of tests/ref_nlik.py checked by finite differences of its own loss."""
+cl_nlik_forward / cl_nlik_backward, and the fp64 reference (the oracle's neural likelihood) checked by finite differences of its own loss."""
 import ctypes as C
 import math
 import os
@@ -74,9 +74,9 @@ def test_call_log_prob_matches_the_fp64_reference(L, w, seed):
     net, _ = RN.pick_net(L, w, x.iobs, x.sigiobs, first_seed=seed)
     lik = NeuralNormalLikelihood(L, w)
     lik.set_weights([t.numpy() for t in net])
-    net = [RN.f64(np.asarray(t)) for t in lik.weights]            # (the fp32 values the class holds)
-    ipred = O.elbo_forward(params, x, cfg, RN.f64(u_f), RN.f64(eta))["ipred"].detach()
-    delta, sigpred, _, _ = RN.forward(net, x.iobs, x.sigiobs)
+    net = [O.f64(np.asarray(t)) for t in lik.weights]            # (the fp32 values the class holds)
+    ipred = O.elbo_forward(params, x, cfg, O.f64(u_f), O.f64(eta))["ipred"].detach()
+    delta, sigpred, _, _ = O.nlik_forward(net, x.iobs, x.sigiobs)
     want = O.normal_log_prob(ipred, x.iobs[None, :], sigpred[None, :]).numpy()
     dist = lik(util.reference_inputs(data))
     got = dist.log_prob(ipred.numpy())
@@ -260,23 +260,23 @@ def test_entry_checks_reject_one_clause_at_a_time(which):
 def test_reference_gradient_matches_finite_differences_of_its_own_loss(L, w, seed, klw):
     data, cfg, params, x, u_f, eta = util.make_problem(N=120, R=20, S=2, seed=seed, kl_weight=klw)
     net, _ = RN.pick_net(L, w, x.iobs, x.sigiobs, first_seed=seed)
-    out, grads = RN.elbo_value_and_grads(params, net, x, cfg, u_f, eta)
+    out, grads = O.elbo_value_and_grads(RN.with_net(params, net), x, RN.under(cfg), O.f64(u_f), O.f64(eta))
     assert out["kink"] > RN.KINK_REL
     g_net = grads[-len(net):]
     rng = np.random.default_rng(seed)
     for k, t in enumerate(net):
-        v = RN.f64(rng.normal(size=tuple(t.shape)))
+        v = O.f64(rng.normal(size=tuple(t.shape)))
         h = 1e-6 * max(float(t.abs().max()), 1e-2)
         lo, hi = ([s.clone() for s in net] for _ in range(2))
         lo[k] -= h * v
         hi[k] += h * v
-        fd = (float(RN.elbo_value_and_grads(params, hi, x, cfg, u_f, eta)[0]["loss"]) -
-              float(RN.elbo_value_and_grads(params, lo, x, cfg, u_f, eta)[0]["loss"])) / (2 * h)
+        fd = (float(O.elbo_value_and_grads(RN.with_net(params, hi), x, RN.under(cfg), O.f64(u_f), O.f64(eta))[0]["loss"]) -
+              float(O.elbo_value_and_grads(RN.with_net(params, lo), x, RN.under(cfg), O.f64(u_f), O.f64(eta))[0]["loss"])) / (2 * h)
         an = float((g_net[k] * v).sum())
         # (central differences: truncation ~ h^2, rounding ~ eps64 |loss| / h)
         assert abs(fd - an) <= 1e-5 * abs(an) + 1e-14 * abs(float(out["loss"])) / h, (k, fd, an)
     # the model's own gradients are the oracle's with the Normal term traded: they differ from the plain Normal step's
-    _, g_plain = O.elbo_value_and_grads(params, x, cfg, RN.f64(u_f), RN.f64(eta))
+    _, g_plain = O.elbo_value_and_grads(params, x, cfg, O.f64(u_f), O.f64(eta))
     assert util.rel_err(grads[0].numpy(), g_plain[0].numpy()) > 1e-3
 
 
@@ -284,7 +284,7 @@ def test_kernel_reference_agrees_with_the_whole_step_reference():
     """`kernel_reference` (what the GPU kernels are held to on injected predictions) is the network part of the whole-step reference."""
     data, cfg, params, x, u_f, eta = util.make_problem(N=150, R=20, S=3, seed=9)
     net, _ = RN.pick_net(2, 10, x.iobs, x.sigiobs, first_seed=4)
-    out, grads = RN.elbo_value_and_grads(params, net, x, cfg, u_f, eta)
+    out, grads = O.elbo_value_and_grads(RN.with_net(params, net), x, RN.under(cfg), O.f64(u_f), O.f64(eta))
     assert np.isfinite(float(out["loss"])) and float(out["delta"].min()) > 4e-5
     delta, sigpred, g, kink = RN.kernel_reference(net, x.iobs, x.sigiobs, out["ipred"].t(), 1.0 / 3)
     assert torch.equal(sigpred, out["sigpred"]) and kink == out["kink"]
@@ -297,5 +297,5 @@ def test_kernel_reference_agrees_with_the_whole_step_reference():
     T, m, N = float((gi * sigpred).sum()), float(delta.mean()), len(io)
     dd = (gi * sg - T / N) / m
     assert abs(float((delta * dd).sum())) <= 1e-9 * float((delta * dd).abs().sum())            # scale invariance
-    _, _, zh, _ = RN.forward(net, x.iobs, x.sigiobs)
+    _, _, zh, _ = O.nlik_forward(net, x.iobs, x.sigiobs)
     assert util.rel_err(float((dd * torch.sigmoid(zh)).sum()), float(g[-1][0])) < 1e-10       # the head's bias gradient

@@ -1,6 +1,6 @@
 """The neural likelihood on the GPU: cl_nlik_forward / cl_nlik_backward called directly on injected predictions against fp64, whole
-training steps of the engine against the fp64 restatement of tests/ref_nlik.py (the unchanged oracle with the Normal term on SigIobs
-traded for the one on sigpred), the frozen scaler, NLL_val, a shard cut into pieces, an Adam trajectory, the non-finite step contract
+training steps of the engine against the fp64 oracle under its neural likelihood
+(`ElboConfig.likelihood = "neural"`, the network in `ElboParams.nlik`), the frozen scaler, NLL_val, a shard cut into pieces, an Adam trajectory, the non-finite step contract
 and finite differences of the engine's own loss.
 
 The whole-step cases are the monochromatic rows without Ev11 of tests/test_nonfinite.py's MATRIX (its keyword dictionaries, routes and
@@ -45,7 +45,7 @@ def _kernel_problem(N, L, w, S, seed=0):
     sig = (5.0 + 0.05 * iobs * rng.uniform(0.5, 1.5, size=N)).astype(np.float32)
     ipred = (iobs[:, None] + 1.5 * sig[:, None] * rng.normal(size=(N, S))).astype(np.float32)
     net, _ = RN.pick_net(L, w, iobs, sig, first_seed=seed)
-    net = [RN.f64(t.to(torch.float32)) for t in net]                         # the fp32 values the kernels read
+    net = [O.f64(t.to(torch.float32)) for t in net]                         # the fp32 values the kernels read
     return iobs, sig, ipred, net
 
 
@@ -162,7 +162,7 @@ def problem(name, poison=None, where="inner", keep_lik=False):
     net = None
     if not _is_refused(case):
         net, _ = RN.pick_net(L, w, data["iobs"], data["sigiobs"], first_seed=case.seed)
-        net = [RN.f64(t.to(torch.float32)) for t in net]
+        net = [O.f64(t.to(torch.float32)) for t in net]
     if poison is not None:
         row = NF._pick_row(data, where)
         column, value = NF.POISONS[poison]
@@ -183,15 +183,6 @@ def neural_model(case, kw, opts, data, cfg, params, net, **attrs):
     return model
 
 
-def engine_order(ts, params, n_net):
-    """The reference's tensor list [model tensors ..., dw_r?, network] in the engine's order (the likelihood's group sits in front of the
-    double-Wilson r in the flat vector)."""
-    ts = list(ts)
-    if params.dw_r_raw is None:
-        return ts
-    return ts[:-n_net - 1] + ts[-n_net:] + [ts[-n_net - 1]]
-
-
 def assert_terms(terms, out, name):
     for k in ("nll", "kl", "loss"):
         den = max(abs(float(out[k])), 1.0) if k == "kl" else abs(float(out[k]))
@@ -209,13 +200,13 @@ def assert_grads(g_hip, grads, prob, name, order=lambda g: g):
     data, cfg, params, u_f, eta, net = prob
     x = O.inputs_from_numpy(data)
     near = []
-    RN.elbo_value_and_grads(params, net, x, cfg, u_f, eta, near=near)
+    O.elbo_value_and_grads(RN.with_net(params, net), x, RN.under(cfg), O.f64(u_f), O.f64(eta), near=near)
     near.sort()
     cand = [(l, r, u) for _, l, r, u in near[:P.MAX_FLIP_CANDIDATES]]
     assert cand, f"{name}: gradient errors {errs} and no LeakyReLU pre-activation of the scaler within fp32 rounding of zero: not a branch flip"
     for k in range(1, len(cand) + 1):
         for sub in itertools.combinations(cand, k):
-            _, gf = RN.elbo_value_and_grads(params, net, x, cfg, u_f, eta, flips=sub)
+            _, gf = O.elbo_value_and_grads(RN.with_net(params, net), x, RN.under(cfg), O.f64(u_f), O.f64(eta), flips=sub)
             if max(util.rel_err(a, b.numpy()) for a, b in zip(g_hip, order(gf))) < P.RTOL_GRAD:
                 print(f"{name}: gradients match with the scaler's LeakyReLU unit(s) {list(sub)} on the engine's branch")
                 return
@@ -227,7 +218,7 @@ def assert_grads(g_hip, grads, prob, name, order=lambda g: g):
 def test_whole_step_matches_the_fp64_reference(name):
     case, kw, opts, data, cfg, params, u_f, eta, net = problem(name)
     x = O.inputs_from_numpy(data)
-    out, grads = RN.elbo_value_and_grads(params, net, x, cfg, u_f, eta)
+    out, grads = O.elbo_value_and_grads(RN.with_net(params, net), x, RN.under(cfg), O.f64(u_f), O.f64(eta))
     assert out["kink"] > RN.KINK_REL and float(out["delta"].min()) > 4e-5, (out["kink"], float(out["delta"].min()))
     model = neural_model(case, kw, opts, data, cfg, params, net)
     inputs = util.reference_inputs(data)
@@ -245,7 +236,7 @@ def test_whole_step_matches_the_fp64_reference(name):
     print(f"{name}: sigpred {util.rel_err(sp, out['sigpred'].numpy()):.1e}, kink {out['kink']:.1e}")
     assert util.rel_err(sp, out["sigpred"].numpy()) < P.RTOL_GRAD
     assert_terms(eng.loss_terms(), out, name)
-    order = lambda g: engine_order(g, params, len(net))
+    order = list                     # (`ElboParams.tensors()` is in the engine's order: the likelihood's group in front of the double-Wilson r)
     g_hip = [g.cpu().numpy() for g in eng.grad_tensors()]
     g_ref = order(grads)
     assert len(g_hip) == len(g_ref) and [a.shape for a in g_hip] == [tuple(b.shape) for b in g_ref]
@@ -258,7 +249,7 @@ def test_whole_step_matches_the_fp64_reference(name):
     assert all(float(np.abs(g).max()) > 0.0 for g in g_hip[-len(net):])
     assert_grads(g_hip, g_ref, (data, cfg, params, u_f, eta, net), name, pick)
     # the likelihood matters: the same step under the plain Normal likelihood has another NLL
-    nll_n = float(O.elbo_value_and_grads(params, x, cfg, RN.f64(u_f), RN.f64(eta))[0]["nll"])
+    nll_n = float(O.elbo_value_and_grads(params, x, cfg, O.f64(u_f), O.f64(eta))[0]["nll"])
     assert abs(float(out["nll"]) - nll_n) > 1e-2 * abs(nll_n)
 
 
@@ -292,7 +283,7 @@ def test_frozen_scaler_trains_the_network_and_repeats_bit_for_bit(form):
     name = "frozen_mono_20x10"
     case, kw, opts, data, cfg, params, u_f, eta, net = problem(name)
     x = O.inputs_from_numpy(data)
-    out, grads = RN.elbo_value_and_grads(params, net, x, cfg, u_f, eta)
+    out, grads = O.elbo_value_and_grads(RN.with_net(params, net), x, RN.under(cfg), O.f64(u_f), O.f64(eta))
     assert out["kink"] > RN.KINK_REL
     inputs = util.reference_inputs(data)
     n = len(net)
@@ -360,7 +351,7 @@ def test_validation_nll_takes_the_mean_over_the_validation_rows():
         return O.inputs_from_numpy(d)
     x_tr, x_te = as_x(train), as_x(test)
     net, _ = RN.pick_net(2, 8, data["iobs"], data["sigiobs"], first_seed=3)
-    net = [RN.f64(t.to(torch.float32)) for t in net]
+    net = [O.f64(t.to(torch.float32)) for t in net]
     rng = np.random.default_rng(12)
     noise = (u_f, eta[:, :n_tr])
     vnoise = (rng.random((2, 48)).astype(np.float32), rng.normal(size=(2, kw["N"] - n_tr)).astype(np.float32))
@@ -369,12 +360,12 @@ def test_validation_nll_takes_the_mean_over_the_validation_rows():
     model.likelihood.set_weights([t.numpy() for t in net])
     hist = model.train_model(train, 1, progress=False, validation_data=test, validation_frequency=1, noise=lambda i: noise, validation_noise=lambda i: vnoise)
     p, nt = params.clone(), [t.clone() for t in net]
-    rec = RN.train_step(p, nt, x_tr, cfg, O.AdamState.zeros_like(p.tensors() + nt), *noise)
+    rec = O.train_step(RN.with_net(p, nt), x_tr, RN.under(cfg), O.AdamState.zeros_like(p.tensors() + nt), *map(O.f64, noise))
     assert rec["kink"] > RN.KINK_REL
-    ref = RN.validation_nll(p, nt, x_te, cfg, vnoise[0], vnoise[1], n_tr)
+    ref = O.validation_nll(RN.with_net(p, nt), x_te, RN.under(cfg), O.f64(vnoise[0]), O.f64(vnoise[1]), n_tr)
     # ... not the training set's mean: sigpred of the validation rows under the mean over ALL rows is another number
-    _, sp_all, _, _ = RN.forward(nt, data["iobs"], data["sigiobs"])
-    _, sp_te, _, kink_te = RN.forward(nt, data["iobs"][n_tr:], data["sigiobs"][n_tr:])
+    _, sp_all, _, _ = O.nlik_forward(nt, data["iobs"], data["sigiobs"])
+    _, sp_te, _, kink_te = O.nlik_forward(nt, data["iobs"][n_tr:], data["sigiobs"][n_tr:])
     assert kink_te > RN.KINK_REL and util.rel_err(sp_all[n_tr:].detach().numpy(), sp_te.detach().numpy()) > 1e-3
     print("NLL_val", hist["NLL_val"], "reference", ref)
     assert len(hist["NLL_val"]) == 1 and abs(hist["NLL_val"][0] - ref) <= P.RTOL_LOSS * abs(ref)
@@ -387,7 +378,7 @@ def test_chunked_shard_equals_the_uncut_step(monkeypatch):
     name = "mlp32_2x32"
     case, kw, opts, data, cfg, params, u_f, eta, net = problem(name)
     inputs = util.reference_inputs(data)
-    out, grads = RN.elbo_value_and_grads(params, net, O.inputs_from_numpy(data), cfg, u_f, eta)
+    out, grads = O.elbo_value_and_grads(RN.with_net(params, net), O.inputs_from_numpy(data), RN.under(cfg), O.f64(u_f), O.f64(eta))
     assert out["kink"] > RN.KINK_REL
     whole = ElboEngine(neural_model(case, kw, opts, data, cfg, params, net), inputs, seed=5)
     monkeypatch.setenv("CARELESS_HIP_MAX_LAUNCH_BYTES", str(32 * 128))            # 128 rows of 8 metadata floats per launch
@@ -417,13 +408,13 @@ def test_adam_trajectory_of_twenty_steps():
     rng = np.random.default_rng(18)
     noises = [(rng.random((2, 48)).astype(np.float32), rng.normal(size=(2, 384)).astype(np.float32)) for _ in range(steps)]
     net, _ = RN.pick_net(2, 8, data["iobs"], data["sigiobs"], first_seed=3)
-    net = [RN.f64(t.to(torch.float32)) for t in net]
+    net = [O.f64(t.to(torch.float32)) for t in net]
     model = util.build_model(data, cfg, params, kw["L"], kw["w"])
     model.likelihood = NeuralNormalLikelihood(2, 8)
     model.likelihood.set_weights([t.numpy() for t in net])
     p, nt = params.clone(), [t.clone() for t in net]
     st = O.AdamState.zeros_like(p.tensors() + nt)
-    ref = [RN.train_step(p, nt, x, cfg, st, u, e) for u, e in noises]
+    ref = [O.train_step(RN.with_net(p, nt), x, RN.under(cfg), st, O.f64(u), O.f64(e)) for u, e in noises]
     assert min(r["kink"] for r in ref) > RN.KINK_REL, min(r["kink"] for r in ref)
     hist = model.train_model(util.reference_inputs(data), steps, progress=False, noise=lambda i: noises[i])
     assert len(hist["loss"]) == steps

@@ -1,8 +1,7 @@
 """What holds tests/ref_mlp.py -- the fp64 reference, the bounds and the case list of tests/test_mlp_kernels_gpu.py -- without a GPU:
 
   * the reference against oracle/elbo_oracle.py: the scaler's outputs against O.mlp_forward / O.scale_bijector, the NLL and the gradients of the
-    scaler, the image scales and the Evans-2011 triple against O.elbo_value_and_grads (the KL does not reach them; the Laplace kind through
-    tests/ref_laplace.py), dz_f through the oracle's own graph;
+    scaler, the image scales and the Evans-2011 triple against O.elbo_value_and_grads (the KL does not reach them), dz_f through the oracle's own graph;
   * an fp32 emulation of the launch (numpy float32 in any summation order -- the fp32 MFMA is an fmaf chain, DESIGN 4.1 -- with the scalar
     math of the host build of csrc/cl_math.h) stays inside a QUARTER of every bound on the inputs of every GPU case;
   * every wrong kernel of ref_mlp.MUTANTS misses at least one bound on a case of the list (the factor is printed);
@@ -16,7 +15,6 @@ import pytest
 import torch
 
 from oracle import elbo_oracle as O
-from tests import ref_laplace
 from tests import ref_mlp as RM
 from tests import ref_rows as RR
 from tests import ref_wide as RW
@@ -52,7 +50,7 @@ def test_reference_equals_the_oracle(c):
     sig = O.scale_bijector(out[:, 1], c.bij, float(x.eps))
     assert np.allclose(x.fw.loc[0], out[:, 0].numpy(), rtol=1e-12, atol=1e-13) and np.allclose(x.fw.sig[0], sig.numpy(), rtol=1e-12, atol=1e-13)
     lap = c.lik == "laplace"
-    cfg = O.ElboConfig(mc_samples=x.S, likelihood="normal" if lap else c.lik, dof=float(x.dof), scale_bijector=c.bij, epsilon=float(x.eps), scale_shift=float(x.shift),
+    cfg = O.ElboConfig(mc_samples=x.S, likelihood=c.lik, dof=float(x.dof), scale_bijector=c.bij, epsilon=float(x.eps), scale_shift=float(x.shift),
                        use_image_scales=x.img is not None, ev11=c.ev11, leakiness=RM.LEAK)
     rng = np.random.default_rng(5)
     p = O.ElboParams(T(rng.normal(0.0, 0.3, x.R)), T(np.log(rng.uniform(0.05, 0.3, x.R))), ws, bs, img_raw=T(x.img) if x.img is not None else None,
@@ -61,7 +59,7 @@ def test_reference_equals_the_oracle(c):
     inp = O.ElboInputs(torch.as_tensor(x.refl_id.astype(np.int64)), torch.as_tensor(image_id.astype(np.int64)), T(x.X), T(x.iobs), T(x.sig),
                        torch.zeros(x.R, dtype=torch.bool), T(np.ones(x.R)), T(np.full(x.R, 1e-32)), sigma=T(1.0))
     u_f, eta = T(rng.uniform(0.05, 0.95, (x.S, x.R))), T(x.eta.T)
-    res, grads = (ref_laplace if lap else O).elbo_value_and_grads(p, inp, cfg, u_f, eta)
+    res, grads = O.elbo_value_and_grads(p, inp, cfg, u_f, eta)
     x.z_f = res["z_f"].numpy().T.copy()                               # the oracle's own amplitudes, in fp64
     x.w_ll = 1.0 / x.S                                                # (the oracle's weight: the device gets its fp32 rounding)
     ref = RM.reference(x)

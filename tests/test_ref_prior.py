@@ -1,4 +1,4 @@
-"""Empirical reference priors without a device: the fp64 reference functions of tests/ref_prior.py against independent closed forms, the
+"""Empirical reference priors without a device: the oracle's fp64 restatement of them against independent closed forms, the
 plugin classes of careless_amd/models/priors/empirical.py held to the reference's own test (tests/models/priors/test_empirical.py:30-47 of
 the reference), the C-ABI of `cl_ref_prior` (struct size, entry checks that answer before any launch) and the engine's acceptance rules."""
 import ctypes as C
@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from careless_amd import _lib
+from oracle import elbo_oracle as O
 from tests import ref_prior as RP
 
 KINDS = RP.KINDS
@@ -26,24 +27,24 @@ def _problem(n=64, seed=3):
 # ---- the reference functions ---------------------------------------------------------------------------------------------------------
 def test_normal_laplace_studentt_match_torch_distributions():
     z, loc, scale, _ = _problem()
-    zt, lt, st = RP.f64(z), RP.f64(loc), RP.f64(scale)
+    zt, lt, st = O.f64(z), O.f64(loc), O.f64(scale)
     want = {"normal": torch.distributions.Normal(lt, st), "laplace": torch.distributions.Laplace(lt, st),
             "studentt": torch.distributions.StudentT(torch.tensor(4.0, dtype=torch.float64), lt, st)}
     for kind, dist in want.items():
-        got = RP.ref_log_prob(kind, zt, lt, st, dof=4.0)
+        got = O.ref_log_prob(kind, zt, lt, st, dof=4.0)
         assert got.dtype == torch.float64 and float((got - dist.log_prob(zt)).abs().max()) < 1e-12, kind
 
 
 def test_rice_and_folded_normal_match_scipy():
     from scipy import stats
     z, loc, scale, centric = _problem()
-    got = RP.ref_log_prob("rice_woolfson", z, loc, scale, centric=centric).numpy()
+    got = O.ref_log_prob("rice_woolfson", z, loc, scale, centric=centric).numpy()
     rice = stats.rice.logpdf(z, loc / scale, scale=scale)
     fold = stats.foldnorm.logpdf(z, loc / scale, scale=scale)
     assert centric.any() and not centric.all()
     assert np.max(np.abs(got - np.where(centric, fold, rice))) < 1e-10
     for all_c, want in ((True, fold), (False, rice)):
-        got = RP.ref_log_prob("rice_woolfson", z, loc, scale, centric=np.full(len(loc), all_c)).numpy()
+        got = O.ref_log_prob("rice_woolfson", z, loc, scale, centric=np.full(len(loc), all_c)).numpy()
         assert np.max(np.abs(got - want)) < 1e-10
 
 
@@ -52,13 +53,13 @@ def test_z_derivatives_match_central_differences(kind):
     z, loc, scale, centric = _problem()
     if kind == "laplace":
         assert np.min(np.abs(z - loc)) > 1e-4              # (no sample on the kink: the difference quotient would straddle it)
-    zt = RP.f64(z).requires_grad_(True)
-    lp = RP.ref_log_prob(kind, zt, loc, scale, centric=centric, dof=4.0)
+    zt = O.f64(z).requires_grad_(True)
+    lp = O.ref_log_prob(kind, zt, loc, scale, centric=centric, dof=4.0)
     (g,) = torch.autograd.grad(lp.sum(), zt)
     h = 1e-6
     with torch.no_grad():
-        fd = (RP.ref_log_prob(kind, RP.f64(z) + h, loc, scale, centric=centric, dof=4.0) -
-              RP.ref_log_prob(kind, RP.f64(z) - h, loc, scale, centric=centric, dof=4.0)) / (2 * h)
+        fd = (O.ref_log_prob(kind, O.f64(z) + h, loc, scale, centric=centric, dof=4.0) -
+              O.ref_log_prob(kind, O.f64(z) - h, loc, scale, centric=centric, dof=4.0)) / (2 * h)
     # central differences in fp64: truncation h^2 f''' / 6 ~ 1e-12 |f'''|, rounding eps |f| / h ~ 1e-10 |f|; |f|, |f'''| reach ~1e3 at scale 0.05
     assert float((g - fd).abs().max()) < 1e-6 * max(1.0, float(g.abs().max())), kind
 
@@ -68,8 +69,8 @@ def test_unobserved_reflections_are_exact_zeros_with_zero_gradient():
     observed = np.arange(len(loc)) % 3 != 1
     loc = np.where(observed, loc, np.nan)                   # the parameters of unobserved reflections are never looked at
     for kind in KINDS:
-        zt = RP.f64(z).requires_grad_(True)
-        lp = RP.ref_log_prob(kind, zt, loc, scale, observed=observed, centric=centric, dof=4.0)
+        zt = O.f64(z).requires_grad_(True)
+        lp = O.ref_log_prob(kind, zt, loc, scale, observed=observed, centric=centric, dof=4.0)
         (g,) = torch.autograd.grad(lp.sum(), zt)
         assert torch.isfinite(lp).all() and torch.isfinite(g).all()
         assert (lp[:, ~observed] == 0).all() and (g[:, ~observed] == 0).all() and (lp[:, observed] != 0).all()
@@ -114,11 +115,11 @@ def test_plugin_classes_follow_the_reference_test(kind, mc_samples):
     lp = p.log_prob(z)
     assert lp.shape == z.shape and lp.dtype == np.float32 and np.all(np.isfinite(lp))
     assert np.all(lp[..., ~observed] == 0.0)
-    want = RP.ref_log_prob(*RP.prior_arrays(p, R)[:1], z, *RP.prior_arrays(p, R)[1:]).numpy()
+    want = O.ref_log_prob(*RP.prior_arrays(p, R)[:1], z, *RP.prior_arrays(p, R)[1:]).numpy()
     assert np.allclose(lp[..., observed], want[..., observed], atol=1e-5)
     # ... and against the full-length distribution the reference's test builds (Laplace: the float32 SigFobs / sqrt 2)
     scale = (sig / math.sqrt(2.0)).astype(np.float32) if kind == "laplace" else sig
-    full = RP.ref_log_prob(kind, z, fobs, scale, None, centric, 4.0).numpy()
+    full = O.ref_log_prob(kind, z, fobs, scale, None, centric, 4.0).numpy()
     assert np.allclose(lp[..., observed], full[..., observed], atol=1e-5)
     # without `observed` every index is evaluated
     q = _make(kind, observed, fobs, sig, centric, masked=False)

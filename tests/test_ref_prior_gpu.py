@@ -1,6 +1,6 @@
 """Empirical reference priors on the GPU: `cl_ref_prior` (csrc/elbo_q.hip: ref_prior_kernel) called directly, one launch per case, on
 operands carved from one guarded allocation, and whole training steps of the engine under the four prior classes, both against the fp64
-restatement of tests/ref_prior.py (the unchanged oracle with the Wilson term traded for the reference prior's).
+oracle (`O.ref_log_prob`; whole steps under `ElboConfig.prior = "reference"` with the arrays of tests/ref_prior.py in `ElboInputs.ref`).
 
 Tolerances are the project's own: an fp32 gradient tensor within 2e-4 of its max-norm, a loss term within 1e-4 relative
 (denominator max(|kl|, 1) for the KL), `RTOL_LOSS` / `RTOL_GRAD` of tests/test_gpu_parity.py with its LeakyReLU branch gate.
@@ -98,9 +98,9 @@ def run_direct(kind, R, S, obs_kind, rng_kind, with_part, stop=False):
         return
     what = (kind, R, S, obs_kind, rng_kind, with_part)
     # fp64 reference: [S][R] orientation
-    zt = RP.f64(z.T).requires_grad_(True)
-    lp = RP.ref_log_prob(kind, zt, loc, scale, None if observed is None else observed.astype(bool), centric.astype(bool), dof)
-    lp = lp * RP.f64(active.astype(np.float64))
+    zt = O.f64(z.T).requires_grad_(True)
+    lp = O.ref_log_prob(kind, zt, loc, scale, None if observed is None else observed.astype(bool), centric.astype(bool), dof)
+    lp = lp * O.f64(active.astype(np.float64))
     (dlp,) = torch.autograd.grad(lp.sum(), zt)
     inc_ref = (-np.float64(np.float32(w_kl)) * mult * dlp.numpy()).T
     kl_ref = -np.float64(np.float32(w_kl)) * float(lp.detach().sum())
@@ -174,13 +174,13 @@ def assert_grads(g_hip, grads, prob, prior, name):
     data, cfg, params, u_f, eta = prob
     x = O.inputs_from_numpy(data)
     near = []
-    RP.elbo_value_and_grads(params, x, cfg, u_f, eta, prior, near=near)
+    O.elbo_value_and_grads(params, *RP.under(x, cfg, prior), O.f64(u_f), O.f64(eta), near=near)
     near.sort()
     cand = [(l, r, u) for _, l, r, u in near[:P.MAX_FLIP_CANDIDATES]]
     assert cand, f"{name}: gradient errors {errs} and no LeakyReLU pre-activation within fp32 rounding of zero: not a branch flip"
     for k in range(1, len(cand) + 1):
         for sub in itertools.combinations(cand, k):
-            _, gf = RP.elbo_value_and_grads(params, x, cfg, u_f, eta, prior, flips=sub)
+            _, gf = O.elbo_value_and_grads(params, *RP.under(x, cfg, prior), O.f64(u_f), O.f64(eta), flips=sub)
             if max(util.rel_err(a, b.numpy()) for a, b in zip(g_hip, gf)) < P.RTOL_GRAD:
                 print(f"{name}: gradients match with the LeakyReLU unit(s) {list(sub)} on the engine's branch")
                 return
@@ -235,7 +235,7 @@ def test_whole_step_matches_the_fp64_reference(name):
     kind, masked, kw = STEP_CASES[name]
     fresh, prior, prob, x, inputs = build(kind, masked, kw)
     data, cfg, params, u_f, eta = prob
-    out, grads = RP.elbo_value_and_grads(params, x, cfg, u_f, eta, prior)
+    out, grads = O.elbo_value_and_grads(params, *RP.under(x, cfg, prior), O.f64(u_f), O.f64(eta))
     check_laplace_kink(kind, out, prior)
     model = fresh()
     ipred = model(inputs, u_f=u_f, eta=eta)
@@ -246,7 +246,7 @@ def test_whole_step_matches_the_fp64_reference(name):
     assert util.rel_err(ipred.cpu().numpy(), out["ipred"].numpy()) < 1e-4
     assert_grads([g.cpu().numpy() for g in eng.grad_tensors()], grads, prob, prior, name)
     # the prior matters: the same step under the Wilson prior has another KL (the comparison above is not vacuous)
-    assert abs(float(out["kl"]) - float(O.elbo_value_and_grads(params, x, cfg, RP.f64(u_f), RP.f64(eta))[0]["kl"])) > 1e-2
+    assert abs(float(out["kl"]) - float(O.elbo_value_and_grads(params, x, cfg, O.f64(u_f), O.f64(eta))[0]["kl"])) > 1e-2
 
 
 def test_deterministic_mode_matches_and_repeats_bit_for_bit():
@@ -254,7 +254,7 @@ def test_deterministic_mode_matches_and_repeats_bit_for_bit():
     kind, masked, kw = "rice_woolfson", True, dict(N=900, R=50, d0=5, L=5, w=64, S=3)
     fresh, prior, prob, x, inputs = build(kind, masked, kw, deterministic=True)
     data, cfg, params, u_f, eta = prob
-    out, grads = RP.elbo_value_and_grads(params, x, cfg, u_f, eta, prior)
+    out, grads = O.elbo_value_and_grads(params, *RP.under(x, cfg, prior), O.f64(u_f), O.f64(eta))
     model = fresh()
     model(inputs, u_f=u_f, eta=eta)
     eng = model._engine
@@ -343,7 +343,7 @@ def test_adam_trajectory_matches_the_reference_loop():
     hist = model.train_model(inputs, steps, progress=False, noise=lambda i: noises[i])
     p = params.clone()
     st = O.AdamState.zeros_like(p.tensors())
-    ref = [RP.train_step(p, x, cfg, st, u, e, prior) for u, e in noises]
+    ref = [O.train_step(p, *RP.under(x, cfg, prior), st, O.f64(u), O.f64(e)) for u, e in noises]
     for k in ("loss", "NLL", "F KLDiv", "Grad Norm"):
         a, b = np.array(hist[k]), np.array([r[k] for r in ref])
         assert len(a) == steps and np.max(np.abs(a - b) / np.maximum(np.abs(b), 1.0)) < 2e-4, (k, a, b)
@@ -360,7 +360,7 @@ def test_nan_in_the_reference_data_follows_the_non_finite_step_contract():
     h = 7
     fresh, prior, prob, x, inputs = build("normal", False, kw, nan_at=h)
     data, cfg, params, u_f, eta = prob
-    out, grads = RP.elbo_value_and_grads(params, x, cfg, u_f, eta, prior)
+    out, grads = O.elbo_value_and_grads(params, *RP.under(x, cfg, prior), O.f64(u_f), O.f64(eta))
     grads = [g.numpy() for g in grads]
     for k, g in enumerate(grads):                        # the reference's mask is sharp
         bad = ~np.isfinite(g)
@@ -380,7 +380,7 @@ def test_nan_in_the_reference_data_follows_the_non_finite_step_contract():
     assert abs(terms["nll"] - float(out["nll"])) <= P.RTOL_LOSS * abs(float(out["nll"]))
     # four steps asked for, one applied
     p = params.clone()
-    rec = RP.train_step(p, x, cfg, O.AdamState.zeros_like(p.tensors()), u_f, eta, prior)
+    rec = O.train_step(p, *RP.under(x, cfg, prior), O.AdamState.zeros_like(p.tensors()), O.f64(u_f), O.f64(eta))
     model = fresh()
     hist = model.train_model(inputs, 4, progress=False, noise=lambda i: (u_f, eta))
     assert len(hist["loss"]) == 1 and not np.isfinite(hist["Grad Norm"][0]) and not np.isfinite(rec["Grad Norm"])

@@ -31,7 +31,6 @@ import pytest
 import torch
 
 from oracle import elbo_oracle as O
-from tests import ref_laplace
 from tests import ref_rows as RR
 from tests import ref_step
 
@@ -75,7 +74,7 @@ def _oracle_problem(laue, kind, ev11, seed):
     else:
         x.slot = None
     x.count = np.ones(n, bool)
-    cfg = O.ElboConfig(mc_samples=S, likelihood="normal" if kind == "laplace" else kind, dof=x.dof, scale_bijector="exp", epsilon=eps, scale_shift=shift,
+    cfg = O.ElboConfig(mc_samples=S, likelihood=kind, dof=x.dof, scale_bijector="exp", epsilon=eps, scale_shift=shift,
                        use_image_scales=True, laue=laue, ev11=ev11)
     p = O.ElboParams(T(rng.normal(0.0, 0.3, R)), T(np.log(rng.uniform(0.05, 0.3, R))), [torch.eye(2, dtype=torch.float64)], [torch.zeros(2, dtype=torch.float64)],
                      img_raw=T(x.img), ev11_raw=T(x.ev11) if ev11 else None)
@@ -91,12 +90,12 @@ def _oracle_problem(laue, kind, ev11, seed):
 def test_reference_equals_the_oracle_with_the_scaler_replaced(laue, kind, ev11):
     """ipred, NLL and every gradient the kernels write against O.elbo_value_and_grads (the image scales and the Evans-2011 triple: the KL does
     not depend on them) and against autograd through O.elbo_forward's own graph (dz_f, d / d(loc, sigma)), at 1e-12 of the summand size; the
-    Laplace kind through tests/ref_laplace.py; the summand sizes dominate every entry."""
+    summand sizes dominate every entry."""
     for seed in (0, 1):
         x, cfg, p, inp, u_f, raw, eps = _oracle_problem(laue, kind, ev11, seed)
         eta = T(x.eta_row.T)
         lap = kind == "laplace"
-        out, grads = (ref_laplace if lap else O).elbo_value_and_grads(p, inp, cfg, u_f, eta)
+        out, grads = O.elbo_value_and_grads(p, inp, cfg, u_f, eta)
         x.z_f = out["z_f"].numpy().T.copy()
         ref = RR.reference(x)
         assert np.all(np.abs(ref.ipred - out["ipred"].numpy().T) <= 1e-12 * ref.M_ipred)

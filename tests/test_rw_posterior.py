@@ -1,4 +1,4 @@
-"""The Rice-Woolfson surrogate posterior without a GPU: the fp64 reference of tests/ref_rw.py against scipy and finite differences, the
+"""The Rice-Woolfson surrogate posterior without a GPU: the oracle's fp64 restatement of it against scipy and finite differences, the
 host build of the element math of csrc/cl_math.h against that reference, the trainable plugin class' host side, the C-ABI (symbols, struct
 sizes, one rejecting call per clause of every entry check) and the engine's acceptance rule."""
 import ctypes as C
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from careless_amd import _lib
+from oracle import elbo_oracle as O
 from tests import ref_rw as RR
 from tests.test_ref_prior import PARENT_ABI_SIZES, pinned_abi_sizes
 
@@ -33,49 +34,49 @@ def test_reference_log_prob_is_scipy_rice_and_foldnorm():
     from scipy import stats
     loc, scale, c, rng = _params(400, 1, -1.0, 1.0)          # (scipy's own rice.logpdf is the cancelling form: moderate loc / scale)
     n = rng.normal(size=(2, 3, 400))
-    z = RR.rw_sample(RR.f64(loc), RR.f64(scale), torch.as_tensor(c), RR.f64(n))
-    lq = RR.rw_log_prob(z, RR.f64(loc), RR.f64(scale), torch.as_tensor(c)).numpy()
+    z = O.rw_sample(O.f64(loc), O.f64(scale), torch.as_tensor(c), O.f64(n))
+    lq = O.rw_log_prob(z, O.f64(loc), O.f64(scale), torch.as_tensor(c)).numpy()
     z = z.numpy()
     ref = np.where(c, stats.foldnorm.logpdf(z, loc / scale, scale=scale), stats.rice.logpdf(z, loc / scale, scale=scale))
     assert np.max(np.abs(lq - ref) / np.maximum(np.abs(ref), 1.0)) < 1e-12
     # the draws: centric |loc + scale n1| + eps32, acentric |loc + scale (n2 + i n1)|
-    assert np.array_equal(z[:, c], np.abs(loc + scale * n[0])[:, c] + RR.EPS32)
+    assert np.array_equal(z[:, c], np.abs(loc + scale * n[0])[:, c] + O.EPS_F32)
     assert np.max(np.abs(z[:, ~c] - np.abs((loc + scale * n[1]) + 1j * scale * n[0])[:, ~c]) / z[:, ~c]) < 1e-14
 
 
 def test_reference_pathwise_gradient_matches_central_differences():
     loc, scale, c, rng = _params(300, 2)
-    n = RR.f64(RR.noise_for(loc, scale, c, 2, 5))
+    n = O.f64(RR.noise_for(loc, scale, c, 2, 5))
     ct = torch.as_tensor(c)
-    L, S = RR.f64(loc).requires_grad_(True), RR.f64(scale).requires_grad_(True)
-    z = RR.rw_sample(L, S, ct, n)
+    L, S = O.f64(loc).requires_grad_(True), O.f64(scale).requires_grad_(True)
+    z = O.rw_sample(L, S, ct, n)
     gl, gs = torch.autograd.grad(z.sum(), [L, S])
     h = 1e-6
     with torch.no_grad():
-        fl = (RR.rw_sample(RR.f64(loc * (1 + h)), S, ct, n) - RR.rw_sample(RR.f64(loc * (1 - h)), S, ct, n)).sum(0) / RR.f64(2 * h * loc)
-        fs = (RR.rw_sample(L, RR.f64(scale * (1 + h)), ct, n) - RR.rw_sample(L, RR.f64(scale * (1 - h)), ct, n)).sum(0) / RR.f64(2 * h * scale)
+        fl = (O.rw_sample(O.f64(loc * (1 + h)), S, ct, n) - O.rw_sample(O.f64(loc * (1 - h)), S, ct, n)).sum(0) / O.f64(2 * h * loc)
+        fs = (O.rw_sample(L, O.f64(scale * (1 + h)), ct, n) - O.rw_sample(L, O.f64(scale * (1 - h)), ct, n)).sum(0) / O.f64(2 * h * scale)
     for g, f in ((gl, fl), (gs, fs)):
         assert float((g - f).abs().max() / f.abs().max()) < 1e-7
 
 
 def test_patched_oracle_is_restored_and_runs_whole_steps():
-    from oracle import elbo_oracle as O
+    """(The name is from when this posterior was patched into the oracle for the length of a call.)  The oracle under
+    `posterior="rice_woolfson"` runs whole steps and the output step's moments, and leaves its own functions and scipy's class as they are."""
     from tests import util
     saved = (O.tn_sample, O.tn_log_prob, O.tn_mean, O.tn_variance)
     data, cfg, params, x, u_f, eta = util.make_problem(N=120, R=20, S=2)
     loc, scale = (t.numpy() for t in O.tn_loc_scale(params.q_loc_raw, params.q_scale_raw, cfg.epsilon))
     n_f = RR.noise_for(loc, scale, data["centric"], 2, 3)
-    out, grads = RR.elbo_value_and_grads(params, x, cfg, n_f, eta, data["centric"])
+    out, grads = O.elbo_value_and_grads(params, x, RR.under(cfg), O.f64(n_f), O.f64(eta))
     assert (O.tn_sample, O.tn_log_prob, O.tn_mean, O.tn_variance) == saved
-    z = RR.rw_sample(RR.f64(loc), RR.f64(scale), torch.as_tensor(np.asarray(data["centric"], bool)), RR.f64(n_f))
+    z = O.rw_sample(O.f64(loc), O.f64(scale), torch.as_tensor(np.asarray(data["centric"], bool)), O.f64(n_f))
     assert torch.equal(out["z_f"], z) and np.isfinite(float(out["loss"])) and all(torch.isfinite(g).all() for g in grads)
-    tn_out, _ = O.elbo_value_and_grads(params, x, cfg, RR.f64(u_f), RR.f64(eta))
+    tn_out, _ = O.elbo_value_and_grads(params, x, cfg, O.f64(u_f), O.f64(eta))
     assert abs(float(tn_out["kl"]) - float(out["kl"])) > 1e-3          # another posterior: another KL
     import scipy.stats
-    with RR.patched(data["centric"], moments=True):
-        res = O.merged_results(params, x, cfg)
+    res = O.merged_results(params, x, RR.under(cfg))
     assert "moment" not in vars(scipy.stats.truncnorm)
-    mean, var, m4 = RR.rw_moments(loc, scale, data["centric"])
+    mean, var, m4 = O.rw_moments(loc, scale, data["centric"])
     assert np.allclose(res["F"].numpy(), mean, rtol=1e-14) and np.allclose(res["SigF"].numpy() ** 2, var, rtol=1e-10)
 
 
@@ -107,14 +108,14 @@ def test_host_element_math_matches_fp64(rwm):
     cu, out = c.astype(np.uint8), np.zeros((n, 8), np.float32)
     p = lambda x: x.ctypes.data_as(C.c_void_p)
     rwm.rw_eval(n, p(a), p(b), eps, p(cu), p(n1), p(n2), p(out))
-    L = torch.exp(RR.f64(a)).requires_grad_(True)
-    S = (torch.exp(RR.f64(b)) + float(np.float32(eps))).requires_grad_(True)
-    ct, N = torch.as_tensor(c), RR.f64(np.stack([n1, n2]))
+    L = torch.exp(O.f64(a)).requires_grad_(True)
+    S = (torch.exp(O.f64(b)) + float(np.float32(eps))).requires_grad_(True)
+    ct, N = torch.as_tensor(c), O.f64(np.stack([n1, n2]))
     assert RR.kink_margin(L.detach().numpy(), S.detach().numpy(), c, N.numpy()) >= RR.KINK_GUARD
-    z = RR.rw_sample(L, S, ct, N)
+    z = O.rw_sample(L, S, ct, N)
     dzl, dzs = torch.autograd.grad(z.sum(), [L, S])
     zd = z.detach().clone().requires_grad_(True)
-    lq = RR.rw_log_prob(zd, L, S, ct)
+    lq = O.rw_log_prob(zd, L, S, ct)
     gz, gl, gs = torch.autograd.grad(lq.sum(), [zd, L, S])
     Ln, Sn = L.detach().numpy(), S.detach().numpy()
     assert (c & (Ln + Sn * n1 < 0)).sum() > 100 and ((Ln / Sn) > 40).sum() > 1000

@@ -1,6 +1,5 @@
 """The Rice-Woolfson surrogate posterior on the GPU: `cl_rw_forward` / `cl_rw_backward` / `cl_rw_moments` called directly on injected
-normals, whole training steps of the engine against the fp64 reference of tests/ref_rw.py (the unchanged oracle with its two posterior
-functions swapped), deterministic mode, shards, the non-finite step contract, the production noise, the output step and an
+normals, whole training steps of the engine against the fp64 oracle under `ElboConfig.posterior = "rice_woolfson"`, deterministic mode, shards, the non-finite step contract, the production noise, the output step and an
 oracle-independent recovery run.
 
 Whole-step cases are rows of tests/test_nonfinite.py's MATRIX with `model.surrogate_posterior` replaced and that file's routing assertions
@@ -92,15 +91,15 @@ def run_direct(R, S, family, with_part, inner_kl, owned, prior="wilson", stop=Fa
         return
     what = (R, S, family, with_part, inner_kl, owned, prior)
     # fp64 reference, [S][R] orientation
-    ta, tb = RR.f64(a).requires_grad_(True), RR.f64(b).requires_grad_(True)
+    ta, tb = O.f64(a).requires_grad_(True), O.f64(b).requires_grad_(True)
     loc, scale = torch.exp(ta), torch.exp(tb) + float(np.float32(EPS))
     ct = torch.as_tensor(centric)
-    z = RR.rw_sample(loc, scale, ct, RR.f64(n_f))
-    lq = RR.rw_log_prob(z, loc, scale, ct)
-    lp = torch.zeros_like(lq) if ref_kind else O.wilson_log_prob(z, ct, RR.f64(np.ones(R)), RR.f64(es))
+    z = O.rw_sample(loc, scale, ct, O.f64(n_f))
+    lq = O.rw_log_prob(z, loc, scale, ct)
+    lp = torch.zeros_like(lq) if ref_kind else O.wilson_log_prob(z, ct, O.f64(np.ones(R)), O.f64(es))
     wk = np.float64(np.float32(w_kl))
-    kl_e = ((lq - lp) * RR.f64(in_kl.astype(np.float64))).sum()
-    loss = (RR.f64(dz.T) * z * RR.f64(own.astype(np.float64))).sum() + wk * mult * kl_e
+    kl_e = ((lq - lp) * O.f64(in_kl.astype(np.float64))).sum()
+    loss = (O.f64(dz.T) * z * O.f64(own.astype(np.float64))).sum() + wk * mult * kl_e
     ga, gb = torch.autograd.grad(loss, [ta, tb])
     zf = g.get("z_f")
     zr = z.detach().numpy().T
@@ -148,7 +147,7 @@ def test_cl_rw_moments_matches_the_host_class_and_the_closed_forms():
     a, b, centric, loc64, scale64, *_ = direct_inputs(R, 1, "alternating", 3)
     q = RiceWoolfson.from_loc_and_scale(np.ones(R), np.ones(R), centric, scale_shift=EPS)
     q.loc_raw, q.scale_raw = torch.as_tensor(a), torch.as_tensor(b)
-    mean, var, m4 = RR.rw_moments(loc64, scale64, centric)
+    mean, var, m4 = O.rw_moments(loc64, scale64, centric)
     host = RiceWoolfson(loc64, scale64, centric)                       # the fp32 host class itself, pinned to scipy by tests/test_ref_prior.py
     assert np.allclose(host.mean(), mean, rtol=1e-5)
     for got, ref, k in ((q.mean(), mean, "mean"), (q.stddev(), np.sqrt(var), "std"), (q.variance(), var, "var"), (q.moment_4(), m4, "m4")):
@@ -245,7 +244,7 @@ def test_whole_step_matches_the_fp64_reference(name):
     case, kw, opts, data, cfg, params, n_f, eta, centric = problem(name)
     x = O.inputs_from_numpy(data)
     assert RR.kink_margin(*q_loc_scale(params, cfg), centric, n_f) >= RR.KINK_GUARD
-    reference = lambda **k: RR.elbo_value_and_grads(params, x, cfg, n_f, eta, centric, **k)
+    reference = lambda **k: O.elbo_value_and_grads(params, x, RR.under(cfg), O.f64(n_f), O.f64(eta), **k)
     out, grads = reference()
     model = rw_model(case, kw, opts, data, cfg, params, centric)
     inputs = util.reference_inputs(data)
@@ -264,7 +263,7 @@ def test_whole_step_matches_the_fp64_reference(name):
     assert_grads(g_hip, reference, name)
     # the posterior matters: the same problem under the truncated normal has another KL
     u = np.random.default_rng(1).random((cfg.mc_samples, len(centric)))
-    assert abs(float(out["kl"]) - float(O.elbo_value_and_grads(params, x, cfg, RR.f64(u), RR.f64(eta))[0]["kl"])) > 1e-3
+    assert abs(float(out["kl"]) - float(O.elbo_value_and_grads(params, x, cfg, O.f64(u), O.f64(eta))[0]["kl"])) > 1e-3
 
 
 def test_whole_step_under_a_reference_prior():
@@ -275,9 +274,7 @@ def test_whole_step_under_a_reference_prior():
     prior = make_prior("rice_woolfson", data, params, True)
     n_f = RR.noise_for(*q_loc_scale(params, cfg), centric, kw["S"], 7)
 
-    def reference(**k):
-        with RR.patched(centric):
-            return RP.elbo_value_and_grads(params, x, cfg, RR.f64(n_f), eta, prior, **k)
+    reference = lambda **k: O.elbo_value_and_grads(params, *RP.under(x, RR.under(cfg), prior), O.f64(n_f), O.f64(eta), **k)
     out, grads = reference()
     model = util.build_model(data, cfg, params, kw["L"], kw["w"])
     model.prior, model.surrogate_posterior = prior, rw_posterior(params, cfg, centric)
@@ -315,7 +312,7 @@ def test_adam_trajectory_matches_the_reference_loop():
     for i in range(steps):                           # the noise of step i keeps the kink guard at the reference's parameters of step i
         n_f = RR.noise_for(*q_loc_scale(p, cfg), centric, kw["S"], 100 + 10 * i)
         noises.append((n_f, rng.normal(size=(kw["S"], kw["N"])).astype(np.float32)))
-        ref.append(RR.train_step(p, x, cfg, st, *noises[-1], centric))
+        ref.append(O.train_step(p, x, RR.under(cfg), st, *map(O.f64, noises[-1])))
     model = fresh()
     hist = model.train_model(util.reference_inputs(data), steps, progress=False, noise=lambda i: noises[i])
     for k in ("loss", "NLL", "F KLDiv", "Grad Norm"):
@@ -341,9 +338,9 @@ def test_validation_nll_matches_the_reference():
     rng = np.random.default_rng(12)
     noise = (RR.noise_for(*q_loc_scale(params, cfg), centric, 2, 3), rng.normal(size=(2, n_tr)).astype(np.float32))
     p = params.clone()
-    rec = RR.train_step(p, x_tr, cfg, O.AdamState.zeros_like(p.tensors()), *noise, centric)
+    rec = O.train_step(p, x_tr, RR.under(cfg), O.AdamState.zeros_like(p.tensors()), *map(O.f64, noise))
     vnoise = (RR.noise_for(*q_loc_scale(p, cfg), centric, 2, 40), rng.normal(size=(2, kw["N"] - n_tr)).astype(np.float32))
-    ref = RR.validation_nll(p, x_te, cfg, vnoise[0], vnoise[1], n_tr, centric)
+    ref = O.validation_nll(p, x_te, RR.under(cfg), O.f64(vnoise[0]), O.f64(vnoise[1]), n_tr)
     model = fresh()
     hist = model.train_model(train, 1, progress=False, validation_data=test, validation_frequency=1, noise=lambda i: noise, validation_noise=lambda i: vnoise)
     print("NLL_val", hist["NLL_val"], "reference", ref)
@@ -412,7 +409,7 @@ NONFINITE_ROWS = ["lane_20x10_d5_S1", "mlp64_5x64_posenc_studentt_S8"]
 def _poisoned(name):
     case, kw, opts, data, cfg, params, n_f, eta, centric = problem(name, "iobs_nan")
     near = []
-    out, grads = RR.elbo_value_and_grads(params, O.inputs_from_numpy(data), cfg, n_f, eta, centric, near=near)
+    out, grads = O.elbo_value_and_grads(params, O.inputs_from_numpy(data), RR.under(cfg), O.f64(n_f), O.f64(eta), near=near)
     assert not [t for t in near if np.isfinite(t[0])]          # no LeakyReLU branch in doubt (tests/test_nonfinite.py: `_oracle_grads`)
     return case, kw, opts, data, cfg, params, n_f, eta, centric, out, [g.numpy() for g in grads]
 
@@ -445,7 +442,7 @@ def test_training_stops_after_the_sanitised_step(name):
     inputs = util.reference_inputs(data)
     NF._assert_route(model.engine(inputs), case)
     p = params.clone()
-    rec = RR.train_step(p, O.inputs_from_numpy(data), cfg, O.AdamState.zeros_like(p.tensors()), n_f, eta, centric)
+    rec = O.train_step(p, O.inputs_from_numpy(data), RR.under(cfg), O.AdamState.zeros_like(p.tensors()), O.f64(n_f), O.f64(eta))
     after = [t.numpy() for t in p.tensors()]
     hist = model.train_model(inputs, 4, progress=False, noise=lambda i: (n_f, eta))
     assert len(hist["loss"]) == 1 and not np.isfinite(hist["Grad Norm"][0]) and not np.isfinite(rec["Grad Norm"])
@@ -514,10 +511,9 @@ def test_predictions_and_results_match_the_reference(kw):
     inputs = util.reference_inputs(data)
     pred = results.get_predictions(model, inputs)
     res = results.get_results(model.surrogate_posterior, inputs)
-    with RR.patched(centric, moments=True):
-        ie, isd = O.prediction_mean_stddev(params, x, cfg)
-        sm, ssd = O.scale_mean_stddev(params, x, cfg)
-        ref = O.merged_results(params, x, cfg)
+    ie, isd = O.prediction_mean_stddev(params, x, RR.under(cfg))
+    sm, ssd = O.scale_mean_stddev(params, x, RR.under(cfg))
+    ref = O.merged_results(params, x, RR.under(cfg))
     for k, r in (("Ipred", ie), ("SigIpred", isd), ("Scale", sm), ("SigScale", ssd)):
         assert len(pred[k]) == kw["N"] and _close(pred[k], r.numpy()), k
     for k in ("F", "SigF", "I", "SigI"):
