@@ -20,6 +20,10 @@ CL_BIJ_EXP, CL_BIJ_SOFTPLUS = 0, 1
 CL_PRIOR_WILSON, CL_PRIOR_DOUBLE_WILSON, CL_PRIOR_REFERENCE = 0, 1, 2
 # cl_ref_prior: the base density of an empirical reference prior (include/careless_hip.h, cl_refprior_args.kind)
 CL_REFPRIOR_NORMAL, CL_REFPRIOR_LAPLACE, CL_REFPRIOR_STUDENTT, CL_REFPRIOR_RICE_WOOLFSON = range(4)
+# cl_scale_kl: the scale prior's family and the form of the term (include/careless_hip.h, cl_sprior_args.kind / .form)
+CL_SPRIOR_NORMAL, CL_SPRIOR_LAPLACE, CL_SPRIOR_STUDENTT = range(3)
+CL_SPRIOR_ANALYTIC, CL_SPRIOR_SAMPLE = range(2)
+CL_HIST_SCALE_KL = 5            # the history record's sixth double: "Σ KLDiv" (cl_scale_kl_record)
 CL_LAUE_LIK_MAX_BLOCKS = 2048
 CL_EV11_WAVES = 8               # wave slots per workgroup in ev11_part (include/careless_hip.h)
 # cl_mlp_route: the launcher a scaler launch goes to (include/careless_hip.h, enum cl_route)
@@ -166,6 +170,27 @@ class NlikArgs(C.Structure):
     ]
 
 
+class SpriorArgs(C.Structure):
+    """mirror of `cl_sprior_args` (include/careless_hip.h)"""
+    _fields_ = [
+        ("loc", _vp), ("sigma", _vp), ("image_id", _vp), ("img", _vp),
+        ("use_img", C.c_int),
+        ("shift", C.c_float), ("has_shift", C.c_int),
+        ("kind", C.c_int), ("p_loc", C.c_float), ("p_scale", C.c_float), ("p_df", C.c_float),
+        ("form", C.c_int),
+        ("n", C.c_int),
+        ("obs_offset", C.c_longlong),
+        ("row_index", _vp),
+        ("S", C.c_int),
+        ("eta", _vp),
+        ("seed", C.c_ulonglong), ("step", C.c_uint),
+        ("weight", C.c_float),
+        ("dO", _vp), ("d_img", _vp), ("dimg_obs", _vp), ("kl_part", _vp), ("value", _vp),
+        ("accumulate", C.c_int),
+        ("stop_flag", _vp),
+    ]
+
+
 class AdamArgs(C.Structure):
     """mirror of `cl_adam_args` (include/careless_hip.h)"""
     _fields_ = [
@@ -185,7 +210,8 @@ class AdamArgs(C.Structure):
 # every argument struct of include/careless_hip.h and its mirror: get_lib() compares the sizes with the library's (cl_abi_sizeof),
 # tests/test_abi_layout.py every field's offset and size with the header's
 ABI_STRUCTS = {"cl_tn_args": TnArgs, "cl_mlp_args": MlpArgs, "cl_adam_args": AdamArgs, "cl_laue_args": LaueArgs, "cl_det_args": DetArgs,
-               "cl_frozen_args": FrozenArgs, "cl_refprior_args": RefPriorArgs, "cl_rw_args": RwArgs, "cl_nlik_args": NlikArgs}
+               "cl_frozen_args": FrozenArgs, "cl_refprior_args": RefPriorArgs, "cl_rw_args": RwArgs, "cl_nlik_args": NlikArgs,
+               "cl_sprior_args": SpriorArgs}
 
 EXPORTS = {
     # name: (restype, argtypes)
@@ -250,6 +276,9 @@ EXPORTS = {
     "cl_nlik_param_count": (C.c_size_t, [C.c_int, C.c_int]),
     "cl_nlik_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
     "cl_nlik_grid": (C.c_int, [C.c_longlong]),
+    "cl_scale_kl": (C.c_int, [C.POINTER(SpriorArgs), _vp]),
+    "cl_scale_kl_grid": (C.c_int, [C.c_longlong]),
+    "cl_scale_kl_record": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "cl_reduce_partials": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "cl_grad_sqnorm": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cl_adam_step": (C.c_int, [C.POINTER(AdamArgs), _vp]),

@@ -48,6 +48,7 @@ UNITS = [("cl_api.hip", "cl_api", []), ("mlp_launch.hip", "mlp_launch", []),
          ("elbo_laue.hip", "elbo_laue", []), ("wide_gemm.hip", "wide_gemm", []),
          ("elbo_peel.hip", "elbo_peel", []), ("elbo_frozen.hip", "elbo_frozen", []),
          ("elbo_nlik.hip", "elbo_nlik", []),        # the neural likelihood's network: NaNs honoured, so that a poisoned row reaches every sigpred
+         ("elbo_sprior.hip", "elbo_sprior", []),    # the scale prior's KL term: NaNs honoured, a NaN in loc / sigma reaches value and gradient
 
          # host threads, no device code: the formatter's symmetry bookkeeping (exact products kept apart from their sums)
          ("host_format.cpp", "host_format", ["-ffp-contract=off", "-pthread"])]

@@ -15,6 +15,7 @@ size_t cl_abi_sizeof(const char* struct_name) {
     static const struct { const char* name; size_t size; } table[] = {
         CL_ABI(cl_tn_args),     CL_ABI(cl_mlp_args),      CL_ABI(cl_adam_args), CL_ABI(cl_laue_args), CL_ABI(cl_det_args),
         CL_ABI(cl_frozen_args), CL_ABI(cl_refprior_args), CL_ABI(cl_rw_args),   CL_ABI(cl_nlik_args),
+        CL_ABI(cl_sprior_args),
     };
 #undef CL_ABI
     if (struct_name == nullptr) return 0;

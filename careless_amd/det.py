@@ -6,7 +6,7 @@ What the module owns: the per-observation-set buffers (`DetBuffers`), where each
 the closing reduction (`_det_reduce`).  Whether the mode is on and what it refuses is decided before (`plan.check_deterministic`,
 `ElboEngine._read_plugins`); the launches fill their `dzf_obs / dimg_obs / det_slot / nll_part / ev11_part` fields themselves (`_mlp_args`,
 `_slot_likelihood`, `_laue_pad_slots`) from what is attached here.
-Reads of the engine: `device, lib, R, S, laue, wide, ev11, layout, dz_f, scalars, stop_flag`, `_max_images`, `_grad_ptr`.
+Reads of the engine: `device, lib, R, S, laue, wide, ev11, sprior, layout, dz_f, scalars, stop_flag`, `_max_images`, `_grad_ptr`.
 Attaches: `obs.det` on the set (`ObsData` or `ObsChunks`), `det_parent` / `det_index` on each of its pieces.
 """
 from __future__ import annotations
@@ -71,14 +71,18 @@ class DetPath:
         if 4 * n * self.S < (1 << 32):          # (the kernels address a record with a 32-bit byte offset from the buffer's start)
             slot = torch.empty(n, dtype=torch.int32, device=dev)
             slot[perm_r.long()] = torch.arange(n, dtype=torch.int32, device=dev)
+        # (the slot likelihood's launches: one on the whole set -- Laue, wide --, or one per piece: monochromatic rows under a scale prior)
+        sprior = getattr(self, "sprior", None) is not None
+        slot_launches = len(pieces) if sprior else (1 if (self.laue or self.wide) else 0)
         obs.det = DetBuffers(slot=slot, dzf=torch.zeros(n * self.S, dtype=torch.float32, device=dev), dimg=torch.zeros(n, dtype=torch.float32, device=dev),
-                             nll=torch.zeros(len(pieces) * pieces[0].grid + (_lib.CL_LAUE_LIK_MAX_BLOCKS if (self.laue or self.wide) else 0),
+                             nll=torch.zeros(len(pieces) * pieces[0].grid + _lib.CL_LAUE_LIK_MAX_BLOCKS * slot_launches,
                                              dtype=torch.float64, device=dev),
                              refl=(perm_r, seg_r), img=order(img, M), M=M, pieces=len(pieces), grid=pieces[0].grid)
         if self.ev11:
             # Evans-2011 gradients: one slot of three floats per wave of every launch (the fused launches' CL_EV11_WAVES per workgroup, then
             # four per workgroup of the slot / padded-slot likelihood launch), summed in slot order by cl_det_reduce
-            obs.det.ev11 = torch.zeros(3 * (_lib.CL_EV11_WAVES * len(pieces) * pieces[0].grid + 4 * _lib.CL_LAUE_LIK_MAX_BLOCKS), dtype=torch.float32, device=dev)
+            obs.det.ev11 = torch.zeros(3 * (_lib.CL_EV11_WAVES * len(pieces) * pieces[0].grid + 4 * _lib.CL_LAUE_LIK_MAX_BLOCKS * max(1, slot_launches)),
+                                       dtype=torch.float32, device=dev)
         for k, p in enumerate(pieces):
             p.det_parent, p.det_index = obs, k
 
@@ -89,6 +93,13 @@ class DetPath:
         det = obs.det_parent.det
         return (det.nll.data_ptr() + 8 * det.grid * k,
                 det.ev11.data_ptr() + 4 * 3 * _lib.CL_EV11_WAVES * det.grid * k if self.ev11 else None)
+
+    def _det_slot_parts(self, obs: ObsData):
+        """(nll_part, ev11_part) of the slot likelihood's launch on `obs`: behind the fused launches' parts (`_det_parts(obs, det.pieces)`), and -- a
+        piece of a chunked shard, which has a slot launch of its own under a scale prior -- behind the slot parts of the pieces in front of it."""
+        nll, ev11 = self._det_parts(obs, obs.det_parent.det.pieces)
+        k = obs.det_index if obs.is_piece else 0
+        return nll + 8 * _lib.CL_LAUE_LIK_MAX_BLOCKS * k, None if ev11 is None else ev11 + 4 * 3 * 4 * _lib.CL_LAUE_LIK_MAX_BLOCKS * k
 
     def _det_reduce(self, obs, st):
         det, lay = obs.det, self.layout

@@ -25,16 +25,23 @@ def allreduce_flat_(grads: torch.Tensor, group=None) -> None:
     dist.all_reduce(grads, op=dist.ReduceOp.SUM, group=group)
 
 
-def allreduce_history_(history: torch.Tensor, stride: int, kl_mult: float, group=None) -> None:
+def allreduce_history_(history: torch.Tensor, stride: int, kl_mult: float, group=None, scale_kl: bool = False) -> None:
     """`history` = fp64 [steps][stride] records (loss, KL, NLL, grad norm, skipped) holding this rank's partial NLL / KL:
     sum those two columns over the ranks and rebuild the loss column.  The gradient norm and the skipped flag are already
-    identical on every rank (both derive from the all-reduced gradient)."""
+    identical on every rank (both derive from the all-reduced gradient).  `scale_kl`: the records also hold this rank's share of a scale
+    prior's "Σ KLDiv" in their sixth double, carried the same way and added to the loss with weight 1."""
     import torch.distributed as dist
     h = history.view(-1, stride)
     part = h[:, 1:3].contiguous()
     dist.all_reduce(part, op=dist.ReduceOp.SUM, group=group)
     h[:, 1:3] = part
-    h[:, 0] = torch.where(h[:, 4] == 0.0, part[:, 1] + float(kl_mult) * part[:, 0], h[:, 0])
+    loss = part[:, 1] + float(kl_mult) * part[:, 0]
+    if scale_kl:
+        skl = h[:, 5].contiguous()
+        dist.all_reduce(skl, op=dist.ReduceOp.SUM, group=group)
+        h[:, 5] = skl
+        loss = loss + skl
+    h[:, 0] = torch.where(h[:, 4] == 0.0, loss, h[:, 0])
 
 
 def gather_owned_(q_params: torch.Tensor, R: int, r0: int, r1: int, group=None) -> None:

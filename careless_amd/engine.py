@@ -6,10 +6,11 @@ What one step replaces in the reference: `train_step_with_gradient_norm` (carele
 
 Step schedule (all on one HIP stream, no host synchronisation):
     cl_tn_forward (clears the step's accumulators on its way) -> [cl_nlik_forward: neural likelihood] -> cl_elbo_mono_fwd_bwd
+    (a scale prior: cl_mlp_forward -> cl_slot_rows -> cl_scale_kl -> cl_mlp_backward_ext in its place, careless_amd/sprior.py)
     -> [cl_nlik_backward: neural likelihood] -> [cl_ref_prior: empirical reference priors]
     -> cl_tn_backward (carries cl_reduce_partials)        (a Rice-Woolfson posterior: cl_rw_forward / cl_rw_backward in their place)
     -> [cl_owner_qnorm + all-reduce, data-parallel only: the flat gradient (row split) or its tail + 4 norm terms (reflection-owner
-    split)] -> [cl_grad_sqnorm: clip modes only] -> cl_adam_step -> cl_step_finalize
+    split)] -> [cl_grad_sqnorm: clip modes only] -> cl_adam_step -> cl_step_finalize -> [cl_scale_kl_record: a scale prior]
 
 HBM layout owned by the engine (see include/careless_hip.h):
     params / m / v / grads : one flat fp32 vector  [ q_loc_raw (R) | q_scale_raw (R) | scaler W^T layout (P) | image scales (M-1) | ... ]
@@ -27,6 +28,7 @@ What lives where (one role per module; every class below is a mixin of `ElboEngi
     slots.py    `SlotPath`: the slot likelihood those three routes share
     det.py      `DetPath`: deterministic mode's buffers and fixed-order sums
     nlik.py     `NlikPath`: the neural likelihood's buffers and launches
+    sprior.py   `SpriorPath`: the scale prior's KL term between the two-pass launches, its value and its history column
 This file keeps the engine itself -- the constructor's named steps, the posterior launches, the step schedule (`forward_backward`,
 `_data_term`, the route question `_route`), the optimizer, the history, the validation NLL -- and the stand-alone helpers behind the
 plugin protocol methods.
@@ -50,13 +52,14 @@ from careless_amd.obs import (GRANULE, ObsChunks, ObsData, Shard, _EmptyObs, _Sh
                               pack_by_image, pack_laue)
 from careless_amd.flat import FLAT_GROUPS, FlatLayout, Workspace, bind_flat, carve_workspace, make_layout, split_flat  # noqa: F401
 from careless_amd.plan import (BIJ_KINDS, REFPRIOR_KINDS, LayerBlock, Route, ScalerPlan, chain_plan, check_deterministic,  # noqa: F401
-                               check_neural_likelihood, data_term_route, plan_scaler, posterior_kind, prior_kind, reference_prior_arrays,
-                               switch, wants_owner_shard)
+                               check_neural_likelihood, check_scale_prior, check_scale_prior_route, data_term_route, plan_scaler,
+                               posterior_kind, prior_kind, reference_prior_arrays, switch, wants_owner_shard)
 from careless_amd.det import DetBuffers, DetPath  # noqa: F401
 from careless_amd.frozen import FrozenPath
 from careless_amd.fused import FusedPath, PeelBuffers, _copy_args, block_fields, scaler_fields  # noqa: F401
 from careless_amd.nlik import NlikBuffers, NlikPath  # noqa: F401
 from careless_amd.slots import SlotPath
+from careless_amd.sprior import SCALE_KL_KEY, SpriorBuffers, SpriorPath  # noqa: F401
 from careless_amd.wide import WidePath, WideShape, hidden_forward, row_chunks
 
 TILE = _lib.CL_MLP_TILE
@@ -79,7 +82,7 @@ def _stream() -> int:
 # ------------------------------------------------------------------------------------------------------------
 # the engine
 # ------------------------------------------------------------------------------------------------------------
-class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
+class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath, SpriorPath):
     local_only = False               # test hook: a rank shard on one device, the per-rank partial gradient stays in place (no collective call)
     force_allreduce = False          # CARELESS_FORCE_DIST=1: a one-rank run makes every collective call of the multi-GPU step
 
@@ -105,6 +108,8 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
             check_deterministic(self.plan, self.laue, two_pass, self.imgl is not None, self.S, self.dw_trainable)
         self._bind_parameters()
         self._decide_shard(inputs, shard)
+        if self.sprior is not None:
+            check_scale_prior_route(self.wide, self.owner, self.deterministic, self.laue, self.imgl is not None, self.S)
         # A frozen scaling model (`--freeze-scales`; the half-dataset trainings of `--merge-half-datasets`, reference careless.py:102-128):
         # its output (loc, sigma) per observation does not change from step to step, so a step needs neither its forward nor its backward
         # pass -- only the sampling / likelihood part (careless_amd/frozen.py).  An engine built around a frozen scaler lays its observations
@@ -115,6 +120,7 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         self.scaler_frozen = False
         self.obs = self._build_obs(inputs, self.shard.start, self.shard.stop, grid, self.laue_groups, rows=self.shard.rows if self.owner else None)
         self._build_workspace()
+        self._sprior_setup()
         self.refresh_config()
 
     def _read_plugins(self, model, inputs):
@@ -148,8 +154,8 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
             mlp, img = scaler, None
         else:
             raise NotImplementedError(f"scaling model {type(scaler).__name__} is not supported by the HIP engine yet")
-        if model.scale_prior is not None:
-            raise NotImplementedError("scale_prior is never enabled by the reference CLI and is not supported")
+        # the KL term on the scale distribution ("Σ KLDiv", reference variational.py:156-163): None without a scale prior
+        self.sprior = check_scale_prior(model.scale_prior, model.scale_kl_weight)
         self.q, self.prior, self.lik, self.mlp, self.img, self.imgl = q, prior, lik, mlp, img, imgl
         self.R = int(q.loc_raw.numel())
         self.N_total = int(_np(BaseModel.get_refl_id(inputs)).reshape(-1).shape[0])
@@ -206,11 +212,12 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         mlp, imgl = self.mlp, self.imgl
         mlp.build(self.d)
         self.w, self.L = mlp.width, mlp.n_layers
-        two_pass = self.laue and bool(getattr(self.model, "laue_two_pass", False))
+        # (Laue data under a scale prior take the two-pass path: the prior's term sits between its launches)
+        two_pass = self.two_pass = self.laue and (bool(getattr(self.model, "laue_two_pass", False)) or self.sprior is not None)
         gmax = int(np.bincount(_np(BaseModel.get_harmonic_id(inputs)).reshape(-1).astype(np.int64)).max()) if self.laue else 1
         self.plan = plan_scaler(self.lib, self.d, self.w, self.L, imgl.n_image_layers if imgl is not None else 0, laue=self.laue,
                                 two_pass=two_pass, gmax=gmax, ev11=self.ev11, deterministic=self.deterministic,
-                                lik_kind=_lib.CL_LIK_LAPLACE if self.lik.kind == "laplace" else 0)
+                                lik_kind=_lib.CL_LIK_LAPLACE if self.lik.kind == "laplace" else 0, scale_prior=self.sprior is not None)
         self.wide, self.peel, self.blocks, self.chain_lane = self.plan.wide, self.plan.peel, self.plan.blocks, self.plan.chain_lane
         if imgl is not None:
             imgl.build(self.d)
@@ -284,7 +291,8 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         bound of a launch asks for (`ObsChunks`)."""
         kw = dict(grid=grid, n_refl=self.R, n_images=self._max_images(), laue_groups=laue_groups, pack_images=self.imgl is not None and not self.wide,
                   sort_images=self.imgl is not None and self.wide,
-                  laue_single_pass=not getattr(self.model, "laue_two_pass", False) and self.blocks is None and not self.wide, wide=self.wide)
+                  laue_single_pass=not getattr(self.model, "laue_two_pass", False) and self.blocks is None and not self.wide and self.sprior is None,
+                  wide=self.wide, slot_buffers=self.sprior is not None)
         kw.update((self._frozen_layout and self._frozen_layout_kw()) or {})
         n_total = int(_np(BaseModel.get_refl_id(inputs)).reshape(-1).shape[0])
         stop = n_total if stop is None else stop
@@ -486,7 +494,9 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         # cl_tn_backward; a's and b's gradient follows when that kernel is done.  (Not with a trainable double-Wilson r: its gradient
         # sits in the tail and comes out of cl_tn_backward.)
         split = dist_on and not self.owner and not self.dw_trainable and switch(self.model, "split_message", "CARELESS_HIP_SPLIT_MESSAGE")
+        self._sprior_live, self._sprior_first = True, True
         self._data_term(self.obs, step, eta, ipred_out, st, defer_reduce=not split, train=True)
+        self._sprior_live = False
         tail_work = None
         if split:
             import torch.distributed as dist
@@ -563,7 +573,8 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         frozen scaler's answer for the step, and the plan's `wide`.  Left at their defaults the answer is the route of the fused scaler
         launch alone, which the frozen and the layer-by-layer route do not have (`_likelihood_args` behind `training_launch`);
         `chained=False`: of a chain's last block taken by itself."""
-        return data_term_route(form, wide, self.blocks is not None if chained is None else chained, self.laue, obs.fused_laue, self.peel)
+        return data_term_route(form, wide, self.blocks is not None if chained is None else chained, self.laue, obs.fused_laue, self.peel,
+                               scale_prior=self.sprior is not None)
 
     def _data_term_launch(self, obs: ObsData, step: int, eta, ipred_out, st, defer_reduce: bool):
         """The data term of one `ObsData`: the route question, then the route's method -- each ends with the reduction of the
@@ -692,6 +703,7 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         check(lib.cl_adam_step(C.byref(a), st), "cl_adam_step")
         check(lib.cl_step_finalize(ptr(self.scalars), self.kl_mult, ptr(self.history_buf), step_index,
                                    ptr(self.stop_flag), ptr(self.norm_part) if n_part else None, n_part, st), "cl_step_finalize")
+        self._scale_kl_record(step_index, st)
 
     def alloc_history(self, steps: int):
         self.history_buf = torch.zeros(max(1, steps) * _lib.CL_HIST_STRIDE, dtype=torch.float64, device=self.device)
@@ -715,7 +727,7 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
             self._hist_reduced = True
             # the records hold this rank's partial NLL / KL: summed over the ranks once, in fp64 (careless_amd/distributed.py)
             from careless_amd.distributed import allreduce_history_
-            allreduce_history_(self.history_buf, _lib.CL_HIST_STRIDE, self.kl_mult, self.process_group)
+            allreduce_history_(self.history_buf, _lib.CL_HIST_STRIDE, self.kl_mult, self.process_group, scale_kl=self.sprior is not None)
         h = self.history_buf.view(-1, _lib.CL_HIST_STRIDE)[:steps].cpu().numpy()
         keep = h[:, 4] == 0.0
         h = h[keep]
@@ -723,6 +735,8 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
         out["loss"] = h[:, 0].tolist()
         out["F KLDiv"] = h[:, 1].tolist()
         out["NLL"] = h[:, 2].tolist()
+        if self.sprior is not None:
+            out[SCALE_KL_KEY] = h[:, _lib.CL_HIST_SCALE_KL].tolist()
         if self.dw_trainable:
             r = self.rdw_hist[:steps].cpu().numpy()[keep]
             for i in range(r.shape[1]):
@@ -732,6 +746,9 @@ class ElboEngine(FusedPath, WidePath, FrozenPath, SlotPath, DetPath, NlikPath):
     # -- accessors used by tests -----------------------------------------------------------------------------
     def loss_terms(self) -> Dict[str, float]:
         s = self.scalars.cpu().numpy()
+        if self.sprior is not None:         # (+ Σ KLDiv with weight 1, whatever kl_weight is)
+            skl = self.scale_kl_value()
+            return {"nll": float(s[0]), "kl": float(s[1]), "scale_kl": skl, "loss": float(s[0] + self.kl_mult * s[1] + skl)}
         return {"nll": float(s[0]), "kl": float(s[1]), "loss": float(s[0] + self.kl_mult * s[1])}
 
     def grad_tensors(self) -> List[torch.Tensor]:

@@ -115,8 +115,8 @@ class FrozenPath:
         plain rows (the scaler's output is a constant: no tile / image constraint) -- except Laue data, which keep the packed order of the
         single-pass kernels (a group inside a 16-row granule) for `cl_frozen_rows`' group sums.  `self._frozen_layout` holds the answer the
         observations were last laid out under."""
-        if not self.frozen_fast or self.model.scaling_model.trainable or (self.deterministic and self.laue):
-            return None
+        if not self.frozen_fast or self.model.scaling_model.trainable or (self.deterministic and self.laue) or self.sprior is not None:
+            return None             # (a scale prior: its KL term needs the scaler's launches around it, careless_amd/sprior.py)
         return dict(pack_images=False, sort_images=False,
                     laue_single_pass=bool(self.laue and self.FROZEN_LAUE_PACKED and not getattr(self.model, "laue_two_pass", False)))
 
@@ -124,7 +124,7 @@ class FrozenPath:
         """Step time.  None: the scaler trains, the short cut is off, or the sampling / likelihood kernels do not take this observation image
         as it is -- they want rows in the caller's order (not packed or sorted by image) or harmonic groups in the packed order an engine built
         around a frozen scaler keeps.  `injected`: the step brings eta or asks for ipred_out."""
-        if not (self.scaler_frozen and self.frozen_fast) or obs.host_inputs is None:
+        if not (self.scaler_frozen and self.frozen_fast) or obs.host_inputs is None or self.sprior is not None:
             return None
         if obs.fused_laue:
             ok = self._frozen_layout and self.FROZEN_LAUE_PACKED and not self.deterministic and obs.tile_img is None

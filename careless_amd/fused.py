@@ -10,7 +10,7 @@ What the module decides: nothing about the route -- `ElboEngine._route` asks `da
 takes its branch from that answer (`training_launch`: from the same question, put for the engine's first piece) -- and one thing about
 the reduction: hand it to the step's `cl_tn_backward` launch (`self._pending_reduce`) or run `cl_reduce_partials` now (`_reduce_or_defer`).
 Reads of the engine: `lib, device, layout, mlp, imgl, d, w, L, S, blocks, chain_lane, deterministic, stop_flag`, `_route`, `_step_fields`,
-`_shard_rows`, `_param_ptr`, `_grad_ptr`, `_sig`, `_det_parts`, `_slot_likelihood`, `_laue_pad_slots`; it sets `peel_params`, `peel_grad`
+`_shard_rows`, `_param_ptr`, `_grad_ptr`, `_sig`, `_det_parts`, `_slot_likelihood`, `_laue_pad_slots`, `_scale_kl`; it sets `peel_params`, `peel_grad`
 and `_pending_reduce`.
 Reads of an `ObsData`: the row arrays, `partials`, `grid`, the chain's `chain_act / chain_dact / chain_dz0`, the two-pass buffers
 `laue_loc / laue_sig / laue_dO`, `det_parent.det`.  Attaches: `obs.peel` (`PeelBuffers`).
@@ -112,6 +112,8 @@ class FusedPath:
         elif route is Route.TWO_PASS:
             mode = 2 if mode == 0 else mode
             ma.dO_ext = ptr(obs.laue_dO)
+            if self.deterministic:          # (as `_laue_passes`: the two scaler launches carry no store targets)
+                ma.dzf_obs = ma.dimg_obs = ma.nll_part = ma.det_slot = ma.ev11_part = None
         elif route is Route.PEEL and mode == 0:
             ma = self._peel_args(ma, obs)
         return ma, mode
@@ -198,14 +200,20 @@ class FusedPath:
 
     def _laue_passes(self, ma: MlpArgs, obs: ObsData, step: int, eta, ipred_out, st):
         """Harmonic deconvolution (reference likelihoods/laue.py:9-47): scaler forward, predict + group sums, likelihood on
-        the slots, gradient broadcast back to the rows, scaler backward from dL/d(loc, sigma).  `ma`: the backward launch's arguments
+        the slots, gradient broadcast back to the rows, scaler backward from dL/d(loc, sigma).  Under a scale prior monochromatic rows
+        come here as well (every row its own slot: `cl_slot_rows`).  `ma`: the backward launch's arguments
         (`dO_ext` set: `_likelihood_args`); the forward launch runs on a copy without it."""
         lib = self.lib
+        if self.deterministic:
+            # (monochromatic rows under a scale prior: neither scaler launch holds a float atomic -- the stores are the slot likelihood's -- and
+            #  a launch that carries the store targets is a full step to `cl_mlp_route`)
+            ma.dzf_obs = ma.dimg_obs = ma.nll_part = ma.det_slot = ma.ev11_part = None
         ma.loc_out, ma.sig_out = ptr(obs.laue_loc), ptr(obs.laue_sig)
         fwd = _copy_args(ma)
         fwd.dO_ext = None
         check(lib.cl_mlp_forward(C.byref(fwd), obs.grid, st), "cl_mlp_forward")
         self._slot_likelihood(ma, obs, step, eta, ipred_out, st)
+        self._scale_kl(ma, obs, step, eta, st)          # a scale prior's KL term adds to dL/d(loc, sigma) (careless_amd/sprior.py); else nothing
         check(lib.cl_mlp_backward_ext(C.byref(ma), obs.grid, st), "cl_mlp_backward_ext")
 
     # -- a chain of layer blocks: CHAIN ----------------------------------------------------------------------------------------

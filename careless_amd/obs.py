@@ -417,7 +417,7 @@ class ObsData:
 
     def __init__(self, lib, inputs, start: int, stop: int, S: int, P: int, device, grid=None, n_refl=None, n_images=None,
                  laue_groups=None, pack_images: bool = False, laue_single_pass: bool = True, wide: bool = False, sort_images: bool = False,
-                 rows: Optional[np.ndarray] = None, host_inputs=None):
+                 rows: Optional[np.ndarray] = None, host_inputs=None, slot_buffers: bool = False):
         # 1. the library's answers for this metadata width, asked when a step needs one (a launch trace shows the queries too)
         size = lambda name: int(getattr(lib, name)(self.d))
         # 2. which rows
@@ -433,8 +433,12 @@ class ObsData:
         for name in Layout.ARRAYS:
             v = getattr(lay, name)
             setattr(self, name, None if v is None else torch.as_tensor(np.ascontiguousarray(v), device=device))
+        # (monochromatic rows packed by image on the two-pass launches: the scaler launches write loc / sigma and read dL/d(loc, sigma) by the
+        #  caller's local row -- row_map --, so the slot kernels between them get the row arrays in that order: `slot_rows`, on those sets only)
+        if slot_buffers and not self.laue and self.row_map is not None:
+            self.slot_rows = {k: torch.as_tensor(np.ascontiguousarray(getattr(s, k)), device=device) for k in ("refl_id", "image_id", "iobs", "sig")}
         # 5. work buffers: the slot kernels' (two-pass Laue, wide), the padded slots', the fused kernel's gradient partials
-        slots = wide or (self.laue and not self.fused_laue)
+        slots = wide or (self.laue and not self.fused_laue) or slot_buffers       # (slot_buffers: monochromatic rows on the two-pass launches, a scale prior)
         self.laue_loc = torch.empty(self.N, dtype=torch.float32, device=device) if slots else None
         self.laue_sig = torch.empty(self.N, dtype=torch.float32, device=device) if slots else None
         self.laue_iconv = torch.empty(self.N * S, dtype=torch.float32, device=device) if slots else None

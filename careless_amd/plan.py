@@ -18,6 +18,7 @@ from careless_amd.obs import GRANULE
 
 REFPRIOR_KINDS = {"normal": _lib.CL_REFPRIOR_NORMAL, "laplace": _lib.CL_REFPRIOR_LAPLACE, "studentt": _lib.CL_REFPRIOR_STUDENTT,
                   "rice_woolfson": _lib.CL_REFPRIOR_RICE_WOOLFSON}       # ReferencePrior.engine_kind -> cl_refprior_args.kind
+SPRIOR_KINDS = {"normal": _lib.CL_SPRIOR_NORMAL, "laplace": _lib.CL_SPRIOR_LAPLACE, "studentt": _lib.CL_SPRIOR_STUDENTT}       # ScalePrior.engine_kind -> cl_sprior_args.kind
 BIJ_KINDS = {"exp": _lib.CL_BIJ_EXP, "softplus": _lib.CL_BIJ_SOFTPLUS}       # MetadataScaler.scale_bijector -> cl_mlp_args.bij_kind
 
 
@@ -26,23 +27,24 @@ class Route(enum.Enum):
     FROZEN = 1        # behind a frozen scaler: no scaler launch at all (careless_amd/frozen.py)
     WIDE = 2          # layer by layer on the GEMM kernels (careless_amd/wide.py)
     CHAIN = 3         # a chain of layer blocks (`FusedPath._data_term_chain`)
-    TWO_PASS = 4      # Laue rows the fused kernel does not take as harmonic groups: scaler forward, slot likelihood, scaler backward
+    TWO_PASS = 4      # Laue rows the fused kernel does not take as harmonic groups, any rows under a scale prior: scaler forward, slot likelihood, scaler backward
     PEEL = 5          # the fused launch behind a peeled first layer
     FUSED = 6         # the fused launch on the scaler itself
 
 
-def data_term_route(frozen_form, wide: bool, chained: bool, laue: bool, fused_laue: bool, peel: bool) -> Route:
+def data_term_route(frozen_form, wide: bool, chained: bool, laue: bool, fused_laue: bool, peel: bool, scale_prior: bool = False) -> Route:
     """THE route decision, the precedence written once: a frozen scaler's form (`FrozenPath._frozen_form`, not None) before the plan's
     `wide`, before its chain of blocks (`chained`), before the two-pass Laue path -- `laue` data whose observation image is not packed
-    for the single-pass kernels (`fused_laue`) --, before the plan's `peel`, before the plain fused launch.  Two-pass before peel: the
-    plan may say `peel` for a scaler whose rows `pack_laue` then declines to pack; the two-pass path has no peeled launch."""
+    for the single-pass kernels (`fused_laue`), and any data under a scale prior (`scale_prior`: its KL term sits between the two passes,
+    careless_amd/sprior.py) --, before the plan's `peel`, before the plain fused launch.  Two-pass before peel: the plan may say `peel`
+    for a scaler whose rows `pack_laue` then declines to pack; the two-pass path has no peeled launch."""
     if frozen_form is not None:
         return Route.FROZEN
     if wide:
         return Route.WIDE
     if chained:
         return Route.CHAIN
-    if laue and not fused_laue:
+    if (laue and not fused_laue) or scale_prior:
         return Route.TWO_PASS
     return Route.PEEL if peel else Route.FUSED
 
@@ -91,9 +93,11 @@ class ScalerPlan:
 
 
 def plan_scaler(lib, d: int, w: int, L: int, K: int = 0, laue: bool = False, two_pass: bool = False, gmax: int = 1, ev11: bool = False,
-                deterministic: bool = False, lik_kind: int = 0) -> ScalerPlan:
+                deterministic: bool = False, lik_kind: int = 0, scale_prior: bool = False) -> ScalerPlan:
     """How `ElboEngine` runs L Dense layers of width w on d columns with K per-image layers (`gmax`: the largest harmonic group): the plan
-    chooses the launches -- peel the first layer, cut a deep scaler into blocks, go layer by layer --, the library's routes decide."""
+    chooses the launches -- peel the first layer, cut a deep scaler into blocks, go layer by layer --, the library's routes decide.
+    `scale_prior`: the engine has a scale prior, whose KL term sits between a forward and a backward launch: monochromatic rows take the
+    two-pass launches as well, a chain's last block its two-pass form (no lane kernel: that one is a full step)."""
     NONE, LANE, NARROW, LANE_IMGL = _lib.CL_ROUTE_NONE, _lib.CL_ROUTE_LANE, _lib.CL_ROUTE_NARROW, _lib.CL_ROUTE_LANE_IMGL
     proto = dict(d=d, w=w, L=L, S=1, refl_id=1, meta_t=1, iobs=1, sig=1, mlp=1, z_f=1, dz_f=1, partials=1, scalars=1, stop_flag=1,
                  ev11=int(ev11), d_ev11=int(ev11), lik_kind=lik_kind)      # (the lane and the narrow kernel refuse CL_LIK_LAPLACE: the routes say so)
@@ -107,12 +111,12 @@ def plan_scaler(lib, d: int, w: int, L: int, K: int = 0, laue: bool = False, two
         # without spilled registers) and the head on the lane kernel where it takes them, dZ_0 out, `cl_chain_dx` turns it into the gradient
         # of the block's input (round 6: 24 x 10 at 4 M observations 3.13 -> 1.4 ms per step).  Laue data: the two-pass path.
         last = 19 if w in (11, 12) else 20
-        chain_lane = not laue and route(0, d=w, L=last, dZ0_out=1) == LANE
+        chain_lane = not laue and not scale_prior and route(0, d=w, L=last, dZ0_out=1) == LANE
         blocks = chain_plan(d, w, L, min(max_plain, last) if chain_lane else max_plain, last=last if chain_lane else 0)
         last_block = dict(d=w, L=blocks[-1].l1 - blocks[-1].l0, **({"dZ0_out": 1} if chain_lane else {"dX_out": 1}))
         return ScalerPlan(False, False, blocks, chain_lane, route(0, **last_block, **det))
     # Laue rows the fused kernel cannot take as harmonic groups: the two-pass path, cl_mlp_forward + cl_mlp_backward_ext on the scaler itself
-    two_pass = laue and (two_pass or gmax > GRANULE)
+    two_pass = (laue and (two_pass or gmax > GRANULE)) or scale_prior
     layout = dict(dict(row_map=1, tile_img=1, imgl=1, d_imgl=1, n_imgl=K, n_images=1) if K else {},
                   **(dict(row_map=1, gmeta=1, tile_gmax=1) if laue and not two_pass else {}))
     unpeeled, peeled = route(0, **layout), route(0, **layout, d=w, dZ0_out=1)
@@ -181,6 +185,41 @@ def check_neural_likelihood(lik, laue: bool, world: int = 1, lib=None) -> bool:
     if not lib.cl_nlik_supports(int(lik.n_layers), int(lik.width)):
         raise NotImplementedError(f"likelihood {name}({lik.n_layers}, {lik.width}): the HIP kernels hold 1 .. 4 hidden layers of width 1 .. 32")
     return True
+
+
+def check_scale_prior(scale_prior, scale_kl_weight):
+    """The scale prior the engine runs (`models/priors/scale.py`), or None without one.  As the reference executes it (careless/models/
+    merging/variational.py:156-163): a prior beside `scale_kl_weight=None` reaches `add_kl_div(..., weight=None)` and fails in
+    `add_loss(None * kl_div)` -- a TypeError here too; with a weight, the term is added with weight 1 and reduction 'mean' WHATEVER the
+    weight's value (only that it is not None is read).  NotImplementedError for anything that is not one of the three families whose density
+    the library evaluates.  Host logic: needs no device."""
+    if scale_prior is None:
+        return None
+    from careless_amd.models.priors.scale import ScalePrior
+    if not isinstance(scale_prior, ScalePrior) or scale_prior.engine_kind not in SPRIOR_KINDS:
+        raise NotImplementedError(f"scale_prior {type(scale_prior).__name__} is not supported by the HIP engine: use NormalScalePrior, "
+                                  "LaplaceScalePrior or StudentTScalePrior (careless_amd.models.priors.scale)")
+    if scale_kl_weight is None:
+        raise TypeError("unsupported operand type(s) for *: 'NoneType' and 'Tensor': a scale_prior with scale_kl_weight=None fails in the "
+                        "reference as well (careless/models/merging/variational.py:160-161 call add_kl_div with weight=None); pass any "
+                        "scale_kl_weight -- its value is not used, the term has weight 1")
+    return scale_prior
+
+
+def check_scale_prior_route(wide: bool, owner: bool, deterministic: bool = False, laue: bool = False, imgl: bool = False, S: int = 1) -> None:
+    """NotImplementedError for the routes a scale prior's KL term has no launch on.  It sits between cl_mlp_forward and
+    cl_mlp_backward_ext of the two-pass launches (careless_amd/sprior.py): the layer-by-layer route of scalers wider than 64 (`wide`) has
+    neither, and the reflection-owner split (`owner`) cuts rows by reflection where the term is a mean over rows.  `deterministic`: the
+    mode takes the route where `cl_slot_rows` has its store form -- monochromatic rows (not `laue`), no per-image layers (`imgl`), `S`
+    dividing 64.  Host logic: needs no device."""
+    if wide:
+        raise NotImplementedError("scale_prior: the layer-by-layer route (scaler width or metadata width beyond 64) has no two-pass launches "
+                                  "for the term to sit between; it runs on scalers the fused kernels hold")
+    if owner:
+        raise NotImplementedError("scale_prior: the reflection-owner split is not supported (the term is a mean over rows); use the row split")
+    if deterministic and (laue or imgl or 64 % S != 0):
+        raise NotImplementedError("scale_prior: deterministic mode covers monochromatic rows without per-image layers and a sample count that divides "
+                                  "64 (the store form of cl_slot_rows: a row's samples inside one wave); the Laue slot kernels keep their float atomics")
 
 
 def switch(model, attr: Optional[str], env: str, default: bool = False, env_adds: bool = False) -> bool:

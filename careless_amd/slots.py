@@ -8,8 +8,8 @@ the harmonic-group form of a frozen scaler.
 
 What the module decides: which of the slot kernels run -- rows that are their own slot in one `cl_slot_rows` launch (always in
 deterministic mode; else while `SLOT_ROWS_ONE_LAUNCH`), otherwise `cl_laue_predict`, `cl_laue_likelihood`, `cl_laue_backward`.
-Reads of the engine: `lib, S, deterministic, lik_kind, dof, lik_const, scalars, stop_flag`, `_step_fields`, `_sig`, `_det_parts`.
-Reads of an `ObsData`: the row arrays, `laue_loc, laue_sig, laue_iconv, laue_dO, row_index, harmonic_id`, the padded slots' `pad_*`, and
+Reads of the engine: `lib, S, deterministic, lik_kind, dof, lik_const, scalars, stop_flag`, `_step_fields`, `_shard_rows`, `_sig`, `_det_parts`, `_det_slot_parts`.
+Reads of an `ObsData`: the row arrays, `laue_loc, laue_sig, laue_iconv, laue_dO, row_index, harmonic_id, slot_rows`, the padded slots' `pad_*`, and
 `det_parent.det`; it attaches nothing.
 """
 from __future__ import annotations
@@ -29,11 +29,18 @@ class SlotPath:
         la = self._step_fields(LaueArgs(), obs, step)
         n = obs.N - a if n is None else n
         off = lambda t, size: None if t is None else t.data_ptr() + size * a
-        la.refl_id, la.image_id, la.harmonic_id = off(obs.refl_id, 4), off(obs.image_id, 4), off(obs.harmonic_id, 4)
-        la.loc, la.sigma, la.iobs, la.sig = off(obs.laue_loc, 4), off(obs.laue_sig, 4), off(obs.iobs, 4), off(self._sig(obs, obs.sig), 4)
+        rows = getattr(obs, "slot_rows", None) or {}       # packed monochromatic rows under a scale prior: the row arrays in the caller's order
+        col = lambda k: rows[k] if k in rows else getattr(obs, k)
+        sig = self._sig(obs, obs.sig)
+        if rows:            # (a neural likelihood's sigpred is in that order itself)
+            sig = obs.nlik.sigpred if self.neural else rows["sig"]
+        la.refl_id, la.image_id, la.harmonic_id = off(col("refl_id"), 4), off(col("image_id"), 4), off(obs.harmonic_id, 4)
+        la.loc, la.sigma, la.iobs, la.sig = off(obs.laue_loc, 4), off(obs.laue_sig, 4), off(col("iobs"), 4), off(sig, 4)
         la.n_obs, la.obs_offset = n, obs.start + a
         la.img, la.use_img, la.d_img = ma.img, ma.use_img, ma.d_img
-        la.eta, la.ipred_out = off(eta, 4 * self.S), off(ipred_out, 4 * self.S)
+        # (eta / ipred_out are the whole shard's: a piece of a chunked shard starts at its row0, `_shard_rows`)
+        rows = lambda t: None if t is None else self._shard_rows(obs, t) + 4 * self.S * a
+        la.eta, la.ipred_out = rows(eta), rows(ipred_out)
         la.iconv, la.dO = off(obs.laue_iconv, 4 * self.S), off(obs.laue_dO, 8)
         la.row_index = off(obs.row_index, 8)
         return la
@@ -48,9 +55,13 @@ class SlotPath:
         if self.deterministic and obs.harmonic_id is None:
             # no float atomics: the amplitude gradient of every (row, sample) and the image-scale term of every row are stored (records in
             # reflection order: det_slot), every workgroup stores its NLL; cl_det_reduce sums them in a fixed order after the backward pass
-            det = obs.det_parent.det
-            la.dzf_obs, la.dimg_obs, la.det_slot = ptr(det.dzf), ptr(det.dimg), ptr(det.slot)
-            la.nll_part, la.ev11_part = self._det_parts(obs, det.pieces)
+            det = obs.det_parent.det           # (a piece of a chunked shard -- a scale prior's route -- stores at its row0 inside the shard's records)
+            if det.slot is not None:
+                la.dzf_obs, la.det_slot = ptr(det.dzf), det.slot.data_ptr() + 4 * obs.row0
+            else:
+                la.dzf_obs = det.dzf.data_ptr() + 4 * self.S * obs.row0
+            la.dimg_obs = det.dimg.data_ptr() + 4 * obs.row0
+            la.nll_part, la.ev11_part = self._det_slot_parts(obs)
             check(lib.cl_slot_rows(C.byref(la), st), "cl_slot_rows")
             return
         if obs.harmonic_id is None and self.SLOT_ROWS_ONE_LAUNCH:

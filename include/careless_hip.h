@@ -48,7 +48,7 @@ extern "C" {
 #endif /* width <= 15 with per-image layers: Dense + image layers (the default 20 + --image-layers <= 4) */
 #define CL_MLP_LMAX_W32 10 /* width 17 .. 32 */
 #define CL_MLP_LMAX_W64 5  /* width <= 64 */
-#define CL_HIST_STRIDE 8  /* doubles per history record: loss, F KLDiv, NLL, Grad Norm, skipped, 3 spare */
+#define CL_HIST_STRIDE 8  /* doubles per history record: loss, F KLDiv, NLL, Grad Norm, skipped, Σ KLDiv (cl_scale_kl_record), 2 spare */
 
 /* indices into the double-precision scalar block of one step */
 enum { CL_SC_NLL = 0, CL_SC_KL = 1, CL_SC_GNORM2 = 2, CL_SC_GNORM2_SANE = 3, CL_SC_COUNT = 4 };
@@ -635,6 +635,60 @@ size_t cl_nlik_param_count(int L, int w);
 size_t cl_nlik_workspace_bytes(long long n, int L, int w);
 int cl_nlik_grid(long long n);                     /* workgroups of every launch = rows of the partial buffers         */
 
+/* --- the KL term on the scale distribution, "Σ KLDiv" (csrc/elbo_sprior.hip) ---------------------------------------------------------
+ * replaces: the scale_prior branch of VariationalMergingModel.call (careless/models/merging/variational.py:156-163) through add_kl_div
+ *           (:123-139: weight 1, reduction 'mean', metric "Σ KLDiv"), and tape.gradient through it (variational.py:197-202).
+ * With y_is = loc_i + sigma_i eta_is + shift, z_is = a_i y_is (a_i = img[image_id_i - 1], 1 for image 0 or without image scales) and
+ * l(z) = log p_prior(z), p_prior a Normal / Laplace / Student-t with location p_loc and scale p_scale:
+ *   CL_SPRIOR_ANALYTIC (a bare Normal scale distribution against a Normal prior: the KL TFP has registered)
+ *     value = weight sum_i [log(p_scale / sigma_i) + (sigma_i^2 + (loc_i - p_loc)^2) / (2 p_scale^2) - 1/2]
+ *   CL_SPRIOR_SAMPLE (everything else: log q - log p on the step's own samples)
+ *     value = (weight / S) sum_is [-log sigma_i - eta_is^2 / 2 - log(2 pi) / 2 - log|a_i| - l(z_is)]
+ * weight = 1 / N of the set the model is called on (all ranks' rows).  eta: the injected draws [n][S], or the data term's own for
+ * (seed, step, global row, sample) -- the global row is row_index[i] where given, else obs_offset + i, as in cl_laue_args.
+ * Called between the slot likelihood and cl_mlp_backward_ext: dO[i][0 .. 1] += d value / d(loc_i, sigma_i) (a plain read-modify-write
+ * by the row's own thread), d_img[image - 1] += d value / d a (dimg_obs given: dimg_obs[i] += the row's term instead, no atomic);
+ * kl_part [cl_scale_kl_grid(n)] receives one fp64 partial per workgroup and *value = (accumulate ? *value : 0) + their sum in a fixed
+ * order.  No float atomic on the value's way: two calls on the same inputs agree bit for bit.  A NaN in loc / sigma reaches the value and
+ * both derivatives.  stop_flag non-zero: nothing is written.
+ * -1: a NULL loc / sigma / dO / kl_part / value, n < 1, an unknown kind or form, p_scale <= 0, p_df <= 0 (Student-t), and in the sample
+ * form S < 1 or use_img without image_id / img / a gradient buffer.  -2: the analytic form asked with a non-Normal prior, a shift or
+ * image scales.  Both answers come before anything touches the device.
+ * cl_scale_kl_record, behind cl_step_finalize: history record `step_index` takes *value as its sixth double and adds it to the loss
+ * where the step was not skipped (0 where it was).                                                                                    */
+typedef struct cl_sprior_args {
+    const float* loc;           /* [n] what cl_mlp_forward wrote (loc_out)                                         */
+    const float* sigma;         /* [n] (sig_out)                                                                   */
+    const int* image_id;        /* [n], with use_img                                                               */
+    const float* img;           /* image scales of images 1 ..                                                     */
+    int use_img;
+    float shift;                /* c of tfb.Shift(c); 0 without one                                                */
+    int has_shift;              /* a shift bijector is present (its value may be 0)                                */
+    int kind;                   /* CL_SPRIOR_NORMAL | _LAPLACE | _STUDENTT                                         */
+    float p_loc, p_scale, p_df;
+    int form;                   /* CL_SPRIOR_ANALYTIC | _SAMPLE                                                    */
+    int n;
+    long long obs_offset;
+    const long long* row_index; /* optional [n]: the global row that keys the noise                                */
+    int S;
+    const float* eta;           /* optional [n][S] injected draws                                                  */
+    unsigned long long seed;
+    unsigned int step;
+    float weight;               /* 1 / N_total                                                                     */
+    float* dO;                  /* [n][2] +=                                                                       */
+    float* d_img;               /* +=                                                                              */
+    float* dimg_obs;            /* optional [n] += (deterministic records)                                         */
+    double* kl_part;            /* [cl_scale_kl_grid(n)]                                                           */
+    double* value;
+    int accumulate;
+    const int* stop_flag;
+} cl_sprior_args;
+enum { CL_SPRIOR_NORMAL = 0, CL_SPRIOR_LAPLACE = 1, CL_SPRIOR_STUDENTT = 2 };
+enum { CL_SPRIOR_ANALYTIC = 0, CL_SPRIOR_SAMPLE = 1 };
+int cl_scale_kl(const cl_sprior_args* args, void* stream);
+int cl_scale_kl_grid(long long n);                 /* workgroups of the launch = doubles of kl_part                    */
+int cl_scale_kl_record(const double* value, double* history, int step_index, void* stream);
+
 /* --- gradient norm, sanitise, clip, Adam -------------------------------------------------------------------------
  * replaces: tf.linalg.global_norm, tf.where(is_finite), optimizer.apply_gradients (variational.py:202-209)
  *           tfk.optimizers.Adam(lr, b1, b2, clipnorm, clipvalue, global_clipnorm) (careless/io/manager.py:494-501)
@@ -791,7 +845,7 @@ int cl_host_crystfel_parse(const char* buf, long long nbytes, long long n_rows, 
 /* --- diagnostics -------------------------------------------------------------------------------------------------- */
 const char* cl_version(void);
 /* The binding handshake: sizeof(<struct_name>) as the library was compiled, for every argument struct of this header -- "cl_tn_args",
- * "cl_mlp_args", "cl_adam_args", "cl_laue_args", "cl_det_args", "cl_frozen_args", "cl_refprior_args", "cl_rw_args", "cl_nlik_args" --,
+ * "cl_mlp_args", "cl_adam_args", "cl_laue_args", "cl_det_args", "cl_frozen_args", "cl_refprior_args", "cl_rw_args", "cl_nlik_args", "cl_sprior_args" --,
  * 0 for a name the library does not know (or NULL).  A binding compares each of its mirrors once, at load time.                       */
 size_t cl_abi_sizeof(const char* struct_name);
 /* out[n][S]: kind 0 = the uniforms of cl_tn_*, kind 1 = the normals of cl_elbo_mono_fwd_bwd, for (seed, step);
